@@ -2,6 +2,7 @@
 """bench.py -- env-steps/s of the CM3 rollout hot path on MI355X (one process per GPU).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last step's outputs as DIR/<name>.npy
     python bench.py --gpus 8 ...            # re-executes itself through torch.distributed.run with 8 ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -298,7 +299,7 @@ class RolloutAdvStepper(object):
         self.ro.collect_normalized(gamma=0.99, segments=self.K)
         self.ro1.collect_normalized(gamma=0.99)
         self.device = self.env.device
-        self.last = None
+        self.last = self.last_ro = None
         self.launches_per_tick = 1
         self.collective_s, self.rollouts = 0.0, 0     # host time inside the all-gather call, summed over rollouts
 
@@ -312,10 +313,12 @@ class RolloutAdvStepper(object):
             *self.last, t_coll = self.ro.collect_normalized(gamma=0.99, time_collective=True, segments=self.K)
             self.collective_s += t_coll
             self.rollouts += self.K
+            self.last_ro = self.ro
         for _ in range(rest):
             *self.last, t_coll = self.ro1.collect_normalized(gamma=0.99, time_collective=True)
             self.collective_s += t_coll
             self.rollouts += 1
+            self.last_ro = self.ro1
 
     def close(self):
         self.ro.close()
@@ -343,6 +346,69 @@ def timed_ticks(stepper, n_ticks):
         stop.record(stream)
         stop.synchronize()
         return start.elapsed_time(stop)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together
+DUMP_MAX_ENVS = 256           # envs of the fixed sample (fewer where the budget demands it)
+
+
+def last_step_outputs(stepper):
+    """name -> (device tensor, env axis or None): what the caller of the timed path holds after its last step -- the collector's
+    trajectory (trajectory mode; c4 also the normalised returns and their moments) or the env's live buffers (in-place mode)."""
+    if isinstance(stepper, (TrajectoryStepper, RolloutAdvStepper)):
+        ro = stepper.ro if isinstance(stepper, TrajectoryStepper) else stepper.last_ro
+        out = {"state": (ro.state, 2), "obs_others": (ro.obs_others, 1), "actions": (ro.actions, 1), "reward": (ro.reward, 1),
+               "reward_n": (ro.reward_n, 1), "done": (ro.done, 1), "goals": (ro.goals, 2), "term_state": (ro.term_state, 2),
+               "term_obs_others": (ro.term_obs_others, 1), "collisions": (ro.collisions, 1)}
+        if isinstance(stepper, RolloutAdvStepper):
+            returns, (mean, std, count) = stepper.last
+            out.update(returns=(returns, 1), returns_mean=(mean, None), returns_std=(std, None), returns_count=(count, None))
+        return {k: v for k, v in out.items() if v[0] is not None}
+    if isinstance(stepper, CheckersTrajectoryStepper):
+        ro = stepper.ro
+        names = ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions", "local_rewards", "reward", "done",
+                 "term_grid", "term_vec", "term_obs_others", "term_obs_self_t", "term_obs_self_v", "goal_slots")
+        return {k: (getattr(ro, k), 1) for k in names if getattr(ro, k) is not None}
+    if isinstance(stepper, ParticleStepper):
+        e = stepper.env          # (the in-place launches read and write buffer set 0: ParticleStepper.traj)
+        return {"state": (e._state[0], 1), "obs_others": (e._obs_others[0], 0), "actions": (e._actions[0], 0),
+                "reward": (e._reward[0], 0), "reward_n": (e._reward_n[0], 0), "done": (e._done[0], 0), "goals": (e._goals, 1)}
+    if isinstance(stepper, CheckersStepper):
+        s = stepper.env._slots[0]
+        return {k: (s[k], 0) for k in ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions", "local_rewards",
+                                       "reward", "done")}
+    raise TypeError("no output dump for %s" % type(stepper).__name__)
+
+
+def dump_outputs(stepper, out_dir, seed=0):
+    """--dump-outputs: the arrays of last_step_outputs() as out_dir/<name>.npy, float32 (float32 and 8-/16-bit integer data) or
+    float64 (everything else), restricted to a fixed seeded sample of envs (out_dir/env_index.npy) so that all of it stays under
+    DUMP_LIMIT_BYTES.  Inputs are seeded, so the same arguments give the same arrays on every run of the same build."""
+    import numpy as np
+    torch = stepper.torch
+    torch.cuda.synchronize(stepper.device)
+    arrays = last_step_outputs(stepper)
+    wide = (torch.float64, torch.int32, torch.int64, torch.uint32, torch.uint64)
+    out_dtype = {k: np.float64 if t.dtype in wide else np.float32 for k, (t, _) in arrays.items()}
+    E = next(t.shape[ax] for t, ax in arrays.values() if ax is not None)
+    per_env = sum(t.numel() // E * np.dtype(out_dtype[k]).itemsize for k, (t, ax) in arrays.items() if ax is not None)
+    fixed = sum(t.numel() * np.dtype(out_dtype[k]).itemsize for k, (t, ax) in arrays.items() if ax is None)
+    n = min(E, DUMP_MAX_ENVS, (DUMP_LIMIT_BYTES - fixed - (1 << 16)) // (per_env + 8))     # (1 << 16: the .npy headers)
+    envs = np.sort(np.random.default_rng(seed).choice(E, size=n, replace=False))
+    idx = torch.as_tensor(envs, device=stepper.device)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, ".gitignore"), "w") as fh:      # (a dump inside a checkout stays out of git)
+        fh.write("*\n")
+    total = 0
+    for name, (t, ax) in sorted(arrays.items()):
+        assert ax is None or t.shape[ax] == E, (name, tuple(t.shape))
+        a = (t if ax is None else t.index_select(ax, idx)).cpu().numpy().astype(out_dtype[name])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += os.path.getsize(os.path.join(out_dir, name + ".npy"))
+    np.save(os.path.join(out_dir, "env_index.npy"), envs.astype(np.float64))
+    total += os.path.getsize(os.path.join(out_dir, "env_index.npy"))
+    assert total <= DUMP_LIMIT_BYTES, total
+    sys.stderr.write("bench: %d arrays of %d of %d envs (%.1f MB) -> %s\n" % (len(arrays) + 1, n, E, total / 1e6, out_dir))
 
 
 def measure_bandwidth(device, gib=4.0, reps=5):
@@ -1079,9 +1145,16 @@ def main():
                          "the default keeps one launch per tick")
     ap.add_argument("--kernel", choices=["auto", "env", "pair", "agent"], default="auto",
                     help="step-kernel mapping (auto = library heuristic)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32 / float64; a "
+                         "fixed seeded sample of the envs, at most 64 MB in all; rank 0's envs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.workload == "c1":
+        if args.dump_outputs:
+            ap.error("--dump-outputs: c1 has no GPU path to dump")
         return run_c1(args)
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.gpus > 1 and not under_launcher:
@@ -1128,7 +1201,7 @@ def main():
     cfg = cm3_amd.load_config(cfg_name)
     N = cfg["n_agents"]
     E = args.envs_per_gpu or default_e
-    steps, warm = max(args.steps, 1), max(args.warmup, 0)
+    steps, warm = args.steps, max(args.warmup, 0)
     stepper, ticks_per_step, bytes_per_env_step, dtype_name, mode = build_headline(args, kind, cfg, N, E, device, rank)
     K, W = steps * ticks_per_step, max(warm, 1) * ticks_per_step      # in ticks
     stepper.run(W)
@@ -1160,6 +1233,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max, ev_max = float(t[0]), float(t[1])
     rccl = rccl_report(dist, torch, device, local_rank, world) if use_dist else None    # (every rank takes part; rank 0 prints it)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(stepper, args.dump_outputs)
 
     fused_ticks = ticks_per_step if (args.fused and kind != "particle_adv") else 1
     # (the extras below quote the headline's time and bytes per launch; headline_record() derives the same from the same clock)

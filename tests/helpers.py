@@ -24,3 +24,32 @@ def load_golden(name):
 def load_cfg(name):
     with open(os.path.join(CFG_DIR, name)) as f:
         return json.load(f)
+
+
+def particle_transition_columns(g, ep):
+    """The reference's 11 transition columns of episode ``ep`` of a particle golden fixture -> (columns, T, N)."""
+    T = int(g["ep_len"][ep])
+    N = g["meta"]["n_agents"]
+    gs = np.concatenate([g["init_gs"][ep][None], g["gs"][ep, :T]])
+    oo = np.concatenate([g["init_obs_others"][ep][None], g["obs_others"][ep, :T]])
+    goals = np.repeat(g["landmarks"][ep][None], T, axis=0)
+    return dict(v_global=gs[:-1], obs_others=oo[:-1], v_local=gs[:-1], actions=g["actions"][ep, :T],
+                reward=g["reward"][ep, :T], reward_local=g["reward_n"][ep, :T], v_global_next=gs[1:],
+                obs_others_next=oo[1:], v_local_next=gs[1:], done=g["done"][ep, :T], goals=goals), T, N
+
+
+def checkers_transition_columns(g, ep):
+    """The reference's 16 transition columns of episode ``ep`` of a Checkers golden fixture -> (columns, T, N)."""
+    T, N = int(g["ep_len"][ep]), g["meta"]["n_agents"]
+
+    def seq(init, per_tick):
+        return np.concatenate([g[init][ep][None], g[per_tick][ep, :T]])
+    grid, vec = seq("init_grid", "grid"), seq("init_vec", "vec")
+    oo, ot, ov = seq("init_obs_others", "obs_others"), seq("init_obs_self_t", "obs_self_t"), seq("init_obs_self_v", "obs_self_v")
+    acts = g["actions"][ep, :T]
+    prev = np.concatenate([np.zeros((1, N), acts.dtype), acts[:-1]])
+    return dict(grid=grid[:-1], vec=vec[:-1], obs_others=oo[:-1], obs_self_t=ot[:-1], obs_self_v=ov[:-1],
+                actions_prev=prev, actions=acts, reward=g["reward"][ep, :T], local_rewards=g["local_rewards"][ep, :T],
+                next_grid=grid[1:], next_vec=vec[1:], next_obs_others=oo[1:], next_obs_self_t=ot[1:],
+                next_obs_self_v=ov[1:], done=g["done"][ep, :T],
+                goals=np.repeat(g["goals"][ep][None], T, axis=0).astype(float)), T, N

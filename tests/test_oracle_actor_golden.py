@@ -2,7 +2,7 @@
 the REFERENCE's own function bodies networks.actor_particle / networks.actor_checkers under a NumPy stand-in for the TF1
 calls they make (oracle/tf_numpy_shim.py, oracle/gen_golden_actor.py -> tests/golden/actor_*.npz): layer wiring, concat
 order, variable names and shapes are the reference's; the primitive-op semantics are the shim's (TensorFlow itself is not
-installable here).  Where /root/reference exists the vectors are re-derived and compared with the committed ones."""
+installable here).  Re-running oracle/gen_golden_actor.py where the reference tree is at hand re-derives the committed vectors."""
 import os
 
 import numpy as np
@@ -11,8 +11,6 @@ import pytest
 from oracle import actor_checkers_oracle as CO
 from oracle import actor_oracle as PO
 from tests.helpers import GOLDEN
-
-REF = "/root/reference"
 
 
 def load_cases(name):
@@ -43,22 +41,3 @@ def test_checkers_actor_oracle_matches_reference_wiring(tag):
     assert set(w) == set(CO.init_weights(np.random.default_rng(0), int(tag[1]), stage=int(tag[-1])))
     for k, v in CO.init_weights(np.random.default_rng(0), int(tag[1]), stage=int(tag[-1])).items():
         assert v.shape == w[k].shape, k
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "alg")), reason="reference tree not present")
-def test_reference_functions_under_the_shim_reproduce_the_committed_vectors():
-    from oracle import tf_numpy_shim as S
-    for name, fn in (("actor_particle", "actor_particle"), ("actor_checkers", "actor_checkers")):
-        for tag, (w, inp, probs) in load_cases(name).items():
-            shim = S.Shim(weights=dict(w))
-            net = S.load_networks(shim)
-            stage = int(tag[-1])
-            if name == "actor_particle":
-                got = net.actor_particle(S._t(inp["obs_others"]), S._t(inp["v_obs"]), S._t(inp["v_goal"]), n_actions=5,
-                                         n_h1_self=64, n_h1_others=128, n_h2=64, stage=stage)
-            else:
-                a1 = np.eye(5, dtype=np.float32)[inp["a_prev"]]
-                got = net.actor_checkers(S._t(a1), S._t(inp["obs_self_t"]), S._t(inp["obs_self_v"]), S._t(inp["obs_others"]),
-                                         S._t(inp["goals"]), f1=6, k1=[3, 3], n_h1=256, n_h2=256, n_actions=5, stage=stage)
-            assert not shim.created, shim.created          # every variable the reference asks for is in the fixture
-            assert np.array_equal(np.asarray(got), probs), (name, tag)

@@ -1,16 +1,12 @@
-"""CPU: the host logic of the device replay buffers (ring bookkeeping, the dual buffer's split rule) and the CSV rows against the
-reference's own classes (container) and against outputs recorded from them (tests/golden/replay_csv.json).  The buffers themselves
+"""CPU: the host logic of the device replay buffers (ring bookkeeping, the dual buffer's split rule) and the CSV rows against
+outputs recorded from the reference's own classes and statements (tests/golden/replay_csv.json, oracle/gen_golden_replay_csv.py).  The buffers themselves
 live on the GPU: tests/test_gpu_replay.py runs the same fixtures, and a real rollout, through DeviceReplayBuffer /
 DeviceDualReplayBuffer on cuda:0."""
 import os
-import random
-import sys
 
 import pytest
 
 from cm3_amd.replay import CsvLog, RingIndex, dual_take
-
-REF_ALG = "/root/reference/alg"
 
 
 class HostRing(object):
@@ -34,14 +30,9 @@ def test_ring_semantics_match_reference_buffer():
     for chunk in (4, 5, 6, 3):
         ours.add(list(range(start, start + chunk)))
         start += chunk
-    if os.path.isdir(REF_ALG):
-        sys.path.insert(0, REF_ALG)
-        sys.dont_write_bytecode = True
-        import replay_buffer
-        ref = replay_buffer.Replay_Buffer(size=10)
-        for t in range(18):
-            ref.add(t)
-        assert ours.stored() == ref.memory                                       # same slots
+    # replay_buffer.Replay_Buffer(size=10) after add(t) for t in range(18), as recorded from the real class
+    ref, = [c for c in _fixture()["ring"] if c["size"] == 10 and c["chunks"] == [4, 5, 6, 3]]
+    assert ours.stored() == ref["memory"]                                    # same slots
     assert ours.ring.len == 10 and sorted(ours.stored()) == list(range(8, 18))
 
 
@@ -59,16 +50,9 @@ def test_dual_buffer_split_rule(n1, n2, size, want1, want2):
     k1, all1, k2, all2 = dual_take(n1, n2, size)
     assert (k1, k2) == (want1, want2)
     assert (not all1 or k1 == n1) and (not all2 or k2 == n2)
-    if os.path.isdir(REF_ALG):
-        import numpy as np      # noqa: F401
-        sys.path.insert(0, REF_ALG)
-        import replay_buffer_dual
-        ref = replay_buffer_dual.Replay_Buffer(size=1000)
-        ref.add(list(range(n1)), is_bad=True)
-        ref.add(list(range(n1, n1 + n2)), is_bad=False)
-        random.seed(0)
-        r = ref.sample_batch(size)
-        assert (int((r < n1).sum()), int((r >= n1).sum())) == (k1, k2)
+    # replay_buffer_dual.Replay_Buffer(size=1000): add n1 bad, add n2 good, random.seed(0), sample_batch(size) -- as recorded
+    ref, = [c for c in _fixture()["dual"] if (c["n_bad"], c["n_good"], c["size"]) == (n1, n2, size)]
+    assert (ref["taken_bad"], ref["taken_good"]) == (k1, k2)
 
 
 def test_csv_rows_have_the_reference_format(tmp_path):
