@@ -289,7 +289,8 @@ def source_id():
 
 
 def last_kernel_variant():
-    """The kernel instantiation the most recent env call of this thread launched (cm3_last_kernel_variant): a debug / test query."""
+    """The kernel instantiation the most recent env, policy or actor call of this thread launched (cm3_last_kernel_variant): a
+    debug / test query."""
     return lib().cm3_last_kernel_variant().decode()
 
 

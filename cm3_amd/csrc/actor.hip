@@ -706,6 +706,7 @@ template <int N, int PREC> __global__ void CM3_MATRIX_KERNEL k_actor_particle(co
 template <int N> static int actor_launch(const ActorParams &p, hipStream_t s) {
   const size_t rows = (size_t)p.E * N;
   const unsigned blocks = (unsigned)((rows + 63) / 64);
+  note_variant("k_actor_particle", 4, N, 4, 0, 0, 0, 0, 0, 0, p.bf16);
   if (p.bf16 == kPrecF16x3)
     hipLaunchKernelGGL((k_actor_particle<N, kPrecF16x3>), dim3(blocks), dim3(256), 0, s, p);
   else if (p.bf16 == kPrecBf16)

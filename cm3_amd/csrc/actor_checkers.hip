@@ -1506,6 +1506,7 @@ extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm
   p.packed = (const float *)wt->packed;
   const size_t rows = (size_t)p.E * p.N;
   const dim3 grid((unsigned)((rows + 63) / 64));
+  note_variant(d->precision == 2 ? "k_ck_actor_x3" : "k_ck_actor", 4, p.N, d->precision == 2 ? 8 : 4, 0, 0, 0, 0, 0, 0, d->precision);
   if (d->precision == 1) hipLaunchKernelGGL(k_ck_actor<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else if (d->precision == 2) hipLaunchKernelGGL(k_ck_actor_x3, grid, dim3(512), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(k_ck_actor<false>, grid, dim3(256), 0, (hipStream_t)stream, p);

@@ -140,10 +140,11 @@ struct KernelVariant {
   const char *kernel;  // template name
   int real_bytes;      // 4 / 8 (0: not a template parameter)
   int n, waves, fused, sp, live, tu, early, g;
+  int prec;            // actor kernels: 0 float32, 1 bf16, 2 split float16 (-1: not a template parameter)
 };
 KernelVariant &last_variant();  // thread-local (util.hip)
 static inline void note_variant(const char *kernel, int real_bytes, int n, int waves, int fused, int sp, int live, int tu,
-                                int early = 0, int g = 0) {
+                                int early = 0, int g = 0, int prec = -1) {
   KernelVariant &v = last_variant();
   v.kernel = kernel;
   v.real_bytes = real_bytes;
@@ -155,6 +156,7 @@ static inline void note_variant(const char *kernel, int real_bytes, int n, int w
   v.tu = tu;
   v.early = early;
   v.g = g;
+  v.prec = prec;
 }
 
 #define CM3_HIP_CHECK(expr)                                                                  \

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY -- NumPy restatement of the reference's Checkers actor and its action sampling.
 
-Restates (float32, like the TF1 graph):
+Restates (float32, like the TF1 graph; actor_probs(..., dtype=np.float64) is the same graph in float64):
   networks.convnet_1                 /root/reference/alg/networks.py:67-75
       tf.contrib.layers.conv2d(num_outputs=f1, kernel_size=[3,3], stride=1, padding="SAME", relu) on NHWC
       [rows, 5, 5, 3]; flattened row-major over (row, column, filter)
@@ -51,37 +51,42 @@ def init_weights(rng, n_agents, stage=2, scale=None):
     return w
 
 
-def conv_same_3x3(x, w, b):
-    """x [rows, 5, 5, 3] float32 NHWC, w [3, 3, 3, F] (kh, kw, cin, cout), stride 1, zero "SAME" padding,
-    cross-correlation (TF does not flip the kernel): out[r, c] = sum_{dr, dc} x[r + dr - 1, c + dc - 1] . w[dr, dc]."""
+def conv_same_3x3(x, w, b, dtype=np.float32):
+    """x [rows, 5, 5, 3] NHWC, w [3, 3, 3, F] (kh, kw, cin, cout), stride 1, zero "SAME" padding, cross-correlation (TF does
+    not flip the kernel): out[r, c] = sum_{dr, dc} x[r + dr - 1, c + dc - 1] . w[dr, dc].  Computed in `dtype`."""
+    f = np.dtype(dtype).type
     rows, H, W, _ = x.shape
-    xp = np.zeros((rows, H + 2, W + 2, x.shape[3]), np.float32)
+    xp = np.zeros((rows, H + 2, W + 2, x.shape[3]), f)
     xp[:, 1:H + 1, 1:W + 1] = x
-    out = np.zeros((rows, H, W, w.shape[3]), np.float32)
+    w = np.asarray(w, dtype=f)
+    out = np.zeros((rows, H, W, w.shape[3]), f)
     for dr in range(3):
         for dc in range(3):
             out += xp[:, dr:dr + H, dc:dc + W, :] @ w[dr, dc]
-    return out + b
+    return out + np.asarray(b, dtype=f)
 
 
-def actor_probs(w, a_prev, obs_self_t, obs_self_v, obs_others, goals_onehot):
+def actor_probs(w, a_prev, obs_self_t, obs_self_v, obs_others, goals_onehot, dtype=np.float32):
     """Rows = agents of a batch.  a_prev int [rows]; obs_self_t [rows,5,5,3]; obs_self_v [rows,4]; obs_others
-    [rows, 2(N-1)]; goals_onehot [rows,2].  Returns softmax probabilities [rows, 5] in float32."""
-    f32 = np.float32
+    [rows, 2(N-1)]; goals_onehot [rows,2].  Returns softmax probabilities [rows, 5] in `dtype`: float32 (the default)
+    restates the TF1 graph's own arithmetic; float64 upcasts weights and inputs and is the high-precision reference the
+    device actor is measured against (tests/test_gpu_actor_checkers_f64.py)."""
+    f = np.dtype(dtype).type
+    W = lambda k: np.asarray(w[k], dtype=f)  # noqa: E731
     rows = obs_self_t.shape[0]
-    relu = lambda v: np.maximum(v, f32(0))  # noqa: E731
-    conv = relu(conv_same_3x3(obs_self_t.astype(f32), w["conv/Conv/weights"], w["conv/Conv/biases"]))
-    lin = relu(conv.reshape(rows, -1) @ w["conv_linear/kernel"] + w["conv_linear/bias"])
-    a1 = np.zeros((rows, N_ACTIONS), f32)
+    relu = lambda v: np.maximum(v, f(0))  # noqa: E731
+    conv = relu(conv_same_3x3(obs_self_t.astype(f), w["conv/Conv/weights"], w["conv/Conv/biases"], dtype=f))
+    lin = relu(conv.reshape(rows, -1) @ W("conv_linear/kernel") + W("conv_linear/bias"))
+    a1 = np.zeros((rows, N_ACTIONS), f)
     a1[np.arange(rows), np.asarray(a_prev).reshape(-1)] = 1
-    x = np.concatenate([lin, obs_self_v.astype(f32), a1, goals_onehot.astype(f32)], axis=1)
-    h_self = relu(x @ w["branch_self/kernel"] + w["branch_self/bias"])
-    acc = h_self @ w["W_self_h2"]
+    x = np.concatenate([lin, obs_self_v.astype(f), a1, goals_onehot.astype(f)], axis=1)
+    h_self = relu(x @ W("branch_self/kernel") + W("branch_self/bias"))
+    acc = h_self @ W("W_self_h2")
     if "stage-2/branch_others/kernel" in w:
-        h_oth = relu(obs_others.astype(f32) @ w["stage-2/branch_others/kernel"] + w["stage-2/branch_others/bias"])
-        acc = acc + h_oth @ w["stage-2/W_others_h2"]
-    h2 = relu(acc + w["b"])
-    out = h2 @ w["actor_out/kernel"] + w["actor_out/bias"]
+        h_oth = relu(obs_others.astype(f) @ W("stage-2/branch_others/kernel") + W("stage-2/branch_others/bias"))
+        acc = acc + h_oth @ W("stage-2/W_others_h2")
+    h2 = relu(acc + W("b"))
+    out = h2 @ W("actor_out/kernel") + W("actor_out/bias")
     out = out - out.max(axis=1, keepdims=True)
     e = np.exp(out)
-    return (e / e.sum(axis=1, keepdims=True)).astype(f32)
+    return (e / e.sum(axis=1, keepdims=True)).astype(f)

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY -- NumPy restatement of the reference's particle actor and its action sampling.
 
-Restates (float32, like the TF1 graph):
+Restates (float32, like the TF1 graph; actor_probs(..., dtype=np.float64) is the same graph in float64):
   networks.actor_particle            /root/reference/alg/networks.py:517-538
       concat(v_obs, v_goal) -> dense 64 relu ("actor_branch_self") -> x W_branch_self_h2
       stage > 1: obs_others -> dense n_h1_others relu ("stage-2/actor_others") -> x W_others_h2
@@ -42,21 +42,24 @@ def init_weights(rng, n_agents, n_h1_others=128, stage=2, scale=None):
     return w
 
 
-def actor_probs(w, obs_others, v_obs, v_goal):
-    """Rows = agents of a batch.  Returns softmax probabilities [rows, 5] in float32."""
-    f32 = np.float32
-    x = np.concatenate([v_obs, v_goal], axis=1).astype(f32)
-    h_self = np.maximum(x @ w["actor_branch_self/kernel"] + w["actor_branch_self/bias"], f32(0))
-    acc = h_self @ w["W_branch_self_h2"]
+def actor_probs(w, obs_others, v_obs, v_goal, dtype=np.float32):
+    """Rows = agents of a batch.  Returns softmax probabilities [rows, 5] in `dtype`: float32 (the default) restates the
+    TF1 graph's own arithmetic; float64 upcasts weights and inputs and is the high-precision reference the device actor is
+    measured against (tests/test_gpu_actor_f64.py)."""
+    f = np.dtype(dtype).type
+    W = lambda k: np.asarray(w[k], dtype=f)  # noqa: E731
+    x = np.concatenate([v_obs, v_goal], axis=1).astype(f)
+    h_self = np.maximum(x @ W("actor_branch_self/kernel") + W("actor_branch_self/bias"), f(0))
+    acc = h_self @ W("W_branch_self_h2")
     if "stage-2/actor_others/kernel" in w:
-        h_oth = np.maximum(obs_others.astype(f32) @ w["stage-2/actor_others/kernel"]
-                           + w["stage-2/actor_others/bias"], f32(0))
-        acc = acc + h_oth @ w["stage-2/W_others_h2"]
-    h2 = np.maximum(acc + w["b"], f32(0))
-    out = h2 @ w["actor_out/kernel"] + w["actor_out/bias"]
+        h_oth = np.maximum(obs_others.astype(f) @ W("stage-2/actor_others/kernel")
+                           + W("stage-2/actor_others/bias"), f(0))
+        acc = acc + h_oth @ W("stage-2/W_others_h2")
+    h2 = np.maximum(acc + W("b"), f(0))
+    out = h2 @ W("actor_out/kernel") + W("actor_out/bias")
     out = out - out.max(axis=1, keepdims=True)
     e = np.exp(out)
-    return (e / e.sum(axis=1, keepdims=True)).astype(f32)
+    return (e / e.sum(axis=1, keepdims=True)).astype(f)
 
 
 def mixed_probs(probs, epsilon):

@@ -252,13 +252,15 @@ def _same_rollout(a, ea, b, eb):
     assert torch.equal(ea.episode, eb.episode) and torch.equal(ea.global_state, eb.global_state)
 
 
-@pytest.mark.parametrize("precision", ["f32", "f16x3"])
-@pytest.mark.parametrize("N,cfg", [(4, "particle_stage2_cross.json"), (8, "particle_merge8.json"), (2, "particle_stage2_merge.json")])
+@pytest.mark.parametrize("precision", ["f32", "f16x3", "bf16"])
+@pytest.mark.parametrize("N,cfg", [(4, "particle_stage2_cross.json"), (8, "particle_merge8.json"), (2, "particle_stage2_merge.json"),
+                                   (1, "particle_stage1.json")])
 def test_every_row_tile_build_of_the_policy_rollout_is_the_same_rollout(N, cfg, precision, monkeypatch):
     """k_policy_rollout<N, prec, RT>: 16 / 32 / 64 agent rows per workgroup are three builds of the kernel (policy.hip picks one by
     batch size; the small test batches elsewhere only ever reach RT = 1).  cm3_policy_force_row_tiles forces each in turn on ONE
     batch: all three must reproduce the alternating actor / step launches bit for bit, and cm3_last_kernel_variant() must name the
-    build that ran."""
+    build that ran.  With N in {1, 2, 4, 8} and the three precisions these are all 36 builds; the actor launches they are compared
+    with are held to the float64 oracle at the same N and precision in tests/test_gpu_actor_f64.py."""
     from cm3_amd import _lib
     E, T = 600, 16            # ragged: 600 x N rows is no multiple of 64
     _lib.check(_lib.lib().cm3_policy_force_row_tiles(0))
@@ -346,7 +348,9 @@ def test_device_actor_matches_vectors_from_the_reference_function_body(tag, N, s
 
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
 @pytest.mark.parametrize("w2_scale,w1_scale", [(1e-3, 60.0), (3e-5, 300.0), (0.05, 1.0)])
-@pytest.mark.parametrize("N,cfg", [(4, "particle_stage2_antipodal.json"), (8, "particle_merge8.json")])   # (N = 8: actor_others in split float16 too)
+@pytest.mark.parametrize("N,cfg", [(4, "particle_stage2_antipodal.json"), (8, "particle_merge8.json"),   # (N = 5..9: actor_others in split
+                                   (5, "particle_merge8.json"), (6, "particle_merge8.json"),             #  float16 too, L = 16 .. 32 inputs)
+                                   (7, "particle_merge8.json"), (9, "particle_ring10.json")])
 def test_actor_split_precision_with_small_weights_and_large_activations(precision, w2_scale, w1_scale, N, cfg):
     """the float16 split x = hi + lo loses its residual to float16's subnormals once |x| < 0.125 unless the residual
     is kept scaled (csrc/actor.hip kLoScale).  Second-layer weights of 1e-3 / 3e-5 against first-layer activations of 1e2 / 1e3

@@ -324,7 +324,7 @@ def test_device_actor_matches_vectors_from_the_reference_function_body(tag, N, s
 
 @pytest.mark.parametrize("stage", [1, 2])
 def test_split_float16_layers_stay_in_the_float32_error_class(stage):
-    """precision="f16x3" against the float64-accumulated oracle next to precision="f32": worst error of the same order (the
+    """precision="f16x3" against the float32 oracle next to precision="f32": worst error of the same order (the
     parity bound 2e-5 holds for both), a different kernel, and the same sampled actions off CDF boundaries."""
     from cm3_amd.actor import CheckersActor
     rng = np.random.default_rng(33)
