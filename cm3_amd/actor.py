@@ -12,6 +12,10 @@
 
 Weights stay float32 [in][out] as TensorFlow shapes them, so a checkpoint exported with
 ``{v.name: sess.run(v)}`` loads unchanged (names below; a "Policy_main/" prefix and ":0" suffix are ignored).
+
+The actor reads float32 and float64 env buffers (VecParticleEnv(dtype=...)).  On a float64 env -- the reference-precision mode --
+it rounds the observation to float32 as it stages its inputs, which is what the reference's tf.float32 placeholders do with its
+float64 observations (alg_credit.py:96-111): the network itself is float32 either way.
 """
 import ctypes
 
@@ -30,6 +34,15 @@ def _epsilon_args(epsilon):
             raise Cm3Error("a device epsilon must be one float32 element on the GPU")
         return 0.0, epsilon.data_ptr()
     return float(epsilon), 0
+
+def _actor_entry(lib, dtype):
+    """cm3_actor_particle_f32 / _f64 by the real of the env buffers the launch reads."""
+    if dtype == torch.float32:
+        return lib.cm3_actor_particle_f32
+    if dtype == torch.float64:
+        return lib.cm3_actor_particle_f64
+    raise Cm3Error("the device actor reads float32 or float64 env buffers, not %s" % (dtype,))
+
 
 H1_SELF, H1_OTHERS, H2, N_ACTIONS = 64, 128, 64, 5
 PRECISIONS = {"f32": 0, "bf16": 1, "f16x3": 2}       # cm3_actor_particle_desc.precision
@@ -106,28 +119,28 @@ class ParticleActor(object):
         return d
 
     def enqueue(self, n_envs, obs_others, state, goals, meta, episode, actions, epsilon, probs=None, stream=None,
-                env_id_base=None):
-        """Raw launch on device pointers/tensors (float32 env buffers)."""
+                env_id_base=None, dtype=torch.float32):
+        """Raw launch on device pointers/tensors; dtype: the real of obs_others / state / goals (torch.float32 or torch.float64 --
+        cm3_actor_particle_f32 / _f64).  actions int32, probs float32 either way."""
+        fn = _actor_entry(self._lib, dtype)
         b = _lib.ActorParticleBufs()
         b.obs_others, b.state, b.goals = _lib.ptr(obs_others), _lib.ptr(state), _lib.ptr(goals)
         b.meta, b.episode, b.actions, b.probs = _lib.ptr(meta), _lib.ptr(episode), _lib.ptr(actions), _lib.ptr(probs)
         epsilon, b.epsilon_dev = _epsilon_args(epsilon)
         d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base)
         s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_actor_particle_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
+        _lib.check(fn(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
 
     def act(self, env, epsilon, return_probs=False):
         """Actions [E, N] int32 for the env's CURRENT observation (alg.run_actor); optionally the mixed
-        probabilities [E, N, 5]."""
-        if env.dtype != torch.float32:
-            raise Cm3Error("the device actor reads float32 env buffers")
+        probabilities [E, N, 5] (float32).  float32 and float64 envs alike."""
         if env.n != self.n:
             raise Cm3Error("actor built for %d agents, env has %d" % (self.n, env.n))
         cur = env._cur
         actions = torch.empty(env.E, env.n, dtype=torch.int32, device=self.device)
         probs = torch.empty(env.E, env.n, N_ACTIONS, dtype=torch.float32, device=self.device) if return_probs else None
         self.enqueue(env.E, env._obs_others[cur], env._state[cur], env._goals, env._meta, env._episode, actions,
-                     epsilon, probs, env_id_base=env.env_id_base)
+                     epsilon, probs, env_id_base=env.env_id_base, dtype=env.dtype)
         return (actions, probs) if return_probs else actions
 
 

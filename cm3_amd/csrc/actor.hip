@@ -28,7 +28,7 @@ struct ActorParams {
   int bf16;  // precision of the second layer: kPrecF32 / kPrecBf16 / kPrecF16x3 (see ActorGeom)
   int64_t env_id_base;
   uint64_t seed;
-  const float *obs_others, *state, *goals;
+  const void *obs_others, *state, *goals;  // env buffers of the kernel's input real (float32 or float64)
   const int32_t *meta, *episode;
   int32_t *actions;
   float *probs;
@@ -623,8 +623,13 @@ __device__ __forceinline__ int bcast_row0(int v) {
   return (int)x;
 }
 
-template <int N, int PREC> __global__ void CM3_MATRIX_KERNEL k_actor_particle(const ActorParams p) {
+// RIN = real of the env buffers the kernel reads: float, or double for a float64 env -- rounded to float32 (round to nearest even)
+// as the input tile is staged, which is what the reference's tf.float32 placeholders do to its float64 observations
+// (alg_credit.py:96-111).  Everything after the staging is the same code for both.
+template <int N, int PREC, typename RIN> __global__ void CM3_MATRIX_KERNEL k_actor_particle(const ActorParams p) {
   using G = ActorGeom<N, PREC>;
+  using V4 = typename Vec<RIN>::v4;
+  using V2 = typename Vec<RIN>::v2;
   constexpr int L = G::L;
   CM3_ACTOR_LDS(N, PREC, lds);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -652,16 +657,16 @@ template <int N, int PREC> __global__ void CM3_MATRIX_KERNEL k_actor_particle(co
   CM3_STAMP(8, false);
   // the 64 input rows [v_obs(4) | v_goal(2) | obs_others(L)], one row per lane: wave 0 stages them into LDS; the other waves
   // request the same (coalesced, cached) lines rather than branch around the loads
-  float4 in_s, in_o[L / 4];
-  float2 in_g;
+  V4 in_s, in_o[L / 4];
+  V2 in_g;
   {
     const size_t r = row_base + lane;
     const size_t rc = r < rows ? r : rows - 1;
     const size_t e = rc / N;
     const int i = (int)(rc - e * N);
-    in_s = reinterpret_cast<const float4 *>(p.state)[(size_t)i * p.E + e];
-    in_g = reinterpret_cast<const float2 *>(p.goals)[(size_t)i * p.E + e];
-    const float4 *o4 = reinterpret_cast<const float4 *>(p.obs_others + rc * L);
+    in_s = reinterpret_cast<const V4 *>(p.state)[(size_t)i * p.E + e];
+    in_g = reinterpret_cast<const V2 *>(p.goals)[(size_t)i * p.E + e];
+    const V4 *o4 = reinterpret_cast<const V4 *>(reinterpret_cast<const RIN *>(p.obs_others) + rc * L);
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) in_o[k] = o4[k];
   }
@@ -672,12 +677,12 @@ template <int N, int PREC> __global__ void CM3_MATRIX_KERNEL k_actor_particle(co
   // ... everything is on its way: now the LDS side
   actor_tables_store<N, PREC, 4>(lds, tid, tab);
   if (w == 0) {
-    lds.xs[lane][0] = in_s.x; lds.xs[lane][1] = in_s.y; lds.xs[lane][2] = in_s.z; lds.xs[lane][3] = in_s.w;
-    lds.xs[lane][4] = in_g.x; lds.xs[lane][5] = in_g.y;
+    lds.xs[lane][0] = (float)in_s.x; lds.xs[lane][1] = (float)in_s.y; lds.xs[lane][2] = (float)in_s.z; lds.xs[lane][3] = (float)in_s.w;
+    lds.xs[lane][4] = (float)in_g.x; lds.xs[lane][5] = (float)in_g.y;
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) {
-      lds.xs[lane][6 + 4 * k + 0] = in_o[k].x; lds.xs[lane][6 + 4 * k + 1] = in_o[k].y;
-      lds.xs[lane][6 + 4 * k + 2] = in_o[k].z; lds.xs[lane][6 + 4 * k + 3] = in_o[k].w;
+      lds.xs[lane][6 + 4 * k + 0] = (float)in_o[k].x; lds.xs[lane][6 + 4 * k + 1] = (float)in_o[k].y;
+      lds.xs[lane][6 + 4 * k + 2] = (float)in_o[k].z; lds.xs[lane][6 + 4 * k + 3] = (float)in_o[k].w;
     }
   }
   CM3_STAMP(1, true);
@@ -703,16 +708,16 @@ template <int N, int PREC> __global__ void CM3_MATRIX_KERNEL k_actor_particle(co
   CM3_STAMP(7, true);
 }
 
-template <int N> static int actor_launch(const ActorParams &p, hipStream_t s) {
+template <int N, typename RIN> static int actor_launch(const ActorParams &p, hipStream_t s) {
   const size_t rows = (size_t)p.E * N;
   const unsigned blocks = (unsigned)((rows + 63) / 64);
-  note_variant("k_actor_particle", 4, N, 4, 0, 0, 0, 0, 0, 0, p.bf16);
+  note_variant("k_actor_particle", (int)sizeof(RIN), N, 4, 0, 0, 0, 0, 0, 0, p.bf16);
   if (p.bf16 == kPrecF16x3)
-    hipLaunchKernelGGL((k_actor_particle<N, kPrecF16x3>), dim3(blocks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((k_actor_particle<N, kPrecF16x3, RIN>), dim3(blocks), dim3(256), 0, s, p);
   else if (p.bf16 == kPrecBf16)
-    hipLaunchKernelGGL((k_actor_particle<N, kPrecBf16>), dim3(blocks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((k_actor_particle<N, kPrecBf16, RIN>), dim3(blocks), dim3(256), 0, s, p);
   else
-    hipLaunchKernelGGL((k_actor_particle<N, kPrecF32>), dim3(blocks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((k_actor_particle<N, kPrecF32, RIN>), dim3(blocks), dim3(256), 0, s, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
@@ -786,9 +791,10 @@ extern "C" int cm3_actor_particle_pack(const cm3_actor_particle_desc *d, const c
   return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
 
-extern "C" int cm3_actor_particle_f32(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
-                                      const cm3_actor_particle_bufs *b, void *stream) {
-  using namespace cm3;
+namespace cm3 {
+template <typename RIN>
+static int actor_particle_call(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt, const cm3_actor_particle_bufs *b,
+                               void *stream) {
   CM3_REQUIRE(d && wt && b, "null desc/weights/bufs");
   CM3_REQUIRE(d->n_envs > 0, "n_envs must be positive");
   CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= CM3_MAX_AGENTS, "n_agents must be in 1..%d", CM3_MAX_AGENTS);
@@ -808,9 +814,9 @@ extern "C" int cm3_actor_particle_f32(const cm3_actor_particle_desc *d, const cm
   p.bf16 = d->precision;
   p.env_id_base = d->env_id_base;
   p.seed = d->seed;
-  p.obs_others = (const float *)b->obs_others;
-  p.state = (const float *)b->state;
-  p.goals = (const float *)b->goals;
+  p.obs_others = b->obs_others;
+  p.state = b->state;
+  p.goals = b->goals;
   p.meta = b->meta;
   p.episode = b->episode;
   p.actions = b->actions;
@@ -818,17 +824,29 @@ extern "C" int cm3_actor_particle_f32(const cm3_actor_particle_desc *d, const cm
   p.packed = (const float *)wt->packed;
   hipStream_t s = (hipStream_t)stream;
   switch (d->n_agents) {
-    case 1: return actor_launch<1>(p, s);
-    case 2: return actor_launch<2>(p, s);
-    case 3: return actor_launch<3>(p, s);
-    case 4: return actor_launch<4>(p, s);
-    case 5: return actor_launch<5>(p, s);
-    case 6: return actor_launch<6>(p, s);
-    case 7: return actor_launch<7>(p, s);
-    case 8: return actor_launch<8>(p, s);
-    case 9: return actor_launch<9>(p, s);
-    case 10: return actor_launch<10>(p, s);
+    case 1: return actor_launch<1, RIN>(p, s);
+    case 2: return actor_launch<2, RIN>(p, s);
+    case 3: return actor_launch<3, RIN>(p, s);
+    case 4: return actor_launch<4, RIN>(p, s);
+    case 5: return actor_launch<5, RIN>(p, s);
+    case 6: return actor_launch<6, RIN>(p, s);
+    case 7: return actor_launch<7, RIN>(p, s);
+    case 8: return actor_launch<8, RIN>(p, s);
+    case 9: return actor_launch<9, RIN>(p, s);
+    case 10: return actor_launch<10, RIN>(p, s);
   }
   return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+}
+}  // namespace cm3
+
+extern "C" int cm3_actor_particle_f32(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
+                                      const cm3_actor_particle_bufs *b, void *stream) {
+  return cm3::actor_particle_call<float>(d, wt, b, stream);
+}
+
+// float64 env buffers (VecParticleEnv(dtype=torch.float64)): the same network, its inputs rounded to float32 as they are staged
+extern "C" int cm3_actor_particle_f64(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
+                                      const cm3_actor_particle_bufs *b, void *stream) {
+  return cm3::actor_particle_call<double>(d, wt, b, stream);
 }
 #endif  // CM3_NO_ENTRY_POINTS

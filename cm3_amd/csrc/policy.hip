@@ -18,8 +18,19 @@
 //     written both to the trajectory (global) and back into the LDS tile that feeds the next tick's phase A.
 // Arithmetic per agent is the reference's operation order, so trajectories are bit-identical to the unfused path
 // (tests/test_gpu_actor.py::test_fused_policy_rollout_equals_launch_per_tick).
+//
+// float64 envs (VecParticleEnv(dtype=torch.float64), the reference-precision mode): build.sh compiles this file twice, with
+// -DCM3_PARTICLE_F32 and -DCM3_PARTICLE_F64, and PolicyReal below is the real of the env side -- state, contact chain,
+// integration, reward / collision / reached, re-initialisation and every trajectory store.  The network is float32 in both (the
+// reference feeds its float64 observations into tf.float32 placeholders, alg_credit.py:96-111): the next tick's observation is
+// rounded into the float32 input tile on the way in, exactly as k_actor_particle<., ., double> stages it from the env's buffers.
+// What the physics reads back is never that rounded tile: in float64 the rows' pre-step state lives in the double exchange slots
+// `ns` and their goals in `gd` (see the kernel), so an f64 episode is bit-identical to alternating cm3_actor_particle_f64 and
+// cm3_particle_step_f64 launches.
 #define CM3_NO_ENTRY_POINTS 1
+#if !defined(CM3_PARTICLE_F32) && !defined(CM3_PARTICLE_F64)
 #define CM3_PARTICLE_F32 1
+#endif
 #include "particle.hip"
 #include "actor.hip"
 #include <stdlib.h>
@@ -27,9 +38,15 @@
 
 namespace cm3 {
 
+#ifdef CM3_PARTICLE_F64
+using PolicyReal = double;
+#else
+using PolicyReal = float;
+#endif
+
 struct PolicyParams {
   ParticleParams p;  // trajectory pointers/strides of the fused rollout (state_in = slot 0, *_out = slot 1 ...)
-  const float *obs_in;  // obs_others slot 0
+  const void *obs_in;   // obs_others slot 0 (PolicyReal)
   const float *packed;
   float *probs;         // optional [T][E][N][5]
   size_t st_probs;
@@ -42,14 +59,19 @@ struct PolicyParams {
 // (round 4: the per-env chain actor -> physics -> observation is serial, and at one wave per SIMD the tick was latency-bound:
 // ~1 us of matrix time inside 5.0 us).  Waves w >= RT take part in the layers (every wave owns 16 columns of all row tiles) and
 // in the barriers, but have no rows of their own in the head and the physics.
-template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_rollout(const PolicyParams q) {
+// R = the env's real (PolicyReal of the translation unit).  R = double: the physics reads its own and the other agents' pre-step
+// state from `ns` (double, written at the end of every tick) and the goals from `gd`, never from the float32 input tile; the
+// wave's post-step exchange goes through the same `ns` slots.  +3 KB of LDS at 64 rows, the per-env reductions by shuffles.
+template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL k_policy_rollout(const PolicyParams q) {
   using G = ActorGeom<N, BF16, RT>;
-  using V4 = float4;
-  using V2 = float2;
+  using V4 = typename Vec<R>::v4;
+  using V2 = typename Vec<R>::v2;
+  constexpr bool F64 = sizeof(R) == 8;
   constexpr int L = G::L, NO = N > 1 ? N - 1 : 1;
   const ParticleParams &p = q.p;
   CM3_ACTOR_LDS_RT(N, BF16, RT, lds);
-  __shared__ __attribute__((aligned(16))) float4 ns[16 * RT];  // post-step (vx, vy, px, py) of every row, exchanged inside a wave
+  __shared__ __attribute__((aligned(16))) V4 ns[16 * RT];  // post-step (vx, vy, px, py) of every row, exchanged inside a wave
+  __shared__ __attribute__((aligned(16))) V2 gd[F64 ? 16 * RT : 1];   // float64: the rows' goals (float32 reads them from the tile)
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const size_t E = (size_t)p.E;
@@ -94,7 +116,7 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
   {
     s0 = reinterpret_cast<const V4 *>(p.state_in)[(size_t)i * E + e];
     g0 = reinterpret_cast<const V2 *>(p.goals_in)[(size_t)i * E + e];
-    const V4 *o4 = reinterpret_cast<const V4 *>(q.obs_in + r * L);
+    const V4 *o4 = reinterpret_cast<const V4 *>(reinterpret_cast<const R *>(q.obs_in) + r * L);
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) o0[k] = o4[k];
   }
@@ -103,26 +125,37 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
   const uint32_t episode_in = episode;
   actor_tables_store<N, BF16, RT>(lds, tid, tab);
   if (part0) {
-    lds.xs[rl][0] = s0.x; lds.xs[rl][1] = s0.y; lds.xs[rl][2] = s0.z; lds.xs[rl][3] = s0.w;
-    lds.xs[rl][4] = g0.x; lds.xs[rl][5] = g0.y;
+    lds.xs[rl][0] = (float)s0.x; lds.xs[rl][1] = (float)s0.y; lds.xs[rl][2] = (float)s0.z; lds.xs[rl][3] = (float)s0.w;
+    lds.xs[rl][4] = (float)g0.x; lds.xs[rl][5] = (float)g0.y;
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) {
-      lds.xs[rl][6 + 4 * k + 0] = o0[k].x; lds.xs[rl][6 + 4 * k + 1] = o0[k].y;
-      lds.xs[rl][6 + 4 * k + 2] = o0[k].z; lds.xs[rl][6 + 4 * k + 3] = o0[k].w;
+      lds.xs[rl][6 + 4 * k + 0] = (float)o0[k].x; lds.xs[rl][6 + 4 * k + 1] = (float)o0[k].y;
+      lds.xs[rl][6 + 4 * k + 2] = (float)o0[k].z; lds.xs[rl][6 + 4 * k + 3] = (float)o0[k].w;
+    }
+    if constexpr (F64) {
+      ns[rl] = s0;
+      gd[rl] = g0;
     }
   }
   __syncthreads();
   CM3_STAMP(14, true);    // tables, weights and the input tile are in
   ActorHeadB hb;
-  actor_head_load(lds.wout, lane, hb);      // output-layer operands of this lane, once per launch
-  ActorFirstB<N> f1;                        // ... and its first-layer operands (round 4: they were re-read from LDS every tick)
-  actor_first_b<N, float>(&lds.ws_self[0][0], &lds.ws_oth[0][0], w, lane, q.stage > 1, f1);
+  ActorFirstB<N> f1;
+  if constexpr (!F64) {
+    actor_head_load(lds.wout, lane, hb);      // output-layer operands of this lane, once per launch
+    actor_first_b<N, float>(&lds.ws_self[0][0], &lds.ws_oth[0][0], w, lane, q.stage > 1, f1);  // ... and its first-layer operands
+                                              // (round 4: they were re-read from LDS every tick)
+  }
 
-  const float kDt = 0.1f, kKeep = 1.0f - 0.25f;
+  const R kDt = R(0.1), kKeep = R(1) - R(0.25);
 #pragma unroll 1
   for (int t = 0; t < p.n_ticks; ++t) {
     // ---- policy: forward pass, probabilities and the sampled action of row rl (alg_credit.py:113-122) -----------------
     CM3_STAMP(0, false);
+    // float64: the operands of the first layer and the head are read from the LDS tables every tick (the float32 build holds them
+    // for the whole launch): their 40 (N = 4) to 56 (N = 8) registers are what the double physics and the re-initialisation's
+    // double transcendentals need -- held, every f64 build spilled (20 - 340 bytes of scratch per lane)
+    if constexpr (F64) actor_first_b<N, float>(&lds.ws_self[0][0], &lds.ws_oth[0][0], w, lane, q.stage > 1, f1);
     actor_mlp<N, BF16, RT>(lds, b, f1, w, lane, q.stage > 1);
 #ifdef CM3_PROBE_P_NO_ROWS   // (probe builds only: the matrix phases and the barriers alone)
     if (false) {
@@ -136,6 +169,7 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
     __builtin_amdgcn_s_setprio(2);
     float pr[kA];
     const float u = actor_uniform_from(ublock, episode, steps);
+    if constexpr (F64) actor_head_load(lds.wout, lane, hb);
 #ifndef CM3_PROBE_P_NO_HEAD   // (probe builds only, tools/r6/policy_whatif.sh)
     actor_head_probs(lds.h2s, hb, wr, lane, q.eps, pr);
 #else
@@ -148,30 +182,38 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
 
     // ---- physics of agent i (environment.py:81-123), lanes of part 0 ------------------------------------------------------
     V4 si;
-    si.x = lds.xs[rl][0]; si.y = lds.xs[rl][1]; si.z = lds.xs[rl][2]; si.w = lds.xs[rl][3];
     V2 gl;
-    gl.x = lds.xs[rl][4]; gl.y = lds.xs[rl][5];
-    float ux = 0.0f, uy = 0.0f;
-    if (act == 1) ux = -1.0f;
-    if (act == 2) ux = +1.0f;
-    if (act == 3) uy = -1.0f;
-    if (act == 4) uy = +1.0f;
-    float Fx = ux * 5.0f + 0.0f, Fy = uy * 5.0f + 0.0f;
+    if constexpr (F64) {
+      si = ns[rl];
+      gl = gd[rl];
+    } else {
+      si.x = lds.xs[rl][0]; si.y = lds.xs[rl][1]; si.z = lds.xs[rl][2]; si.w = lds.xs[rl][3];
+      gl.x = lds.xs[rl][4]; gl.y = lds.xs[rl][5];
+    }
+    R ux = R(0), uy = R(0);
+    if (act == 1) ux = R(-1);
+    if (act == 2) ux = R(+1);
+    if (act == 3) uy = R(-1);
+    if (act == 4) uy = R(+1);
+    R Fx = ux * R(5.0) + R(0.0), Fy = uy * R(5.0) + R(0.0);
 #ifndef CM3_PROBE_P_NO_PHYS
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) {  // the reference's accumulation order: other agents ascending (core.py:145-155)
       const int j = k < i ? k : k + 1;
       const int rj = rl - i + j;
-      float f_x, f_y;
-      contact_force<float>(si.z - lds.xs[rj][2], si.w - lds.xs[rj][3], f_x, f_y);
+      R f_x, f_y;
+      if constexpr (F64)
+        contact_force<R>(si.z - ns[rj].z, si.w - ns[rj].w, f_x, f_y);
+      else
+        contact_force<R>(si.z - lds.xs[rj][2], si.w - lds.xs[rj][3], f_x, f_y);
       Fx = f_x + Fx;
       Fy = f_y + Fy;
     }
 #endif
     si.x = si.x * kKeep;
     si.y = si.y * kKeep;
-    si.x = si.x + (Fx / 1.0f) * kDt;
-    si.y = si.y + (Fy / 1.0f) * kDt;
+    si.x = si.x + (Fx / R(1.0)) * kDt;
+    si.y = si.y + (Fy / R(1.0)) * kDt;
     si.z = si.z + si.x * kDt;
     si.w = si.w + si.y * kDt;
     steps += 1;
@@ -179,37 +221,51 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
     // only: lanes 16..63 repeat their physics and used to store their copy into the same slot -- the same value by the code,
     // but this way nothing a copy computes is ever stored.  Round 5 found what made copies differ: a packed multiply of the contact
     // chain returning a wrong low half in lanes 48..63 under a co-resident matrix wave, profiles/r05_policy_fault.txt)
+    if constexpr (F64) wave_lds_sync();   // float64: every lane has read the pre-step rows from `ns` before they are overwritten
     if (part0) ns[rl] = si;
     wave_lds_sync();  // the other agents of this env live in the same wave
     V4 oth[NO];
+    if constexpr (!F64) {
 #pragma unroll
-    for (int k = 0; k < NO; ++k) {
-      const int j = (N > 1) ? (k < i ? k : k + 1) : 0;
-      oth[k] = ns[rl - i + j];
+      for (int k = 0; k < NO; ++k) {
+        const int j = (N > 1) ? (k < i ? k : k + 1) : 0;
+        oth[k] = ns[rl - i + j];
+      }
     }
+    // the post-step state of the k-th other agent: float64 reads it from `ns` where it is used (seven double4 held from here to the
+    // observation stores are 56 registers at N = 8); `ns` holds the reset states once a re-initialisation has written them
+    auto other = [&](int k) -> V4 {
+      if constexpr (F64) {
+        const int j = (N > 1) ? (k < i ? k : k + 1) : 0;
+        return ns[rl - i + j];
+      } else {
+        return oth[k];
+      }
+    };
 
     CM3_STAMP(8, false);
     // ---- reward / reached / collisions (multi-goal_spread.py:114-143) ----------------------------------------------------------
-    float rew;
+    R rew;
     bool reached;
     {
-      const float dx = si.z - gl.x, dy = si.w - gl.y;
-      const float d2 = dx * dx + dy * dy;
-      rew = 0.0f - sqrtf(d2);
-      reached = d2 < Thresh<float>::kReach2;  // rew >= -0.05f (thresholds.h)
+      const R dx = si.z - gl.x, dy = si.w - gl.y;
+      const R d2 = dx * dx + dy * dy;
+      rew = R(0) - Math<R>::sqrt(d2);
+      reached = d2 < Thresh<R>::kReach2;  // rew >= -0.05 (thresholds.h)
     }
     int hits = 0;
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) {
-      if (is_collision<float>(oth[k].z - si.z, oth[k].w - si.w)) {  // is_collision(a = j, agent = i)
-        rew = rew - 1.0f;
+      const V4 ok = other(k);
+      if (is_collision<R>(ok.z - si.z, ok.w - si.w)) {  // is_collision(a = j, agent = i)
+        rew = rew - R(1);
         hits += 1;
       }
     }
-    float rews[N];
+    R rews[N];
     int hit_sum = 0;
     bool all_reached = true;
-    if constexpr (N == 4) {  // the env's four agents are one DPP quad: broadcasts and sums without the LDS crossbar
+    if constexpr (N == 4 && !F64) {  // the env's four agents are one DPP quad: broadcasts and sums without the LDS crossbar
       rews[0] = dpp_f32<0x00>(rew);
       rews[1] = dpp_f32<0x55>(rew);
       rews[2] = dpp_f32<0xAA>(rew);
@@ -220,7 +276,7 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
       r4 &= dpp_i32<kDppXor1>(r4);
       r4 &= dpp_i32<kDppXor2>(r4);
       all_reached = r4 != 0;
-    } else if constexpr (N == 8) {  // an env is half a DPP row: sums over its 8 lanes by xor 1, xor 2, half mirror (lane i <-> 7 - i)
+    } else if constexpr (N == 8 && !F64) {  // an env is half a DPP row: sums over its 8 lanes by xor 1, xor 2, half mirror (lane i <-> 7 - i)
       hit_sum = hits + dpp_i32<kDppXor1>(hits);
       hit_sum += dpp_i32<kDppXor2>(hit_sum);
       hit_sum += dpp_i32<kDppHalfMirror>(hit_sum);
@@ -238,19 +294,19 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
       }
     }
     collisions += hit_sum;
-    float reward;
-    if constexpr (N == 8) {
+    R reward;
+    if constexpr (N == 8 && !F64) {
       // NumPy's pairwise tree for 8 values, ((v0+v1)+(v2+v3)) + ((v4+v5)+(v6+v7)) (sum_agents), by the same three DPP steps: every
       // partial sum meets its partner with the operands possibly swapped, and float addition is commutative bit for bit
       float tsum = rew + dpp_f32<kDppXor1>(rew);
       tsum = tsum + dpp_f32<kDppXor2>(tsum);
       reward = tsum + dpp_f32<kDppHalfMirror>(tsum);
     } else {
-      reward = sum_agents<float, N>(rews);
+      reward = sum_agents<R, N>(rews);
     }
     const bool done = (steps == p.max_steps) || all_reached;
     if (head_lane) {
-      reinterpret_cast<float *>(tick_ptr(p.reward, p.st_reward, t))[e] = reward;
+      reinterpret_cast<R *>(tick_ptr(p.reward, p.st_reward, t))[e] = reward;
       tick_ptr(p.done, p.st_done, t)[e] = done ? 1 : 0;
       if (p.collisions_tick) tick_ptr(p.collisions_tick, p.st_coll, t)[e] = collisions;
     }
@@ -272,21 +328,21 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
         for (int k = 0; k < NO; ++k) {
           const int j = (N > 1) ? (k < i ? k : k + 1) : 0;
           (void)j;
-          o[k] = sub4<float, V4>(oth[k], si);
+          o[k] = sub4<R, V4>(other(k), si);
         }
       }
       wave_lds_sync();  // every lane of the env has read the terminal states before they are overwritten
       episode += 1;
       const bool rnd = episode_is_random(p, genv, episode);
       static_assert(offsetof(PolicyParams, p) == 0, "preset_table(0): the ParticleParams lead the kernel's only argument");
-      init_agent<float, N, true>(p, genv, episode, rnd, i, si, gl, preset_table(0));
+      init_agent<R, N, true>(p, genv, episode, rnd, i, si, gl, preset_table(0));
       steps = 0;
       collisions = 0;
       was_reset = true;
       if (part0) ns[rl] = si;
       wave_lds_sync();
     }
-    if (auto_reset && __any(done)) {  // fresh episodes in this wave: the observation is that of the reset states
+    if (!F64 && auto_reset && __any(done)) {  // fresh episodes in this wave: the observation is that of the reset states
 #pragma unroll
       for (int k = 0; k < NO; ++k) {
         const int j = (N > 1) ? (k < i ? k : k + 1) : 0;
@@ -306,7 +362,7 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
 #pragma unroll
           for (int a = 0; a < kA; ++a) pt[a] = pr[a];
         }
-        reinterpret_cast<float *>(tick_ptr(p.reward_n, p.st_reward_n, t))[r] = rew;
+        reinterpret_cast<R *>(tick_ptr(p.reward_n, p.st_reward_n, t))[r] = rew;
         reinterpret_cast<V4 *>(tick_ptr(p.state_out, p.st_state, t))[(size_t)i * E + e] = si;
         if (p.goals_out != p.goals_in || was_reset)
           reinterpret_cast<V2 *>(tick_ptr(p.goals_out, p.st_goals, t))[(size_t)i * E + e] = gl;
@@ -317,15 +373,16 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
       for (int k = 0; k < NO; ++k) {  // observation (multi-goal_spread.py:145-154)
         const int j = (N > 1) ? (k < i ? k : k + 1) : 0;
         (void)j;
-        const V4 d = sub4<float, V4>(oth[k], si);
+        const V4 d = sub4<R, V4>(other(k), si);
 #ifndef CM3_PROBE_P_NO_STORES
         if (row_ok) o[k] = d;
 #endif
-        lds.xs[rl][6 + 4 * k + 0] = d.x; lds.xs[rl][6 + 4 * k + 1] = d.y;
-        lds.xs[rl][6 + 4 * k + 2] = d.z; lds.xs[rl][6 + 4 * k + 3] = d.w;
+        lds.xs[rl][6 + 4 * k + 0] = (float)d.x; lds.xs[rl][6 + 4 * k + 1] = (float)d.y;
+        lds.xs[rl][6 + 4 * k + 2] = (float)d.z; lds.xs[rl][6 + 4 * k + 3] = (float)d.w;
       }
-      lds.xs[rl][0] = si.x; lds.xs[rl][1] = si.y; lds.xs[rl][2] = si.z; lds.xs[rl][3] = si.w;
-      lds.xs[rl][4] = gl.x; lds.xs[rl][5] = gl.y;
+      lds.xs[rl][0] = (float)si.x; lds.xs[rl][1] = (float)si.y; lds.xs[rl][2] = (float)si.z; lds.xs[rl][3] = (float)si.w;
+      lds.xs[rl][4] = (float)gl.x; lds.xs[rl][5] = (float)gl.y;
+      if constexpr (F64) gd[rl] = gl;   // (ns[rl] already holds si: the post-step store above, or the reset's)
     }
     CM3_STAMP(11, false);
     __builtin_amdgcn_s_setprio(0);
@@ -345,15 +402,16 @@ template <int N, int BF16, int RT> __global__ void CM3_MATRIX_KERNEL k_policy_ro
 }
 
 template <int N, int RT> static int policy_launch_rt(const PolicyParams &q, int prec, hipStream_t s) {
+  using R = PolicyReal;
   const size_t rows = (size_t)q.p.E * N;
   const unsigned blocks = (unsigned)((rows + 16 * RT - 1) / (16 * RT));
-  note_variant("k_policy_rollout", 4, N, 4, q.p.n_ticks > 1, prec, 0, 0, 0, RT);
+  note_variant("k_policy_rollout", (int)sizeof(R), N, 4, q.p.n_ticks > 1, prec, 0, 0, 0, RT);
   if (prec == kPrecF16x3)
-    hipLaunchKernelGGL((k_policy_rollout<N, kPrecF16x3, RT>), dim3(blocks), dim3(256), 0, s, q);
+    hipLaunchKernelGGL((k_policy_rollout<N, kPrecF16x3, RT, R>), dim3(blocks), dim3(256), 0, s, q);
   else if (prec == kPrecBf16)
-    hipLaunchKernelGGL((k_policy_rollout<N, kPrecBf16, RT>), dim3(blocks), dim3(256), 0, s, q);
+    hipLaunchKernelGGL((k_policy_rollout<N, kPrecBf16, RT, R>), dim3(blocks), dim3(256), 0, s, q);
   else
-    hipLaunchKernelGGL((k_policy_rollout<N, kPrecF32, RT>), dim3(blocks), dim3(256), 0, s, q);
+    hipLaunchKernelGGL((k_policy_rollout<N, kPrecF32, RT, R>), dim3(blocks), dim3(256), 0, s, q);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
@@ -369,7 +427,8 @@ template <int N, int RT> static int policy_launch_rt(const PolicyParams &q, int 
 // registers, one wave per SIMD; every build is under 256 now).  cm3_policy_force_row_tiles(1 | 2 | 4) overrides the choice (tests and
 // measurements; its initial value is the environment's CM3_POLICY_RT, read ONCE -- not per launch).
 constexpr size_t kPolicyCus = 256;
-static std::atomic<int> g_policy_rt_override{-1};   // -1: not initialised, 0: the rule decides
+// (one knob for both translation units of this file: an inline variable is one object in the library)
+inline std::atomic<int> g_policy_rt_override{-1};   // -1: not initialised, 0: the rule decides
 static int policy_rt_override() {
   int v = g_policy_rt_override.load(std::memory_order_relaxed);
   if (v < 0) {
@@ -400,17 +459,20 @@ template <int N> static int policy_launch(const PolicyParams &q, int prec, hipSt
 
 }  // namespace cm3
 
+#ifdef CM3_PARTICLE_F32
 extern "C" int cm3_policy_force_row_tiles(int32_t row_tiles) {
   using namespace cm3;
   CM3_REQUIRE(row_tiles == 0 || row_tiles == 1 || row_tiles == 2 || row_tiles == 4, "row_tiles must be 0 (rule), 1, 2 or 4; got %d", row_tiles);
   g_policy_rt_override.store(row_tiles, std::memory_order_relaxed);
   return CM3_OK;
 }
+#endif
 
-extern "C" int cm3_policy_rollout_f32(const cm3_particle_desc *d, const cm3_particle_traj *t,
-                                      const cm3_actor_particle_desc *ad, const cm3_actor_particle_weights *wt,
-                                      float *probs, size_t probs_stride, int32_t n_ticks, void *stream) {
-  using namespace cm3;
+namespace cm3 {
+// cm3_policy_rollout_f32 / _f64: the same validation and launch, PolicyReal of this translation unit
+static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_traj *t, const cm3_actor_particle_desc *ad,
+                               const cm3_actor_particle_weights *wt, float *probs, size_t probs_stride, int32_t n_ticks,
+                               void *stream) {
   CM3_REQUIRE(d && t && ad && wt, "null argument");
   CM3_REQUIRE(n_ticks >= 1, "n_ticks must be >= 1");
   CM3_REQUIRE(d->n_agents == 1 || d->n_agents == 2 || d->n_agents == 4 || d->n_agents == 8,
@@ -464,7 +526,7 @@ extern "C" int cm3_policy_rollout_f32(const cm3_particle_desc *d, const cm3_part
   q.p.st_term_state = t->term_state_stride;
   q.p.st_term_obs = t->term_obs_others_stride;
   q.p.st_coll = t->collisions_stride;
-  q.obs_in = (const float *)t->obs_others;
+  q.obs_in = t->obs_others;
   q.packed = (const float *)wt->packed;
   q.probs = probs;
   q.st_probs = probs_stride;
@@ -481,3 +543,19 @@ extern "C" int cm3_policy_rollout_f32(const cm3_particle_desc *d, const cm3_part
   }
   return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
+}  // namespace cm3
+
+#ifdef CM3_PARTICLE_F32
+extern "C" int cm3_policy_rollout_f32(const cm3_particle_desc *d, const cm3_particle_traj *t,
+                                      const cm3_actor_particle_desc *ad, const cm3_actor_particle_weights *wt,
+                                      float *probs, size_t probs_stride, int32_t n_ticks, void *stream) {
+  return cm3::policy_rollout_call(d, t, ad, wt, probs, probs_stride, n_ticks, stream);
+}
+#endif
+#ifdef CM3_PARTICLE_F64
+extern "C" int cm3_policy_rollout_f64(const cm3_particle_desc *d, const cm3_particle_traj *t,
+                                      const cm3_actor_particle_desc *ad, const cm3_actor_particle_weights *wt,
+                                      float *probs, size_t probs_stride, int32_t n_ticks, void *stream) {
+  return cm3::policy_rollout_call(d, t, ad, wt, probs, probs_stride, n_ticks, stream);
+}
+#endif

@@ -86,6 +86,11 @@ def _copy_pairs(pairs, stream):
 _Mode = collections.namedtuple("_Mode", "kind live sparse")
 
 
+def _policy_rollout_entry(lib, dtype):
+    """cm3_policy_rollout_f32 / _f64 (the one-launch policy kernel) by the env's real."""
+    return lib.cm3_policy_rollout_f64 if dtype == torch.float64 else lib.cm3_policy_rollout_f32
+
+
 class _ActorGraphCache(object):
     """One captured (actor launch, step launch) x T graph per rollout object.  The key is the policy OBJECT (a strong
     reference: `id()` of a collected actor can be reused); epsilon is not part of it -- the actor launches read it from
@@ -138,7 +143,7 @@ class ParticleRollout(object):
         # policy_mode: how collect(policy=<device actor>) launches (all three are bit-identical, tests/test_gpu_actor.py):
         #   "episode"  the whole policy-driven episode in ONE launch (csrc/policy.hip) -- the fastest (C2: 5.6 vs 10.6 us per tick);
         #   "tick"     an actor launch and a step launch per tick inside one hipGraph;
-        #   "auto"     (default, round 3) "episode" whenever the fused kernel applies -- n_agents in {1, 2, 4, 8}, float32 env,
+        #   "auto"     (default, round 3) "episode" whenever the fused kernel applies -- n_agents in {1, 2, 4, 8} (float64 envs: 1, 2, 4),
         #              actor.seed == env.seed (one Philox key) -- else "tick".  fused=True / fused_policy_tick=True
         #              still force their modes.
         if policy_mode not in ("auto", "episode", "tick"):
@@ -304,7 +309,7 @@ class ParticleRollout(object):
         for t in range(self.T):
             goals = self._goals_buf[t] if (self._goals_buf is not None and not live) else env._goals   # (live: goals in place)
             actor.enqueue(env.E, self.obs_others[t], self.state[t], goals, env._meta, env._episode, self.actions[t],
-                          epsilon, stream=stream, env_id_base=env.env_id_base)
+                          epsilon, stream=stream, env_id_base=env.env_id_base, dtype=env.dtype)
             self._enqueue(t, 1, base_flags, stream, live=live)
 
     def _enqueue_fused_policy_ticks(self, actor, epsilon, base_flags, stream):
@@ -312,10 +317,10 @@ class ParticleRollout(object):
         env = self.env
         env._desc.flags = base_flags & FLAG_AUTO_RESET
         ad = actor._desc(env.E, epsilon, env.env_id_base)
+        fn = _policy_rollout_entry(self._lib, env.dtype)
         for t in range(self.T):
             traj = self._traj(t)
-            _lib.check(self._lib.cm3_policy_rollout_f32(ctypes.byref(env._desc), ctypes.byref(traj), ctypes.byref(ad),
-                                                        ctypes.byref(actor._wt), None, 0, 1, stream))
+            _lib.check(fn(ctypes.byref(env._desc), ctypes.byref(traj), ctypes.byref(ad), ctypes.byref(actor._wt), None, 0, 1, stream))
 
     def _mode(self, policy):
         """How this collect() launches -- the one place that decides it.  -> _Mode(kind, live, sparse):
@@ -332,8 +337,8 @@ class ParticleRollout(object):
                   random-action branch at streaming sizes (sparse_goals = True / False forces that)."""
         env = self.env
         dev_policy = policy is not None and hasattr(policy, "enqueue") and hasattr(policy, "act")
-        if dev_policy and env.dtype != torch.float32:
-            raise Cm3Error("the device actor reads float32 env buffers")
+        if dev_policy and env.dtype not in (torch.float32, torch.float64):
+            raise Cm3Error("the device actor reads float32 or float64 env buffers")
         same_key = dev_policy and getattr(policy, "seed", None) == env.seed
         if policy is None:
             kind = "random_fused" if self.fused else "random"
@@ -341,7 +346,11 @@ class ParticleRollout(object):
             kind = "host_policy"
         else:
             episode_ok = env.n in (1, 2, 4, 8) and same_key and not self.fused_policy_tick
-            if self.fused or (self.policy_mode in ("auto", "episode") and episode_ok):
+            # "auto" leaves float64 envs of eight agents to the launch pairs: measured at C5 (8192 x 8, f16x3) the f64 one-launch
+            # episode runs 40.8 us per tick against 33.5 (its 64-row build needs 83.7 KB of LDS: one workgroup per CU;
+            # profiles/r07_policy_f64.txt).  policy_mode="episode" still runs it.
+            auto_ok = episode_ok and not (env.dtype == torch.float64 and env.n == 8)
+            if self.fused or (self.policy_mode == "episode" and episode_ok) or (self.policy_mode == "auto" and auto_ok):
                 kind = "policy_episode"
             elif self.policy_mode == "episode":
                 raise Cm3Error("policy_mode='episode' needs n_agents in {1, 2, 4, 8} and actor.seed == env.seed")
@@ -407,8 +416,9 @@ class ParticleRollout(object):
             env._desc.flags = base & FLAG_AUTO_RESET
             traj = self._traj(0)
             ad = policy._desc(env.E, epsilon, env.env_id_base)
-            _lib.check(self._lib.cm3_policy_rollout_f32(ctypes.byref(env._desc), ctypes.byref(traj), ctypes.byref(ad),
-                                                        ctypes.byref(policy._wt), None, 0, self.T, stream))
+            fn = _policy_rollout_entry(self._lib, env.dtype)
+            _lib.check(fn(ctypes.byref(env._desc), ctypes.byref(traj), ctypes.byref(ad), ctypes.byref(policy._wt), None, 0, self.T,
+                          stream))
         elif mode.kind == "policy_fused_tick":
             if self.use_graph:      # epsilon is a by-value argument of these launches: part of the graph's key
                 self._actor_graph.launch(self._lib, policy, epsilon, lambda s: self._enqueue_fused_policy_ticks(policy, epsilon, base, s),

@@ -46,7 +46,8 @@
 extern "C" {
 #endif
 
-#define CM3_ABI_VERSION 7   /* 7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
+#define CM3_ABI_VERSION 8   /* 8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
+                               7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
                                with desc->env_offset / env_count).  ADDED cm3_td_target_f64, cm3_policy_rollout_checkers; cm3_actor_checkers_packed_bytes grew by the others-branch table; the
                                precision-2 Checkers actor adds branch_others W_others_h2 to h2's accumulators BEFORE branch_self
@@ -331,7 +332,9 @@ int cm3_checkers_reset(const cm3_checkers_desc *desc, const cm3_checkers_bufs *b
  *   w_others_h2 [128][64]                   "stage-2/W_others_h2"
  *   b_h2 [64]                               "b"
  *   w_out [64][5] + b_out [5]               "actor_out"
- * Inputs are the env's own buffers (obs_others [E][N][L], state [N][E][4], goals [N][E][2], meta, episode);
+ * Inputs are the env's own buffers (obs_others [E][N][L], state [N][E][4], goals [N][E][2], meta, episode) -- float32 for
+ * cm3_actor_particle_f32, float64 for cm3_actor_particle_f64, which rounds them to float32 (to nearest even) as it stages them,
+ * as the reference's tf.float32 placeholders do with its float64 observations; the network is float32 either way;
  * outputs actions int32 [E][N] (what cm3_particle_step_* consumes) and optionally the mixed probabilities
  * float [E][N][5].  Sampling inverts the CDF in action order with one uniform per agent-step from the Philox
  * stream keyed (seed, global env id, episode, step).
@@ -379,6 +382,10 @@ int cm3_actor_particle_pack(const cm3_actor_particle_desc *desc, const cm3_actor
                             void *packed, void *stream);
 int cm3_actor_particle_f32(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
                            const cm3_actor_particle_bufs *bufs, void *stream);
+/* The same actor on a float64 env's buffers (ABI 8): actions and probabilities bit-identical to cm3_actor_particle_f32 on the
+ * float32 roundings of those buffers.  probs stays float32. */
+int cm3_actor_particle_f64(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
+                           const cm3_actor_particle_bufs *bufs, void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
@@ -390,7 +397,14 @@ int cm3_actor_particle_f32(const cm3_actor_particle_desc *desc, const cm3_actor_
 int cm3_policy_rollout_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj,
                            const cm3_actor_particle_desc *actor_desc, const cm3_actor_particle_weights *weights,
                            float *probs, size_t probs_stride, int32_t n_ticks, void *stream);
-/* Test / measurement knob (ABI 6): 16-row tiles per workgroup of cm3_policy_rollout_f32 -- 1, 2 or 4 forces that build of the
+/* The same one-launch episode on a float64 env (ABI 8): trajectory arrays float64 as for cm3_particle_rollout_f64, the physics,
+ * rewards and re-initialisation in float64 (the operation order and contact-skip threshold of cm3_particle_step_f64), the network
+ * float32 on the float32 roundings of each tick's observation.  probs stays float32.  Same validation as the _f32 entry.
+ * Bit-identical to alternating cm3_actor_particle_f64 and cm3_particle_step_f64 launches. */
+int cm3_policy_rollout_f64(const cm3_particle_desc *desc, const cm3_particle_traj *traj,
+                           const cm3_actor_particle_desc *actor_desc, const cm3_actor_particle_weights *weights,
+                           float *probs, size_t probs_stride, int32_t n_ticks, void *stream);
+/* Test / measurement knob (ABI 6): 16-row tiles per workgroup of cm3_policy_rollout_f32 and _f64 -- 1, 2 or 4 forces that build of the
  * kernel for every later launch of the process, 0 gives the choice back to the library's rule (by batch size).  Results do not
  * depend on it (tests/test_gpu_actor.py forces each build on one batch).  Initial value: the environment's CM3_POLICY_RT, read
  * once at the first launch. */

@@ -1,5 +1,11 @@
 #!/usr/bin/env python
-"""Times policy-driven collection on the device: T x (actor launch + step launch) as one hipGraph replay."""
+"""Times policy-driven collection on the device: T x (actor launch + step launch) as one hipGraph replay.
+
+    python tools/policy_rollout_timing.py                    (the original sweep: N = 4, float32 envs)
+    python tools/policy_rollout_timing.py --dtype f64        (C2 = 4096 x 4 antipodal and C5 = 8192 x 8 merge8, actor f16x3, auto-reset:
+                                                              the one-launch episode and the launch pairs on float64 envs, and the
+                                                              float32 one-launch episode alongside, in the same process)"""
+import argparse
 import json
 import os
 import sys
@@ -23,7 +29,50 @@ def init_weights(rng, n_agents):
     return {k: (rng.standard_normal(v) * 0.5).astype(np.float32) for k, v in shapes.items()}
 
 
+def _time(ro, actor, reps):
+    for _ in range(3):
+        ro.collect(policy=actor, epsilon=0.1, reset=False)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        ro.collect(policy=actor, epsilon=0.1, reset=False)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / (reps * ro.T)
+
+
+def main_f64(reps, rounds):
+    """float64 policy collection at C2 and C5: one-launch episode vs launch pairs, next to the float32 one-launch episode; `rounds`
+    alternating rounds of the three, every round a fresh rollout object."""
+    from cm3_amd import _lib
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_stream(torch.cuda.Stream(device=dev))
+    for tag, cfg_name, E, N in (("C2", "particle_stage2_antipodal", 4096, 4), ("C5", "particle_merge8", 8192, 8)):
+        cfg = cm3_amd.load_config(cfg_name)
+        for rnd in range(rounds):
+            for dtype, mode in ((torch.float64, "episode"), (torch.float64, "tick"), (torch.float32, "episode")):
+                env = VecParticleEnv(cfg, N, 0.2, 33, E, device=dev, auto_reset=True, dtype=dtype)
+                env.reset()
+                actor = ParticleActor(init_weights(np.random.default_rng(0), N), N, device=dev, precision="f16x3")
+                ro = ParticleRollout(env, use_graph=True, policy_mode=mode)
+                us = _time(ro, actor, reps)
+                print(json.dumps({"config": tag, "envs": E, "agents": N, "env_dtype": str(dtype).replace("torch.", ""), "policy_mode": mode,
+                                  "round": rnd, "actor_precision": "f16x3", "us_per_tick": round(us, 2),
+                                  "variant": _lib.last_kernel_variant()}), flush=True)
+                ro.close()
+                del ro, env
+                torch.cuda.empty_cache()
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", choices=("f32", "f64"), default="f32")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    if args.dtype == "f64":
+        return main_f64(args.reps, args.rounds)
     dev = torch.device("cuda", 0)
     torch.cuda.set_stream(torch.cuda.Stream(device=dev))
     cfg = cm3_amd.load_config("particle_stage2_antipodal")
