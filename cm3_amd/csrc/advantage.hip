@@ -466,6 +466,9 @@ static int returns_normalize(const void *x, const uint8_t *done, const uint8_t *
   hipLaunchKernelGGL((k_fold_normalize<R>), dim3((unsigned)nblocks, n_seg), dim3(kAdvBlock), 0, s, (R *)out, valid,
                      (const double *)scratch, n_partials, moments, stats, n_elem, C, eps, apply);
   CM3_HIP_CHECK(hipGetLastError());
+  // launch A's build and its number of partial blocks (N=): tests/test_gpu_advantage_f64.py asserts the path each case is named for
+  note_variant(T <= kKeepTicks && blocks <= kAdvMaxBlocks ? "k_returns_partials_keep" : "k_returns_partials", (int)sizeof(R),
+               n_partials, kAdvBlock / 64, 0, 0, 0, 0);
   return CM3_OK;
 }
 
@@ -494,6 +497,8 @@ static int normalize(void *x, const uint8_t *valid, const double *parts, int n_p
   CM3_REQUIRE(n_seg >= 1 && n_seg <= 4096, "n_segments must be in 1..4096");
   CM3_REQUIRE(!apply || x, "null pointer");
   CM3_REQUIRE(n_elem >= 1 && C >= 1, "n_elem and C must be positive");
+  // valid is [n_elem / C] per segment: a remainder would shift every later segment's mask
+  CM3_REQUIRE(n_elem % C == 0, "n_elem must be a multiple of C");
   size_t blocks = apply ? (n_elem + kAdvBlock - 1) / kAdvBlock : 1;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL((k_normalize<R>), dim3((unsigned)blocks, n_seg), dim3(kAdvBlock), 0, (hipStream_t)stream, (R *)x, valid,

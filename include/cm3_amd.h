@@ -497,12 +497,12 @@ int cm3_policy_rollout_checkers(const cm3_checkers_desc *desc, const cm3_checker
  *   next call on the same stream -- no memset launch per call);
  *   moments double[3] = (sum, sum of squares, count) of this rank's valid returns, computed deterministically.
  *   The host all-gathers the three numbers over the ranks (RCCL); cm3_normalize_* sums the n_parts triples in rank order
- *   and applies x = (x - (real)mean) / (real)(std + eps) with the GLOBAL moments (x real [n_elem], valid indexed by
- *   element / C; the same expression as the host helper cm3_amd.shard.normalize_advantages, bit for bit);
+ *   and applies x = (x - (real)mean) / (real)(std + eps) with the GLOBAL moments (x real [n_elem], n_elem a multiple of C,
+ *   valid indexed by element / C; the same expression as the host helper cm3_amd.shard.normalize_advantages, bit for bit);
  *   stats (optional) receives (mean, std, count); apply = 0 only computes stats.
  * ---------------------------------------------------------------------------------------- */
 size_t cm3_returns_scratch_bytes(void);
-/* NOTE (scratch layout): cm3_returns_moments_* keeps its arrival ticket BEHIND 3 * 512 partial slots of `scratch`;
+/* NOTE (scratch layout): cm3_returns_moments_* keeps its arrival ticket BEHIND 3 * 1024 partial slots of `scratch`;
  * cm3_returns_normalize_segments_* with n_segments >= 2 uses that range for partials.  Give the two entry-point families SEPARATE
  * scratch buffers (cm3_returns_scratch_bytes / cm3_returns_segments_scratch_bytes): a shared one leaves a garbage ticket and the
  * moments silently stale. */
@@ -518,6 +518,8 @@ int cm3_normalize_f64(void *x, const uint8_t *valid, const double *parts, int32_
  * n_parts = 1 on its own moments, bit for bit.  Launch A computes the returns and per-block partial moments (short trajectories,
  * T <= 40: the whole column in one memory round trip), launch B folds the partials in block order in every block -- the fold of
  * cm3_returns_moments_*, so `moments` receives the same bits -- and normalises; no atomics, no arrival counter.
+ * cm3_last_kernel_variant() then names launch A's build (k_returns_partials_keep: T <= 40 and <= 1024 column blocks, else
+ * k_returns_partials) with N = its number of partial blocks.
  * `shift` (optional) adds the slot bookkeeping of the rollout whose rewards these are to launch A, element by element:
  * first_dst[r] <- mid[r], then mid[r] <- last_src[r] (r < n <= 4; 16-byte aligned pointers and sizes).  With mid = the env's live
  * buffers, first_dst = slot 0 and last_src = slot T of a trajectory whose first tick READ the live buffers, this records the
