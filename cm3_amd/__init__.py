@@ -29,4 +29,7 @@ def __getattr__(name):
     if name == "ParticleActor":
         from .actor import ParticleActor
         return ParticleActor
+    if name == "ParticleQmixAgent":
+        from .qmix import ParticleQmixAgent
+        return ParticleQmixAgent
     raise AttributeError(name)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CM3_AMD_LIB: load another build of the SAME ABI instead (tools/*_ab.py compare two builds on one box)
 LIB_PATH = os.environ.get("CM3_AMD_LIB") or os.path.join(_HERE, "libcm3_hip.so")
 MAX_AGENTS = 10
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 FLAG_AUTO_RESET = 1
 FLAG_GEN_ACTIONS = 2
@@ -182,6 +182,10 @@ SYMBOLS = {
     "cm3_policy_rollout_f64": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), P(ActorParticleDesc),
                                               P(ActorParticleWeights), c_void_p, c_size_t, c_int32, c_void_p]),
     "cm3_policy_force_row_tiles": (ctypes.c_int, [c_int32]),
+    "cm3_qmix_particle_packed_bytes": (c_size_t, [c_int32]),
+    "cm3_qmix_particle_pack": (ctypes.c_int, [P(ActorParticleDesc), P(c_void_p), c_void_p, c_void_p]),
+    "cm3_qmix_particle_f32": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(ActorParticleBufs), c_void_p]),
+    "cm3_qmix_particle_f64": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(ActorParticleBufs), c_void_p]),
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
     "cm3_transitions_gather_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), c_void_p, c_size_t, c_void_p, c_void_p, c_int64,
                                                   P(TransitionCols), c_void_p]),

@@ -714,6 +714,279 @@ template <int N, typename RIN> static int actor_launch(const ActorParams &p, hip
 }  // namespace cm3
 
 namespace cm3 {
+
+// ---- QMIX agent network (ABI 9): networks.Qmix_single_particle (networks.py:581-594) + the epsilon-greedy choice of
+// alg_qmix.run_actor (alg_qmix.py:160-184), for all E*N agent rows in one launch.
+//   concat(o_others[L], o_self[4], goal[2]) -> dense 64 relu ("h") -> dense 64 relu ("h2") -> dense 5 ("out"): Q values, no softmax
+// Same mapping as k_actor_particle: 256 threads = 4 waves (one per SIMD) own 64 rows, every layer on the exact-f32 MFMA
+// (v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain), float32 throughout.
+//   layer 1 (K = L + 6, padded to L + 8 with zero inputs and weights): TRANSPOSED like the actor's first layer, C[unit][row]:
+//     A[i = l&15][k = l>>4] = W_h[4s + (l>>4)][16w + (l&15)]  (per-lane operands, packed), B = xs[16t + (l&15)][4s + (l>>4)];
+//     lane l then holds units 16w + 4 (l>>4) + reg of row 16t + (l&15): bias as the start value, relu, two 8-byte LDS stores.
+//   layer 2 (64 -> 64): wave w owns columns [16w, 16w+16) as the actor's second layer, 16 k-steps x 4 row tiles.
+//   head (64 -> 5): one 16 x 16 tile per wave as actor_head_probs, ONE accumulator (k-ordered); argmax with the lowest index on
+//     ties (tf.argmax), then epsilon-greedy.
+// Exploration draws: a stream of its own, kPurposeExplore (below) -- two independent values per row, "explore?" and the uniform
+// action, stateless in (seed, global env id, episode, step, agent).
+constexpr int kQH = 64;                     // both hidden widths (networks.py:585-589)
+constexpr uint32_t kPurposeExplore = 0x20000000u;   // | (agent >> 1) << 24; distinct from kAction (0), kReset (bit 31), kPolicy (bit 30)
+
+template <int N> struct QmixLayout {
+  static constexpr int L = 4 * (N > 1 ? N - 1 : 1);
+  static constexpr int K1 = L + 8;                  // L + 6 inputs, two zero pads: whole k-steps of 4
+  static constexpr int S1 = K1 / 4;                 // layer-1 k-steps (3 .. 11)
+  static constexpr int S1P = (S1 + 3) / 4 * 4;      // per-lane stride of the layer-1 operands (16-byte loads)
+  static constexpr int XW = K1 + 1;                 // input tile row (odd stride)
+  static constexpr int HS = kQH + 2;                // hidden rows in LDS: 16 rows x 2 k per half-wave read hit distinct banks
+  static constexpr int kW1 = 0;                     // [4 waves][64 lanes][S1P]  A operands of layer 1
+  static constexpr int kB1 = kW1 + 4 * 64 * S1P;    // [64]
+  static constexpr int kW2 = kB1 + kQH;             // [4 waves][64 lanes][16]   B operands of layer 2
+  static constexpr int kB2 = kW2 + 4 * 64 * 16;     // [64]
+  static constexpr int kWo = kB2 + kQH;             // [64 lanes][16]            A operands of the head (0 for actions >= 5)
+  static constexpr int kBo = kWo + 64 * 16;         // [16]                      bias, 0 past action 4
+  static constexpr int kTotal = kBo + 16;
+};
+
+struct QmixParams {
+  int E;
+  float eps;
+  int64_t env_id_base;
+  uint64_t seed;
+  const void *obs_others, *state, *goals;
+  const int32_t *meta, *episode;
+  int32_t *actions;
+  float *q;               // optional [E][N][5]
+  const float *eps_dev;   // optional: epsilon read at launch
+  const float *packed;
+  const float *w[6];      // pack kernel only: h/kernel, h/bias, h2/kernel, h2/bias, out/kernel, out/bias
+};
+
+template <int N> __global__ void __launch_bounds__(256) k_qmix_pack(const QmixParams p, float *out) {
+  using QL = QmixLayout<N>;
+  constexpr int K = QL::L + 6;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < QL::kTotal; t += gridDim.x * 256) {
+    float v = 0.0f;
+    if (t < QL::kB1) {
+      const int s = t % QL::S1P, lane = (t / QL::S1P) & 63, w = t / QL::S1P / 64;
+      const int k = 4 * s + (lane >> 4), j = 16 * w + (lane & 15);
+      v = (s < QL::S1 && k < K) ? p.w[0][k * kQH + j] : 0.0f;
+    } else if (t < QL::kW2) {
+      v = p.w[1][t - QL::kB1];
+    } else if (t < QL::kB2) {
+      const int u = t - QL::kW2, s = u & 15, lane = (u >> 4) & 63, w = u >> 10;
+      v = p.w[2][(4 * s + (lane >> 4)) * kQH + 16 * w + (lane & 15)];
+    } else if (t < QL::kWo) {
+      v = p.w[3][t - QL::kB2];
+    } else if (t < QL::kBo) {
+      const int u = t - QL::kWo, s = u & 15, lane = u >> 4, j = lane & 15;
+      v = j < kA ? p.w[4][(4 * s + (lane >> 4)) * kA + j] : 0.0f;
+    } else {
+      const int a = t - QL::kBo;
+      v = a < kA ? p.w[5][a] : 0.0f;
+    }
+    out[t] = v;
+  }
+}
+
+template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle(const QmixParams p) {
+  using QL = QmixLayout<N>;
+  using V4 = typename Vec<RIN>::v4;
+  using V2 = typename Vec<RIN>::v2;
+  constexpr int L = QL::L, S1 = QL::S1;
+  __shared__ float xs[64][QL::XW];
+  __shared__ __attribute__((aligned(16))) float h1s[64][QL::HS];
+  __shared__ float h2s[64][QL::HS];
+  const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, hi = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t rows = (size_t)p.E * N;
+  const size_t row_base = (size_t)blockIdx.x * 64;
+
+  // the row this lane finishes in the head (row 16w + (l&15); lanes 0..15 write it) and its exploration key
+  size_t hr = row_base + 16 * w + col;
+  const bool head_ok = hr < rows && hi == 0;
+  hr = hr < rows ? hr : rows - 1;
+  const size_t he = hr / N;
+  const int agent = (int)(hr - he * N);
+  const int head_steps = p.meta[2 * he];
+  const uint32_t head_episode = (uint32_t)p.episode[he];
+
+  // every global request first: wave 0's input rows, then the lane's weight operands
+  V4 in_s, in_o[L / 4];
+  V2 in_g;
+  if (w == 0) {
+    const size_t r = row_base + lane;
+    const size_t rc = r < rows ? r : rows - 1;
+    const size_t e = rc / N;
+    const int i = (int)(rc - e * N);
+    in_s = reinterpret_cast<const V4 *>(p.state)[(size_t)i * p.E + e];
+    in_g = reinterpret_cast<const V2 *>(p.goals)[(size_t)i * p.E + e];
+    const V4 *o4 = reinterpret_cast<const V4 *>(reinterpret_cast<const RIN *>(p.obs_others) + rc * L);
+#pragma unroll
+    for (int k = 0; k < L / 4; ++k) in_o[k] = o4[k];
+  }
+  float a1[QL::S1P], bw[16], wo[16];
+  {
+    const float4 *src = reinterpret_cast<const float4 *>(p.packed + QL::kW1) + (size_t)(w * 64 + lane) * (QL::S1P / 4);
+#pragma unroll
+    for (int s4 = 0; s4 < QL::S1P / 4; ++s4) {
+      const float4 v = src[s4];
+      a1[4 * s4 + 0] = v.x; a1[4 * s4 + 1] = v.y; a1[4 * s4 + 2] = v.z; a1[4 * s4 + 3] = v.w;
+    }
+    const float4 *s2 = reinterpret_cast<const float4 *>(p.packed + QL::kW2) + (size_t)(w * 64 + lane) * 4;
+    const float4 *so = reinterpret_cast<const float4 *>(p.packed + QL::kWo) + (size_t)lane * 4;
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      const float4 v = s2[s4], u = so[s4];
+      bw[4 * s4 + 0] = v.x; bw[4 * s4 + 1] = v.y; bw[4 * s4 + 2] = v.z; bw[4 * s4 + 3] = v.w;
+      wo[4 * s4 + 0] = u.x; wo[4 * s4 + 1] = u.y; wo[4 * s4 + 2] = u.z; wo[4 * s4 + 3] = u.w;
+    }
+  }
+  const float4 b1 = reinterpret_cast<const float4 *>(p.packed + QL::kB1)[4 * w + hi];   // units 16w + 4 (l>>4) + 0..3
+  const float b2 = p.packed[QL::kB2 + 16 * w + col];
+  const float4 bo = reinterpret_cast<const float4 *>(p.packed + QL::kBo)[hi];           // actions 4 (l>>4) + 0..3
+  if (w == 0) {
+    // concat(o_others, o_self, goal) (networks.py:583), rounded to float32 as staged (a float64 env: the reference's tf.float32
+    // placeholders), two zero pads
+#pragma unroll
+    for (int k = 0; k < L / 4; ++k) {
+      xs[lane][4 * k + 0] = (float)in_o[k].x; xs[lane][4 * k + 1] = (float)in_o[k].y;
+      xs[lane][4 * k + 2] = (float)in_o[k].z; xs[lane][4 * k + 3] = (float)in_o[k].w;
+    }
+    xs[lane][L + 0] = (float)in_s.x; xs[lane][L + 1] = (float)in_s.y; xs[lane][L + 2] = (float)in_s.z; xs[lane][L + 3] = (float)in_s.w;
+    xs[lane][L + 4] = (float)in_g.x; xs[lane][L + 5] = (float)in_g.y;
+    xs[lane][L + 6] = 0.0f; xs[lane][L + 7] = 0.0f;
+  }
+  __syncthreads();
+  // ---- layer "h": units [16w, 16w+16) for all 64 rows, C[unit][row] ---------------------------------------------------------
+  {
+    f32x4 c[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) c[t] = f32x4{b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+    for (int s = 0; s < S1; ++s)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s], xs[16 * t + col][4 * s + hi], c[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      *reinterpret_cast<float2 *>(&h1s[16 * t + col][16 * w + 4 * hi]) = make_float2(relu_f32(c[t][0]), relu_f32(c[t][1]));
+      *reinterpret_cast<float2 *>(&h1s[16 * t + col][16 * w + 4 * hi + 2]) = make_float2(relu_f32(c[t][2]), relu_f32(c[t][3]));
+    }
+  }
+  __syncthreads();
+  // ---- layer "h2": columns [16w, 16w+16), C[row][unit] ----------------------------------------------------------------------
+  {
+    f32x4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int s = 0; s < kQH / 4; ++s)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1s[16 * t + col][4 * s + hi], bw[s], acc[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) h2s[16 * t + 4 * hi + reg][16 * w + col] = relu_f32(acc[t][reg] + b2);
+  }
+  __syncthreads();
+  // exploration words first: the Philox rounds are VALU work that issues between the head's dependent matrix instructions
+  uint32_t w_explore, w_action;
+  {
+    const uint64_t genv = (uint64_t)(p.env_id_base + (int64_t)he);
+    u32x4 ctr;
+    ctr.x = (uint32_t)genv;
+    ctr.y = (uint32_t)(genv >> 32);
+    ctr.z = 0u;
+    ctr.w = kPurposeExplore | ((uint32_t)(agent >> 1) << 24);
+    const u32x4 wd = philox4x32_10(ctr, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+    const bool odd = (agent & 1) != 0;
+    w_explore = action_word(odd ? wd.z : wd.x, head_episode, (uint32_t)head_steps);
+    w_action = action_word(odd ? wd.w : wd.y, head_episode, (uint32_t)head_steps);
+  }
+  // ---- head "out": C[action][row] of rows [16w, 16w+16), bias as the start value, one k-ordered chain ----------------------
+  float hx[kQH / 4];
+#pragma unroll
+  for (int s = 0; s < kQH / 4; ++s) hx[s] = h2s[16 * w + col][4 * s + hi];
+  f32x4 acc = f32x4{bo.x, bo.y, bo.z, bo.w};
+#pragma unroll
+  for (int s = 0; s < kQH / 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wo[s], hx[s], acc, 0, 0, 0);
+  float q[kA];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) q[a] = acc[a];
+  {
+    // action 4 of the row sits in register 0 of the lane 16 further on (see actor_head_probs)
+    uint32_t x;
+    __builtin_memcpy(&x, &q[0], 4);
+    const auto sw = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    const uint32_t y = sw[1];
+    __builtin_memcpy(&q[4], &y, 4);
+  }
+  // argmax, the first index on ties (tf.argmax, alg_qmix.py:98)
+  int greedy = 0;
+  float best = q[0];
+#pragma unroll
+  for (int a = 1; a < kA; ++a) {
+    const bool gt = q[a] > best;
+    greedy = gt ? a : greedy;
+    best = gt ? q[a] : best;
+  }
+  // epsilon-greedy (alg_qmix.py:177-182): explore with probability eps (compared in double: eps = 1 always explores), then a
+  // uniform action
+  const float eps = p.eps_dev ? *p.eps_dev : p.eps;
+  const bool explore = u01(w_explore) < (double)eps;
+  const int act = explore ? rand5(w_action) : greedy;
+  if (head_ok) {
+    p.actions[hr] = act;
+    if (p.q) {
+#pragma unroll
+      for (int a = 0; a < kA; ++a) p.q[hr * kA + a] = q[a];
+    }
+  }
+}
+
+template <int N, typename RIN> static int qmix_launch(const QmixParams &p, hipStream_t s) {
+  const size_t rows = (size_t)p.E * N;
+  const unsigned blocks = (unsigned)((rows + 63) / 64);
+  note_variant("k_qmix_particle", (int)sizeof(RIN), N, 4, 0, 0, 0, 0, 0, 0, kPrecF32);
+  hipLaunchKernelGGL((k_qmix_particle<N, RIN>), dim3(blocks), dim3(256), 0, s, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+template <int N> static int qmix_pack_launch(const QmixParams &p, float *out, hipStream_t s) {
+  hipLaunchKernelGGL((k_qmix_pack<N>), dim3(16), dim3(256), 0, s, p, out);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+static int qmix_check_desc(const cm3_actor_particle_desc *d) {
+  CM3_REQUIRE(d, "null desc");
+  CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= CM3_MAX_AGENTS, "n_agents must be in 1..%d", CM3_MAX_AGENTS);
+  CM3_REQUIRE(d->n_h1_self == kQH && d->n_h2 == kQH && d->n_actions == kA,
+              "the QMIX agent network is 64/64/5 (networks.Qmix_single_particle): n_h1_self, n_h2, n_actions; got %d/%d/%d",
+              d->n_h1_self, d->n_h2, d->n_actions);
+  CM3_REQUIRE(d->precision == 0, "the QMIX agent runs in float32 only: precision must be 0");
+  return CM3_OK;
+}
+
+static size_t qmix_floats_for(int n) {
+  switch (n) {
+    case 1: return QmixLayout<1>::kTotal;
+    case 2: return QmixLayout<2>::kTotal;
+    case 3: return QmixLayout<3>::kTotal;
+    case 4: return QmixLayout<4>::kTotal;
+    case 5: return QmixLayout<5>::kTotal;
+    case 6: return QmixLayout<6>::kTotal;
+    case 7: return QmixLayout<7>::kTotal;
+    case 8: return QmixLayout<8>::kTotal;
+    case 9: return QmixLayout<9>::kTotal;
+    case 10: return QmixLayout<10>::kTotal;
+  }
+  return 0;
+}
+
+}  // namespace cm3
+
+namespace cm3 {
 static int actor_check_desc(const cm3_actor_particle_desc *d) {
   CM3_REQUIRE(d, "null desc");
   CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= CM3_MAX_AGENTS, "n_agents must be in 1..%d", CM3_MAX_AGENTS);
@@ -837,5 +1110,89 @@ extern "C" int cm3_actor_particle_f32(const cm3_actor_particle_desc *d, const cm
 extern "C" int cm3_actor_particle_f64(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
                                       const cm3_actor_particle_bufs *b, void *stream) {
   return cm3::actor_particle_call<double>(d, wt, b, stream);
+}
+
+// ---- QMIX agent (ABI 9) ------------------------------------------------------------------------------------------------------
+extern "C" size_t cm3_qmix_particle_packed_bytes(int32_t n_agents) {
+  return cm3::qmix_floats_for(n_agents) * sizeof(float);
+}
+
+extern "C" int cm3_qmix_particle_pack(const cm3_actor_particle_desc *d, const float *const *tensors, void *packed, void *stream) {
+  using namespace cm3;
+  int rc = qmix_check_desc(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(tensors && packed, "null tensors / packed buffer");
+  QmixParams p;
+  memset(&p, 0, sizeof(p));
+  for (int k = 0; k < 6; ++k) {
+    CM3_REQUIRE(tensors[k], "missing QMIX weight %d (h/kernel, h/bias, h2/kernel, h2/bias, out/kernel, out/bias)", k);
+    p.w[k] = tensors[k];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  switch (d->n_agents) {
+    case 1: return qmix_pack_launch<1>(p, (float *)packed, s);
+    case 2: return qmix_pack_launch<2>(p, (float *)packed, s);
+    case 3: return qmix_pack_launch<3>(p, (float *)packed, s);
+    case 4: return qmix_pack_launch<4>(p, (float *)packed, s);
+    case 5: return qmix_pack_launch<5>(p, (float *)packed, s);
+    case 6: return qmix_pack_launch<6>(p, (float *)packed, s);
+    case 7: return qmix_pack_launch<7>(p, (float *)packed, s);
+    case 8: return qmix_pack_launch<8>(p, (float *)packed, s);
+    case 9: return qmix_pack_launch<9>(p, (float *)packed, s);
+    case 10: return qmix_pack_launch<10>(p, (float *)packed, s);
+  }
+  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+}
+
+namespace cm3 {
+template <typename RIN>
+static int qmix_particle_call(const cm3_actor_particle_desc *d, const void *packed, const cm3_actor_particle_bufs *b, void *stream) {
+  int rc = qmix_check_desc(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(b, "null bufs");
+  CM3_REQUIRE(d->n_envs > 0, "n_envs must be positive");
+  CM3_REQUIRE(d->epsilon >= 0.0f && d->epsilon <= 1.0f, "epsilon must be in [0,1]");
+  CM3_REQUIRE(packed, "packed weights are NULL: run cm3_qmix_particle_pack once per weight update");
+  CM3_REQUIRE(b->obs_others && b->state && b->goals && b->meta && b->episode && b->actions, "missing buffers");
+  QmixParams p;
+  memset(&p, 0, sizeof(p));
+  p.E = d->n_envs;
+  p.eps = d->epsilon;
+  p.eps_dev = b->epsilon_dev;
+  p.env_id_base = d->env_id_base;
+  p.seed = d->seed;
+  p.obs_others = b->obs_others;
+  p.state = b->state;
+  p.goals = b->goals;
+  p.meta = b->meta;
+  p.episode = b->episode;
+  p.actions = b->actions;
+  p.q = b->probs;
+  p.packed = (const float *)packed;
+  hipStream_t s = (hipStream_t)stream;
+  switch (d->n_agents) {
+    case 1: return qmix_launch<1, RIN>(p, s);
+    case 2: return qmix_launch<2, RIN>(p, s);
+    case 3: return qmix_launch<3, RIN>(p, s);
+    case 4: return qmix_launch<4, RIN>(p, s);
+    case 5: return qmix_launch<5, RIN>(p, s);
+    case 6: return qmix_launch<6, RIN>(p, s);
+    case 7: return qmix_launch<7, RIN>(p, s);
+    case 8: return qmix_launch<8, RIN>(p, s);
+    case 9: return qmix_launch<9, RIN>(p, s);
+    case 10: return qmix_launch<10, RIN>(p, s);
+  }
+  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+}
+}  // namespace cm3
+
+extern "C" int cm3_qmix_particle_f32(const cm3_actor_particle_desc *d, const void *packed, const cm3_actor_particle_bufs *b,
+                                     void *stream) {
+  return cm3::qmix_particle_call<float>(d, packed, b, stream);
+}
+
+extern "C" int cm3_qmix_particle_f64(const cm3_actor_particle_desc *d, const void *packed, const cm3_actor_particle_bufs *b,
+                                     void *stream) {
+  return cm3::qmix_particle_call<double>(d, packed, b, stream);
 }
 #endif  // CM3_NO_ENTRY_POINTS

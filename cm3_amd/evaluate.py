@@ -14,7 +14,8 @@ from .rollout import CheckersRollout, ParticleRollout
 def test_particle(env, actor, n_rounds=1, epsilon=0.0, rollout=None, reset=True):
     """-> (reward_local_avg [N], reward_global_avg, n_episodes) like evaluate.test_particle, over
     n_rounds x env.n_envs episodes.  `env` must not auto-reset (one episode per env per round).  `actor` is the on-device
-    ParticleActor or a host callable policy(obs_others, obs_self, goals) -> [E,N]; reset=False evaluates from the states
+    ParticleActor, the on-device ParticleQmixAgent (greedy at epsilon = 0, as alg/evaluate.py:104 calls the QMIX run_actor)
+    or a host callable policy(obs_others, obs_self, goals) -> [E,N]; reset=False evaluates from the states
     the env currently holds (state injection: how tests replay the episodes the reference evaluator saw)."""
     if env.auto_reset:
         raise ValueError("evaluation runs one episode per env: build the env with auto_reset=False")

@@ -327,6 +327,7 @@ class ParticleRollout(object):
           kind    random_fused | random            the reference's random-action branch, all ticks in one launch / a launch per tick
                   policy_episode                   on-device actor, the whole episode in ONE launch (csrc/policy.hip)
                   policy_fused_tick | policy_tick  on-device actor, one fused launch / an actor + a step launch per tick
+                                                   (a policy with fused_kernels = False, the QMIX agent: policy_tick only)
                   host_policy                      a Python callable per tick
           live    per-tick step launches step IN PLACE on the env's buffers and copy every tick's state to its slot -- only while a
                   tick's state is small (<= 1 MiB: the slot copy is extra write traffic, the gain is load latency: C2 2.87 -> 2.74 us)
@@ -344,6 +345,12 @@ class ParticleRollout(object):
             kind = "random_fused" if self.fused else "random"
         elif not dev_policy:
             kind = "host_policy"
+        elif not getattr(policy, "fused_kernels", True):
+            # an agent the one-launch kernels do not run (ParticleQmixAgent: they evaluate the CM3 actor): launch pairs only
+            if self.fused or self.fused_policy_tick or self.policy_mode == "episode":
+                raise Cm3Error("%s runs as an agent launch plus a step launch per tick: policy_mode='episode', fused=True and "
+                               "fused_policy_tick=True run the CM3 actor" % type(policy).__name__)
+            kind = "policy_tick"
         else:
             episode_ok = env.n in (1, 2, 4, 8) and same_key and not self.fused_policy_tick
             # "auto" leaves float64 envs of eight agents to the launch pairs: measured at C5 (8192 x 8, f16x3) the f64 one-launch

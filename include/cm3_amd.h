@@ -46,7 +46,8 @@
 extern "C" {
 #endif
 
-#define CM3_ABI_VERSION 8   /* 8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
+#define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
+                               8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
                                with desc->env_offset / env_count).  ADDED cm3_td_target_f64, cm3_policy_rollout_checkers; cm3_actor_checkers_packed_bytes grew by the others-branch table; the
@@ -386,6 +387,29 @@ int cm3_actor_particle_f32(const cm3_actor_particle_desc *desc, const cm3_actor_
  * float32 roundings of those buffers.  probs stays float32. */
 int cm3_actor_particle_f64(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
                            const cm3_actor_particle_bufs *bufs, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * On-device QMIX agent (ABI 9): networks.Qmix_single_particle (networks.py:581-594) + the epsilon-greedy choice of
+ * alg_qmix.run_actor (alg_qmix.py:160-184), for all E*N agent rows in one launch.  Float32 weights, row-major [in][out] as
+ * the TF variables "Agent_main/..." are shaped (L = 4*max(N-1,1)):
+ *   tensors[0] h/kernel [L+6][64]    tensors[1] h/bias [64]     (input = concat(o_others[L], o_self[4], goal[2]))
+ *   tensors[2] h2/kernel [64][64]    tensors[3] h2/bias [64]
+ *   tensors[4] out/kernel [64][5]    tensors[5] out/bias [5]    (Q values, no softmax)
+ * The descriptor and buffers are the particle actor's: n_agents 1..10, n_envs >= 1, n_h1_self = n_h2 = 64, n_actions = 5,
+ * precision 0 (float32 throughout; n_h1_others and stage are not read), epsilon in [0,1] (or bufs->epsilon_dev, read at launch).
+ * Inputs as for cm3_actor_particle_f32 / _f64 (float64 envs are rounded to float32 as the inputs are staged).  Outputs:
+ * actions int32 [E][N] -- argmax Q (the first index on ties), replaced with probability epsilon by a uniform action -- and, when
+ * bufs->probs is set, the Q values float [E][N][5].  The two exploration draws per agent-step ("explore?", the uniform action)
+ * come from the build's Philox stream with a purpose of their own, keyed (seed, global env id, episode, step, agent).
+ * ---------------------------------------------------------------------------------------- */
+size_t cm3_qmix_particle_packed_bytes(int32_t n_agents);
+/* Re-arranges the six TensorFlow-shaped tensors into the forward kernel's layout; one small launch per weight update.
+ * Only desc->n_agents and the widths are read. */
+int cm3_qmix_particle_pack(const cm3_actor_particle_desc *desc, const float *const *tensors, void *packed, void *stream);
+int cm3_qmix_particle_f32(const cm3_actor_particle_desc *desc, const void *packed, const cm3_actor_particle_bufs *bufs,
+                          void *stream);
+int cm3_qmix_particle_f64(const cm3_actor_particle_desc *desc, const void *packed, const cm3_actor_particle_bufs *bufs,
+                          void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
