@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # + everything else: baselines, other configs, extras, sweep
     python bench.py --gpus 8 ...            # re-executes itself through torch.distributed.run with 8 ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -17,12 +18,15 @@ collection object (cm3_amd.rollout.ParticleRollout), replayed as one hipGraph pe
 drawn in-kernel (train_onpolicy.py:305-307), auto-reset at max_steps.  --steps K times exactly K phases after --warmup W.
 Env instances shard across ranks with NO data-path collective => "weak" scaling.
 
-Rank 0 prints the driver's line LAST and keeps it under 4 KB (compact_line(): contract keys + numbers); everything else this
-run measured goes to bench_extras.json and, as bare numbers, to the stdout line before it (extras_summary()).
+Rank 0 prints the driver's line LAST and keeps it under 4 KB (compact_line(): contract keys + numbers).  A plain run measures
+the headline and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds everything else (CPU
+baselines, measured bandwidth, launch floor, the other BASELINE configs, launch modes, policy rollouts, the E-sweep, host-side
+timings); what it measured goes to bench_extras.json and, as bare numbers, to the stdout line before the driver's
+(extras_summary()).
 The line:  metric = env-steps/s summed over all GPUs (max-over-ranks wall clock between two barriers);
 roofline  = algorithmic bytes of the timed launches (400 B x E per launch for N=4) / the SAME wall
             clock, against the 8 TB/s HBM3E peak (the HIP-event time of the same region is reported beside it);
-cpu_baseline = the reference-shaped scalar NumPy port (oracle.particle_oracle.ParticleEnvOracle) timed on the host
+cpu_baseline (--full) = the reference-shaped scalar NumPy port (oracle.particle_oracle.ParticleEnvOracle) timed on the host
             cores of this box (rank 0, at every N; the other ranks wait at the closing barrier).
 """
 import argparse
@@ -728,7 +732,7 @@ def pin_rank_to_gpu_numa_node(device_index):
 
 
 def measure_other_config(name, args, device, steps=20, cpu_budget_s=6.0):
-    """One of the OTHER BASELINE workloads (c3 / c5 / c4), timed inside the default `bench.py --gpus 1` run exactly like the
+    """One of the OTHER BASELINE workloads (c3 / c5 / c4), timed inside `bench.py --gpus 1 --full` exactly like the
     headline -- the product's own collector in trajectory mode, one step launch per tick, hipGraph replays, wall clock between
     two device synchronisations with the HIP-event time of the same region beside it -- so that the driver's record carries a
     driver-timed number for every BASELINE config, each with its own roofline (algorithmic bytes per launch / time per launch
@@ -960,12 +964,14 @@ def extras_summary(out):
     return s
 
 
-def emit(out, extras_file=None):
+def emit(out, extras_file=None, write_default=True):
     """rank 0: bench_extras.json (the whole record; also under gpurun_out/ when that exists; `--extras-file` names another place),
-    then the summary line, then THE line."""
+    then the summary line, then THE line.  write_default=False (a plain run): the record is written only where `extras_file` says."""
     full = json.dumps(out, indent=1)
     targets = [extras_file] if extras_file else [os.path.join(d, EXTRAS_FILE) for d in (ROOT, os.path.join(ROOT, "gpurun_out"))
                                                  if os.path.isdir(d)]
+    if not (extras_file or write_default):
+        targets = []
     for path in targets:
         try:
             with open(path, "w") as fh:
@@ -1129,17 +1135,21 @@ def main():
                          "in-place: every tick overwrites the same live buffers (stepping only)")
     ap.add_argument("--envs-per-gpu", type=int, default=0, help="override the workload's batch size")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the E-sweep (extra 'sweep' field)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too: read / copy bandwidth, CPU baselines, launch floor, the other "
+                         "BASELINE configs (c2), launch modes, policy rollouts, E-sweep, host-side timings; the full record goes to "
+                         "%s (a plain run writes it only to --extras-file)" % EXTRAS_FILE)
+    ap.add_argument("--no-sweep", action="store_true", help="--full without the E-sweep (extra 'sweep' field)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short c3 / c5 / c4 runs that the default c2 line carries as 'other_configs'")
+                    help="--full without the short c3 / c5 / c4 runs that the c2 line carries as 'other_configs'")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline only: skip the in-place / fused / policy-rollout / launch-floor extras (clean profiles)")
+                    help="--full without the in-place / fused / policy-rollout / launch-floor / host-side extras")
     ap.add_argument("--live-state", choices=["auto", "on", "off"], default="auto",
                     help="trajectory mode of the particle workloads: step in place on the env's buffers and copy every tick's state to "
                          "its slot (on), chain the ticks through the slots (off), or by size (auto, the product's rule)")
     ap.add_argument("--extras-file", default=None,
-                    help="where the full record goes (default: %s next to bench.py and under gpurun_out/)" % EXTRAS_FILE)
+                    help="where the full record goes (default with --full: %s next to bench.py)" % EXTRAS_FILE)
     ap.add_argument("--fused", action="store_true",
                     help="random-action rollouts with all ticks of a phase in ONE launch (CM3_FLAG_FUSED_TICKS); "
                          "the default keeps one launch per tick")
@@ -1277,7 +1287,7 @@ def main():
                 "source": "profiles/" + SPAN_FILE + " (tools/kernel_span.py, two-stamp build, unprofiled 330-launch hipGraph): "
                           "span = first wave in -> last wave out; start-to-start includes the dependent-launch boundary and is "
                           "what roofline.avg_launch_us of THIS run measures live"}
-    extras = world == 1 and rank == 0 and not args.no_extras and not args.fused
+    extras = args.full and world == 1 and rank == 0 and not args.no_extras and not args.fused
     if extras and kind in ("particle", "checkers"):
         stepper.close()
         del stepper
@@ -1516,8 +1526,7 @@ def main():
                        "test_checkers_policy_rollout_equals_launch_per_tick); its roofline counts the matrix instructions it EXECUTES "
                        "(the others branch of the two-agent network is a table lookup there)")
         out["policy_rollout"] = pol
-    if world == 1 and rank == 0 and args.workload == "c2" and mode == "trajectory" and not args.no_other_configs \
-            and not args.no_extras and not args.fused and not args.envs_per_gpu:
+    if extras and args.workload == "c2" and mode == "trajectory" and not args.no_other_configs and not args.envs_per_gpu:
         # the other BASELINE workloads, driver-timed in the same run (each a short run of ITS configuration; the headline stays c2)
         if stepper is not None:
             stepper.close()
@@ -1527,13 +1536,13 @@ def main():
         out["other_configs"] = {name: measure_other_config(name, args, device) for name in ("c3", "c5", "c4")}
         out["other_configs"]["note"] = ("each: the workload's own BASELINE configuration through the product's collector, 20 hipGraph "
                                         "replays (collection phases) after 5 warm-up ones as the headline, same clock; "
-                                        "`python bench.py --workload cN` runs it as the headline with its extras")
-    if rank == 0 and world > 1:
+                                        "`python bench.py --workload cN --full` runs it as the headline with its extras")
+    if args.full and rank == 0 and world > 1:
         if stepper is not None:
             stepper.close()
             stepper = None
         rank0_baselines(out, kind, cfg, N, world, device, args.no_cpu_baseline)
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         bw_read, bw_copy = rank0_baselines(out, kind, cfg, N, world, device, no_cpu_baseline=True)   # (CPU baseline: last, below)
         if kind in ("particle", "checkers") and extras:
             # What one launch per tick cannot go below at this batch: the same number of 256-lane workgroups reading and
@@ -1616,7 +1625,7 @@ def main():
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_checkers(cfg) if kind == "checkers" else cpu_baseline(cfg, N)
     if rank == 0:
-        emit(out, args.extras_file)
+        emit(out, args.extras_file, write_default=args.full)
     if use_dist:
         dist.barrier(device_ids=[local_rank])
         dist.destroy_process_group()

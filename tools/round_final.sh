@@ -13,9 +13,9 @@ CM3_AMD_LIB=$R/tools/variants/libcm3_hip_span.so timeout 900 python tools/kernel
 grep "^{" "$O/kernel_span.txt" | tail -1 > "$O/kernel_span.json"; cp "$O/kernel_span.json" "$R/gpurun_out/r0${RN}_kernel_span.json"
 if [ -f "$R/tools/variants/libcm3_hip_marks.so" ]; then CM3_AMD_LIB=$R/tools/variants/libcm3_hip_marks.so timeout 600 python tools/kernel_span.py c2 c3 c5 > "$O/kernel_span_marks.txt" 2>&1; echo "marks rc=$?"; fi
 # (since round 5 the LAST stdout line is the driver's compact record, < 4 KB; the full record goes to --extras-file)
-timeout 1200 python bench.py --extras-file "$O/bench_c2.json" > "$O/bench_c2.stdout" 2> "$O/bench_c2.err"; echo "bench c2 rc=$?"
+timeout 1200 python bench.py --full --extras-file "$O/bench_c2.json" > "$O/bench_c2.stdout" 2> "$O/bench_c2.err"; echo "bench c2 rc=$?"
 tail -1 "$O/bench_c2.stdout" > "$O/driver_line_c2.json"; echo "driver line: $(wc -c < "$O/driver_line_c2.json") bytes"
-for wl in c3 c4 c5; do timeout 900 python bench.py --workload $wl --no-sweep --extras-file "$O/bench_$wl.json" > "$O/bench_$wl.stdout" 2> "$O/bench_$wl.err"; echo "bench $wl rc=$?"; tail -1 "$O/bench_$wl.stdout" > "$O/driver_line_$wl.json"; done
+for wl in c3 c4 c5; do timeout 900 python bench.py --workload $wl --full --no-sweep --extras-file "$O/bench_$wl.json" > "$O/bench_$wl.stdout" 2> "$O/bench_$wl.err"; echo "bench $wl rc=$?"; tail -1 "$O/bench_$wl.stdout" > "$O/driver_line_$wl.json"; done
 for wl in c2 c3 c4 c5; do python - "$O/bench_$wl.json" $wl <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
