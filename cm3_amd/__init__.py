@@ -32,4 +32,7 @@ def __getattr__(name):
     if name == "ParticleQmixAgent":
         from .qmix import ParticleQmixAgent
         return ParticleQmixAgent
+    if name == "CheckersQmixAgent":
+        from .qmix import CheckersQmixAgent
+        return CheckersQmixAgent
     raise AttributeError(name)

@@ -198,6 +198,8 @@ SYMBOLS = {
                                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, P(CheckersBufs), c_int32, c_void_p]),
     "cm3_actor_checkers_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersBufs),
                                               c_void_p]),
+    "cm3_qmix_checkers_pack": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), c_void_p, c_void_p]),
+    "cm3_qmix_checkers_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersBufs), c_void_p]),
     "cm3_returns_scratch_bytes": (c_size_t, []),
     "cm3_returns_moments_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_int32, c_int32, c_int32, c_double, c_void_p]),

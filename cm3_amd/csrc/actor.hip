@@ -726,10 +726,9 @@ namespace cm3 {
 //   layer 2 (64 -> 64): wave w owns columns [16w, 16w+16) as the actor's second layer, 16 k-steps x 4 row tiles.
 //   head (64 -> 5): one 16 x 16 tile per wave as actor_head_probs, ONE accumulator (k-ordered); argmax with the lowest index on
 //     ties (tf.argmax), then epsilon-greedy.
-// Exploration draws: a stream of its own, kPurposeExplore (below) -- two independent values per row, "explore?" and the uniform
-// action, stateless in (seed, global env id, episode, step, agent).
+// Exploration draws: the QMIX agents' own stream (explore_words in actor_common.h, shared with the Checkers agent) -- two
+// independent values per row, "explore?" and the uniform action, stateless in (seed, global env id, episode, step, agent).
 constexpr int kQH = 64;                     // both hidden widths (networks.py:585-589)
-constexpr uint32_t kPurposeExplore = 0x20000000u;   // | (agent >> 1) << 24; distinct from kAction (0), kReset (bit 31), kPolicy (bit 30)
 
 template <int N> struct QmixLayout {
   static constexpr int L = 4 * (N > 1 ? N - 1 : 1);
@@ -890,18 +889,7 @@ template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle
   __syncthreads();
   // exploration words first: the Philox rounds are VALU work that issues between the head's dependent matrix instructions
   uint32_t w_explore, w_action;
-  {
-    const uint64_t genv = (uint64_t)(p.env_id_base + (int64_t)he);
-    u32x4 ctr;
-    ctr.x = (uint32_t)genv;
-    ctr.y = (uint32_t)(genv >> 32);
-    ctr.z = 0u;
-    ctr.w = kPurposeExplore | ((uint32_t)(agent >> 1) << 24);
-    const u32x4 wd = philox4x32_10(ctr, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-    const bool odd = (agent & 1) != 0;
-    w_explore = action_word(odd ? wd.z : wd.x, head_episode, (uint32_t)head_steps);
-    w_action = action_word(odd ? wd.w : wd.y, head_episode, (uint32_t)head_steps);
-  }
+  explore_words(p.seed, (uint64_t)(p.env_id_base + (int64_t)he), head_episode, (uint32_t)head_steps, agent, w_explore, w_action);
   // ---- head "out": C[action][row] of rows [16w, 16w+16), bias as the start value, one k-ordered chain ----------------------
   float hx[kQH / 4];
 #pragma unroll
@@ -920,20 +908,8 @@ template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle
     const uint32_t y = sw[1];
     __builtin_memcpy(&q[4], &y, 4);
   }
-  // argmax, the first index on ties (tf.argmax, alg_qmix.py:98)
-  int greedy = 0;
-  float best = q[0];
-#pragma unroll
-  for (int a = 1; a < kA; ++a) {
-    const bool gt = q[a] > best;
-    greedy = gt ? a : greedy;
-    best = gt ? q[a] : best;
-  }
-  // epsilon-greedy (alg_qmix.py:177-182): explore with probability eps (compared in double: eps = 1 always explores), then a
-  // uniform action
-  const float eps = p.eps_dev ? *p.eps_dev : p.eps;
-  const bool explore = u01(w_explore) < (double)eps;
-  const int act = explore ? rand5(w_action) : greedy;
+  // argmax (the first index on ties: tf.argmax, alg_qmix.py:98), epsilon-greedy (alg_qmix.py:177-182)
+  const int act = epsilon_greedy(q, p.eps_dev ? *p.eps_dev : p.eps, w_explore, w_action);
   if (head_ok) {
     p.actions[hr] = act;
     if (p.q) {

@@ -438,8 +438,44 @@ __device__ __forceinline__ void ck_actor_head(const CkActorParams &p, const floa
   }
 }
 
-// BF16: the two 256 x 256 layers on the bf16 matrix cores (precision = 1, not a parity path); otherwise float32 throughout
-template <bool BF16> __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
+// ---- the QMIX agent's head (GREEDY instantiations): networks.Qmix_single_checkers (networks.py:617-637) is this forward pass with
+// the others branch at every agent count (p.stage = 2, Lo = 2 at N = 1), the output layer read as Q values (no softmax), and the
+// epsilon-greedy choice of alg_qmix_checkers.run_actor (alg_qmix_checkers.py:153-182) instead of sampling.
+// The exploration words of agent row 16 w + (l & 15) (lanes 0..15 use them): the stream of the particle agent (explore_words), keyed
+// with the counters ck_actor_head passes to actor_sample.
+__device__ __forceinline__ void ck_qmix_words(const CkActorParams &p, int w, int lane, size_t row_base, size_t rows, uint32_t &w_explore,
+                                              uint32_t &w_action) {
+  size_t row = row_base + 16 * w + (lane & 15);
+  row = row < rows ? row : rows - 1;
+  const size_t e = row / p.N;
+  const int i = (int)(row - e * p.N);
+  explore_words(p.seed, (uint64_t)(p.env_id_base + (int64_t)e), (uint32_t)p.episode[e], (uint32_t)p.steps[e], i, w_explore, w_action);
+}
+
+// lane l < 16 finishes row 16w + l on the same logits as ck_actor_head: argmax (the first index on ties), epsilon-greedy; the raw Q
+// values go to p.probs when it is set
+__device__ __forceinline__ void ck_qmix_head(const CkActorParams &p, const float (*sLG)[8], int w, int lane, size_t row_base, size_t rows,
+                                             uint32_t w_explore, uint32_t w_action) {
+  if (lane < 16) {
+    const size_t row = row_base + 16 * w + lane;
+    if (row < rows) {
+      float q[kA];
+#pragma unroll
+      for (int a = 0; a < kA; ++a) q[a] = sLG[16 * w + lane][a];
+      p.actions[row] = epsilon_greedy(q, p.eps_dev ? *p.eps_dev : p.eps, w_explore, w_action);
+      if (p.probs) {
+#pragma unroll
+        for (int a = 0; a < kA; ++a) p.probs[row * kA + a] = q[a];
+      }
+    }
+  }
+}
+
+// BF16: the two 256 x 256 layers on the bf16 matrix cores (precision = 1, not a parity path); otherwise float32 throughout.
+// GREEDY: the QMIX agent's head (ck_qmix_head) instead of the actor's sampling head (float32 only)
+template <bool BF16, bool GREEDY = false>
+__global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
+  static_assert(!(BF16 && GREEDY), "the QMIX agent has no bf16 build: argmax would flip");
   using namespace ck_actor;
   // H: [64][260] first-layer activations / h2; before that it holds X0 [64][84] and C1 [64][164]
   __shared__ __attribute__((aligned(16))) float sH[64 * kLdH];
@@ -622,6 +658,8 @@ template <bool BF16> __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorP
   __syncthreads();
   CM3_STAMP(11, false);
   // ---- actor_out : wave w finishes rows [16w, 16w + 16) -------------------------------------------------------------------------
+  uint32_t w_explore = 0u, w_action = 0u;
+  if constexpr (GREEDY) ck_qmix_words(p, w, lane, row_base, rows, w_explore, w_action);   // (VALU work between the head's MFMAs)
   {
     f32x4 acc[1][1];
     zero_tiles(acc);
@@ -635,7 +673,8 @@ template <bool BF16> __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorP
   }
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
-  ck_actor_head(p, sLG, w, lane, row_base, rows);
+  if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
+  else ck_actor_head(p, sLG, w, lane, row_base, rows);
   CM3_STAMP(12, true);
 }
 
@@ -1275,6 +1314,18 @@ __device__ __forceinline__ void ck_x3_stage_inputs(const CkActorParams &p, const
 }
 
 #ifndef CM3_NO_ENTRY_POINTS
+// GREEDY: the QMIX agent (ck_qmix_head); its exploration words are drawn behind branch_self's barrier, ahead of the h2 pass
+struct CkQmixHooks : CkNoHooks {
+  const CkActorParams *p;
+  int w, lane;
+  size_t row_base, rows;
+  uint32_t *w_explore, *w_action;
+  __device__ __forceinline__ void before_h2(f32x4 (&)[4][kCkBCT]) const {
+    if (w < 4) ck_qmix_words(*p, w, lane, row_base, rows, *w_explore, *w_action);
+  }
+};
+
+template <bool GREEDY = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_actor_x3(const CkActorParams p) {
   using namespace ck_actor;
   __shared__ __attribute__((aligned(16))) _Float16 sH[kCkX3HBytes / 2];
@@ -1302,11 +1353,25 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
   f32x4 acc2[4][kCkBCT];
   ck_x3_h2_bias(pk, w, lane, acc2);
   if (p.stage > 1) ck_x3_others(L, pk, w, lane, acc2);
-  ck_x3_self_chain(L, pk, w, lane, b_conv, acc2);
+  uint32_t w_explore = 0u, w_action = 0u;
+  if constexpr (GREEDY) {
+    CkQmixHooks hooks;
+    hooks.p = &p;
+    hooks.w = w;
+    hooks.lane = lane;
+    hooks.row_base = row_base;
+    hooks.rows = rows;
+    hooks.w_explore = &w_explore;
+    hooks.w_action = &w_action;
+    ck_x3_self_chain(L, pk, w, lane, b_conv, acc2, hooks);
+  } else {
+    ck_x3_self_chain(L, pk, w, lane, b_conv, acc2);
+  }
   if (w < 4) {
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    ck_actor_head(p, sLG, w, lane, row_base, rows);
+    if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
+    else ck_actor_head(p, sLG, w, lane, row_base, rows);
   }
   CM3_STAMP(12, true);
 }
@@ -1408,11 +1473,11 @@ extern "C" int cm3_actor_checkers_pack(const cm3_actor_checkers_desc *d, const c
   return CM3_OK;
 }
 
-extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
-                                      const cm3_actor_checkers_bufs *b, void *stream) {
-  using namespace cm3;
-  int rc = ck_actor_check(d);
-  if (rc != CM3_OK) return rc;
+namespace cm3 {
+// the checks and the parameters a forward launch shares (cm3_actor_checkers_f32, cm3_qmix_checkers_f32): every argument is checked
+// before anything touches the GPU
+static int ck_actor_call_params(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, const cm3_actor_checkers_bufs *b,
+                                CkActorParams &p) {
   CM3_REQUIRE(wt && b, "null weights/bufs");
   CM3_REQUIRE(d->n_envs > 0, "n_envs must be positive");
   CM3_REQUIRE(d->epsilon >= 0.0f && d->epsilon <= 1.0f, "epsilon must be in [0,1]");
@@ -1422,7 +1487,6 @@ extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm
               "missing buffers");
   CM3_REQUIRE(d->obs_self_t_stride >= d->n_agents * ck_actor::kObs, "obs_self_t_stride %d smaller than one env record",
               d->obs_self_t_stride);
-  CkActorParams p;
   memset(&p, 0, sizeof(p));
   p.E = d->n_envs;
   p.N = d->n_agents;
@@ -1444,12 +1508,81 @@ extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm
   p.actions = b->actions;
   p.probs = b->probs;
   p.packed = (const float *)wt->packed;
+  return CM3_OK;
+}
+}  // namespace cm3
+
+extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                      const cm3_actor_checkers_bufs *b, void *stream) {
+  using namespace cm3;
+  int rc = ck_actor_check(d);
+  if (rc != CM3_OK) return rc;
+  CkActorParams p;
+  rc = ck_actor_call_params(d, wt, b, p);
+  if (rc != CM3_OK) return rc;
   const size_t rows = (size_t)p.E * p.N;
   const dim3 grid((unsigned)((rows + 63) / 64));
   note_variant(d->precision == 2 ? "k_ck_actor_x3" : "k_ck_actor", 4, p.N, d->precision == 2 ? 8 : 4, 0, 0, 0, 0, 0, 0, d->precision);
   if (d->precision == 1) hipLaunchKernelGGL(k_ck_actor<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  else if (d->precision == 2) hipLaunchKernelGGL(k_ck_actor_x3, grid, dim3(512), 0, (hipStream_t)stream, p);
+  else if (d->precision == 2) hipLaunchKernelGGL(k_ck_actor_x3<>, grid, dim3(512), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(k_ck_actor<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+// ---- QMIX agent (ABI 9, additive): the actor's forward pass with the others branch at every agent count and the greedy head ---------
+namespace cm3 {
+static int ck_qmix_check(const cm3_actor_checkers_desc *d) {
+  using namespace ck_actor;
+  CM3_REQUIRE(d, "null desc");
+  CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= 8, "Checkers QMIX agent: n_agents must be in 1..8; got %d", d->n_agents);
+  CM3_REQUIRE(d->conv_f == kConvF && d->n_conv_linear == kLin && d->n_h1 == kH1 && d->n_h2 == kH2 && d->n_actions == kA,
+              "the Checkers QMIX agent's widths are the actor's nn block: conv_f 6 / conv_linear 32 / h1 256 / h2 256 / 5 actions; "
+              "got %d/%d/%d/%d/%d", d->conv_f, d->n_conv_linear, d->n_h1, d->n_h2, d->n_actions);
+  CM3_REQUIRE(d->n_obs == 2, "the Checkers QMIX agent reads 5x5x3 windows (n_obs = 2); got n_obs = %d", d->n_obs);
+  return CM3_OK;
+}
+}  // namespace cm3
+
+extern "C" int cm3_qmix_checkers_pack(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, void *packed,
+                                      void *stream) {
+  using namespace cm3;
+  int rc = ck_qmix_check(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(wt && packed, "null weights / packed buffer");
+  CM3_REQUIRE(wt->conv_w && wt->conv_b && wt->lin_w && wt->lin_b && wt->self_w && wt->self_b && wt->w_self_h2 &&
+                  wt->b_h2 && wt->out_w && wt->out_b, "missing weights");
+  CM3_REQUIRE(wt->others_w && wt->others_b && wt->w_others_h2,
+              "the QMIX agent network has the others branch at every agent count (networks.Qmix_single_checkers): "
+              "branch_others/kernel, branch_others/bias and W_others_h2 are required");
+  CkActorParams p;
+  memset(&p, 0, sizeof(p));
+  p.N = d->n_agents;
+  p.stage = 2;                                      // (desc->stage is not read)
+  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
+  ck_actor_weights(p, wt);
+  hipLaunchKernelGGL(k_ck_actor_pack, dim3(128), dim3(256), 0, (hipStream_t)stream, p, (float *)packed);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+extern "C" int cm3_qmix_checkers_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                     const cm3_actor_checkers_bufs *b, void *stream) {
+  using namespace cm3;
+  int rc = ck_qmix_check(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(d->precision == 0 || d->precision == 2,
+              "the Checkers QMIX agent runs at precision 0 (float32) or 2 (split float16); got %d (bf16 is not a parity path: argmax "
+              "would flip)", d->precision);
+  CkActorParams p;
+  rc = ck_actor_call_params(d, wt, b, p);
+  if (rc != CM3_OK) return rc;
+  p.stage = 2;                                      // the others branch at every N (Lo = 2 at N = 1)
+  const size_t rows = (size_t)p.E * p.N;
+  const dim3 grid((unsigned)((rows + 63) / 64));
+  note_variant(d->precision == 2 ? "k_ck_qmix_x3" : "k_ck_qmix", 4, p.N, d->precision == 2 ? 8 : 4, 0, 0, 0, 0, 0, 0, d->precision);
+  if (d->precision == 2) hipLaunchKernelGGL(k_ck_actor_x3<true>, grid, dim3(512), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((k_ck_actor<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }

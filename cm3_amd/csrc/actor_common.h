@@ -71,4 +71,39 @@ __device__ __forceinline__ int actor_sample(const float (&pr)[kA], uint64_t seed
   return actor_pick(pr, actor_uniform(seed, genv, episode, steps, agent));
 }
 
+// ---- the QMIX agents' epsilon-greedy choice (k_qmix_particle in actor.hip, k_ck_actor<.., true> / k_ck_actor_x3<true> in
+// actor_checkers.hip): ONE exploration stream for both.  Two independent words per (seed, global env id, episode, step, agent) --
+// "explore?" and the uniform action -- from a Philox block of their own purpose: words 2 (agent & 1) and 2 (agent & 1) + 1 of the
+// block (env id lo, env id hi, 0, kPurposeExplore | (agent >> 1) << 24), each mixed with the episode / step counters (action_word).
+// Callers issue it before their head's dependent matrix work: the Philox rounds are VALU work that fills the matrix waits.
+constexpr uint32_t kPurposeExplore = 0x20000000u;   // distinct from kAction (0), kReset (bit 31), kPolicy (bit 30)
+
+__device__ __forceinline__ void explore_words(uint64_t seed, uint64_t genv, uint32_t episode, uint32_t steps, int agent,
+                                              uint32_t &w_explore, uint32_t &w_action) {
+  u32x4 ctr;
+  ctr.x = (uint32_t)genv;
+  ctr.y = (uint32_t)(genv >> 32);
+  ctr.z = 0u;
+  ctr.w = kPurposeExplore | ((uint32_t)(agent >> 1) << 24);
+  const u32x4 wd = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const bool odd = (agent & 1) != 0;
+  w_explore = action_word(odd ? wd.z : wd.x, episode, steps);
+  w_action = action_word(odd ? wd.w : wd.y, episode, steps);
+}
+
+// argmax Q with the first index on ties (tf.argmax), replaced with probability eps by a uniform action (alg_qmix.py:177-182,
+// alg_qmix_checkers.py:176-181).  eps is compared in double: eps = 1 always explores.
+__device__ __forceinline__ int epsilon_greedy(const float (&q)[kA], float eps, uint32_t w_explore, uint32_t w_action) {
+  int greedy = 0;
+  float best = q[0];
+#pragma unroll
+  for (int a = 1; a < kA; ++a) {
+    const bool gt = q[a] > best;
+    greedy = gt ? a : greedy;
+    best = gt ? q[a] : best;
+  }
+  const bool explore = u01(w_explore) < (double)eps;
+  return explore ? rand5(w_action) : greedy;
+}
+
 }  // namespace cm3

@@ -35,7 +35,8 @@ def test_particle(env, actor, n_rounds=1, epsilon=0.0, rollout=None, reset=True)
 
 def test_checkers(env, actor, n_rounds=1, epsilon=0.0, rollout=None, generator=None, goals=None):
     """-> (reward_local_avg [N], reward_global_avg, n_episodes, dist_action [N,5]) like evaluate.test_checkers
-    (alg/evaluate.py:159-203) over n_rounds x env.n_envs episodes: goals = eye(N), or one random one-hot goal per episode
+    (alg/evaluate.py:159-203) over n_rounds x env.n_envs episodes (`actor`: a CheckersActor, a CheckersQmixAgent -- greedy at
+    epsilon = 0 -- or a host callable): goals = eye(N), or one random one-hot goal per episode
     when N == 1 (:167-173); actions_prev starts at zeros (:178); dist_action is the normalised action histogram the
     reference prints (:163,:183-184,:200-201).  goals (optional, one-hot [E,N,2]) replaces the draw (tests replay the goals
     the reference evaluator drew)."""

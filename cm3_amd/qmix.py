@@ -1,4 +1,5 @@
-"""ParticleQmixAgent -- the QMIX baseline's per-agent Q network and its epsilon-greedy choice, evaluated on the device.
+"""ParticleQmixAgent / CheckersQmixAgent -- the QMIX baseline's per-agent Q network and its epsilon-greedy choice, evaluated on
+the device (CheckersQmixAgent: see its docstring).
 
     reference                                                    here
     ---------------------------------------------------------   -----------------------------------------
@@ -112,4 +113,121 @@ class ParticleQmixAgent(object):
         q = torch.empty(env.E, env.n, N_ACTIONS, dtype=torch.float32, device=self.device) if return_q else None
         self.enqueue(env.E, env._obs_others[cur], env._state[cur], env._goals, env._meta, env._episode, actions,
                      epsilon, q, env_id_base=env.env_id_base, dtype=env.dtype)
+        return (actions, q) if return_q else actions
+
+
+# ---- Checkers -------------------------------------------------------------------------------------------------------------------
+# the thirteen variables of networks.Qmix_single_checkers (networks.py:617-637) by the fields of cm3_actor_checkers_weights
+CK_NAMES = {
+    "conv_w": "conv/Conv/weights", "conv_b": "conv/Conv/biases", "lin_w": "conv_linear/kernel", "lin_b": "conv_linear/bias",
+    "self_w": "branch_self/kernel", "self_b": "branch_self/bias", "w_self_h2": "W_self_h2",
+    "others_w": "branch_others/kernel", "others_b": "branch_others/bias", "w_others_h2": "W_others_h2", "b_h2": "b",
+    "out_w": "Qmix_single_out/kernel", "out_b": "Qmix_single_out/bias"}
+CK_PRECISIONS = {"f32": 0, "f16x3": 2}       # cm3_actor_checkers_desc.precision (bf16 is refused: argmax would flip)
+
+
+class CheckersQmixAgent(object):
+    """The QMIX baseline's Checkers agent network and its epsilon-greedy choice, evaluated on the device.
+
+        reference                                                        here
+        -------------------------------------------------------------   ----------------------------------------
+        networks.Qmix_single_checkers(a_prev, t_obs_self, v_obs_self,    CheckersQmixAgent(weights, n_agents)
+            v_obs_others, v_goal, f1=6, k1=[3,3], n_h1=256, n_h2=256)      weights: dict keyed by the TF variable names
+            (networks.py:617-637; variables Agent_main/...)
+        argmax Q, else uniform with probability epsilon                  agent.act(env, epsilon, actions_prev)
+            (alg_qmix_checkers.py:90, run_actor :153-182)                  -> actions [E, N] (one launch)
+        alg.run_actor(actions_prev, obs_others, obs_self_t, obs_self_v,  CheckersRollout.collect(goals, policy=agent,
+            goals, eps, sess)  (train_offpolicy.py:316-317)                epsilon=..): agent and step launches alternate
+                                                                           inside ONE hipGraph
+
+    The network is the CM3 Checkers actor's forward pass (csrc/actor_checkers.hip) with the others branch at every agent count
+    and a greedy head.  precision: "f32" (every layer on the exact-f32 MFMA) or "f16x3" (every layer in split float16, the
+    actor's precision 2).  Exploration draws come from the particle QMIX agent's stream (keyed with the Checkers env's episode
+    and step counters).  The one-launch rollout kernel runs the CM3 actor: CheckersRollout runs this agent as launch pairs.
+    """
+
+    def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0, precision="f32"):
+        from .actor import CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2
+        if precision not in CK_PRECISIONS:
+            raise Cm3Error("precision must be one of %s (bf16 is not a parity path: argmax would flip)" % sorted(CK_PRECISIONS))
+        self.device = _lib.require_gpu(device)
+        self.precision = precision
+        self.n = int(n_agents)
+        if not 1 <= self.n <= 8:
+            raise Cm3Error("the Checkers QMIX agent supports 1..8 agents")
+        self.Lo = 2 * max(self.n - 1, 1)
+        self.seed = int(seed)
+        self.env_id_base = int(env_id_base)
+        self._widths = (CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2)
+        src = {_canon(k): v for k, v in weights.items()}
+        shapes = {"conv_w": (3, 3, 3, CK_CONV_F), "conv_b": (CK_CONV_F,), "lin_w": (25 * CK_CONV_F, CK_CONV_LIN),
+                  "lin_b": (CK_CONV_LIN,), "self_w": (CK_CONV_LIN + 4 + N_ACTIONS + 2, CK_H1), "self_b": (CK_H1,),
+                  "w_self_h2": (CK_H1, CK_H2), "others_w": (self.Lo, CK_H1), "others_b": (CK_H1,),
+                  "w_others_h2": (CK_H1, CK_H2), "b_h2": (CK_H2,), "out_w": (CK_H2, N_ACTIONS), "out_b": (N_ACTIONS,)}
+        self.w = {}
+        for short, shape in shapes.items():
+            name = CK_NAMES[short]
+            if name not in src:
+                raise Cm3Error("missing QMIX weight %r" % name)
+            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise Cm3Error("QMIX weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            self.w[short] = t.to(self.device)
+        self._wt = _lib.ActorCheckersWeights()
+        for short in CK_NAMES:
+            setattr(self._wt, short, _lib.ptr(self.w[short]))
+        self._lib = _lib.lib()
+        nbytes = self._lib.cm3_actor_checkers_packed_bytes()
+        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        self._wt.packed = self._packed.data_ptr()
+        self.repack()
+
+    def _desc(self, n_envs, epsilon, env_id_base, obst_stride):
+        conv_f, lin, h1, h2 = self._widths
+        d = _lib.ActorCheckersDesc()
+        d.n_envs, d.n_agents, d.stage, d.n_obs = int(n_envs), self.n, 2, 2
+        d.conv_f, d.n_conv_linear, d.n_h1, d.n_h2, d.n_actions = conv_f, lin, h1, h2, N_ACTIONS
+        d.epsilon = float(epsilon)
+        d.precision = CK_PRECISIONS[self.precision]
+        d.obs_self_t_stride = int(obst_stride)
+        d.env_id_base = int(env_id_base)
+        d.seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        return d
+
+    def repack(self):
+        """Re-arrange the (possibly updated in place) TF-shaped weights into the forward kernel's layout: after every update."""
+        d = self._desc(1, 0.0, 0, 75 * self.n)
+        _lib.check(self._lib.cm3_qmix_checkers_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
+                                                    _lib.current_stream_handle(self.device)))
+
+    def enqueue(self, n_envs, obs_self_t_raw, obst_stride, obs_self_v, obs_others, goals, actions_prev, steps, episode,
+                actions, epsilon, probs=None, stream=None, env_id_base=None, prev_done=None):
+        """Raw launch on the env's device buffers, the signature of CheckersActor.enqueue.  probs (optional) receives the Q
+        values float32 [E, N, 5]."""
+        b = _lib.ActorCheckersBufs()
+        b.obs_self_t, b.obs_self_v, b.obs_others = _lib.ptr(obs_self_t_raw), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
+        b.goals, b.actions_prev, b.steps, b.episode = (_lib.ptr(goals), _lib.ptr(actions_prev), _lib.ptr(steps),
+                                                       _lib.ptr(episode))
+        b.actions, b.probs = _lib.ptr(actions), _lib.ptr(probs)
+        b.prev_done = _lib.ptr(prev_done)
+        epsilon, b.epsilon_dev = _epsilon_args(epsilon)
+        d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base, obst_stride)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_qmix_checkers_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
+
+    def act(self, env, epsilon, actions_prev=None, return_q=False):
+        """Actions [E, N] int32 for the env's CURRENT observation (alg_qmix_checkers.run_actor); actions_prev None = zeros
+        (train_offpolicy.py:300); optionally the Q values [E, N, 5] (float32)."""
+        if env.n != self.n:
+            raise Cm3Error("QMIX agent built for %d agents, env has %d" % (self.n, env.n))
+        if env.K != 5:
+            raise Cm3Error("the device agent reads 5x5 windows (n_obs = 2)")
+        s = env._slots[env._cur]
+        prev = None
+        if actions_prev is not None:
+            prev = torch.as_tensor(actions_prev, device=self.device).to(torch.int32).reshape(env.E, env.n).contiguous()
+        actions = torch.empty(env.E, env.n, dtype=torch.int32, device=self.device)
+        q = torch.empty(env.E, env.n, N_ACTIONS, dtype=torch.float32, device=self.device) if return_q else None
+        self.enqueue(env.E, s["obs_self_t_raw"], env.obst_stride, s["obs_self_v"], s["obs_others"], env._goals, prev,
+                     env._steps, env._episode, actions, epsilon, q, env_id_base=env._desc.env_id_base)
         return (actions, q) if return_q else actions

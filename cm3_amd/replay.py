@@ -197,8 +197,8 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
     from it (:350) for a training step.  Vectorised: `rollout` (a ParticleRollout / CheckersRollout in continuous mode with
     n_ticks = steps_per_train) collects one chunk of ticks for all its envs, all transitions of the chunk are added to `buffer`
     (DeviceReplayBuffer: ONE launch) and one batch is sampled -- yielded as device columns; `collect_kwargs` go to
-    rollout.collect() (policy=..., epsilon=..., goals=... for Checkers; policy= a ParticleQmixAgent is the QMIX baseline's
-    collection, train_offpolicy.py:319 with use_qmix = 1).  The buffer outlives the chunks: old transitions are
+    rollout.collect() (policy=..., epsilon=..., goals=... for Checkers; policy= a ParticleQmixAgent / CheckersQmixAgent is the
+    QMIX baseline's collection, train_offpolicy.py:319 / :317 with use_qmix = 1).  The buffer outlives the chunks: old transitions are
     overwritten only when it is full (replay_buffer.py:11-16)."""
     dual = isinstance(buffer, DeviceDualReplayBuffer)
     if dual and not hasattr(rollout, "episode_is_bad"):

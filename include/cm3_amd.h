@@ -47,6 +47,7 @@ extern "C" {
 #endif
 
 #define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
+                                  Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network).
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -494,6 +495,25 @@ int cm3_actor_checkers_pack(const cm3_actor_checkers_desc *desc, const cm3_actor
                             void *stream);
 int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
                            const cm3_actor_checkers_bufs *bufs, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * On-device Checkers QMIX agent (part of ABI 9, additive): networks.Qmix_single_checkers (networks.py:617-637) + the
+ * epsilon-greedy choice of alg_qmix_checkers.run_actor (alg_qmix_checkers.py:153-182), for all E*N agent rows in one launch.
+ * The network is the actor's above with three differences: the others branch exists at every agent count (N = 1 included: its
+ * input is the agent's own normalised position, 2 values), the output layer ("Qmix_single_out") gives Q values (no softmax),
+ * and the head takes argmax Q (the first index on ties), replaced with probability epsilon by a uniform action.  Same structs:
+ * weights under the names "conv/Conv/...", "conv_linear", "branch_self", "W_self_h2", "branch_others", "W_others_h2", "b",
+ * "Qmix_single_out" (out_w / out_b), all thirteen required; desc->stage is not read; precision 0 (float32) or 2 (split
+ * float16) -- 1 (bf16) is refused; epsilon from desc->epsilon or bufs->epsilon_dev.  Outputs: actions int32 [E][N] and, when
+ * bufs->probs is set, the raw Q values float [E][N][5].  The two exploration draws per agent-step come from the stream of the
+ * particle QMIX agent (cm3_qmix_particle_f32), keyed (seed, global env id, episode, step, agent).
+ * ---------------------------------------------------------------------------------------- */
+/* Packs into cm3_actor_checkers_packed_bytes() bytes; one small launch per weight update. */
+int cm3_qmix_checkers_pack(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights, void *packed,
+                           void *stream);
+/* Reads ONLY weights->packed (written by cm3_qmix_checkers_pack). */
+int cm3_qmix_checkers_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
+                          const cm3_actor_checkers_bufs *bufs, void *stream);
 
 /* A whole POLICY-DRIVEN Checkers rollout in ONE launch (ABI 7; csrc/policy_checkers.hip): per tick the actor above (precision 2),
  * epsilon-mixed sampling and Checkers.step with the actions just drawn -- train_onpolicy.py:309-347 / train_offpolicy.py:309-368 without
