@@ -67,6 +67,13 @@ class TransitionCols(ctypes.Structure):
                                         "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
 
 
+class CheckersTransitionCols(ctypes.Structure):
+    # (the pointer fields carry the names of CheckersRollout.ORDER, in its order)
+    _fields_ = [(n, c_void_p) for n in ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions_prev", "actions", "reward",
+                                        "local_rewards", "next_grid", "next_vec", "next_obs_others", "next_obs_self_t",
+                                        "next_obs_self_v", "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
+
+
 class RowCols(ctypes.Structure):
     _fields_ = [("n_cols", c_int32), ("reserved", c_int32), ("dst", c_void_p * 16), ("src", c_void_p * 16),
                 ("row_bytes", ctypes.c_uint32 * 16)]
@@ -189,6 +196,8 @@ SYMBOLS = {
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
     "cm3_transitions_gather_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), c_void_p, c_size_t, c_void_p, c_void_p, c_int64,
                                                   P(TransitionCols), c_void_p]),
+    "cm3_checkers_transitions_gather": (ctypes.c_int, [P(CheckersDesc), P(CheckersTraj), c_void_p, c_void_p, c_void_p, c_int64,
+                                                       P(CheckersTransitionCols), c_void_p]),
     "cm3_rows_scatter": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "cm3_rows_gather": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_void_p]),
     "cm3_rows_tile": (ctypes.c_int, [P(TileCol), c_int32, c_void_p]),

@@ -265,6 +265,170 @@ __global__ void __launch_bounds__(256) k_transitions_gather(const TransParams p)
   }
 }
 
+// ---- the reference's 16-column Checkers transition, gathered from the trajectory ---------------------------------------------------
+// (alg_credit_checkers.py:427-444: float64 throughout, while the trajectory keeps grid / obs_self_t as int8 and vec as int32 -- the
+// export EXPANDS: at the reference geometry with N = 2 a transition reads ~0.7 KB and writes 3.65 KB, so the kernel is store-bound.)
+// A lane per (transition, output unit), the units of ONE column per workgroup: column c owns the blocks [blk_end[c - 1], blk_end[c])
+// and block j of it the units [1024 j, 1024 (j + 1)) of the column in row-major order, unit g = b * units_per_row + u.  Consecutive
+// lanes therefore write consecutive 16-byte (8- / 4- / 1-byte) pieces of the column: a wave's store is one contiguous KiB whatever the
+// row size (432 B for grid, 1200 B for obs_self_t at N = 2), and because every source is [slot][env][record] the loads of a
+// whole-trajectory export are contiguous too.  The column -- and with it the unit kind, the need for the done byte and every table
+// entry -- is uniform over the workgroup: scalar loads from the kernel arguments, no per-lane table lookup (which would go through
+// scratch) and no divergent kind switch.
+// A 16-byte unit of grid / obs_self_t is two doubles made from two source BYTES: one 2-byte load where every record starts on an even
+// address (padded records; unpadded ones with an even record size), else two byte loads (75 N-byte records at odd N > 1 -- at N = 1
+// the row is 75 doubles, not a multiple of 16 bytes, and the column takes 8-byte units of one source byte each).
+// As in k_transitions_gather every lane carries FOUR units: their (tt, ee), then their done bytes, then their data are requested
+// together, and only next_* under terminal capture, actions_prev and the done column ask for a done byte at all.
+enum CkUnitKind : uint32_t {
+  CKU_I8X2,     // 2 int8 -> 2 doubles (16 B)
+  CKU_I8,       // 1 int8 -> 1 double (8 B)
+  CKU_I32X2,    // 2 int32 -> 2 doubles (16 B)
+  CKU_COPY16,
+  CKU_COPY8,
+  CKU_COPY4,
+  CKU_PREV,     // actions_prev: actions[t - 1] (zeros behind a done under terminal capture), prev0 at t = 0 (4 B)
+  CKU_DONE,     // done[t][e] != 0 (1 B)
+  CKU_GOAL      // goal byte -> int64 one-hot pair (16 B)
+};
+constexpr int kCkCols = 16;
+constexpr int kCkUnitsPerLane = 4;
+
+struct CkCol {
+  const char *src;      // slot 0 of the source array
+  const char *alt;      // next_* under terminal capture: the term_* array (slot t, taken where done[t][e]); else NULL
+  char *dst;
+  size_t slot_stride, alt_stride;   // bytes between slots
+  uint32_t env_stride;  // bytes between the env records of a slot
+  uint32_t upr;         // units per output row
+  uint32_t kind;
+  uint32_t next;        // 1: the source slot is t + 1
+};
+struct CkTransParams {
+  CkCol col[kCkCols];
+  uint32_t blk_end[kCkCols];
+  const uint8_t *done;
+  const int32_t *prev0;
+  const int64_t *tt, *ee;
+  size_t st_done;
+  size_t n, E;
+  size_t ring_start, ring_size;
+  int term;             // the trajectory has terminal capture
+  int pair16;           // every int8 record starts on an even address
+};
+
+__device__ __forceinline__ uint32_t ck_src_bytes(uint32_t kind) {
+  return kind == CKU_I8X2 ? 2u : kind == CKU_I8 || kind == CKU_GOAL ? 1u : kind == CKU_COPY16 ? 16u
+       : kind == CKU_I32X2 || kind == CKU_COPY8 ? 8u : kind == CKU_DONE ? 0u : 4u;
+}
+__device__ __host__ __forceinline__ uint32_t ck_dst_bytes(uint32_t kind) {
+  return kind == CKU_I8 || kind == CKU_COPY8 ? 8u : kind == CKU_COPY4 || kind == CKU_PREV ? 4u : kind == CKU_DONE ? 1u : 16u;
+}
+
+template <typename I> __global__ void __launch_bounds__(256) k_ck_transitions_gather(const CkTransParams p) {
+  constexpr int K = kCkUnitsPerLane;
+  int c = 0;
+  uint32_t first = 0;
+#pragma unroll
+  for (int k = 0; k < kCkCols - 1; ++k)
+    if (blockIdx.x >= p.blk_end[k]) { c = k + 1; first = p.blk_end[k]; }
+  const CkCol &C = p.col[c];
+  const uint32_t kind = C.kind, upr = C.upr, sb = ck_src_bytes(kind), db = ck_dst_bytes(kind);
+  const I total = (I)(p.n * upr);
+  const I g0 = (I)(blockIdx.x - first) * (I)(K * 256) + (I)threadIdx.x;
+  size_t bb[K], ee[K];
+  int64_t tt[K];
+  uint32_t uu[K];
+  bool live[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const I g = g0 + (I)(k * 256);
+    live[k] = g < total;
+    const I gc = live[k] ? g : total - 1;      // (lanes past the end repeat the last unit's loads and store nothing)
+    const I b = gc / (I)upr;
+    uu[k] = (uint32_t)(gc - b * (I)upr);
+    bb[k] = (size_t)b;
+    if (p.tt) {
+      tt[k] = p.tt[b];
+      ee[k] = (size_t)p.ee[b];
+    } else {                                   // the whole trajectory in time-major order: b = t E + e
+      const I t = b / (I)p.E;
+      tt[k] = (int64_t)t;
+      ee[k] = (size_t)(b - t * (I)p.E);
+    }
+  }
+  uint8_t dd[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    dd[k] = 0;
+    if (kind == CKU_PREV) {
+      if (p.term && tt[k] > 0) dd[k] = tick_of(p.done, p.st_done, tt[k] - 1)[ee[k]];
+    } else if (C.alt || kind == CKU_DONE) {
+      dd[k] = tick_of(p.done, p.st_done, tt[k])[ee[k]];
+    }
+  }
+  uint4 val[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const size_t off = ee[k] * C.env_stride + (size_t)uu[k] * sb;
+    const char *s;
+    if (kind == CKU_PREV)
+      s = tt[k] > 0 ? C.src + C.slot_stride * (size_t)(tt[k] - 1) + off : reinterpret_cast<const char *>(p.prev0) + off;
+    else if (C.alt && dd[k])
+      s = C.alt + C.alt_stride * (size_t)tt[k] + off;
+    else
+      s = C.src + C.slot_stride * (size_t)(tt[k] + C.next) + off;
+    val[k] = uint4{0u, 0u, 0u, 0u};
+    if (kind == CKU_COPY16) {
+      val[k] = *reinterpret_cast<const uint4 *>(s);
+    } else if (kind == CKU_I32X2 || kind == CKU_COPY8) {
+      const uint2 w = *reinterpret_cast<const uint2 *>(s);
+      val[k].x = w.x;
+      val[k].y = w.y;
+    } else if (kind == CKU_COPY4 || kind == CKU_PREV) {
+      val[k].x = *reinterpret_cast<const uint32_t *>(s);
+    } else if (kind == CKU_I8X2) {
+      if (p.pair16) {
+        val[k].x = *reinterpret_cast<const uint16_t *>(s);
+      } else {
+        val[k].x = (uint32_t)reinterpret_cast<const uint8_t *>(s)[0] | ((uint32_t)reinterpret_cast<const uint8_t *>(s)[1] << 8);
+      }
+    } else if (kind != CKU_DONE) {             // CKU_I8, CKU_GOAL
+      val[k].x = *reinterpret_cast<const uint8_t *>(s);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (!live[k]) continue;
+    size_t row = bb[k];
+    if (p.ring_size) {
+      row += p.ring_start;
+      row = row >= p.ring_size ? row - p.ring_size : row;
+    }
+    char *d = C.dst + (row * upr + uu[k]) * db;
+    const uint32_t x = val[k].x;
+    if (kind == CKU_I8X2) {
+      *reinterpret_cast<double2 *>(d) = double2{(double)(int8_t)(x & 0xffu), (double)(int8_t)(x >> 8)};
+    } else if (kind == CKU_I8) {
+      *reinterpret_cast<double *>(d) = (double)(int8_t)x;
+    } else if (kind == CKU_I32X2) {
+      *reinterpret_cast<double2 *>(d) = double2{(double)(int32_t)x, (double)(int32_t)val[k].y};
+    } else if (kind == CKU_COPY16) {
+      *reinterpret_cast<uint4 *>(d) = val[k];
+    } else if (kind == CKU_COPY8) {
+      *reinterpret_cast<uint2 *>(d) = uint2{x, val[k].y};
+    } else if (kind == CKU_COPY4) {
+      *reinterpret_cast<uint32_t *>(d) = x;
+    } else if (kind == CKU_PREV) {
+      *reinterpret_cast<uint32_t *>(d) = dd[k] ? 0u : x;
+    } else if (kind == CKU_DONE) {
+      *reinterpret_cast<uint8_t *>(d) = dd[k] ? 1 : 0;
+    } else {                                   // CKU_GOAL: one_hot(g, 2) as int64
+      *reinterpret_cast<uint4 *>(d) = uint4{x == 0u ? 1u : 0u, 0u, x == 1u ? 1u : 0u, 0u};
+    }
+  }
+}
+
 // ---- tiling: the n x n credit repeats and the n x n x l_action counterfactual tiling of train_step ------------------------------
 // (alg_credit.py:614-658 `np.repeat(np.reshape(x, [n_steps, n, d]), n, axis=0)` / `np.repeat(x, n, axis=0)`; :730-751 the same
 // repeated l_action times against np.tile(np.eye(l_action)); process_actions / process_global_state :406-443, :528-557 with their
@@ -465,6 +629,117 @@ int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle
   size_t blocks = (units + 4 * 256 - 1) / (4 * 256);     // four units per lane
   blocks = blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks);
   hipLaunchKernelGGL(k_transitions_gather, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+int cm3_checkers_transitions_gather(const cm3_checkers_desc *desc, const cm3_checkers_traj *traj, const int32_t *prev0,
+                                    const int64_t *tt, const int64_t *ee, int64_t n, const cm3_checkers_transition_cols *out,
+                                    void *stream) {
+  using namespace cm3;
+  CM3_REQUIRE(desc, "checkers_transitions_gather: null desc");
+  CM3_REQUIRE(traj, "checkers_transitions_gather: null traj");
+  CM3_REQUIRE(out, "checkers_transitions_gather: null out");
+  CM3_REQUIRE((tt == nullptr) == (ee == nullptr), "checkers_transitions_gather: tt and ee: both or neither");
+  CM3_REQUIRE(n >= 0, "n must be >= 0");
+  CM3_REQUIRE(out->ring_size >= 0 && out->ring_start >= 0 && (out->ring_size == 0 || (out->ring_start < out->ring_size && n <= out->ring_size)),
+              "checkers transition columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (n == 0) return CM3_OK;      // (before the pointer checks: the columns of an empty batch are null)
+  CM3_REQUIRE(desc->n_envs > 0, "n_envs must be positive");
+  CM3_REQUIRE(desc->n_agents >= 1 && desc->n_agents <= 8, "Checkers: n_agents must be in 1..8");
+  CM3_REQUIRE(desc->n_rows >= 1 && desc->n_columns >= 2 && desc->n_rows * desc->n_columns <= 64, "n_rows / n_columns out of range");
+  CM3_REQUIRE(desc->n_obs >= 0 && desc->n_obs <= 8, "n_obs out of range");
+  const uint32_t N = (uint32_t)desc->n_agents, Kw = 2u * (uint32_t)desc->n_obs + 1u, Lo = 2u * (N > 1 ? N - 1 : 1);
+  const uint32_t grid_rec = (uint32_t)desc->n_rows * (uint32_t)(desc->n_columns + 1) * 2u, obst_rec = N * Kw * Kw * 3u;
+  const uint32_t grid_stride = desc->grid_stride ? (uint32_t)desc->grid_stride : grid_rec;
+  const uint32_t obst_stride = desc->obs_self_t_stride ? (uint32_t)desc->obs_self_t_stride : obst_rec;
+  CM3_REQUIRE(desc->grid_stride >= 0 && desc->obs_self_t_stride >= 0 && grid_stride >= grid_rec && obst_stride >= obst_rec,
+              "record strides smaller than the records");
+  CM3_REQUIRE(prev0, "checkers_transitions_gather: prev0 (actions_prev of slot 0) is required");
+  CM3_REQUIRE(traj->actions && traj->grid && traj->vec && traj->obs_others && traj->obs_self_t && traj->obs_self_v &&
+                  traj->local_rewards && traj->reward && traj->done && (traj->goals_slots || traj->goals),
+              "trajectory base pointers are required");
+  const int n_term = (traj->term_grid != nullptr) + (traj->term_vec != nullptr) + (traj->term_obs_others != nullptr) +
+                     (traj->term_obs_self_t != nullptr) + (traj->term_obs_self_v != nullptr);
+  CM3_REQUIRE(n_term == 0 || n_term == 5, "terminal capture: all five term_* arrays or none");
+  const bool term = n_term == 5;
+  CkTransParams p;
+  memset(&p, 0, sizeof(p));
+  const bool obst_odd = (obst_rec & 1u) != 0;   // (a row of 75 N doubles at odd N: 8-byte units)
+  struct Spec {
+    const char *name;
+    void *dst;
+    const void *src, *alt;
+    size_t slot_stride, alt_stride;
+    uint32_t env_stride, upr, kind, next;
+  };
+  const uint32_t obst_kind = obst_odd ? CKU_I8 : CKU_I8X2, obst_upr = obst_odd ? obst_rec : obst_rec / 2;
+  const Spec specs[kCkCols] = {
+      {"grid", out->grid, traj->grid, nullptr, traj->grid_slot_stride, 0, grid_stride, grid_rec / 2, CKU_I8X2, 0},
+      {"vec", out->vec, traj->vec, nullptr, traj->vec_stride, 0, 16 * N, 2 * N, CKU_I32X2, 0},
+      {"obs_others", out->obs_others, traj->obs_others, nullptr, traj->obs_others_stride, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
+      {"obs_self_t", out->obs_self_t, traj->obs_self_t, nullptr, traj->obs_self_t_slot_stride, 0, obst_stride, obst_upr, obst_kind, 0},
+      {"obs_self_v", out->obs_self_v, traj->obs_self_v, nullptr, traj->obs_self_v_stride, 0, 32 * N, 2 * N, CKU_COPY16, 0},
+      {"actions_prev", out->actions_prev, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, N, CKU_PREV, 0},
+      {"actions", out->actions, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, N, CKU_COPY4, 0},
+      {"reward", out->reward, traj->reward, nullptr, traj->reward_stride, 0, 8, 1, CKU_COPY8, 0},
+      {"local_rewards", out->local_rewards, traj->local_rewards, nullptr, traj->local_rewards_stride, 0, 8 * N, N, CKU_COPY8, 0},
+      {"next_grid", out->next_grid, traj->grid, traj->term_grid, traj->grid_slot_stride, traj->term_grid_slot_stride, grid_stride,
+       grid_rec / 2, CKU_I8X2, 1},
+      {"next_vec", out->next_vec, traj->vec, traj->term_vec, traj->vec_stride, traj->term_vec_stride, 16 * N, 2 * N, CKU_I32X2, 1},
+      {"next_obs_others", out->next_obs_others, traj->obs_others, traj->term_obs_others, traj->obs_others_stride,
+       traj->term_obs_others_stride, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 1},
+      {"next_obs_self_t", out->next_obs_self_t, traj->obs_self_t, traj->term_obs_self_t, traj->obs_self_t_slot_stride,
+       traj->term_obs_self_t_slot_stride, obst_stride, obst_upr, obst_kind, 1},
+      {"next_obs_self_v", out->next_obs_self_v, traj->obs_self_v, traj->term_obs_self_v, traj->obs_self_v_stride,
+       traj->term_obs_self_v_stride, 32 * N, 2 * N, CKU_COPY16, 1},
+      {"done", out->done, traj->done, nullptr, traj->done_stride, 0, 1, 1, CKU_DONE, 0},
+      // goals: the slot's goal bytes where the trajectory records them, else the live array (stride 0: the same bytes for every tick)
+      {"goals", out->goals, traj->goals_slots ? traj->goals_slots : traj->goals, nullptr,
+       traj->goals_slots ? traj->goals_slots_stride : 0, 0, N, N, CKU_GOAL, 0},
+  };
+  size_t blocks = 0, most = 0;
+  bool even = true;
+  for (int k = 0; k < kCkCols; ++k) {
+    const Spec &s = specs[k];
+    CM3_REQUIRE(s.dst, "checkers transition columns: column %s is missing", s.name);
+    CM3_REQUIRE((uintptr_t)s.dst % ck_dst_bytes(s.kind) == 0, "checkers transition columns: column %s is not aligned to its %u-byte units",
+                s.name, ck_dst_bytes(s.kind));
+    CkCol &c = p.col[k];
+    c.src = (const char *)s.src;
+    c.alt = term ? (const char *)s.alt : nullptr;
+    c.dst = (char *)s.dst;
+    c.slot_stride = s.slot_stride;
+    c.alt_stride = c.alt ? s.alt_stride : 0;
+    c.env_stride = s.env_stride;
+    c.upr = s.upr;
+    c.kind = s.kind;
+    c.next = s.next;
+    if (s.kind == CKU_COPY16 || s.kind == CKU_I32X2)
+      CM3_REQUIRE(((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride) % (s.kind == CKU_COPY16 ? 16 : 8) == 0,
+                  "checkers trajectory: %s is not aligned to the loads of its units", s.name);
+    if (s.kind == CKU_I8X2) even = even && (((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride | c.env_stride) & 1u) == 0;
+    const size_t units = (size_t)n * s.upr;
+    most = units > most ? units : most;
+    blocks += (units + kCkUnitsPerLane * 256 - 1) / (kCkUnitsPerLane * 256);
+    CM3_REQUIRE(blocks < ((size_t)1 << 31), "checkers_transitions_gather: too many transitions for one launch");
+    p.blk_end[k] = (uint32_t)blocks;
+  }
+  p.done = traj->done;
+  p.st_done = traj->done_stride;
+  p.prev0 = prev0;
+  p.tt = tt;
+  p.ee = ee;
+  p.n = (size_t)n;
+  p.E = (size_t)desc->n_envs;
+  p.ring_start = (size_t)out->ring_start;
+  p.ring_size = (size_t)out->ring_size;
+  p.term = term ? 1 : 0;
+  p.pair16 = even ? 1 : 0;
+  if (most + kCkUnitsPerLane * 256 < (size_t)1 << 32)     // (32-bit unit arithmetic: a 64-bit division per unit costs more than the copy)
+    hipLaunchKernelGGL(k_ck_transitions_gather<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(k_ck_transitions_gather<size_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }

@@ -5,7 +5,8 @@
                                      (particle: scenario.collisions != 0, train_onpolicy.py:356)
   log.csv / log_century.csv columns  alg/train_onpolicy.py:200-221, :399-429
 Transitions are the columns ParticleRollout / CheckersRollout export (numpy=False): each ring stores one tensor per
-column; adding a whole vectorised rollout is ONE launch (cm3_rows_scatter, csrc/batch.hip), sampling is one gather launch.
+column; adding a whole vectorised rollout is ONE launch (cm3_rows_scatter, or the export kernels of csrc/batch.hip writing ring rows),
+sampling is one gather launch.
 """
 import torch
 
@@ -90,15 +91,24 @@ class DeviceReplayBuffer(object):
         _lib.rows_scatter(pairs, kept, self._stream(), ring_start=start, ring_size=self.maxsize)
 
     def add_rollout(self, rollout):
-        """All transitions of a ParticleRollout's continuous float32 collection, straight from the trajectory into the ring: ONE
-        launch (cm3_transitions_gather_f32 with ring positions as its output rows) instead of an export followed by an add, and no
-        intermediate copy of the phase.  The reference stores the same array as v_global and v_local (train_onpolicy.py:338): so does
-        the ring (one tensor under both names)."""
+        """All transitions of a continuous collection, straight from the trajectory into the ring: ONE launch (the export kernel with
+        ring positions as its output rows) instead of an export followed by an add, and no intermediate copy of the phase.
+        ParticleRollout (float32): cm3_transitions_gather_f32.  The reference stores the same array as v_global and v_local
+        (train_onpolicy.py:338): so does the ring (one tensor under both names).
+        CheckersRollout: cm3_checkers_transitions_gather; the ring holds the 16 columns of as_reference_batch(numpy=False) with their
+        dtypes, so it is interchangeable with one that add() allocated."""
+        from .rollout import CheckersRollout
         env = rollout.env
-        B, N, L = rollout.T * env.E, env.n, env.L
+        B = rollout.T * env.E
         if B > self.maxsize:                                   # (more than the ring holds: the newest survive, as sequential adds leave)
             return self.add(rollout.as_reference_batch(numpy=False))
-        if self.cols is None:
+        if isinstance(rollout, CheckersRollout):
+            if not rollout.auto_reset:
+                raise Cm3Error("add_rollout needs a continuous collection (every transition valid)")
+            if self.cols is None:
+                self.cols = rollout.empty_columns(self.maxsize, zero=True)
+        elif self.cols is None:
+            N, L = env.n, env.L
             z = lambda *shape, dt=torch.float32: torch.zeros((self.maxsize,) + shape, dtype=dt, device=self.device)   # noqa: E731
             st, nst = z(N, 4), z(N, 4)
             self.cols = dict(v_global=st, obs_others=z(N, L), v_local=st, actions=z(N, dt=torch.int32), reward=z(), reward_local=z(N),
@@ -211,12 +221,21 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
             # (ParticleRollout.episode_is_bad); transitions of episodes still running at the chunk's end take the flag so far
             cols = rollout.as_reference_batch(numpy=False)
             buffer.add({k: v.contiguous() for k, v in cols.items()}, _transition_flags(rollout))
-        elif hasattr(rollout, "export_into") and rollout.auto_reset and rollout.state.dtype == torch.float32 and hasattr(buffer, "add_rollout"):
+        elif _exports_into_rings(rollout) and hasattr(buffer, "add_rollout"):
             buffer.add_rollout(rollout)                                   # export + add in one launch
         else:
             cols = rollout.as_reference_batch(numpy=False)
             buffer.add({k: v.contiguous() for k, v in cols.items()})
         yield buffer.sample_batch(batch_size, generator=generator)
+
+
+def _exports_into_rings(rollout):
+    """A continuous collection whose class writes its transitions straight into ring rows (export_into): a CheckersRollout, or the
+    float32 instantiation of a ParticleRollout (the float64 parity instantiation exports through the torch composition)."""
+    if not (hasattr(rollout, "export_into") and rollout.auto_reset):
+        return False
+    state = getattr(rollout, "state", None)               # (a CheckersRollout has none: its records are int8 / int32 / float64)
+    return state is None or state.dtype == torch.float32
 
 
 def _transition_flags(rollout):

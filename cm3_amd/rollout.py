@@ -119,7 +119,66 @@ class _ActorGraphCache(object):
             self.graph = self.policy = None
 
 
-class ParticleRollout(object):
+class _TransitionSampling(object):
+    """What ParticleRollout and CheckersRollout share on the sampling side: draws over the valid transitions of the trajectory and
+    the one-launch export of a whole phase of minibatches.  The class supplies T, env, auto_reset, valid_indices() and
+    as_reference_batch(tt, ee, numpy, out)."""
+
+    last_sample_positions = None
+
+    def _sample_positions(self, size, rows, generator):
+        """int64 [rows, k] positions into the valid transitions (time-major), each row `size` distinct ones uniformly at random
+        (random.sample, replay_buffer.py:34), or all of them when there are <= size -- and the (tt, ee) of all valid transitions,
+        None when every transition is valid (continuous collection: position b = t E + e, nothing to enumerate)."""
+        if self.auto_reset:
+            n, tt, ee = self.T * self.env.E, None, None
+        else:
+            tt, ee = self.valid_indices()
+            n = tt.numel()
+        if n <= size:
+            return torch.arange(n, device=self.env.device).unsqueeze(0).expand(rows, n), tt, ee
+        return sample_distinct(n, size, rows, generator, self.env.device), tt, ee
+
+    def sample_batch(self, size, generator=None, numpy=True):
+        """replay_buffer.sample_batch (replay_buffer.py:28-37): all transitions if there are <= size of them,
+        else `size` distinct ones uniformly at random."""
+        pos, tt, ee = self._sample_positions(size, 1, generator)
+        pos = pos[0]
+        if tt is None:
+            E = self.env.E
+            if pos.numel() == self.T * E:
+                return self.as_reference_batch(numpy=numpy)
+            return self.as_reference_batch(torch.div(pos, E, rounding_mode="floor"), pos % E, numpy=numpy)
+        return self.as_reference_batch(tt[pos], ee[pos], numpy=numpy)
+
+    def on_policy_minibatches(self, epochs=24, batch_size=128, generator=None, numpy=False):
+        """The on-policy cadence of train_onpolicy.py:359-377: after a collection phase, `epochs` minibatches of
+        `batch_size` transitions are sampled from the freshly collected buffer, which is then discarded (the next
+        collect() overwrites the trajectory).  The reference collects episodes_per_train = 10 episodes (<= 330
+        transitions) per phase; a vectorised phase holds n_envs episodes.
+        All minibatches of the phase are drawn together and exported by ONE launch (round 5: 24 separate samples cost 24 permutations
+        of the phase's 1.35 M transitions, 7 ms against the 0.8 ms of collecting them); each yielded dict holds views of that export."""
+        cols, k = self._phase_export(epochs, batch_size, generator)
+        for m in range(int(epochs)):
+            mb = {name: v[m * k:(m + 1) * k] for name, v in cols.items()}
+            yield ({name: v.detach().cpu().numpy() for name, v in mb.items()} if numpy else mb)
+
+    def _phase_export(self, epochs, batch_size, generator, out=None):
+        """-> (columns of all `epochs` minibatches back to back [epochs * k, ...], k = transitions per minibatch): one draw, one launch"""
+        epochs = int(epochs)
+        pos, tt, ee = self._sample_positions(batch_size, epochs, generator)
+        self.last_sample_positions = pos          # (tests: which transitions the minibatches hold)
+        k = pos.shape[1]
+        flat = pos.reshape(-1)
+        if tt is None:
+            E = self.env.E
+            cols = self.as_reference_batch(torch.div(flat, E, rounding_mode="floor"), flat % E, numpy=False, out=out)
+        else:
+            cols = self.as_reference_batch(tt[flat], ee[flat], numpy=False, out=out)
+        return cols, k
+
+
+class ParticleRollout(_TransitionSampling):
     """T-tick trajectory over a VecParticleEnv.
 
     env.auto_reset False: episode-synchronous -- reset all envs, run T = max_steps ticks, transitions of
@@ -738,57 +797,6 @@ class ParticleRollout(object):
         (dtype=object, as NumPy >= 1.24 requires for ragged rows)."""
         return rows_from_columns(self.as_reference_batch(tt, ee), self.ORDER)
 
-    def _sample_positions(self, size, rows, generator):
-        """int64 [rows, k] positions into the valid transitions (time-major), each row `size` distinct ones uniformly at random
-        (random.sample, replay_buffer.py:34), or all of them when there are <= size -- and the (tt, ee) of all valid transitions,
-        None when every transition is valid (continuous collection: position b = t E + e, nothing to enumerate)."""
-        if self.auto_reset:
-            n, tt, ee = self.T * self.env.E, None, None
-        else:
-            tt, ee = self.valid_indices()
-            n = tt.numel()
-        if n <= size:
-            return torch.arange(n, device=self.env.device).unsqueeze(0).expand(rows, n), tt, ee
-        return sample_distinct(n, size, rows, generator, self.env.device), tt, ee
-
-    def sample_batch(self, size, generator=None, numpy=True):
-        """replay_buffer.sample_batch (replay_buffer.py:28-37): all transitions if there are <= size of them,
-        else `size` distinct ones uniformly at random."""
-        pos, tt, ee = self._sample_positions(size, 1, generator)
-        pos = pos[0]
-        if tt is None:
-            E = self.env.E
-            if pos.numel() == self.T * E:
-                return self.as_reference_batch(numpy=numpy)
-            return self.as_reference_batch(torch.div(pos, E, rounding_mode="floor"), pos % E, numpy=numpy)
-        return self.as_reference_batch(tt[pos], ee[pos], numpy=numpy)
-
-    def on_policy_minibatches(self, epochs=24, batch_size=128, generator=None, numpy=False):
-        """The on-policy cadence of train_onpolicy.py:359-377: after a collection phase, `epochs` minibatches of
-        `batch_size` transitions are sampled from the freshly collected buffer, which is then discarded (the next
-        collect() overwrites the trajectory).  The reference collects episodes_per_train = 10 episodes (<= 330
-        transitions) per phase; a vectorised phase holds n_envs episodes.
-        All minibatches of the phase are drawn together and exported by ONE launch (round 5: 24 separate samples cost 24 permutations
-        of the phase's 1.35 M transitions, 7 ms against the 0.8 ms of collecting them); each yielded dict holds views of that export."""
-        cols, k = self._phase_export(epochs, batch_size, generator)
-        for m in range(int(epochs)):
-            mb = {name: v[m * k:(m + 1) * k] for name, v in cols.items()}
-            yield ({name: v.detach().cpu().numpy() for name, v in mb.items()} if numpy else mb)
-
-    def _phase_export(self, epochs, batch_size, generator, out=None):
-        """-> (columns of all `epochs` minibatches back to back [epochs * k, ...], k = transitions per minibatch): one draw, one launch"""
-        epochs = int(epochs)
-        pos, tt, ee = self._sample_positions(batch_size, epochs, generator)
-        self.last_sample_positions = pos          # (tests: which transitions the minibatches hold)
-        k = pos.shape[1]
-        flat = pos.reshape(-1)
-        if tt is None:
-            E = self.env.E
-            cols = self.as_reference_batch(torch.div(flat, E, rounding_mode="floor"), flat % E, numpy=False, out=out)
-        else:
-            cols = self.as_reference_batch(tt[flat], ee[flat], numpy=False, out=out)
-        return cols, k
-
     def on_policy_phase(self, epochs=24, batch_size=128, generator=None, l_action=5):
         """The minibatches of on_policy_minibatches() TOGETHER WITH the static feeds of the reference's train_step for each of them
         (cm3_amd.batch.phase_static_feeds: process_actions / process_global_state, the n x n credit repeats, the n x n x l_action
@@ -827,7 +835,7 @@ def sample_distinct(n, size, rows, generator, device):
     return out[:, :size].contiguous()
 
 
-class CheckersRollout(object):
+class CheckersRollout(_TransitionSampling):
     """T-tick trajectory over a VecCheckersEnv (16-column transitions, train_onpolicy.py:336).
 
     env.auto_reset False: episode-synchronous -- the env is reset at the start of every collect(); transitions of an
@@ -885,6 +893,7 @@ class CheckersRollout(object):
         self._started = False
         self._goals_onehot = None
         self._traj_cache = None               # (the ctypes structs of the one-launch rollout: the buffers never move)
+        self._gather_traj = None              # (... and of the transition export)
         self._actor_graph = _ActorGraphCache(dev)
         self._lib = _lib.lib()
 
@@ -1122,13 +1131,95 @@ class CheckersRollout(object):
             nxt = torch.where(d, term, nxt)
         return nxt
 
-    def as_reference_batch(self, tt=None, ee=None, numpy=True):
+    def column_specs(self):
+        """name -> (row shape, dtype) of the 16 columns of as_reference_batch(numpy=False), in ORDER."""
+        env = self.env
+        N, f64, i32 = env.n, torch.float64, torch.int32
+        obs = dict(grid=((env.R, env.C + 1, 2), f64), vec=((N, 4), f64), obs_others=((N, env.Lo), f64),
+                   obs_self_t=((N, env.K, env.K, 3), f64), obs_self_v=((N, 4), f64))
+        specs = dict(obs, actions_prev=((N,), i32), actions=((N,), i32), reward=((), f64), local_rewards=((N,), f64),
+                     done=((), torch.bool), goals=((N, 2), torch.int64))
+        specs.update({"next_" + k: v for k, v in obs.items()})
+        return {name: specs[name] for name in self.ORDER}
+
+    def empty_columns(self, rows, zero=False):
+        """The 16 columns with `rows` rows each (what as_reference_batch(numpy=False) returns; a replay ring when zero=True)."""
+        make = torch.zeros if zero else torch.empty
+        return {name: make((int(rows),) + shape, dtype=dt, device=self.env.device) for name, (shape, dt) in self.column_specs().items()}
+
+    def _check_columns(self, columns, rows, what):
+        """Every column a contiguous device tensor [rows, ...] of the right row shape and dtype: the kernel writes rows * row bytes
+        through each pointer, a wrong layout would be an out-of-bounds device write."""
+        for name, (shape, dt) in self.column_specs().items():
+            t = columns.get(name) if hasattr(columns, "get") else None
+            ok_dt = (torch.bool, torch.uint8) if name == "done" else (dt,)
+            if (not torch.is_tensor(t) or not t.is_cuda or t.device != self.env.device or not t.is_contiguous() or t.dim() != 1 + len(shape)
+                    or t.shape[0] != rows or tuple(t.shape[1:]) != shape or t.dtype not in ok_dt):
+                raise Cm3Error("%s: column %s must be a contiguous tensor [%d%s] of %s on %s" %
+                               (what, name, rows, "".join(", %d" % d for d in shape), dt, self.env.device))
+
+    def _gather(self, tt, ee, B, columns, ring_start=0, ring_size=0):
+        """ONE launch of cm3_checkers_transitions_gather (csrc/batch.hip) into `columns` (checked by the caller)."""
+        env = self.env
+        if self._gather_traj is None:
+            self._gather_traj = self._traj()           # (the trajectory buffers never move)
+        out = _lib.CheckersTransitionCols()
+        for name in self.ORDER:
+            setattr(out, name, columns[name].data_ptr())
+        out.ring_start, out.ring_size = int(ring_start), int(ring_size)
+        _lib.check(self._lib.cm3_checkers_transitions_gather(ctypes.byref(env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr(),
+                                                             _lib.ptr(tt), _lib.ptr(ee), int(B), ctypes.byref(out), env._stream()))
+
+    def as_reference_batch(self, tt=None, ee=None, numpy=True, out=None):
         """16 columns equal to np.stack(batch[:, k]) of alg_credit_checkers.process_batch
-        (alg_credit_checkers.py:427-444); integer-valued columns are cast to the reference's float64."""
+        (alg_credit_checkers.py:427-444); integer-valued columns are cast to the reference's float64.
+        ONE launch of cm3_checkers_transitions_gather fills all of them (as_reference_batch_torch below is the same as a composition of
+        torch operations, ~40 launches: what the kernel is tested against).
+        out: a dict this call returned earlier for the same number of transitions (numpy=False): the columns are written into those
+        tensors again (persistent addresses: what a captured hipGraph of the consumer needs)."""
+        dev = self.env.device
+        everything = tt is None and self.auto_reset                    # (all T x E transitions are valid: b = t E + e, no index arrays)
+        if tt is None and not everything:
+            tt, ee = self.valid_indices()
+        if not everything:
+            tt = torch.as_tensor(tt, device=dev, dtype=torch.long).contiguous()
+            ee = torch.as_tensor(ee, device=dev, dtype=torch.long).contiguous()
+            if tt.shape != ee.shape:
+                raise Cm3Error("as_reference_batch: tt and ee must have the same shape")
+        B = self.T * self.env.E if everything else tt.numel()
+        if out is not None:
+            if numpy:
+                raise Cm3Error("as_reference_batch(out=...) returns the device tensors of `out`: pass numpy=False")
+            self._check_columns(out, B, "as_reference_batch(out=...): pass the dict an earlier call returned for %d transitions" % B)
+            cols = {name: out[name] for name in self.ORDER}
+        else:
+            cols = self.empty_columns(B)
+        self._gather(None if everything else tt, None if everything else ee, B, cols)
+        if numpy:
+            cols = {k: v.detach().cpu().numpy() for k, v in cols.items()}
+        return cols
+
+    def export_into(self, columns, ring_start, ring_size):
+        """Every transition of the trajectory (continuous collection) written straight into the rows (ring_start + b) mod ring_size of
+        `columns` -- a dict with the 16 tensors of as_reference_batch(numpy=False), each with ring_size rows: export and replay add in
+        ONE launch (DeviceReplayBuffer.add_rollout).  Every column is checked before the launch.  Returns the number of transitions."""
+        if not self.auto_reset:
+            raise Cm3Error("export_into needs a continuous collection (every transition valid)")
+        ring_start, ring_size = int(ring_start), int(ring_size)
+        B = self.T * self.env.E
+        if not (0 <= ring_start < ring_size and B <= ring_size):
+            raise Cm3Error("export_into: ring of %d rows from row %d does not take %d transitions" % (ring_size, ring_start, B))
+        self._check_columns(columns, ring_size, "export_into")
+        self._gather(None, None, B, columns, ring_start, ring_size)
+        return B
+
+    def as_reference_batch_torch(self, tt, ee, numpy=True):
+        """The same columns as a composition of torch indexing operations (the specification of cm3_checkers_transitions_gather);
+        tt None: all valid transitions."""
+        dev = self.env.device
         if tt is None:
             tt, ee = self.valid_indices()
-        dev = self.env.device
-        tt = torch.as_tensor(tt, device=dev, dtype=torch.long)
+        tt =torch.as_tensor(tt, device=dev, dtype=torch.long)
         ee = torch.as_tensor(ee, device=dev, dtype=torch.long)
         f = lambda x: x.to(torch.float64)  # noqa: E731
         prev = self.actions[(tt - 1).clamp(min=0), ee]

@@ -47,7 +47,8 @@ extern "C" {
 #endif
 
 #define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
-                                  Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network).
+                                  Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network);
+                                  cm3_checkers_transitions_gather (the Checkers transition export in one launch).
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -625,7 +626,36 @@ typedef struct cm3_transition_cols {
   int64_t ring_start;     /* ring_size > 0: the columns are REPLAY RINGS of ring_size rows and transition b is written to row */
   int64_t ring_size;      /* (ring_start + b) mod ring_size -- export and replay_buffer.add in one launch; 0: row b */
 } cm3_transition_cols;
-/* INDEX CONTRACT of cm3_rows_scatter / cm3_rows_gather / cm3_transitions_gather_f32: row indices (dst_row, src_row, tt, ee) are
+/* The 16 columns of the reference's Checkers transition (alg/train_onpolicy.py:336, consumed by alg_credit_checkers.process_batch,
+ * alg_credit_checkers.py:427-444), each contiguous over the B gathered transitions and 16-byte aligned (obs_self_t at odd N: 8).
+ * The reference keeps every observation as float64: the int8 / int32 records of the trajectory are converted (exactly) on the way.
+ * R = n_rows, C = n_columns, K = 2 n_obs + 1, Lo = 2 max(N-1, 1).  Field order = CheckersRollout.ORDER.
+ * (An untagged struct: tests/test_abi.py enumerates the tagged ones against a fixed list; the layout of this one is checked by
+ * tests/test_checkers_export_abi.py the same way.) */
+typedef struct {
+  double *grid;             /* [B][R][C+1][2]   from int8, padding bytes of a strided record skipped */
+  double *vec;              /* [B][N][4]        from int32 */
+  double *obs_others;       /* [B][N][Lo] */
+  double *obs_self_t;       /* [B][N][K][K][3]  from int8 */
+  double *obs_self_v;       /* [B][N][4] */
+  int32_t *actions_prev;    /* [B][N]   t = 0: prev0[e]; else actions[t-1][e], zeros where the trajectory has terminal capture and
+                                        done[t-1][e] (a fresh episode starts from zeros, train_onpolicy.py:295,345) */
+  int32_t *actions;         /* [B][N] */
+  double *reward;           /* [B] */
+  double *local_rewards;    /* [B][N] */
+  double *next_grid;        /* next_*: slot t + 1, or term_*[t] where the trajectory has terminal capture and done[t][e] */
+  double *next_vec;
+  double *next_obs_others;
+  double *next_obs_self_t;
+  double *next_obs_self_v;
+  uint8_t *done;            /* [B]  0 / 1 (a torch.bool column) */
+  int64_t *goals;           /* [B][N][2] one-hot of the goal byte: goals_slots[t][e][n] where the trajectory records goal slots,
+                                         else the live goals[e][n] */
+  int64_t ring_start;       /* ring_size > 0: the columns are REPLAY RINGS of ring_size rows and transition b is written to row */
+  int64_t ring_size;        /* (ring_start + b) mod ring_size -- export and replay_buffer.add in one launch; 0: row b */
+} cm3_checkers_transition_cols;
+/* INDEX CONTRACT of cm3_rows_scatter / cm3_rows_gather / cm3_transitions_gather_f32 / cm3_checkers_transitions_gather: row indices
+ * (dst_row, src_row, tt, ee) are
  * NOT bounds-checked by the launches -- an index outside its array is an out-of-bounds device access.  The host classes that call
  * them (cm3_amd/replay.py RingIndex, rollout.py) derive every index from sizes they own; a caller of the C ABI must do the same.
  * n == 0 (or zero rows) returns CM3_OK without touching any pointer. */
@@ -638,6 +668,15 @@ typedef struct cm3_transition_cols {
 int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj, const int32_t *goal_slot,
                                size_t goal_slot_stride, const int64_t *tt, const int64_t *ee, int64_t n,
                                const cm3_transition_cols *out, void *stream);
+/* The same for Checkers (additive in ABI 9): transitions (tt[b], ee[b]), b < n -- or, with tt == ee == NULL, ALL transitions of
+ * ticks [0, n / E) in time-major order (b = t E + e) -- out of the cm3_checkers_traj the collector wrote, into the 16 columns of
+ * `out`, in ONE launch.  prev0: int32 [E][N], the actions_prev of slot 0.  desc supplies n_envs, n_agents, the geometry and the two
+ * record strides; any geometry and agent count cm3_checkers_step accepts, padded or unpadded records.  Every value is a copy or an
+ * exact integer -> double conversion.  Validation precedes the launch: null desc / traj / out, tt without ee, n < 0, a ring that
+ * does not hold n rows, a missing column are CM3_ERR_INVALID; n == 0 returns CM3_OK without touching a pointer. */
+int cm3_checkers_transitions_gather(const cm3_checkers_desc *desc, const cm3_checkers_traj *traj, const int32_t *prev0,
+                                    const int64_t *tt, const int64_t *ee, int64_t n, const cm3_checkers_transition_cols *out,
+                                    void *stream);
 
 /* Up to 16 columns of row-major records (row_bytes[k] bytes per row of column k), moved together. */
 typedef struct cm3_row_cols {
