@@ -94,30 +94,19 @@ class DeviceReplayBuffer(object):
         """All transitions of a continuous collection, straight from the trajectory into the ring: ONE launch (the export kernel with
         ring positions as its output rows) instead of an export followed by an add, and no intermediate copy of the phase.
         ParticleRollout (float32): cm3_transitions_gather_f32.  The reference stores the same array as v_global and v_local
-        (train_onpolicy.py:338): so does the ring (one tensor under both names).
+        (train_onpolicy.py:338): so does the ring (one tensor under both names, rollout.ALIASES).
         CheckersRollout: cm3_checkers_transitions_gather; the ring holds the 16 columns of as_reference_batch(numpy=False) with their
         dtypes, so it is interchangeable with one that add() allocated."""
-        from .rollout import CheckersRollout
-        env = rollout.env
-        B = rollout.T * env.E
+        B = rollout.T * rollout.env.E
         if B > self.maxsize:                                   # (more than the ring holds: the newest survive, as sequential adds leave)
             return self.add(rollout.as_reference_batch(numpy=False))
-        if isinstance(rollout, CheckersRollout):
-            if not rollout.auto_reset:
-                raise Cm3Error("add_rollout needs a continuous collection (every transition valid)")
-            if self.cols is None:
-                self.cols = rollout.empty_columns(self.maxsize, zero=True)
-        elif self.cols is None:
-            N, L = env.n, env.L
-            z = lambda *shape, dt=torch.float32: torch.zeros((self.maxsize,) + shape, dtype=dt, device=self.device)   # noqa: E731
-            st, nst = z(N, 4), z(N, 4)
-            self.cols = dict(v_global=st, obs_others=z(N, L), v_local=st, actions=z(N, dt=torch.int32), reward=z(), reward_local=z(N),
-                             v_global_next=nst, obs_others_next=z(N, L), v_local_next=nst, done=z(dt=torch.bool), goals=z(N, 2))
-        elif self.cols["v_global"].data_ptr() != self.cols["v_local"].data_ptr():
+        cols = rollout.empty_columns(self.maxsize, zero=True) if self.cols is None else self.cols
+        if not rollout.aliases_hold(cols):
             return self.add(rollout.as_reference_batch(numpy=False))      # (a ring that add() allocated: separate v_local storage)
-        # (validate and launch FIRST, advance the ring after: an export that raises must not leave idx / len pointing at rows that
-        # were never written -- ADVICE r5)
-        rollout.export_into(self.cols, self.ring.idx, self.maxsize)
+        # (validate and launch FIRST, keep the ring and advance it after: an export that raises must not leave idx / len pointing at
+        # rows that were never written -- ADVICE r5)
+        rollout.export_into(cols, self.ring.idx, self.maxsize)
+        self.cols = cols
         self.ring.plan_add(B)
 
     def add_at(self, cols, dst_row, n_added):
@@ -221,21 +210,12 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
             # (ParticleRollout.episode_is_bad); transitions of episodes still running at the chunk's end take the flag so far
             cols = rollout.as_reference_batch(numpy=False)
             buffer.add({k: v.contiguous() for k, v in cols.items()}, _transition_flags(rollout))
-        elif _exports_into_rings(rollout) and hasattr(buffer, "add_rollout"):
+        elif rollout.auto_reset and rollout.kernel_export and hasattr(buffer, "add_rollout"):
             buffer.add_rollout(rollout)                                   # export + add in one launch
         else:
             cols = rollout.as_reference_batch(numpy=False)
             buffer.add({k: v.contiguous() for k, v in cols.items()})
         yield buffer.sample_batch(batch_size, generator=generator)
-
-
-def _exports_into_rings(rollout):
-    """A continuous collection whose class writes its transitions straight into ring rows (export_into): a CheckersRollout, or the
-    float32 instantiation of a ParticleRollout (the float64 parity instantiation exports through the torch composition)."""
-    if not (hasattr(rollout, "export_into") and rollout.auto_reset):
-        return False
-    state = getattr(rollout, "state", None)               # (a CheckersRollout has none: its records are int8 / int32 / float64)
-    return state is None or state.dtype == torch.float32
 
 
 def _transition_flags(rollout):

@@ -39,6 +39,15 @@ def rows_from_columns(cols, order):
     return rows
 
 
+def _to_numpy(cols):
+    return {k: v.detach().cpu().numpy() for k, v in cols.items()}
+
+
+def _is_device_policy(policy):
+    """An on-device agent (cm3_amd.actor / cm3_amd.qmix: enqueue() launches it on a stream) rather than a host callable."""
+    return hasattr(policy, "enqueue") and hasattr(policy, "act")
+
+
 PARTICLE_ORDER = ("v_global", "obs_others", "v_local", "actions", "reward", "reward_local", "v_global_next",
                   "obs_others_next", "v_local_next", "done", "goals")
 CHECKERS_ORDER = ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions_prev", "actions", "reward",
@@ -91,40 +100,154 @@ def _policy_rollout_entry(lib, dtype):
     return lib.cm3_policy_rollout_f64 if dtype == torch.float64 else lib.cm3_policy_rollout_f32
 
 
-class _ActorGraphCache(object):
+class _CapturedGraph(object):
+    """Owner of ONE executable hipGraph: captured on the first launch() after construction or destroy(), replayed by every
+    launch(), destroyed only after the device has drained."""
+
+    def __init__(self, device):
+        self.device = device
+        self.graph = None
+        self._lib = _lib.lib()
+
+    def launch(self, capture, stream):
+        if self.graph is None:
+            self.graph = _lib.capture_graph(self.device, capture)
+        _lib.check(self._lib.cm3_graph_launch(self.graph, stream))
+
+    def destroy(self):
+        if self.graph is not None:
+            torch.cuda.synchronize(self.device)     # a previous replay may still be in flight
+            self._lib.cm3_graph_destroy(self.graph)
+            self.graph = None
+
+
+class _ActorGraphCache(_CapturedGraph):
     """One captured (actor launch, step launch) x T graph per rollout object.  The key is the policy OBJECT (a strong
     reference: `id()` of a collected actor can be reused); epsilon is not part of it -- the actor launches read it from
     a device float that collect() refreshes, so the annealing of train_onpolicy.py:369 never triggers a re-capture."""
 
     def __init__(self, device):
-        self.device = device
-        self.graph = None
-        self.policy = None
-        self.key = None
+        super().__init__(device)
+        self.policy = self.key = None
         self.eps = torch.zeros(1, dtype=torch.float32, device=device)
 
-    def launch(self, lib, policy, epsilon, capture, stream, key=None):
+    def launch(self, policy, epsilon, capture, stream, key=None):
         """key: anything else the captured launches bake in (the per-tick fused policy kernel takes epsilon by value)."""
         self.eps.fill_(float(epsilon))          # ordered before the replay on the same stream
-        if self.graph is None or self.policy is not policy or self.key != key:
-            self.destroy(lib)
-            self.graph = _lib.capture_graph(self.device, capture)
+        if self.policy is not policy or self.key != key:
+            self.destroy()
             self.policy, self.key = policy, key
-        _lib.check(lib.cm3_graph_launch(self.graph, stream))
+        super().launch(capture, stream)
 
-    def destroy(self, lib):
-        if self.graph is not None:
-            torch.cuda.synchronize(self.device)     # a previous replay may still be in flight
-            lib.cm3_graph_destroy(self.graph)
-            self.graph = self.policy = None
+    def destroy(self):
+        super().destroy()
+        self.policy = None
 
 
-class _TransitionSampling(object):
-    """What ParticleRollout and CheckersRollout share on the sampling side: draws over the valid transitions of the trajectory and
-    the one-launch export of a whole phase of minibatches.  The class supplies T, env, auto_reset, valid_indices() and
-    as_reference_batch(tt, ee, numpy, out)."""
+class _Transitions(object):
+    """What ParticleRollout and CheckersRollout share once a trajectory is collected: which transitions are valid, their export as the
+    reference's columns (one launch, into fresh tensors, the caller's, or ring rows), draws over them, the one-launch export of a whole
+    phase of minibatches -- and the ownership of the captured graphs.  The class supplies T, env, auto_reset, done, ORDER,
+    column_specs(), _gather(tt, ee, B, columns, ring_start, ring_size), as_reference_batch_torch(tt, ee, numpy) and `_graphs`."""
 
     last_sample_positions = None
+    ALIASES = {}                # column -> the column whose tensor it shares (the reference stores one array under both names)
+    kernel_export = True        # the export kernel (_gather) applies to this trajectory; else as_reference_batch_torch does the work
+    _finished0 = None
+
+    def _drop_graphs(self):
+        for g in self._graphs:
+            g.destroy()
+
+    def close(self):
+        self._drop_graphs()
+
+    @property
+    def valid(self):
+        """bool [T, E]"""
+        if self.auto_reset:
+            return torch.ones(self.T, self.env.E, dtype=torch.bool, device=self.env.device)
+        return _valid_from_done(self.done, self._finished0)
+
+    def valid_indices(self):
+        """(tt, ee) int64 tensors of all valid transitions, time-major."""
+        idx = self.valid.nonzero(as_tuple=False)
+        return idx[:, 0], idx[:, 1]
+
+    def empty_columns(self, rows, zero=False):
+        """The columns of ORDER with `rows` rows each (what as_reference_batch(numpy=False) returns; a replay ring when zero=True);
+        aliased names share one tensor."""
+        make = torch.zeros if zero else torch.empty
+        cols = {}
+        for name, (shape, dt) in self.column_specs().items():
+            cols[name] = (cols[self.ALIASES[name]] if name in self.ALIASES
+                          else make((int(rows),) + shape, dtype=dt, device=self.env.device))
+        return cols
+
+    def aliases_hold(self, columns):
+        """Every aliased name of `columns` is the tensor of the column it stands for (the kernel writes each distinct column once)."""
+        return all(a in columns and b in columns and columns[a].data_ptr() == columns[b].data_ptr() for a, b in self.ALIASES.items())
+
+    def _check_columns(self, columns, rows, what):
+        """Every column a contiguous device tensor [rows, ...] of the right row shape and dtype: the kernel writes rows * row bytes
+        through each pointer, a wrong layout would be an out-of-bounds device write."""
+        for name, (shape, dt) in self.column_specs().items():
+            t = columns.get(name) if hasattr(columns, "get") else None
+            ok_dt = (torch.bool, torch.uint8) if name == "done" else (dt,)
+            if (not torch.is_tensor(t) or not t.is_cuda or t.device != self.done.device or not t.is_contiguous() or t.dim() != 1 + len(shape)
+                    or t.shape[0] != rows or tuple(t.shape[1:]) != shape or t.dtype not in ok_dt):
+                raise Cm3Error("%s: column %s must be a contiguous tensor [%d%s] of %s on %s" %
+                               (what, name, rows, "".join(", %d" % d for d in shape), dt, self.env.device))
+        if not self.aliases_hold(columns):
+            raise Cm3Error("%s: %s must be the tensors of %s" % (what, ", ".join(self.ALIASES), ", ".join(self.ALIASES.values())))
+
+    def as_reference_batch(self, tt=None, ee=None, numpy=True, out=None):
+        """Columns of the reference's transition batch for the (tick, env) pairs (tt, ee) (default: all valid ones), each equal to
+        np.stack(batch[:, k]) in the reference's process_batch.  ONE launch of the class's export kernel (_gather) fills all of them;
+        where it does not apply (kernel_export) the torch composition as_reference_batch_torch does: same values.
+        out: a dict this call returned earlier for the same number of transitions (numpy=False): the columns are written into those
+        tensors again (persistent addresses: what a captured hipGraph of the consumer needs)."""
+        dev = self.env.device
+        everything = tt is None and self.auto_reset and self.kernel_export    # (all T x E transitions are valid: b = t E + e, no index arrays)
+        if tt is None and not everything:
+            tt, ee = self.valid_indices()
+        if not everything:
+            tt = torch.as_tensor(tt, device=dev, dtype=torch.long).contiguous()
+            ee = torch.as_tensor(ee, device=dev, dtype=torch.long).contiguous()
+        if not self.kernel_export:
+            return self.as_reference_batch_torch(tt, ee, numpy)
+        if not everything and tt.shape != ee.shape:
+            raise Cm3Error("as_reference_batch: tt and ee must have the same shape")
+        B = self.T * self.env.E if everything else tt.numel()
+        if out is not None:
+            if numpy:
+                raise Cm3Error("as_reference_batch(out=...) returns the device tensors of `out`: pass numpy=False")
+            self._check_columns(out, B, "as_reference_batch(out=...): pass the dict an earlier call returned for %d transitions" % B)
+            cols = {name: out[name] for name in self.ORDER}
+        else:
+            cols = self.empty_columns(B)
+        self._gather(None if everything else tt, None if everything else ee, B, cols)
+        return _to_numpy(cols) if numpy else cols
+
+    def export_into(self, columns, ring_start, ring_size):
+        """Every transition of the trajectory (continuous collection the export kernel applies to) written straight into the rows
+        (ring_start + b) mod ring_size of `columns` -- a dict with the tensors of as_reference_batch(numpy=False), each with ring_size
+        rows: export and replay add in ONE launch (DeviceReplayBuffer.add_rollout).  Every column is checked before the launch.
+        Returns the number of transitions."""
+        if not (self.auto_reset and self.kernel_export):
+            raise Cm3Error("export_into needs a continuous collection (every transition valid) that the export kernel reads")
+        ring_start, ring_size = int(ring_start), int(ring_size)
+        B = self.T * self.env.E
+        if not (0 <= ring_start < ring_size and B <= ring_size):
+            raise Cm3Error("export_into: ring of %d rows from row %d does not take %d transitions" % (ring_size, ring_start, B))
+        self._check_columns(columns, ring_size, "export_into")
+        self._gather(None, None, B, columns, ring_start, ring_size)
+        return B
+
+    def as_reference_rows(self, tt=None, ee=None):
+        """Object ndarray [B, len(ORDER)]: row b is the reference's np.array([...fields...]) of train_onpolicy.py:336 / :338
+        (dtype=object, as NumPy >= 1.24 requires for ragged rows)."""
+        return rows_from_columns(self.as_reference_batch(tt, ee), self.ORDER)
 
     def _sample_positions(self, size, rows, generator):
         """int64 [rows, k] positions into the valid transitions (time-major), each row `size` distinct ones uniformly at random
@@ -161,7 +284,7 @@ class _TransitionSampling(object):
         cols, k = self._phase_export(epochs, batch_size, generator)
         for m in range(int(epochs)):
             mb = {name: v[m * k:(m + 1) * k] for name, v in cols.items()}
-            yield ({name: v.detach().cpu().numpy() for name, v in mb.items()} if numpy else mb)
+            yield (_to_numpy(mb) if numpy else mb)
 
     def _phase_export(self, epochs, batch_size, generator, out=None):
         """-> (columns of all `epochs` minibatches back to back [epochs * k, ...], k = transitions per minibatch): one draw, one launch"""
@@ -178,7 +301,7 @@ class _TransitionSampling(object):
         return cols, k
 
 
-class ParticleRollout(_TransitionSampling):
+class ParticleRollout(_Transitions):
     """T-tick trajectory over a VecParticleEnv.
 
     env.auto_reset False: episode-synchronous -- reset all envs, run T = max_steps ticks, transitions of
@@ -241,8 +364,10 @@ class ParticleRollout(_TransitionSampling):
         # at train_onpolicy.py:356 sits at the tick that ends the episode
         # (record_collisions=False drops the slot: episode_is_bad() is then unavailable)
         self.collisions = z(T, E, d=torch.int32) if record_collisions else None
-        self._graph = None
-        self._actor_graph = _ActorGraphCache(dev)
+        # the captured graphs: collect()'s random-action rollout, collect_normalized()'s whole step, the actor / step launch pairs
+        self._graph, self._norm_graph, self._actor_graph = _CapturedGraph(dev), _CapturedGraph(dev), _ActorGraphCache(dev)
+        self._graphs = (self._norm_graph, self._graph, self._actor_graph)
+        self._norm = self._norm_key = None       # collect_normalized's ReturnsNormalizer and the arguments it was built for
         self._live, self._live_cur = False, env._cur
         # episode-synchronous mode: which envs' episodes have ended since their last reset (carried across collects)
         self._finished = torch.zeros(E, dtype=torch.bool, device=dev)
@@ -343,21 +468,29 @@ class ParticleRollout(_TransitionSampling):
         """(dst, src) tensor pairs: one cm3_copy_list launch when every region is 16-byte sized / aligned."""
         _copy_pairs(pairs, self.env._stream())
 
-    def _load_slot0(self):
+    def _slot0_pairs(self):
+        """(dst, src): slot 0 <- the env's current buffers."""
         env = self.env
         pairs = [(self.state[0], env._state[env._cur]), (self.obs_others[0], env._obs_others[env._cur])]
         if self._goals_buf is not None:
             pairs.append((self._goals_buf[0], env._goals))
-        self._copy(pairs)
+        return pairs
 
-    def _store_back(self, live=False):
+    def _store_back_pairs(self, live):
+        """(dst, src): the env's current buffers <- slot T."""
         env = self.env
         pairs = [(env._obs_others[env._cur], self.obs_others[self.T])]
         if not live:    # (live: the env's state / goals buffers ARE the final state)
             pairs.append((env._state[env._cur], self.state[self.T]))
             if self._goals_buf is not None and not self._goals_sparse:     # (sparse goal slots: the live goals array is current)
                 pairs.append((env._goals, self._goals_buf[self.T]))
-        self._copy(pairs)
+        return pairs
+
+    def _load_slot0(self):
+        self._copy(self._slot0_pairs())
+
+    def _store_back(self, live=False):
+        self._copy(self._store_back_pairs(live))
 
     # ---- collection ------------------------------------------------------------------------------------
     def _enqueue_actor_rollout(self, actor, epsilon, base_flags, stream):
@@ -381,6 +514,17 @@ class ParticleRollout(_TransitionSampling):
             traj = self._traj(t)
             _lib.check(fn(ctypes.byref(env._desc), ctypes.byref(traj), ctypes.byref(ad), ctypes.byref(actor._wt), None, 0, 1, stream))
 
+    def _streaming(self):
+        """The trajectory is streaming-size: >= 128 MB of observation slots (see _mode)."""
+        env = self.env
+        return env.E * env.n * env.L * self.state.element_size() * self.T >= (128 << 20)
+
+    def _wants_live_state(self):
+        """The live-state size rule of _mode -- a tick's state <= 1 MiB and a streaming-size trajectory -- unless live_state forces it."""
+        if self.live_state is not None:
+            return bool(self.live_state)
+        return self.env.n * self.env.E * 4 * self.state.element_size() <= (1 << 20) and self._streaming()
+
     def _mode(self, policy):
         """How this collect() launches -- the one place that decides it.  -> _Mode(kind, live, sparse):
           kind    random_fused | random            the reference's random-action branch, all ticks in one launch / a launch per tick
@@ -396,7 +540,7 @@ class ParticleRollout(_TransitionSampling):
           sparse  goal slots are written only where an env restarts: always with live state (the goals live in place), and for the
                   random-action branch at streaming sizes (sparse_goals = True / False forces that)."""
         env = self.env
-        dev_policy = policy is not None and hasattr(policy, "enqueue") and hasattr(policy, "act")
+        dev_policy = _is_device_policy(policy)
         if dev_policy and env.dtype not in (torch.float32, torch.float64):
             raise Cm3Error("the device actor reads float32 or float64 env buffers")
         same_key = dev_policy and getattr(policy, "seed", None) == env.seed
@@ -424,11 +568,7 @@ class ParticleRollout(_TransitionSampling):
                 kind = "policy_fused_tick" if self.fused_policy_tick else "policy_tick"
             if kind in ("policy_episode", "policy_fused_tick") and not same_key:
                 raise Cm3Error("fused policy launches need actor.seed == env.seed (one Philox key)")
-        es = self.state.element_size()
-        stream_size = env.E * env.n * env.L * es * self.T >= (128 << 20)
-        small = env.n * env.E * 4 * es <= (1 << 20) and stream_size
-        if self.live_state is not None:
-            small = bool(self.live_state)
+        stream_size, small = self._streaming(), self._wants_live_state()
         per_tick_steps = kind in ("random", "policy_tick", "host_policy") and not self.fused
         live = bool(self._goals_buf is not None and small and per_tick_steps)
         sparse = bool(self._goals_buf is not None and kind != "random_fused" and (
@@ -470,10 +610,8 @@ class ParticleRollout(_TransitionSampling):
         elif mode.kind == "random":
             flags = base | FLAG_GEN_ACTIONS
             if self.use_graph:
-                if self._graph is None:
-                    self.n_captures += 1
-                    self._graph = _lib.capture_graph(env.device, lambda s: self._enqueue(0, self.T, flags, s, live=live, sparse_goals=sparse))
-                _lib.check(self._lib.cm3_graph_launch(self._graph, stream))
+                self.n_captures += int(self._graph.graph is None)
+                self._graph.launch(lambda s: self._enqueue(0, self.T, flags, s, live=live, sparse_goals=sparse), stream)
             else:
                 self._enqueue(0, self.T, flags, live=live, sparse_goals=sparse)
         elif mode.kind == "policy_episode":
@@ -487,14 +625,14 @@ class ParticleRollout(_TransitionSampling):
                           stream))
         elif mode.kind == "policy_fused_tick":
             if self.use_graph:      # epsilon is a by-value argument of these launches: part of the graph's key
-                self._actor_graph.launch(self._lib, policy, epsilon, lambda s: self._enqueue_fused_policy_ticks(policy, epsilon, base, s),
+                self._actor_graph.launch(policy, epsilon, lambda s: self._enqueue_fused_policy_ticks(policy, epsilon, base, s),
                                          stream, key=("fused_tick", float(epsilon)))
             else:
                 self._enqueue_fused_policy_ticks(policy, epsilon, base, stream)
         elif mode.kind == "policy_tick":
             if self.use_graph:
                 cache = self._actor_graph
-                cache.launch(self._lib, policy, epsilon, lambda s: self._enqueue_actor_rollout(policy, cache.eps, base, s), stream)
+                cache.launch(policy, epsilon, lambda s: self._enqueue_actor_rollout(policy, cache.eps, base, s), stream)
             else:
                 self._enqueue_actor_rollout(policy, epsilon, base, stream)
         else:                       # a host policy: one call and one step launch per tick
@@ -530,14 +668,12 @@ class ParticleRollout(_TransitionSampling):
             raise Cm3Error("collect_normalized runs the continuous, one-launch-per-tick random-action collection")
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         key = (float(gamma), float(eps), bool(normalize), world > 1, int(segments))
-        if getattr(self, "_norm_key", None) != key:
+        if self._norm_key != key:
             self._drop_norm_graph()
             self._norm = ReturnsNormalizer(self.reward_n, self.done, gamma, eps, normalize, segments=segments)
             self._norm_key = key
         self._finished0 = None
-        es = self.state.element_size()
-        small = env.n * env.E * 4 * es <= (1 << 20) and env.E * env.n * env.L * es * self.T >= (128 << 20)
-        live = self._live = bool(small if self.live_state is None else self.live_state)
+        live = self._live = self._wants_live_state()
         if self._graph_mode is not None and self._graph_mode != (live, live):
             self._drop_graphs()
         self._graph_mode = (live, live)
@@ -550,11 +686,7 @@ class ParticleRollout(_TransitionSampling):
         flags = FLAG_AUTO_RESET | env.kernel_flags | FLAG_GEN_ACTIONS
 
         def enqueue(s):
-            pairs = [(self.state[0], env._state[env._cur]), (self.obs_others[0], env._obs_others[env._cur]),
-                     (self._goals_buf[0], env._goals)]
-            back = [(env._obs_others[env._cur], self.obs_others[self.T])]
-            if not live:
-                back += [(env._state[env._cur], self.state[self.T]), (env._goals, self._goals_buf[self.T])]
+            pairs, back = self._slot0_pairs(), self._store_back_pairs(live)      # (what _load_slot0 / _store_back copy)
             if not live and world == 1 and _pairs_aligned(pairs + back):
                 # one rank, one graph: tick 0 reads the env's buffers directly (not slot 0), and the launch that computes the
                 # returns and their partial moments also records slot 0 from the env's buffers and then leaves slot T in them --
@@ -576,9 +708,7 @@ class ParticleRollout(_TransitionSampling):
 
         stream = env._stream()
         if self.use_graph:
-            if getattr(self, "_norm_graph", None) is None:
-                self._norm_graph = _lib.capture_graph(env.device, enqueue)
-            _lib.check(self._lib.cm3_graph_launch(self._norm_graph, stream))
+            self._norm_graph.launch(enqueue, stream)
         else:
             enqueue(stream)
         t_coll = 0.0
@@ -593,21 +723,7 @@ class ParticleRollout(_TransitionSampling):
         return res + (t_coll,) if time_collective else res
 
     def _drop_norm_graph(self):
-        if getattr(self, "_norm_graph", None) is not None:
-            torch.cuda.synchronize(self.env.device)
-            self._lib.cm3_graph_destroy(self._norm_graph)
-        self._norm_graph = None
-
-    def _drop_graphs(self):
-        self._drop_norm_graph()
-        if self._graph is not None:
-            torch.cuda.synchronize(self.env.device)
-            self._lib.cm3_graph_destroy(self._graph)
-            self._graph = None
-        self._actor_graph.destroy(self._lib)
-
-    def close(self):
-        self._drop_graphs()
+        self._norm_graph.destroy()
 
     # ---- views --------------------------------------------------------------------------------------------
     @property
@@ -634,13 +750,6 @@ class ParticleRollout(_TransitionSampling):
             src[1:] = torch.where(self.done.bool(), ticks, torch.zeros_like(ticks))
             self._goal_src = torch.cummax(src, dim=0).values
         return self._goal_src
-
-    @property
-    def valid(self):
-        """bool [T, E]"""
-        if self.auto_reset:
-            return torch.ones(self.T, self.env.E, dtype=torch.bool, device=self.env.device)
-        return _valid_from_done(self.done, self._finished0)
 
     def episode_is_bad(self):
         """The reference's dual-buffer flag `scenario.collisions != 0` per finished episode (train_onpolicy.py:356), read
@@ -681,92 +790,46 @@ class ParticleRollout(_TransitionSampling):
             nxt = torch.where(d, term, nxt)
         return nxt
 
-    def valid_indices(self):
-        """(tt, ee) int64 tensors of all valid transitions, time-major."""
-        idx = self.valid.nonzero(as_tuple=False)
-        return idx[:, 0], idx[:, 1]
+    ORDER = PARTICLE_ORDER
+    ALIASES = {"v_local": "v_global", "v_local_next": "v_global_next"}      # (one array under both names, train_onpolicy.py:338)
+    _COLS_FIELDS = (("state", "v_global"), ("obs_others", "obs_others"), ("actions", "actions"), ("reward", "reward"),
+                    ("reward_n", "reward_local"), ("next_state", "v_global_next"), ("next_obs_others", "obs_others_next"),
+                    ("done", "done"), ("goals", "goals"))                   # cm3_transition_cols field <- column
+    kernel_export = property(lambda self: self.state.dtype == torch.float32)
 
-    def as_reference_batch(self, tt=None, ee=None, numpy=True, out=None):
-        """Columns of the reference's transition batch for the (tick, env) pairs (tt, ee) (default: all valid
-        ones), each equal to np.stack(batch[:, k]) in alg_credit.process_batch (alg_credit.py:458-470).
-        out: a dict this call returned earlier for the same number of transitions (float32 path, numpy=False): the columns are
-        written into those tensors again (persistent addresses: what a captured hipGraph of the consumer needs).
-        float32 trajectories: ONE launch of cm3_transitions_gather_f32 (csrc/batch.hip) fills all columns; the float64 parity
-        instantiation goes through the torch composition below (as_reference_batch_torch: same values, ~25 launches)."""
-        everything = tt is None and self.auto_reset and self.state.dtype == torch.float32     # (all T x E transitions are valid)
-        if tt is None and not everything:
-            tt, ee = self.valid_indices()
-        if not everything:
-            tt = torch.as_tensor(tt, device=self.env.device, dtype=torch.long).contiguous()
-            ee = torch.as_tensor(ee, device=self.env.device, dtype=torch.long).contiguous()
-        if self.state.dtype != torch.float32:
-            return self.as_reference_batch_torch(tt, ee, numpy)
-        env = self.env
-        B, N, L, dev = (self.T * env.E if everything else tt.numel()), env.n, env.L, env.device
-        if out is not None:
-            if numpy or out["v_global"].shape[0] != B or out["v_global"].data_ptr() != out["v_local"].data_ptr():
-                raise Cm3Error("as_reference_batch(out=...): pass the dict an earlier call returned for %d transitions (numpy=False)" % B)
-            state, obs, nstate, nobs = out["v_global"], out["obs_others"], out["v_global_next"], out["obs_others_next"]
-            reward, reward_n, goals, actions, done = out["reward"], out["reward_local"], out["goals"], out["actions"], out["done"]
-        else:
-            f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
-            state, obs, nstate, nobs = f(B, N, 4), f(B, N, L), f(B, N, 4), f(B, N, L)
-            reward, reward_n, goals = f(B), f(B, N), f(B, N, 2)
-            actions = torch.empty(B, N, dtype=torch.int32, device=dev)
-            done = torch.empty(B, dtype=torch.bool, device=dev)
-        traj = self._traj(0)
-        goal_slot, gs_stride = None, 0
-        if self._goals_buf is not None and self._goals_sparse:
-            if self._goal_src32 is None or self._goal_src32_of is not self._goal_source_slots():
-                self._goal_src32_of = self._goal_source_slots()
-                self._goal_src32 = self._goal_src32_of.to(torch.int32)
-            goal_slot, gs_stride = self._goal_src32, env.E * 4
-        out = _lib.TransitionCols()
-        out.state, out.obs_others, out.actions, out.reward, out.reward_n = (state.data_ptr(), obs.data_ptr(), actions.data_ptr(),
-                                                                            reward.data_ptr(), reward_n.data_ptr())
-        out.next_state, out.next_obs_others, out.done, out.goals = nstate.data_ptr(), nobs.data_ptr(), done.data_ptr(), goals.data_ptr()
-        _lib.check(self._lib.cm3_transitions_gather_f32(ctypes.byref(env._desc), ctypes.byref(traj), _lib.ptr(goal_slot), gs_stride,
-                                                        None if everything else tt.data_ptr(), None if everything else ee.data_ptr(), B,
-                                                        ctypes.byref(out), env._stream()))
-        cols = dict(v_global=state, obs_others=obs, v_local=state, actions=actions, reward=reward, reward_local=reward_n,
-                    v_global_next=nstate, obs_others_next=nobs, v_local_next=nstate, done=done, goals=goals)
-        if numpy:
-            cols = {k: v.detach().cpu().numpy() for k, v in cols.items()}
-        return cols
+    def column_specs(self):
+        """name -> (row shape, dtype) of the 11 columns of as_reference_batch(numpy=False) of a float32 trajectory, in ORDER."""
+        N, L, f32 = self.env.n, self.env.L, torch.float32
+        specs = dict(v_global=((N, 4), f32), obs_others=((N, L), f32), actions=((N,), torch.int32), reward=((), f32),
+                     reward_local=((N,), f32), v_global_next=((N, 4), f32), obs_others_next=((N, L), f32), done=((), torch.bool),
+                     goals=((N, 2), f32))
+        specs.update({alias: specs[name] for alias, name in self.ALIASES.items()})
+        return {name: specs[name] for name in self.ORDER}
 
-    def export_into(self, columns, ring_start, ring_size):
-        """Every transition of the trajectory (continuous collection, float32) written straight into the rows (ring_start + b) mod
-        ring_size of `columns` -- a dict with the nine distinct tensors of as_reference_batch (v_global, obs_others, actions, reward,
-        reward_local, v_global_next, obs_others_next, done, goals), each with ring_size rows: export and replay add in ONE launch
-        (DeviceReplayBuffer.add_rollout).  Returns the number of transitions."""
+    def _goal_slots32(self):
+        """The sparse-goal argument of the export kernel: _goal_source_slots() as int32 [T + 1, E], converted once per collection;
+        None while the goal slots are dense."""
+        if self._goals_buf is None or not self._goals_sparse:
+            return None
+        if self._goal_src32 is None or self._goal_src32_of is not self._goal_source_slots():
+            self._goal_src32_of = self._goal_source_slots()
+            self._goal_src32 = self._goal_src32_of.to(torch.int32)
+        return self._goal_src32
+
+    def _gather(self, tt, ee, B, columns, ring_start=0, ring_size=0):
+        """ONE launch of cm3_transitions_gather_f32 (csrc/batch.hip) fills all of `columns` (checked by the caller); float32
+        trajectories only -- the float64 parity instantiation goes through the torch composition below (as_reference_batch_torch: same
+        values, ~25 launches)."""
         env = self.env
-        if not (self.auto_reset and self.state.dtype == torch.float32):
-            raise Cm3Error("export_into needs a continuous float32 collection (every transition valid)")
-        B = self.T * env.E
         traj = self._traj(0)
-        goal_slot, gs_stride = None, 0
-        if self._goals_buf is not None and self._goals_sparse:
-            if self._goal_src32 is None or self._goal_src32_of is not self._goal_source_slots():
-                self._goal_src32_of = self._goal_source_slots()
-                self._goal_src32 = self._goal_src32_of.to(torch.int32)
-            goal_slot, gs_stride = self._goal_src32, env.E * 4
+        goal_slot = self._goal_slots32()
         out = _lib.TransitionCols()
-        for field, name in (("state", "v_global"), ("obs_others", "obs_others"), ("actions", "actions"), ("reward", "reward"),
-                            ("reward_n", "reward_local"), ("next_state", "v_global_next"), ("next_obs_others", "obs_others_next"),
-                            ("done", "done"), ("goals", "goals")):
-            t = columns[name]
-            want_dt = {"actions": torch.int32, "done": (torch.bool, torch.uint8)}.get(name, torch.float32)
-            want_tail = {"v_global": (env.n, 4), "v_global_next": (env.n, 4), "obs_others": (env.n, env.L), "obs_others_next": (env.n, env.L),
-                         "actions": (env.n,), "reward": (), "reward_local": (env.n,), "done": (), "goals": (env.n, 2)}[name]
-            if (not t.is_contiguous() or t.shape[0] != ring_size or tuple(t.shape[1:]) != want_tail
-                    or (t.dtype not in want_dt if isinstance(want_dt, tuple) else t.dtype != want_dt) or not t.is_cuda):
-                raise Cm3Error("export_into: column %s must be a contiguous device tensor [%d%s] of %s (a wrong layout would be an "
-                               "out-of-bounds device write)" % (name, ring_size, "".join(", %d" % d for d in want_tail), want_dt))
-            setattr(out, field, t.data_ptr())
+        for field, name in self._COLS_FIELDS:
+            setattr(out, field, columns[name].data_ptr())
         out.ring_start, out.ring_size = int(ring_start), int(ring_size)
-        _lib.check(self._lib.cm3_transitions_gather_f32(ctypes.byref(env._desc), ctypes.byref(traj), _lib.ptr(goal_slot), gs_stride,
-                                                        None, None, B, ctypes.byref(out), env._stream()))
-        return B
+        _lib.check(self._lib.cm3_transitions_gather_f32(ctypes.byref(env._desc), ctypes.byref(traj), _lib.ptr(goal_slot),
+                                                        0 if goal_slot is None else env.E * 4, _lib.ptr(tt), _lib.ptr(ee), int(B),
+                                                        ctypes.byref(out), env._stream()))
 
     def as_reference_batch_torch(self, tt, ee, numpy=True):
         """The same columns as a composition of torch indexing operations (any dtype; what the kernel path is tested against)."""
@@ -785,17 +848,7 @@ class ParticleRollout(_TransitionSampling):
             actions=self.actions[tt, ee], reward=self.reward[tt, ee], reward_local=self.reward_n[tt, ee],
             v_global_next=nxt_state, obs_others_next=self._next("obs_others", tt, ee), v_local_next=nxt_state,
             done=self.done[tt, ee].bool(), goals=goals)
-        if numpy:
-            cols = {k: v.detach().cpu().numpy() for k, v in cols.items()}
-        return cols
-
-    ORDER = ("v_global", "obs_others", "v_local", "actions", "reward", "reward_local", "v_global_next",
-             "obs_others_next", "v_local_next", "done", "goals")
-
-    def as_reference_rows(self, tt=None, ee=None):
-        """Object ndarray [B, 11]: row b is the reference's np.array([...11 fields...]) of train_onpolicy.py:338
-        (dtype=object, as NumPy >= 1.24 requires for ragged rows)."""
-        return rows_from_columns(self.as_reference_batch(tt, ee), self.ORDER)
+        return _to_numpy(cols) if numpy else cols
 
     def on_policy_phase(self, epochs=24, batch_size=128, generator=None, l_action=5):
         """The minibatches of on_policy_minibatches() TOGETHER WITH the static feeds of the reference's train_step for each of them
@@ -835,7 +888,7 @@ def sample_distinct(n, size, rows, generator, device):
     return out[:, :size].contiguous()
 
 
-class CheckersRollout(_TransitionSampling):
+class CheckersRollout(_Transitions):
     """T-tick trajectory over a VecCheckersEnv (16-column transitions, train_onpolicy.py:336).
 
     env.auto_reset False: episode-synchronous -- the env is reset at the start of every collect(); transitions of an
@@ -861,7 +914,6 @@ class CheckersRollout(_TransitionSampling):
             raise Cm3Error("policy_mode must be 'auto' or 'tick'")
         self.policy_mode = policy_mode
         self.auto_reset = bool(env.auto_reset)
-        self._graph = None
         E, N, T, dev = env.E, env.n, self.T, env.device
         z = lambda *s, d: torch.zeros(*s, dtype=d, device=dev)  # noqa: E731
         self._grid_raw = z(T + 1, E, env.grid_stride, d=torch.int8)
@@ -894,7 +946,9 @@ class CheckersRollout(_TransitionSampling):
         self._goals_onehot = None
         self._traj_cache = None               # (the ctypes structs of the one-launch rollout: the buffers never move)
         self._gather_traj = None              # (... and of the transition export)
-        self._actor_graph = _ActorGraphCache(dev)
+        # the captured graphs: the random-action rollout, the actor / step launch pairs
+        self._graph, self._actor_graph = _CapturedGraph(dev), _ActorGraphCache(dev)
+        self._graphs = (self._graph, self._actor_graph)
         self._lib = _lib.lib()
 
     def _bufs(self, t):
@@ -951,6 +1005,13 @@ class CheckersRollout(_TransitionSampling):
         _lib.check(self._lib.cm3_checkers_rollout(ctypes.byref(env._desc), ctypes.byref(traj), self.T, stream))
         env._desc.flags = 0
 
+    def _enqueue_step(self, t, stream):
+        """One cm3_checkers_step launch: consumes actions[t], writes slot t + 1 (the caller clears env._desc.flags after its last)."""
+        env = self.env
+        env._desc.flags = self._base_flags()
+        b = self._bufs(t)
+        _lib.check(self._lib.cm3_checkers_step(ctypes.byref(env._desc), ctypes.byref(b), stream))
+
     def _enqueue_actor_rollout(self, actor, epsilon, stream):
         """T x (actor launch, step launch) on `stream`: the policy reads trajectory slot t (+ actions[t-1] as
         actions_prev -- prev0 at t = 0, zeros where the previous tick ended an episode: train_onpolicy.py:295,345) and
@@ -963,9 +1024,7 @@ class CheckersRollout(_TransitionSampling):
                           self.actions[t - 1] if t > 0 else self.prev0, env._steps, env._episode, self.actions[t], epsilon,
                           probs=None if self.probs is None else self.probs[t], stream=stream, env_id_base=env._desc.env_id_base,
                           prev_done=self.done[t - 1] if (t > 0 and self.auto_reset) else None)
-            env._desc.flags = self._base_flags()
-            b = self._bufs(t)
-            _lib.check(self._lib.cm3_checkers_step(ctypes.byref(env._desc), ctypes.byref(b), stream))
+            self._enqueue_step(t, stream)
         env._desc.flags = 0
 
     def _enqueue_policy_rollout(self, actor, epsilon, stream, prev0_next=None):
@@ -1054,16 +1113,13 @@ class CheckersRollout(_TransitionSampling):
             if self.fused:
                 self._enqueue_random(stream, True)
             elif self.use_graph:
-                if self._graph is None:
-                    self._graph = _lib.capture_graph(env.device, lambda st: self._enqueue_random(st, False))
-                _lib.check(self._lib.cm3_graph_launch(self._graph, stream))
+                self._graph.launch(lambda st: self._enqueue_random(st, False), stream)
             else:
                 self._enqueue_random(stream, False)
-        elif hasattr(policy, "enqueue") and hasattr(policy, "act"):            # on-device actor, a launch pair per tick
+        elif _is_device_policy(policy):                                          # on-device actor, a launch pair per tick
             if self.use_graph:
                 cache = self._actor_graph
-                cache.launch(self._lib, policy, epsilon,
-                             lambda st: self._enqueue_actor_rollout(policy, cache.eps, st), stream)
+                cache.launch(policy, epsilon, lambda st: self._enqueue_actor_rollout(policy, cache.eps, st), stream)
             else:
                 self._enqueue_actor_rollout(policy, epsilon, stream)
         else:
@@ -1071,9 +1127,7 @@ class CheckersRollout(_TransitionSampling):
                 a = policy(self.actions_prev_at(t), self.obs_others[t], self.obs_self_t[t], self.obs_self_v[t],
                            self.goals_at(t))
                 self.actions[t].copy_(torch.as_tensor(a, device=env.device).reshape(env.E, env.n))
-                env._desc.flags = self._base_flags()
-                b = self._bufs(t)
-                _lib.check(self._lib.cm3_checkers_step(ctypes.byref(env._desc), ctypes.byref(b), stream))
+                self._enqueue_step(t, stream)
             env._desc.flags = 0
         self._store_back()
         return self
@@ -1100,26 +1154,7 @@ class CheckersRollout(_TransitionSampling):
             return self.goals_onehot
         return torch.nn.functional.one_hot(self.goal_slots[t].long(), 2)
 
-    def close(self):
-        if self._graph is not None:
-            torch.cuda.synchronize(self.env.device)
-            self._lib.cm3_graph_destroy(self._graph)
-            self._graph = None
-        self._actor_graph.destroy(self._lib)
-
-    @property
-    def valid(self):
-        if self.auto_reset:
-            return torch.ones(self.T, self.env.E, dtype=torch.bool, device=self.env.device)
-        return _valid_from_done(self.done)
-
-    def valid_indices(self):
-        idx = self.valid.nonzero(as_tuple=False)
-        return idx[:, 0], idx[:, 1]
-
-    ORDER = ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions_prev", "actions", "reward",
-             "local_rewards", "next_grid", "next_vec", "next_obs_others", "next_obs_self_t", "next_obs_self_v",
-             "done", "goals")
+    ORDER = CHECKERS_ORDER
 
     def _next(self, name, tt, ee):
         """next_<name> of transitions (tt, ee): slot t+1, or the captured terminal observation where the env restarted
@@ -1142,24 +1177,10 @@ class CheckersRollout(_TransitionSampling):
         specs.update({"next_" + k: v for k, v in obs.items()})
         return {name: specs[name] for name in self.ORDER}
 
-    def empty_columns(self, rows, zero=False):
-        """The 16 columns with `rows` rows each (what as_reference_batch(numpy=False) returns; a replay ring when zero=True)."""
-        make = torch.zeros if zero else torch.empty
-        return {name: make((int(rows),) + shape, dtype=dt, device=self.env.device) for name, (shape, dt) in self.column_specs().items()}
-
-    def _check_columns(self, columns, rows, what):
-        """Every column a contiguous device tensor [rows, ...] of the right row shape and dtype: the kernel writes rows * row bytes
-        through each pointer, a wrong layout would be an out-of-bounds device write."""
-        for name, (shape, dt) in self.column_specs().items():
-            t = columns.get(name) if hasattr(columns, "get") else None
-            ok_dt = (torch.bool, torch.uint8) if name == "done" else (dt,)
-            if (not torch.is_tensor(t) or not t.is_cuda or t.device != self.env.device or not t.is_contiguous() or t.dim() != 1 + len(shape)
-                    or t.shape[0] != rows or tuple(t.shape[1:]) != shape or t.dtype not in ok_dt):
-                raise Cm3Error("%s: column %s must be a contiguous tensor [%d%s] of %s on %s" %
-                               (what, name, rows, "".join(", %d" % d for d in shape), dt, self.env.device))
-
     def _gather(self, tt, ee, B, columns, ring_start=0, ring_size=0):
-        """ONE launch of cm3_checkers_transitions_gather (csrc/batch.hip) into `columns` (checked by the caller)."""
+        """ONE launch of cm3_checkers_transitions_gather (csrc/batch.hip) fills all of `columns` (checked by the caller); integer-valued
+        columns are cast to the reference's float64 (alg_credit_checkers.py:427-444).  as_reference_batch_torch below is the same as a
+        composition of torch operations, ~40 launches: what the kernel is tested against."""
         env = self.env
         if self._gather_traj is None:
             self._gather_traj = self._traj()           # (the trajectory buffers never move)
@@ -1169,49 +1190,6 @@ class CheckersRollout(_TransitionSampling):
         out.ring_start, out.ring_size = int(ring_start), int(ring_size)
         _lib.check(self._lib.cm3_checkers_transitions_gather(ctypes.byref(env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr(),
                                                              _lib.ptr(tt), _lib.ptr(ee), int(B), ctypes.byref(out), env._stream()))
-
-    def as_reference_batch(self, tt=None, ee=None, numpy=True, out=None):
-        """16 columns equal to np.stack(batch[:, k]) of alg_credit_checkers.process_batch
-        (alg_credit_checkers.py:427-444); integer-valued columns are cast to the reference's float64.
-        ONE launch of cm3_checkers_transitions_gather fills all of them (as_reference_batch_torch below is the same as a composition of
-        torch operations, ~40 launches: what the kernel is tested against).
-        out: a dict this call returned earlier for the same number of transitions (numpy=False): the columns are written into those
-        tensors again (persistent addresses: what a captured hipGraph of the consumer needs)."""
-        dev = self.env.device
-        everything = tt is None and self.auto_reset                    # (all T x E transitions are valid: b = t E + e, no index arrays)
-        if tt is None and not everything:
-            tt, ee = self.valid_indices()
-        if not everything:
-            tt = torch.as_tensor(tt, device=dev, dtype=torch.long).contiguous()
-            ee = torch.as_tensor(ee, device=dev, dtype=torch.long).contiguous()
-            if tt.shape != ee.shape:
-                raise Cm3Error("as_reference_batch: tt and ee must have the same shape")
-        B = self.T * self.env.E if everything else tt.numel()
-        if out is not None:
-            if numpy:
-                raise Cm3Error("as_reference_batch(out=...) returns the device tensors of `out`: pass numpy=False")
-            self._check_columns(out, B, "as_reference_batch(out=...): pass the dict an earlier call returned for %d transitions" % B)
-            cols = {name: out[name] for name in self.ORDER}
-        else:
-            cols = self.empty_columns(B)
-        self._gather(None if everything else tt, None if everything else ee, B, cols)
-        if numpy:
-            cols = {k: v.detach().cpu().numpy() for k, v in cols.items()}
-        return cols
-
-    def export_into(self, columns, ring_start, ring_size):
-        """Every transition of the trajectory (continuous collection) written straight into the rows (ring_start + b) mod ring_size of
-        `columns` -- a dict with the 16 tensors of as_reference_batch(numpy=False), each with ring_size rows: export and replay add in
-        ONE launch (DeviceReplayBuffer.add_rollout).  Every column is checked before the launch.  Returns the number of transitions."""
-        if not self.auto_reset:
-            raise Cm3Error("export_into needs a continuous collection (every transition valid)")
-        ring_start, ring_size = int(ring_start), int(ring_size)
-        B = self.T * self.env.E
-        if not (0 <= ring_start < ring_size and B <= ring_size):
-            raise Cm3Error("export_into: ring of %d rows from row %d does not take %d transitions" % (ring_size, ring_start, B))
-        self._check_columns(columns, ring_size, "export_into")
-        self._gather(None, None, B, columns, ring_start, ring_size)
-        return B
 
     def as_reference_batch_torch(self, tt, ee, numpy=True):
         """The same columns as a composition of torch indexing operations (the specification of cm3_checkers_transitions_gather);
@@ -1238,12 +1216,7 @@ class CheckersRollout(_TransitionSampling):
             next_obs_others=self._next("obs_others", tt, ee), next_obs_self_t=f(self._next("obs_self_t", tt, ee)),
             next_obs_self_v=self._next("obs_self_v", tt, ee), done=self.done[tt, ee].bool(),
             goals=goals)
-        if numpy:
-            cols = {k: v.detach().cpu().numpy() for k, v in cols.items()}
-        return cols
-
-    def as_reference_rows(self, tt=None, ee=None):
-        return rows_from_columns(self.as_reference_batch(tt, ee), self.ORDER)
+        return _to_numpy(cols) if numpy else cols
 
     def episode_returns(self):
         v = self.valid.to(torch.float64)
