@@ -74,6 +74,11 @@ class CheckersTransitionCols(ctypes.Structure):
                                         "next_obs_self_v", "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
 
 
+class CheckersCompactCols(ctypes.Structure):
+    # (cm3_checkers_compact_cols: the same names and order, the columns with the dtypes the trajectory keeps)
+    _fields_ = list(CheckersTransitionCols._fields_)
+
+
 class RowCols(ctypes.Structure):
     _fields_ = [("n_cols", c_int32), ("reserved", c_int32), ("dst", c_void_p * 16), ("src", c_void_p * 16),
                 ("row_bytes", ctypes.c_uint32 * 16)]
@@ -198,6 +203,10 @@ SYMBOLS = {
                                                   P(TransitionCols), c_void_p]),
     "cm3_checkers_transitions_gather": (ctypes.c_int, [P(CheckersDesc), P(CheckersTraj), c_void_p, c_void_p, c_void_p, c_int64,
                                                        P(CheckersTransitionCols), c_void_p]),
+    "cm3_checkers_transitions_pack": (ctypes.c_int, [P(CheckersDesc), P(CheckersTraj), c_void_p, c_int64, P(CheckersCompactCols),
+                                                     c_void_p]),
+    "cm3_checkers_ring_expand": (ctypes.c_int, [P(CheckersDesc), P(CheckersCompactCols), c_void_p, c_int64,
+                                                P(CheckersTransitionCols), c_void_p]),
     "cm3_rows_scatter": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "cm3_rows_gather": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_void_p]),
     "cm3_rows_tile": (ctypes.c_int, [P(TileCol), c_int32, c_void_p]),

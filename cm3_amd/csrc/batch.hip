@@ -348,8 +348,8 @@ template <typename I> __global__ void __launch_bounds__(256) k_ck_transitions_ga
     const I b = gc / (I)upr;
     uu[k] = (uint32_t)(gc - b * (I)upr);
     bb[k] = (size_t)b;
-    if (p.tt) {
-      tt[k] = p.tt[b];
+    if (p.ee) {                                // (ee without tt: slot 0 throughout -- the rows of a compact ring, cm3_checkers_ring_expand)
+      tt[k] = p.tt ? p.tt[b] : 0;
       ee[k] = (size_t)p.ee[b];
     } else {                                   // the whole trajectory in time-major order: b = t E + e
       const I t = b / (I)p.E;
@@ -429,6 +429,216 @@ template <typename I> __global__ void __launch_bounds__(256) k_ck_transitions_ga
   }
 }
 
+// ---- the compact Checkers replay ring: the same 16 columns with the dtypes the trajectory keeps ------------------------------------
+// (cm3_checkers_transitions_pack: 707 B per transition at the reference geometry with N = 2 instead of the 3657 B of the float64
+// columns; nothing is converted -- cm3_checkers_ring_expand widens the rows a learner samples, through k_ck_transitions_gather with a
+// ring row as its source.)  Rows are dense: 54-byte grid and 150-byte obs_self_t rows are no multiple of 16 bytes, so a column is
+// addressed as ONE flat byte array and a lane owns an aligned 16-byte PIECE of it, whatever rows the piece lies in: consecutive lanes
+// store consecutive pieces, a wave's store is one contiguous KiB as in the wide export.  The chunk covers the bytes [lo_a, hi_a) of the
+// column and, where it wraps, [0, hi_b); the first and last piece of either range may be partly outside it and are written granule by
+// granule, every other piece with one 16-byte store.
+// A piece is assembled from GRANULES of `gran` bytes: the largest power of two (<= 16) that divides the row size, every source stride
+// and every base address, so that a granule lies in one row and is one naturally aligned load (2 bytes for grid / obs_self_t records
+// on even strides, 1 byte on odd ones, 16 for the float64 and vec rows, the row itself for the narrow columns).  Rows of 16 bytes or
+// more put at most two rows into a piece: their (tick, env), done bytes and source rows are resolved once per piece, four pieces per
+// lane in flight as in k_ck_transitions_gather.  Narrower rows (done, goals, actions, reward: 27 of the 707 bytes) resolve every
+// granule on its own.  The column is uniform over the workgroup, as above: no per-lane table lookup, nothing in scratch.
+enum PkKind : uint32_t {
+  PK_COPY,      // the record bytes as they are (next_*: slot t + 1, or the term_* slot where done[t][e])
+  PK_PREV,      // actions_prev: actions[t - 1] (zeros behind a done under terminal capture), prev0 at t = 0
+  PK_DONE       // done[t][e] != 0
+};
+constexpr int kPkPiecesPerLane = 4;
+
+struct PkCol {
+  const char *src, *alt;
+  char *dst;
+  size_t slot_stride, alt_stride;
+  size_t lo_a, hi_a, hi_b;   // bytes of the flat column this chunk covers: [lo_a, hi_a), then [0, hi_b) past the wrap
+  uint32_t env_stride, rb;   // bytes between the env records of a slot; bytes per ring row
+  uint32_t gran, kind, next;
+};
+struct PkParams {
+  PkCol col[kCkCols];
+  uint32_t blk_end[kCkCols];
+  const uint8_t *done;
+  const char *prev0;
+  size_t st_done, E, ring_start, ring_size;
+  int term;
+};
+
+template <int G> __device__ __forceinline__ void pk_fetch(uint32_t (&w)[4], int i, const char *s, bool zero, bool norm) {
+  if constexpr (G == 16) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(s);
+    w[0] = zero ? 0u : v.x; w[1] = zero ? 0u : v.y; w[2] = zero ? 0u : v.z; w[3] = zero ? 0u : v.w;
+  } else if constexpr (G == 8) {
+    const uint2 v = *reinterpret_cast<const uint2 *>(s);
+    w[2 * i] = zero ? 0u : v.x; w[2 * i + 1] = zero ? 0u : v.y;
+  } else if constexpr (G == 4) {
+    const uint32_t v = *reinterpret_cast<const uint32_t *>(s);
+    w[i] = zero ? 0u : v;
+  } else if constexpr (G == 2) {
+    const uint32_t v = *reinterpret_cast<const uint16_t *>(s);
+    w[i / 2] |= (zero ? 0u : v) << (16 * (i & 1));
+  } else {
+    uint32_t v = *reinterpret_cast<const uint8_t *>(s);
+    if (norm) v = v ? 1u : 0u;
+    w[i / 4] |= (zero ? 0u : v) << (8 * (i & 3));
+  }
+}
+template <int G> __device__ __forceinline__ void pk_store(char *d, const uint32_t (&w)[4], int i) {   // granule i of the piece at d
+  if constexpr (G == 16) *reinterpret_cast<uint4 *>(d) = uint4{w[0], w[1], w[2], w[3]};
+  else if constexpr (G == 8) *reinterpret_cast<uint2 *>(d + 8 * i) = uint2{w[2 * i], w[2 * i + 1]};
+  else if constexpr (G == 4) *reinterpret_cast<uint32_t *>(d + 4 * i) = w[i];
+  else if constexpr (G == 2) *reinterpret_cast<uint16_t *>(d + 2 * i) = (uint16_t)(w[i / 2] >> (16 * (i & 1)));
+  else *reinterpret_cast<uint8_t *>(d + i) = (uint8_t)(w[i / 4] >> (8 * (i & 3)));
+}
+// the done byte a ring row's source depends on (0 where it depends on none), and the source of the row's first byte
+__device__ __forceinline__ uint32_t pk_row_done(const PkParams &p, const PkCol &C, size_t t, size_t e) {
+  if (C.kind == PK_PREV) return (p.term && t > 0) ? (uint32_t)tick_of(p.done, p.st_done, (int64_t)t - 1)[e] : 0u;
+  return C.alt ? (uint32_t)tick_of(p.done, p.st_done, (int64_t)t)[e] : 0u;
+}
+__device__ __forceinline__ const char *pk_row_src(const PkParams &p, const PkCol &C, size_t t, size_t e, uint32_t d) {
+  const size_t off = e * C.env_stride;
+  if (C.kind == PK_PREV) return t > 0 ? C.src + C.slot_stride * (t - 1) + off : p.prev0 + off;
+  if (C.alt && d) return C.alt + C.alt_stride * t + off;
+  return C.src + C.slot_stride * (t + C.next) + off;
+}
+// piece g of the column -> the range it belongs to ([lo, hi) bytes, `wrapped`: the one past the wrap) and its first byte
+template <typename I> __device__ __forceinline__ I pk_piece(const PkCol &C, I g, I nA, I &lo, I &hi, bool &wrapped) {
+  wrapped = g >= nA;
+  lo = wrapped ? (I)0 : (I)C.lo_a;
+  hi = wrapped ? (I)C.hi_b : (I)C.hi_a;
+  return (wrapped ? g - nA : (I)(C.lo_a / 16) + g) * (I)16;
+}
+// ring row -> (tick, env) of the transition it takes
+template <typename I> __device__ __forceinline__ void pk_row_te(const PkParams &p, I row, bool wrapped, I &t, I &e) {
+  const I b = wrapped ? row + (I)(p.ring_size - p.ring_start) : row - (I)p.ring_start;
+  t = b / (I)p.E;
+  e = b - t * (I)p.E;
+}
+
+template <int G, typename I> __device__ __forceinline__ void pk_wide(const PkParams &p, const PkCol &C, I g0) {   // rows of >= 16 bytes
+  // (K pieces in flight per lane: all four where a piece is one or two loads, two where it is eight or sixteen)
+  constexpr int K = G >= 8 ? kPkPiecesPerLane : 2, NG = 16 / G;
+  const uint32_t rb = C.rb;
+  const I nA = (I)((C.hi_a + 15) / 16 - C.lo_a / 16), total = nA + (I)((C.hi_b + 15) / 16);
+  const bool prev = C.kind == PK_PREV;
+#pragma unroll 1
+  for (int k0 = 0; k0 < kPkPiecesPerLane; k0 += K) {
+  I first[K], tA[K], eA[K], tB[K], eB[K];
+  uint32_t c0[K], c1[K], u0[K], dA[K], dB[K];
+  bool live[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const I g = g0 + (I)((k0 + k) * 256);
+    live[k] = g < total;
+    I lo, hi;
+    bool wrapped;
+    first[k] = pk_piece<I>(C, live[k] ? g : total - 1, nA, lo, hi, wrapped);      // (lanes past the end repeat the last piece's loads)
+    const I start = first[k] > lo ? first[k] : lo, end = first[k] + 16 < hi ? first[k] + 16 : hi;
+    c0[k] = (uint32_t)(start - first[k]);      // the bytes [c0, c1) of the piece belong to the chunk
+    c1[k] = (uint32_t)(end - first[k]);
+    const I row = start / (I)rb;
+    u0[k] = (uint32_t)(start - row * (I)rb);
+    pk_row_te<I>(p, row, wrapped, tA[k], eA[k]);
+    tB[k] = tA[k];
+    eB[k] = eA[k];
+    if (u0[k] + (c1[k] - c0[k]) > rb) {        // the piece runs on into the next row: the next transition
+      eB[k] = eA[k] + 1;
+      if (eB[k] == (I)p.E) { eB[k] = 0; tB[k] = tA[k] + 1; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    dA[k] = pk_row_done(p, C, tA[k], eA[k]);
+    dB[k] = pk_row_done(p, C, tB[k], eB[k]);
+  }
+  uint32_t w[K][4];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const char *sA = pk_row_src(p, C, tA[k], eA[k], dA[k]), *sB = pk_row_src(p, C, tB[k], eB[k], dB[k]);
+    w[k][0] = w[k][1] = w[k][2] = w[k][3] = 0u;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const uint32_t at = (uint32_t)(i * G);
+      const bool in = at >= c0[k] && at < c1[k];
+      const uint32_t pos = in ? u0[k] + at - c0[k] : u0[k];       // (a granule outside the chunk loads the first one inside it)
+      const bool second = pos >= rb;
+      pk_fetch<G>(w[k], i, second ? sB + (pos - rb) : sA + pos, prev && (second ? dB[k] : dA[k]) != 0u, false);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (!live[k]) continue;
+    char *d = C.dst + (size_t)first[k];
+    if (c0[k] == 0u && c1[k] == 16u) {
+      *reinterpret_cast<uint4 *>(d) = uint4{w[k][0], w[k][1], w[k][2], w[k][3]};
+    } else {
+#pragma unroll
+      for (int i = 0; i < NG; ++i)
+        if ((uint32_t)(i * G) >= c0[k] && (uint32_t)(i * G) < c1[k]) pk_store<G>(d, w[k], i);
+    }
+  }
+  }
+}
+
+template <int G, typename I> __device__ __forceinline__ void pk_narrow(const PkParams &p, const PkCol &C, I g0) {   // rows of < 16 bytes
+  constexpr int K = kPkPiecesPerLane, NG = 16 / G;
+  const uint32_t rb = C.rb;
+  const I nA = (I)((C.hi_a + 15) / 16 - C.lo_a / 16), total = nA + (I)((C.hi_b + 15) / 16);
+#pragma unroll 1
+  for (int k = 0; k < K; ++k) {
+    const I g = g0 + (I)(k * 256);
+    if (g >= total) break;
+    I lo, hi;
+    bool wrapped;
+    const I first = pk_piece<I>(C, g, nA, lo, hi, wrapped);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const I at = first + (I)(i * G);
+      if (at < lo || at >= hi) continue;
+      const I row = at / (I)rb;
+      I t, e;
+      pk_row_te<I>(p, row, wrapped, t, e);
+      const uint32_t d = pk_row_done(p, C, t, e);
+      pk_fetch<G>(w, i, pk_row_src(p, C, t, e, d) + (uint32_t)(at - row * (I)rb), C.kind == PK_PREV && d != 0u, C.kind == PK_DONE);
+    }
+    char *dst = C.dst + (size_t)first;
+    if (first >= lo && first + 16 <= hi) {
+      *reinterpret_cast<uint4 *>(dst) = uint4{w[0], w[1], w[2], w[3]};
+    } else {
+#pragma unroll
+      for (int i = 0; i < NG; ++i)
+        if (first + (I)(i * G) >= lo && first + (I)(i * G) < hi) pk_store<G>(dst, w, i);
+    }
+  }
+}
+
+template <typename I> __global__ void __launch_bounds__(256) k_ck_transitions_pack(const PkParams p) {
+  int c = 0;
+  uint32_t first = 0;
+#pragma unroll
+  for (int k = 0; k < kCkCols - 1; ++k)
+    if (blockIdx.x >= p.blk_end[k]) { c = k + 1; first = p.blk_end[k]; }
+  const PkCol &C = p.col[c];
+  const I g0 = (I)(blockIdx.x - first) * (I)(kPkPiecesPerLane * 256) + (I)threadIdx.x;
+  const uint32_t G = C.gran;
+  if (C.rb >= 16u) {
+    if (G == 16u) pk_wide<16, I>(p, C, g0);
+    else if (G == 8u) pk_wide<8, I>(p, C, g0);
+    else if (G == 4u) pk_wide<4, I>(p, C, g0);
+    else if (G == 2u) pk_wide<2, I>(p, C, g0);
+    else pk_wide<1, I>(p, C, g0);
+  } else {
+    if (G == 8u) pk_narrow<8, I>(p, C, g0);
+    else if (G == 4u) pk_narrow<4, I>(p, C, g0);
+    else if (G == 2u) pk_narrow<2, I>(p, C, g0);
+    else pk_narrow<1, I>(p, C, g0);
+  }
+}
+
 // ---- tiling: the n x n credit repeats and the n x n x l_action counterfactual tiling of train_step ------------------------------
 // (alg_credit.py:614-658 `np.repeat(np.reshape(x, [n_steps, n, d]), n, axis=0)` / `np.repeat(x, n, axis=0)`; :730-751 the same
 // repeated l_action times against np.tile(np.eye(l_action)); process_actions / process_global_state :406-443, :528-557 with their
@@ -502,6 +712,105 @@ template <typename R> __global__ void __launch_bounds__(256) k_td_target(const R
     const double gq = gamma * q[i];
     out[i] = (double)reward[i] + gq * (double)mult[i];
   }
+}
+
+// ---- host side shared by the Checkers export, the compact ring's pack and its expansion --------------------------------------------
+struct CkGeom {
+  uint32_t N, Lo, grid_rec, obst_rec, grid_stride, obst_stride;   // record sizes and strides in bytes
+};
+static int ck_geometry(const cm3_checkers_desc *desc, bool need_envs, CkGeom &g) {
+  CM3_REQUIRE(!need_envs || desc->n_envs > 0, "n_envs must be positive");
+  CM3_REQUIRE(desc->n_agents >= 1 && desc->n_agents <= 8, "Checkers: n_agents must be in 1..8");
+  CM3_REQUIRE(desc->n_rows >= 1 && desc->n_columns >= 2 && desc->n_rows * desc->n_columns <= 64, "n_rows / n_columns out of range");
+  CM3_REQUIRE(desc->n_obs >= 0 && desc->n_obs <= 8, "n_obs out of range");
+  const uint32_t Kw = 2u * (uint32_t)desc->n_obs + 1u;
+  g.N = (uint32_t)desc->n_agents;
+  g.Lo = 2u * (g.N > 1 ? g.N - 1 : 1);
+  g.grid_rec = (uint32_t)desc->n_rows * (uint32_t)(desc->n_columns + 1) * 2u;
+  g.obst_rec = g.N * Kw * Kw * 3u;
+  g.grid_stride = desc->grid_stride ? (uint32_t)desc->grid_stride : g.grid_rec;
+  g.obst_stride = desc->obs_self_t_stride ? (uint32_t)desc->obs_self_t_stride : g.obst_rec;
+  CM3_REQUIRE(desc->grid_stride >= 0 && desc->obs_self_t_stride >= 0 && g.grid_stride >= g.grid_rec && g.obst_stride >= g.obst_rec,
+              "record strides smaller than the records");
+  return CM3_OK;
+}
+
+// what both whole-trajectory readers require of the trajectory: prev0, the base pointers, terminal capture all or none
+static int ck_traj_check(const char *entry, const cm3_checkers_traj *traj, const int32_t *prev0, bool &term) {
+  CM3_REQUIRE(prev0, "%s: prev0 (actions_prev of slot 0) is required", entry);
+  CM3_REQUIRE(traj->actions && traj->grid && traj->vec && traj->obs_others && traj->obs_self_t && traj->obs_self_v &&
+                  traj->local_rewards && traj->reward && traj->done && (traj->goals_slots || traj->goals),
+              "trajectory base pointers are required");
+  const int n_term = (traj->term_grid != nullptr) + (traj->term_vec != nullptr) + (traj->term_obs_others != nullptr) +
+                     (traj->term_obs_self_t != nullptr) + (traj->term_obs_self_v != nullptr);
+  CM3_REQUIRE(n_term == 0 || n_term == 5, "terminal capture: all five term_* arrays or none");
+  term = n_term == 5;
+  return CM3_OK;
+}
+
+struct CkSpec {
+  const char *name;
+  void *dst;
+  const void *src, *alt;
+  size_t slot_stride, alt_stride;
+  uint32_t env_stride, upr, kind, next;
+};
+// One k_ck_transitions_gather launch over the 16 columns of `specs`: `cols_what` / `src_what` name the destination and the source in
+// the error texts.  check_small_copies: the sources of the 8- / 4-byte copy units are checked for the alignment of their loads too (a
+// caller's ring columns; the trajectory export keeps the checks it always had).
+static int ck_gather_launch(const char *entry, const char *cols_what, const char *src_what, bool check_small_copies,
+                            const CkSpec (&specs)[kCkCols], bool term, const uint8_t *done,
+                            size_t st_done, const int32_t *prev0, const int64_t *tt, const int64_t *ee, size_t n, size_t E,
+                            int64_t ring_start, int64_t ring_size, hipStream_t stream) {
+  CkTransParams p;
+  memset(&p, 0, sizeof(p));
+  size_t blocks = 0, most = 0;
+  bool even = true;
+  for (int k = 0; k < kCkCols; ++k) {
+    const CkSpec &s = specs[k];
+    CM3_REQUIRE(s.dst, "%s: column %s is missing", cols_what, s.name);
+    CM3_REQUIRE((uintptr_t)s.dst % ck_dst_bytes(s.kind) == 0, "%s: column %s is not aligned to its %u-byte units", cols_what, s.name,
+                ck_dst_bytes(s.kind));
+    CkCol &c = p.col[k];
+    c.src = (const char *)s.src;
+    c.alt = term ? (const char *)s.alt : nullptr;
+    c.dst = (char *)s.dst;
+    c.slot_stride = s.slot_stride;
+    c.alt_stride = c.alt ? s.alt_stride : 0;
+    c.env_stride = s.env_stride;
+    c.upr = s.upr;
+    c.kind = s.kind;
+    c.next = s.next;
+    if (s.kind == CKU_COPY16 || s.kind == CKU_I32X2)
+      CM3_REQUIRE(((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride) % (s.kind == CKU_COPY16 ? 16 : 8) == 0,
+                  "%s: %s is not aligned to the loads of its units", src_what, s.name);
+    if (check_small_copies && (s.kind == CKU_COPY8 || s.kind == CKU_COPY4))
+      CM3_REQUIRE(((uintptr_t)c.src | c.slot_stride) % (s.kind == CKU_COPY8 ? 8 : 4) == 0,
+                  "%s: %s is not aligned to the loads of its units", src_what, s.name);
+    if (s.kind == CKU_I8X2) even = even && (((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride | c.env_stride) & 1u) == 0;
+    const size_t units = n * s.upr;
+    most = units > most ? units : most;
+    blocks += (units + kCkUnitsPerLane * 256 - 1) / (kCkUnitsPerLane * 256);
+    CM3_REQUIRE(blocks < ((size_t)1 << 31), "%s: too many transitions for one launch", entry);
+    p.blk_end[k] = (uint32_t)blocks;
+  }
+  p.done = done;
+  p.st_done = st_done;
+  p.prev0 = prev0;
+  p.tt = tt;
+  p.ee = ee;
+  p.n = n;
+  p.E = E;
+  p.ring_start = (size_t)ring_start;
+  p.ring_size = (size_t)ring_size;
+  p.term = term ? 1 : 0;
+  p.pair16 = even ? 1 : 0;
+  if (most + kCkUnitsPerLane * 256 < (size_t)1 << 32)     // (32-bit unit arithmetic: a 64-bit division per unit costs more than the copy)
+    hipLaunchKernelGGL(k_ck_transitions_gather<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  else
+    hipLaunchKernelGGL(k_ck_transitions_gather<size_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
 }
 
 }  // namespace cm3
@@ -645,36 +954,15 @@ int cm3_checkers_transitions_gather(const cm3_checkers_desc *desc, const cm3_che
   CM3_REQUIRE(out->ring_size >= 0 && out->ring_start >= 0 && (out->ring_size == 0 || (out->ring_start < out->ring_size && n <= out->ring_size)),
               "checkers transition columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
   if (n == 0) return CM3_OK;      // (before the pointer checks: the columns of an empty batch are null)
-  CM3_REQUIRE(desc->n_envs > 0, "n_envs must be positive");
-  CM3_REQUIRE(desc->n_agents >= 1 && desc->n_agents <= 8, "Checkers: n_agents must be in 1..8");
-  CM3_REQUIRE(desc->n_rows >= 1 && desc->n_columns >= 2 && desc->n_rows * desc->n_columns <= 64, "n_rows / n_columns out of range");
-  CM3_REQUIRE(desc->n_obs >= 0 && desc->n_obs <= 8, "n_obs out of range");
-  const uint32_t N = (uint32_t)desc->n_agents, Kw = 2u * (uint32_t)desc->n_obs + 1u, Lo = 2u * (N > 1 ? N - 1 : 1);
-  const uint32_t grid_rec = (uint32_t)desc->n_rows * (uint32_t)(desc->n_columns + 1) * 2u, obst_rec = N * Kw * Kw * 3u;
-  const uint32_t grid_stride = desc->grid_stride ? (uint32_t)desc->grid_stride : grid_rec;
-  const uint32_t obst_stride = desc->obs_self_t_stride ? (uint32_t)desc->obs_self_t_stride : obst_rec;
-  CM3_REQUIRE(desc->grid_stride >= 0 && desc->obs_self_t_stride >= 0 && grid_stride >= grid_rec && obst_stride >= obst_rec,
-              "record strides smaller than the records");
-  CM3_REQUIRE(prev0, "checkers_transitions_gather: prev0 (actions_prev of slot 0) is required");
-  CM3_REQUIRE(traj->actions && traj->grid && traj->vec && traj->obs_others && traj->obs_self_t && traj->obs_self_v &&
-                  traj->local_rewards && traj->reward && traj->done && (traj->goals_slots || traj->goals),
-              "trajectory base pointers are required");
-  const int n_term = (traj->term_grid != nullptr) + (traj->term_vec != nullptr) + (traj->term_obs_others != nullptr) +
-                     (traj->term_obs_self_t != nullptr) + (traj->term_obs_self_v != nullptr);
-  CM3_REQUIRE(n_term == 0 || n_term == 5, "terminal capture: all five term_* arrays or none");
-  const bool term = n_term == 5;
-  CkTransParams p;
-  memset(&p, 0, sizeof(p));
+  CkGeom geo;
+  if (int rc = ck_geometry(desc, true, geo)) return rc;
+  const uint32_t N = geo.N, Lo = geo.Lo, grid_rec = geo.grid_rec, obst_rec = geo.obst_rec, grid_stride = geo.grid_stride,
+                 obst_stride = geo.obst_stride;
+  bool term = false;
+  if (int rc = ck_traj_check("checkers_transitions_gather", traj, prev0, term)) return rc;
   const bool obst_odd = (obst_rec & 1u) != 0;   // (a row of 75 N doubles at odd N: 8-byte units)
-  struct Spec {
-    const char *name;
-    void *dst;
-    const void *src, *alt;
-    size_t slot_stride, alt_stride;
-    uint32_t env_stride, upr, kind, next;
-  };
   const uint32_t obst_kind = obst_odd ? CKU_I8 : CKU_I8X2, obst_upr = obst_odd ? obst_rec : obst_rec / 2;
-  const Spec specs[kCkCols] = {
+  const CkSpec specs[kCkCols] = {
       {"grid", out->grid, traj->grid, nullptr, traj->grid_slot_stride, 0, grid_stride, grid_rec / 2, CKU_I8X2, 0},
       {"vec", out->vec, traj->vec, nullptr, traj->vec_stride, 0, 16 * N, 2 * N, CKU_I32X2, 0},
       {"obs_others", out->obs_others, traj->obs_others, nullptr, traj->obs_others_stride, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
@@ -698,49 +986,145 @@ int cm3_checkers_transitions_gather(const cm3_checkers_desc *desc, const cm3_che
       {"goals", out->goals, traj->goals_slots ? traj->goals_slots : traj->goals, nullptr,
        traj->goals_slots ? traj->goals_slots_stride : 0, 0, N, N, CKU_GOAL, 0},
   };
+  return ck_gather_launch("checkers_transitions_gather", "checkers transition columns", "checkers trajectory", false, specs, term, traj->done, traj->done_stride, prev0, tt, ee,
+                          (size_t)n, (size_t)desc->n_envs, out->ring_start, out->ring_size, (hipStream_t)stream);
+}
+
+int cm3_checkers_transitions_pack(const cm3_checkers_desc *desc, const cm3_checkers_traj *traj, const int32_t *prev0, int64_t n,
+                                  const cm3_checkers_compact_cols *out, void *stream) {
+  using namespace cm3;
+  CM3_REQUIRE(desc, "checkers_transitions_pack: null desc");
+  CM3_REQUIRE(traj, "checkers_transitions_pack: null traj");
+  CM3_REQUIRE(out, "checkers_transitions_pack: null compact columns");
+  CM3_REQUIRE(n >= 0, "n must be >= 0");
+  CM3_REQUIRE(out->ring_size >= 1 && out->ring_start >= 0 && out->ring_start < out->ring_size && n <= out->ring_size,
+              "compact checkers columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (n == 0) return CM3_OK;      // (before the pointer checks: nothing is touched)
+  CkGeom geo;
+  if (int rc = ck_geometry(desc, true, geo)) return rc;
+  const uint32_t N = geo.N, Lo = geo.Lo;
+  bool term = false;
+  if (int rc = ck_traj_check("checkers_transitions_pack", traj, prev0, term)) return rc;
+  // (CkSpec.upr holds the BYTES of a ring row here)
+  const CkSpec specs[kCkCols] = {
+      {"grid", out->grid, traj->grid, nullptr, traj->grid_slot_stride, 0, geo.grid_stride, geo.grid_rec, PK_COPY, 0},
+      {"vec", out->vec, traj->vec, nullptr, traj->vec_stride, 0, 16 * N, 16 * N, PK_COPY, 0},
+      {"obs_others", out->obs_others, traj->obs_others, nullptr, traj->obs_others_stride, 0, 8 * N * Lo, 8 * N * Lo, PK_COPY, 0},
+      {"obs_self_t", out->obs_self_t, traj->obs_self_t, nullptr, traj->obs_self_t_slot_stride, 0, geo.obst_stride, geo.obst_rec, PK_COPY, 0},
+      {"obs_self_v", out->obs_self_v, traj->obs_self_v, nullptr, traj->obs_self_v_stride, 0, 32 * N, 32 * N, PK_COPY, 0},
+      {"actions_prev", out->actions_prev, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, 4 * N, PK_PREV, 0},
+      {"actions", out->actions, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, 4 * N, PK_COPY, 0},
+      {"reward", out->reward, traj->reward, nullptr, traj->reward_stride, 0, 8, 8, PK_COPY, 0},
+      {"local_rewards", out->local_rewards, traj->local_rewards, nullptr, traj->local_rewards_stride, 0, 8 * N, 8 * N, PK_COPY, 0},
+      {"next_grid", out->next_grid, traj->grid, traj->term_grid, traj->grid_slot_stride, traj->term_grid_slot_stride, geo.grid_stride,
+       geo.grid_rec, PK_COPY, 1},
+      {"next_vec", out->next_vec, traj->vec, traj->term_vec, traj->vec_stride, traj->term_vec_stride, 16 * N, 16 * N, PK_COPY, 1},
+      {"next_obs_others", out->next_obs_others, traj->obs_others, traj->term_obs_others, traj->obs_others_stride,
+       traj->term_obs_others_stride, 8 * N * Lo, 8 * N * Lo, PK_COPY, 1},
+      {"next_obs_self_t", out->next_obs_self_t, traj->obs_self_t, traj->term_obs_self_t, traj->obs_self_t_slot_stride,
+       traj->term_obs_self_t_slot_stride, geo.obst_stride, geo.obst_rec, PK_COPY, 1},
+      {"next_obs_self_v", out->next_obs_self_v, traj->obs_self_v, traj->term_obs_self_v, traj->obs_self_v_stride,
+       traj->term_obs_self_v_stride, 32 * N, 32 * N, PK_COPY, 1},
+      {"done", out->done, traj->done, nullptr, traj->done_stride, 0, 1, 1, PK_DONE, 0},
+      {"goals", out->goals, traj->goals_slots ? traj->goals_slots : traj->goals, nullptr,
+       traj->goals_slots ? traj->goals_slots_stride : 0, 0, N, N, PK_COPY, 0},
+  };
+  PkParams p;
+  memset(&p, 0, sizeof(p));
+  const size_t start = (size_t)out->ring_start, size = (size_t)out->ring_size;
+  const size_t rows_a = start + (size_t)n <= size ? (size_t)n : size - start, rows_b = (size_t)n - rows_a;   // before / past the wrap
   size_t blocks = 0, most = 0;
-  bool even = true;
   for (int k = 0; k < kCkCols; ++k) {
-    const Spec &s = specs[k];
-    CM3_REQUIRE(s.dst, "checkers transition columns: column %s is missing", s.name);
-    CM3_REQUIRE((uintptr_t)s.dst % ck_dst_bytes(s.kind) == 0, "checkers transition columns: column %s is not aligned to its %u-byte units",
-                s.name, ck_dst_bytes(s.kind));
-    CkCol &c = p.col[k];
+    const CkSpec &s = specs[k];
+    CM3_REQUIRE(s.dst, "compact checkers columns: column %s is missing", s.name);
+    CM3_REQUIRE((uintptr_t)s.dst % 16 == 0, "compact checkers columns: column %s is not aligned to the 16-byte pieces the kernel stores",
+                s.name);
+    PkCol &c = p.col[k];
     c.src = (const char *)s.src;
     c.alt = term ? (const char *)s.alt : nullptr;
     c.dst = (char *)s.dst;
     c.slot_stride = s.slot_stride;
     c.alt_stride = c.alt ? s.alt_stride : 0;
     c.env_stride = s.env_stride;
-    c.upr = s.upr;
+    c.rb = s.upr;
     c.kind = s.kind;
     c.next = s.next;
-    if (s.kind == CKU_COPY16 || s.kind == CKU_I32X2)
-      CM3_REQUIRE(((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride) % (s.kind == CKU_COPY16 ? 16 : 8) == 0,
-                  "checkers trajectory: %s is not aligned to the loads of its units", s.name);
-    if (s.kind == CKU_I8X2) even = even && (((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride | c.env_stride) & 1u) == 0;
-    const size_t units = (size_t)n * s.upr;
-    most = units > most ? units : most;
-    blocks += (units + kCkUnitsPerLane * 256 - 1) / (kCkUnitsPerLane * 256);
-    CM3_REQUIRE(blocks < ((size_t)1 << 31), "checkers_transitions_gather: too many transitions for one launch");
+    c.lo_a = start * s.upr;
+    c.hi_a = (start + rows_a) * s.upr;
+    c.hi_b = rows_b * s.upr;
+    // the granule: what divides the row, every stride and every base (a granule is one naturally aligned load inside one row)
+    uintptr_t a = (uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride | c.env_stride | c.rb;
+    if (s.kind == PK_PREV) a |= (uintptr_t)prev0;
+    c.gran = a % 16 == 0 ? 16u : a % 8 == 0 ? 8u : a % 4 == 0 ? 4u : a % 2 == 0 ? 2u : 1u;
+    const size_t pieces = (c.hi_a + 15) / 16 - c.lo_a / 16 + (c.hi_b + 15) / 16;
+    const size_t bytes = size * s.upr;
+    most = bytes > most ? bytes : most;
+    blocks += (pieces + kPkPiecesPerLane * 256 - 1) / (kPkPiecesPerLane * 256);
+    CM3_REQUIRE(blocks < ((size_t)1 << 31), "checkers_transitions_pack: too many transitions for one launch");
     p.blk_end[k] = (uint32_t)blocks;
   }
   p.done = traj->done;
   p.st_done = traj->done_stride;
-  p.prev0 = prev0;
-  p.tt = tt;
-  p.ee = ee;
-  p.n = (size_t)n;
+  p.prev0 = (const char *)prev0;
   p.E = (size_t)desc->n_envs;
-  p.ring_start = (size_t)out->ring_start;
-  p.ring_size = (size_t)out->ring_size;
+  p.ring_start = start;
+  p.ring_size = size;
   p.term = term ? 1 : 0;
-  p.pair16 = even ? 1 : 0;
-  if (most + kCkUnitsPerLane * 256 < (size_t)1 << 32)     // (32-bit unit arithmetic: a 64-bit division per unit costs more than the copy)
-    hipLaunchKernelGGL(k_ck_transitions_gather<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  // (32-bit byte offsets into a ring column whenever the largest column fits, the slack of a last workgroup included)
+  if (most + 32 * kPkPiecesPerLane * 256 < (size_t)1 << 32 && 2 * size < (size_t)1 << 32)
+    hipLaunchKernelGGL(k_ck_transitions_pack<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   else
-    hipLaunchKernelGGL(k_ck_transitions_gather<size_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_ck_transitions_pack<size_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
+}
+
+int cm3_checkers_ring_expand(const cm3_checkers_desc *desc, const cm3_checkers_compact_cols *ring, const int64_t *index, int64_t n,
+                             const cm3_checkers_transition_cols *out, void *stream) {
+  using namespace cm3;
+  CM3_REQUIRE(desc, "checkers_ring_expand: null desc");
+  CM3_REQUIRE(ring, "checkers_ring_expand: null compact columns");
+  CM3_REQUIRE(out, "checkers_ring_expand: null out");
+  CM3_REQUIRE(n >= 0, "n must be >= 0");
+  CM3_REQUIRE(ring->ring_size >= 1 && ring->ring_start >= 0 && ring->ring_start < ring->ring_size && n <= ring->ring_size,
+              "compact checkers columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  CM3_REQUIRE(out->ring_size >= 0 && out->ring_start >= 0 && (out->ring_size == 0 || (out->ring_start < out->ring_size && n <= out->ring_size)),
+              "checkers transition columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (n == 0) return CM3_OK;      // (before the pointer checks: the columns of an empty batch are null)
+  CkGeom geo;
+  if (int rc = ck_geometry(desc, false, geo)) return rc;
+  const uint32_t N = geo.N, Lo = geo.Lo, grid_rec = geo.grid_rec, obst_rec = geo.obst_rec;
+  const bool obst_odd = (obst_rec & 1u) != 0;
+  const uint32_t obst_kind = obst_odd ? CKU_I8 : CKU_I8X2, obst_upr = obst_odd ? obst_rec : obst_rec / 2;
+  const struct { const char *name; const void *p; } have[kCkCols] = {
+      {"grid", ring->grid}, {"vec", ring->vec}, {"obs_others", ring->obs_others}, {"obs_self_t", ring->obs_self_t},
+      {"obs_self_v", ring->obs_self_v}, {"actions_prev", ring->actions_prev}, {"actions", ring->actions}, {"reward", ring->reward},
+      {"local_rewards", ring->local_rewards}, {"next_grid", ring->next_grid}, {"next_vec", ring->next_vec},
+      {"next_obs_others", ring->next_obs_others}, {"next_obs_self_t", ring->next_obs_self_t}, {"next_obs_self_v", ring->next_obs_self_v},
+      {"done", ring->done}, {"goals", ring->goals}};
+  for (int k = 0; k < kCkCols; ++k) CM3_REQUIRE(have[k].p, "compact checkers columns: column %s is missing", have[k].name);
+  // the unit kinds of the export with ONE slot (stride 0) of dense ring rows as their source: row index[b] is the "env", the
+  // actions_prev and done a row holds are final (plain copies -- CKU_DONE reads p.done, here the ring's own column)
+  const CkSpec specs[kCkCols] = {
+      {"grid", out->grid, ring->grid, nullptr, 0, 0, grid_rec, grid_rec / 2, CKU_I8X2, 0},
+      {"vec", out->vec, ring->vec, nullptr, 0, 0, 16 * N, 2 * N, CKU_I32X2, 0},
+      {"obs_others", out->obs_others, ring->obs_others, nullptr, 0, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
+      {"obs_self_t", out->obs_self_t, ring->obs_self_t, nullptr, 0, 0, obst_rec, obst_upr, obst_kind, 0},
+      {"obs_self_v", out->obs_self_v, ring->obs_self_v, nullptr, 0, 0, 32 * N, 2 * N, CKU_COPY16, 0},
+      {"actions_prev", out->actions_prev, ring->actions_prev, nullptr, 0, 0, 4 * N, N, CKU_COPY4, 0},
+      {"actions", out->actions, ring->actions, nullptr, 0, 0, 4 * N, N, CKU_COPY4, 0},
+      {"reward", out->reward, ring->reward, nullptr, 0, 0, 8, 1, CKU_COPY8, 0},
+      {"local_rewards", out->local_rewards, ring->local_rewards, nullptr, 0, 0, 8 * N, N, CKU_COPY8, 0},
+      {"next_grid", out->next_grid, ring->next_grid, nullptr, 0, 0, grid_rec, grid_rec / 2, CKU_I8X2, 0},
+      {"next_vec", out->next_vec, ring->next_vec, nullptr, 0, 0, 16 * N, 2 * N, CKU_I32X2, 0},
+      {"next_obs_others", out->next_obs_others, ring->next_obs_others, nullptr, 0, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
+      {"next_obs_self_t", out->next_obs_self_t, ring->next_obs_self_t, nullptr, 0, 0, obst_rec, obst_upr, obst_kind, 0},
+      {"next_obs_self_v", out->next_obs_self_v, ring->next_obs_self_v, nullptr, 0, 0, 32 * N, 2 * N, CKU_COPY16, 0},
+      {"done", out->done, ring->done, nullptr, 0, 0, 1, 1, CKU_DONE, 0},
+      {"goals", out->goals, ring->goals, nullptr, 0, 0, N, N, CKU_GOAL, 0},
+  };
+  // index NULL: rows 0 .. n - 1 -- the whole-trajectory order b = t E + e with E = n is tick 0, env b
+  return ck_gather_launch("checkers_ring_expand", "checkers transition columns", "compact checkers columns", true, specs, false, ring->done, 0, nullptr, nullptr, index,
+                          (size_t)n, (size_t)n, out->ring_start, out->ring_size, (hipStream_t)stream);
 }
 }

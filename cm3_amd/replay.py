@@ -144,6 +144,152 @@ class DeviceReplayBuffer(object):
         return self._take(sample_distinct(self.len, n, 1, generator, self.device)[0])
 
 
+class CompactCheckersReplayBuffer(object):
+    """replay_buffer.Replay_Buffer for Checkers transitions with NARROW storage: the ring keeps every column with the dtype the
+    trajectory keeps (grid / obs_self_t int8, vec int32, goals the uint8 goal index: 707 B per transition at the reference geometry
+    where DeviceReplayBuffer's float64 columns take 3657 B) and only the rows a learner samples are widened.  The surface and the
+    draws are DeviceReplayBuffer's, and sample_batch() returns exactly its 16 float64 / int32 / bool / int64 columns
+    (CheckersRollout.ORDER), bit for bit: int8 -> float64 and int32 -> float64 are exact.
+      add_rollout  ONE launch of cm3_checkers_transitions_pack (csrc/batch.hip), nothing converted;
+      sampling     the draws of DeviceReplayBuffer, then ONE launch of cm3_checkers_ring_expand;
+      add          the wide reference columns, narrowed with torch casts (a cold path; values that do not survive are refused).
+    all() and sample_batch() below `size` return COPIES (expanded rows), never views of the ring.  `self.cols` are the compact
+    columns."""
+
+    def __init__(self, size=int(1e6), device="cuda:0"):
+        self.device = _lib.require_gpu(device)
+        self.ring = RingIndex(size)
+        self.cols = None
+        self._wide = None        # name -> (row shape, dtype) of the columns sample_batch returns
+        self._desc = None
+
+    maxsize = property(lambda self: self.ring.maxsize)
+    idx = property(lambda self: self.ring.idx)
+    len = property(lambda self: self.ring.len)
+
+    def __len__(self):
+        return self.ring.len
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _layout(self, wide):
+        """wide: name -> (row shape, dtype) of the reference columns.  Fixes the geometry on first use; later it must agree."""
+        from .rollout import CHECKERS_ORDER
+        wide = {k: (tuple(shape), dt) for k, (shape, dt) in wide.items()}
+        if self._wide is not None:
+            if wide != self._wide:
+                raise Cm3Error("replay columns changed: %s vs %s" % (wide, self._wide))
+            return
+        if tuple(wide) != CHECKERS_ORDER:
+            raise Cm3Error("a compact Checkers ring takes the 16 columns of CheckersRollout.ORDER, got %s" % (sorted(wide),))
+        grid, obst = wide["grid"][0], wide["obs_self_t"][0]
+        if len(grid) != 3 or grid[2] != 2 or len(obst) != 4 or obst[1] != obst[2] or obst[3] != 3 or obst[1] % 2 != 1:
+            raise Cm3Error("grid must be [B, R, C + 1, 2] and obs_self_t [B, N, K, K, 3] with odd K: %s, %s" % (grid, obst))
+        d = _lib.CheckersDesc()
+        d.n_envs, d.n_agents, d.n_rows, d.n_columns, d.n_obs = 1, obst[0], grid[0], grid[1] - 1, (obst[1] - 1) // 2
+        self._wide, self._desc = wide, d
+
+    def _ring(self):
+        from .rollout import compact_specs
+        if self.cols is None:
+            return {k: torch.zeros((self.maxsize,) + shape, dtype=dt, device=self.device) for k, (shape, dt) in compact_specs(self._wide).items()}
+        return self.cols
+
+    def add_rollout(self, rollout):
+        """All transitions of a continuous Checkers collection, straight from the trajectory into the compact ring: ONE launch
+        (CheckersRollout.pack_into).  A chunk larger than the ring goes through add(): the newest transitions survive, as
+        sequential adds leave them."""
+        if not hasattr(rollout, "pack_into"):
+            raise Cm3Error("a compact Checkers ring takes a CheckersRollout")
+        B = rollout.T * rollout.env.E
+        if B > self.maxsize:
+            return self.add(rollout.as_reference_batch(numpy=False))
+        self._layout(rollout.column_specs())
+        cols = self._ring()
+        # (validate and launch FIRST, keep the ring and advance it after, as DeviceReplayBuffer.add_rollout)
+        rollout.pack_into(cols, self.ring.idx, self.maxsize)
+        self.cols = cols
+        self.ring.plan_add(B)
+
+    def add(self, cols):
+        """cols: the WIDE reference columns (what as_reference_batch(numpy=False) returns), B transitions in order.  They are narrowed
+        here; a value that does not survive -- a grid / obs_self_t entry that is no int8, a vec entry that is no int32, goals that are
+        not one-hot -- raises Cm3Error and leaves the ring as it was."""
+        from .rollout import CHECKERS_ORDER, compact_specs
+        if set(cols) != set(CHECKERS_ORDER):
+            raise Cm3Error("a compact Checkers ring takes the 16 columns of CheckersRollout.ORDER, got %s" % (sorted(cols),))
+        wide = {k: cols[k].to(self.device) for k in CHECKERS_ORDER}
+        B = wide["reward"].shape[0]
+        if B == 0:
+            return
+        self._layout({k: (tuple(v.shape[1:]), torch.bool if k == "done" else v.dtype) for k, v in wide.items()})
+        narrow = {}
+        for name, (shape, dt) in compact_specs(self._wide).items():
+            v = wide[name]
+            if v.shape[0] != B:
+                raise Cm3Error("column %s has %d rows, reward %d" % (name, v.shape[0], B))
+            if name == "goals":
+                if not bool(((v == 0) | (v == 1)).all()) or not bool((v.sum(-1) == 1).all()):
+                    raise Cm3Error("goals must be one-hot pairs: the compact ring stores the goal index")
+                c = v[..., 1].to(torch.uint8)
+            elif name == "done":
+                c = v.bool()
+            else:
+                c = v.to(dt)
+                if dt != v.dtype and not torch.equal(c.to(v.dtype), v):
+                    raise Cm3Error("column %s holds values that are no %s: the compact ring cannot store them" % (name, dt))
+            narrow[name] = c
+        ring = self._ring()
+        # (launch FIRST, keep the ring and advance it after, as add_rollout: a scatter that raises leaves idx / len as they were)
+        skip = max(0, B - self.maxsize)
+        start, kept = (self.ring.idx + skip) % self.maxsize, B - skip
+        _lib.rows_scatter([(ring[k], narrow[k][skip:].contiguous()) for k in ring], kept, self._stream(), ring_start=start,
+                          ring_size=self.maxsize)
+        self.cols = ring
+        assert self.ring.plan_add(B) == (skip, start, kept)
+
+    def _expand(self, index, n, out, what):
+        """Rows index[b] (None: 0 .. n - 1) of the ring as the 16 reference columns: ONE launch of cm3_checkers_ring_expand."""
+        import ctypes
+        from .rollout import check_columns
+        if self.cols is None:
+            raise Cm3Error("%s: the replay buffer is empty" % what)
+        if out is None:
+            out = {k: torch.empty((n,) + shape, dtype=dt, device=self.device) for k, (shape, dt) in self._wide.items()}
+        else:
+            check_columns(self._wide, out, n, self.device, "%s(out=...): pass the dict an earlier call returned for %d transitions" % (what, n))
+            out = {k: out[k] for k in self._wide}
+        if n:
+            src, dst = _lib.CheckersCompactCols(), _lib.CheckersTransitionCols()
+            for name in self._wide:
+                setattr(src, name, self.cols[name].data_ptr())
+                setattr(dst, name, out[name].data_ptr())
+            src.ring_start, src.ring_size = 0, self.maxsize
+            _lib.check(_lib.lib().cm3_checkers_ring_expand(ctypes.byref(self._desc), ctypes.byref(src), _lib.ptr(index), int(n),
+                                                           ctypes.byref(dst), self._stream()))
+        return out
+
+    def all(self):
+        """Everything stored, in storage order, as the reference columns: a COPY by nature (the rows are widened) -- unlike
+        DeviceReplayBuffer.all(), whose views the next add overwrites."""
+        return self._expand(None, self.len, None, "all")
+
+    def sample_batch(self, size, generator=None, out=None):
+        """DeviceReplayBuffer.sample_batch: everything in storage order if len <= size, else `size` distinct rows uniformly (the
+        same draws for the same len and generator state).  Fresh tensors, or with out= (a dict an earlier call returned for the same
+        row count) those tensors written again: the persistent addresses a captured graph of the consumer needs."""
+        if self.len <= size:
+            return self._expand(None, self.len, out, "sample_batch")
+        return self.sample_n(size, generator, out)
+
+    def sample_n(self, n, generator=None, out=None):
+        from .rollout import sample_distinct
+        n = min(int(n), self.len)
+        index = sample_distinct(self.len, n, 1, generator, self.device)[0].to(torch.int64).contiguous()
+        return self._expand(index, n, out, "sample_n")
+
+
 def _cat(a, b):
     if a is None:
         return b
@@ -195,7 +341,8 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
     transition goes into a PERSISTENT replay buffer (:337-346), and every `steps_per_train` env steps (:348) a batch is sampled
     from it (:350) for a training step.  Vectorised: `rollout` (a ParticleRollout / CheckersRollout in continuous mode with
     n_ticks = steps_per_train) collects one chunk of ticks for all its envs, all transitions of the chunk are added to `buffer`
-    (DeviceReplayBuffer: ONE launch) and one batch is sampled -- yielded as device columns; `collect_kwargs` go to
+    (DeviceReplayBuffer, or for Checkers a CompactCheckersReplayBuffer -- a fifth of the memory, the same batches: ONE launch) and
+    one batch is sampled -- yielded as device columns; `collect_kwargs` go to
     rollout.collect() (policy=..., epsilon=..., goals=... for Checkers; policy= a ParticleQmixAgent / CheckersQmixAgent is the
     QMIX baseline's collection, train_offpolicy.py:319 / :317 with use_qmix = 1).  The buffer outlives the chunks: old transitions are
     overwritten only when it is full (replay_buffer.py:11-16)."""

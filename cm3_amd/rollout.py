@@ -144,6 +144,35 @@ class _ActorGraphCache(_CapturedGraph):
         self.policy = None
 
 
+def check_columns(specs, columns, rows, device, what):
+    """Every column of `specs` (name -> (row shape, dtype)) present in `columns` as a contiguous tensor [rows, ...] on `device` with
+    that row shape and dtype (done: bool or uint8): what a kernel that writes through the raw pointers relies on."""
+    for name, (shape, dt) in specs.items():
+        t = columns.get(name) if hasattr(columns, "get") else None
+        ok_dt = (torch.bool, torch.uint8) if name == "done" else (dt,)
+        if (not torch.is_tensor(t) or not t.is_cuda or t.device != device or not t.is_contiguous() or t.dim() != 1 + len(shape)
+                or t.shape[0] != rows or tuple(t.shape[1:]) != shape or t.dtype not in ok_dt):
+            raise Cm3Error("%s: column %s must be a contiguous tensor [%d%s] of %s on %s" %
+                           (what, name, rows, "".join(", %d" % d for d in shape), dt, device))
+
+
+def compact_specs(specs):
+    """The compact form of the Checkers column specs (name -> (row shape, dtype)): every column with the dtype the trajectory keeps --
+    grid / obs_self_t int8, vec int32, goals the uint8 goal index instead of the one-hot int64 pair -- the others as they are."""
+    out = {}
+    for name, (shape, dt) in specs.items():
+        base = name[5:] if name.startswith("next_") else name
+        if base in ("grid", "obs_self_t"):
+            out[name] = (shape, torch.int8)
+        elif base == "vec":
+            out[name] = (shape, torch.int32)
+        elif base == "goals":
+            out[name] = (shape[:-1], torch.uint8)
+        else:
+            out[name] = (shape, dt)
+    return out
+
+
 class _Transitions(object):
     """What ParticleRollout and CheckersRollout share once a trajectory is collected: which transitions are valid, their export as the
     reference's columns (one launch, into fresh tensors, the caller's, or ring rows), draws over them, the one-launch export of a whole
@@ -188,16 +217,10 @@ class _Transitions(object):
         """Every aliased name of `columns` is the tensor of the column it stands for (the kernel writes each distinct column once)."""
         return all(a in columns and b in columns and columns[a].data_ptr() == columns[b].data_ptr() for a, b in self.ALIASES.items())
 
-    def _check_columns(self, columns, rows, what):
+    def _check_columns(self, columns, rows, what, specs=None):
         """Every column a contiguous device tensor [rows, ...] of the right row shape and dtype: the kernel writes rows * row bytes
         through each pointer, a wrong layout would be an out-of-bounds device write."""
-        for name, (shape, dt) in self.column_specs().items():
-            t = columns.get(name) if hasattr(columns, "get") else None
-            ok_dt = (torch.bool, torch.uint8) if name == "done" else (dt,)
-            if (not torch.is_tensor(t) or not t.is_cuda or t.device != self.done.device or not t.is_contiguous() or t.dim() != 1 + len(shape)
-                    or t.shape[0] != rows or tuple(t.shape[1:]) != shape or t.dtype not in ok_dt):
-                raise Cm3Error("%s: column %s must be a contiguous tensor [%d%s] of %s on %s" %
-                               (what, name, rows, "".join(", %d" % d for d in shape), dt, self.env.device))
+        check_columns(self.column_specs() if specs is None else specs, columns, rows, self.done.device, what)
         if not self.aliases_hold(columns):
             raise Cm3Error("%s: %s must be the tensors of %s" % (what, ", ".join(self.ALIASES), ", ".join(self.ALIASES.values())))
 
@@ -1190,6 +1213,34 @@ class CheckersRollout(_Transitions):
         out.ring_start, out.ring_size = int(ring_start), int(ring_size)
         _lib.check(self._lib.cm3_checkers_transitions_gather(ctypes.byref(env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr(),
                                                              _lib.ptr(tt), _lib.ptr(ee), int(B), ctypes.byref(out), env._stream()))
+
+    def compact_column_specs(self):
+        """name -> (row shape, dtype) of the 16 columns of a compact replay ring (replay.CompactCheckersReplayBuffer), in ORDER: the
+        columns of column_specs() with the dtypes the trajectory keeps (707 B per transition at the reference geometry, not 3657)."""
+        return compact_specs(self.column_specs())
+
+    def pack_into(self, columns, ring_start, ring_size):
+        """Every transition of the trajectory (continuous collection the export kernel applies to) written into the rows
+        (ring_start + b) mod ring_size of the compact `columns` (compact_column_specs(), ring_size rows each): ONE launch of
+        cm3_checkers_transitions_pack, nothing converted.  Every column is checked before the launch.  Returns the number of
+        transitions."""
+        if not (self.auto_reset and self.kernel_export):
+            raise Cm3Error("pack_into needs a continuous collection (every transition valid) that the export kernel reads")
+        ring_start, ring_size = int(ring_start), int(ring_size)
+        B = self.T * self.env.E
+        if not (0 <= ring_start < ring_size and B <= ring_size):
+            raise Cm3Error("pack_into: ring of %d rows from row %d does not take %d transitions" % (ring_size, ring_start, B))
+        self._check_columns(columns, ring_size, "pack_into", self.compact_column_specs())
+        env = self.env
+        if self._gather_traj is None:
+            self._gather_traj = self._traj()           # (the trajectory buffers never move)
+        out = _lib.CheckersCompactCols()
+        for name in self.ORDER:
+            setattr(out, name, columns[name].data_ptr())
+        out.ring_start, out.ring_size = ring_start, ring_size
+        _lib.check(self._lib.cm3_checkers_transitions_pack(ctypes.byref(env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr(),
+                                                           B, ctypes.byref(out), env._stream()))
+        return B
 
     def as_reference_batch_torch(self, tt, ee, numpy=True):
         """The same columns as a composition of torch indexing operations (the specification of cm3_checkers_transitions_gather);

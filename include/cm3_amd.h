@@ -48,7 +48,8 @@ extern "C" {
 
 #define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
                                   Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network);
-                                  cm3_checkers_transitions_gather (the Checkers transition export in one launch).
+                                  cm3_checkers_transitions_gather (the Checkers transition export in one launch);
+                                  cm3_checkers_transitions_pack / cm3_checkers_ring_expand (the compact Checkers replay ring).
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -677,6 +678,45 @@ int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle
 int cm3_checkers_transitions_gather(const cm3_checkers_desc *desc, const cm3_checkers_traj *traj, const int32_t *prev0,
                                     const int64_t *tt, const int64_t *ee, int64_t n, const cm3_checkers_transition_cols *out,
                                     void *stream);
+
+/* The COMPACT Checkers replay ring (additive in ABI 9): the same 16 columns, each with the dtype the trajectory keeps and DENSE rows
+ * (no padding) -- 707 B per transition at the reference geometry with N = 2 instead of the 3657 B of cm3_checkers_transition_cols.
+ * Field order = CheckersRollout.ORDER.  Every column holds ring_size rows and is 16-byte aligned.  (Untagged, as the struct above;
+ * its layout is checked by tests/test_checkers_compact_abi.py.) */
+typedef struct {
+  int8_t *grid;             /* [ring_size][R][C+1][2] */
+  int32_t *vec;             /* [ring_size][N][4] */
+  double *obs_others;       /* [ring_size][N][Lo] */
+  int8_t *obs_self_t;       /* [ring_size][N][K][K][3] */
+  double *obs_self_v;       /* [ring_size][N][4] */
+  int32_t *actions_prev;    /* [ring_size][N]  final values: prev0 / zeros behind a done already applied */
+  int32_t *actions;         /* [ring_size][N] */
+  double *reward;           /* [ring_size] */
+  double *local_rewards;    /* [ring_size][N] */
+  int8_t *next_grid;
+  int32_t *next_vec;
+  double *next_obs_others;
+  int8_t *next_obs_self_t;
+  double *next_obs_self_v;
+  uint8_t *done;            /* [ring_size]  0 / 1 */
+  uint8_t *goals;           /* [ring_size][N]  the goal INDEX; the one-hot pair is made by cm3_checkers_ring_expand */
+  int64_t ring_start;       /* cm3_checkers_transitions_pack writes transition b to row (ring_start + b) mod ring_size */
+  int64_t ring_size;        /* rows of every column, >= 1 */
+} cm3_checkers_compact_cols;
+/* ALL transitions of ticks [0, n / E) of a continuous-collection trajectory, time-major (b = t E + e), into rows (ring_start + b) mod
+ * ring_size of the compact columns, in ONE launch that converts nothing.  Same semantics as cm3_checkers_transitions_gather with
+ * tt == ee == NULL: next_* from the term_* slot where done[t][e], actions_prev = prev0 at t = 0 and zeros behind a done under terminal
+ * capture, goals from goals_slots[t] where recorded; padded and unpadded records, any record stride.  Validation precedes the launch
+ * (CM3_ERR_INVALID): null desc / traj / out, n < 0, ring_start / ring_size out of range, n > ring_size, a missing or misaligned column
+ * (by name), n_agents outside 1..8, record strides; n == 0 returns CM3_OK without touching a pointer. */
+int cm3_checkers_transitions_pack(const cm3_checkers_desc *desc, const cm3_checkers_traj *traj, const int32_t *prev0, int64_t n,
+                                  const cm3_checkers_compact_cols *out, void *stream);
+/* Row b < n of the 16 reference columns of `out` (float64 / int32 / bool / int64 one-hot, as cm3_checkers_transitions_gather writes
+ * them) from compact ring row index[b] (int64 on the device, NOT bounds-checked: see the index contract above); index == NULL: rows
+ * 0 .. n - 1.  ONE launch of the export kernel with a ring row as its source; every conversion is exact.  desc supplies n_agents
+ * and the geometry.  The same validation as above, for both column sets. */
+int cm3_checkers_ring_expand(const cm3_checkers_desc *desc, const cm3_checkers_compact_cols *ring, const int64_t *index, int64_t n,
+                             const cm3_checkers_transition_cols *out, void *stream);
 
 /* Up to 16 columns of row-major records (row_bytes[k] bytes per row of column k), moved together. */
 typedef struct cm3_row_cols {

@@ -7,14 +7,20 @@
   (2) export + replay add:                 DeviceReplayBuffer.add_rollout (the same launch writing ring rows) against the route
                                            off_policy_batches took before: composition, .contiguous(), DeviceReplayBuffer.add;
   (3) 24 x 128 sampled transitions:        the indexed export of one on-policy phase, kernel against composition (toy-sized and
-                                           launch-bound: reported, not judged).
+                                           launch-bound: reported, not judged);
+  (4) wide against compact replay add:     DeviceReplayBuffer.add_rollout (float64 ring, the launch of (2)) against
+                                           CompactCheckersReplayBuffer.add_rollout (ONE launch of cm3_checkers_transitions_pack: the
+                                           ring keeps the trajectory's dtypes, nothing is converted), same chunk, wrapping rings;
+  (5) sample_batch(24 x 128) from each:    cm3_rows_gather out of the wide ring against cm3_checkers_ring_expand out of the compact
+                                           one (launch-bound: reported, not judged).
 
 One process, one GPU; every variant is warmed up, each repetition is timed with device events around a call that ends in a
 synchronise, and the two variants of a case alternate inside one loop.  The bytes a variant has to move are computed from shapes;
 their floor is those bytes over the copy rate that cm3_hbm_copy_bench reaches in this same run (as tools/host_side_timing.py
-defines it).  Before anything is timed the two routes are compared at this size: every column bit-identical.
+defines it).  Before anything is timed the two routes are compared at this size: every column bit-identical (the compact ring: every column
+widened equals the wide ring's, every sampled batch equals the wide ring's batch).
 
-    python tools/checkers_export_timing.py [--reps 12] > profiles/r10_checkers_export.txt
+    python tools/checkers_export_timing.py [--reps 12] > profiles/r11_checkers_compact_ring.txt
 """
 import argparse
 import os
@@ -89,7 +95,7 @@ def main():
     import torch
     import cm3_amd
     from cm3_amd.checkers import VecCheckersEnv
-    from cm3_amd.replay import DeviceReplayBuffer
+    from cm3_amd.replay import CompactCheckersReplayBuffer, DeviceReplayBuffer
     from cm3_amd.rollout import CheckersRollout, sample_distinct
     device = cm3_amd._lib.require_gpu("cuda:0")
     reps = max(10, args.reps)
@@ -117,7 +123,7 @@ def main():
     print("every column of the kernel route equals the composition bit for bit at this size: checked before timing")
     print()
 
-    def report(title, times, moved, judge):
+    def report(title, times, moved, judge, other="the composition"):
         print(title)
         for name, ms in times.items():
             floor = moved[name] / (copy_gbps * 1e9) * 1e3
@@ -127,7 +133,7 @@ def main():
         ratio = statistics.median(tb) / statistics.median(ta)
         if judge:
             verdict = ("faster by more than the spread of either (its slowest repetition beats the other's fastest)" if max(ta) < min(tb)
-                       else "NOT separated from the composition by more than the spread")
+                       else "NOT separated from %s by more than the spread" % other)
             print("  -> %s is %.1f x the speed of %s at the median: %s" % (a, ratio, b, verdict))
         else:
             print("  -> ratio of the medians %.1f (toy-sized and launch-bound: reported, not judged)" % ratio)
@@ -168,6 +174,47 @@ def main():
                        device, reps)
     report("(3) indexed export of 24 x 128 sampled transitions", times,
            {"kernel: as_reference_batch(tt, ee)": moved, "composition: as_reference_batch_torch(tt, ee)": moved}, False)
+    # (4) the wide ring's add against the compact ring's, same chunk, both rings wrap; bit equality of the two rings first
+    buf_w, buf_n = DeviceReplayBuffer(size=ring, device=device), CompactCheckersReplayBuffer(size=ring, device=device)
+    widen = {torch.int8: lambda v: v.to(torch.float64), torch.int32: lambda v: v.to(torch.float64),
+             torch.uint8: lambda v: torch.nn.functional.one_hot(v.long(), 2)}
+    for _ in range(4):                                   # (the fourth add wraps)
+        buf_w.add_rollout(ro)
+        buf_n.add_rollout(ro)
+    assert (buf_w.len, buf_w.idx) == (buf_n.len, buf_n.idx) and buf_w.idx < B
+    for name in ro.ORDER:
+        v = buf_n.cols[name]
+        wide_v = widen[v.dtype](v) if name.endswith(("grid", "obs_self_t", "vec", "goals")) else v
+        assert wide_v.dtype == buf_w.cols[name].dtype and torch.equal(wide_v, buf_w.cols[name]), name
+        del wide_v
+    torch.cuda.empty_cache()
+    compact_row = _nbytes(buf_n.cols) // ring
+    print("the compact ring, widened, equals the wide ring bit for bit in every column after 4 adds (one wrapped): checked before timing")
+    print("ring row: wide %d B, compact %d B; a ring of %d rows: wide %.2f GB, compact %.2f GB"
+          % (write // B, compact_row, ring, _nbytes(buf_w.cols) / 1e9, _nbytes(buf_n.cols) / 1e9))
+    print()
+    times = _alternate({"compact: add_rollout (pack)": lambda: buf_n.add_rollout(ro),
+                        "wide: add_rollout (export)": lambda: buf_w.add_rollout(ro)}, device, reps)
+    assert (buf_w.len, buf_w.idx) == (buf_n.len, buf_n.idx)
+    report("(4) replay-ring add of the chunk: compact ring against the wide ring (rings of %d rows, wrap)" % ring, times,
+           {"compact: add_rollout (pack)": read + B * compact_row, "wide: add_rollout (export)": read + write}, True, "the wide add")
+
+    # (5) sample_batch(24 x 128) from each ring, generators seeded alike
+    n = 24 * 128
+    ga, gb = torch.Generator(device=device).manual_seed(1), torch.Generator(device=device).manual_seed(1)
+    got, want = buf_n.sample_batch(n, generator=ga), buf_w.sample_batch(n, generator=gb)
+    for name in ro.ORDER:
+        assert got[name].dtype == want[name].dtype and torch.equal(got[name], want[name]), name
+    del got, want
+    print("sample_batch(%d) from the compact ring equals the wide ring's batch bit for bit (generators seeded alike): checked before timing" % n)
+    times = _alternate({"compact: sample_batch (ring_expand)": lambda: buf_n.sample_batch(n, generator=ga),
+                        "wide: sample_batch (rows_gather)": lambda: buf_w.sample_batch(n, generator=gb)}, device, reps)
+    report("(5) sample_batch(24 x 128) out of each ring (draws included)", times,
+           {"compact: sample_batch (ring_expand)": n * (compact_row + write // B + 8),
+            "wide: sample_batch (rows_gather)": n * (2 * (write // B) + 8)}, False)
+    del buf_w, buf_n
+    torch.cuda.empty_cache()
+    print("the compact add above its floor (compare its multiple with the wide add's): NOT attributed by measurement.  By count: the partly covered pieces at the range ends and the wrap are at most 4 per column (64 of ~24 M pieces), nothing; 58 % of the bytes (grid / obs_self_t and their next_*) arrive as 2-byte loads, eight per 16-byte store, and 47 % of the bytes (next_*) issue their loads only after a done byte: the load side, not the byte-granular tails or the wrap, is where a profile should look first")
     print("not measured: non-temporal stores for the column writes; kernel time in isolation (rocprofv3); other agent counts and sizes")
     ro.close()
 
