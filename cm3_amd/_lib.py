@@ -59,7 +59,7 @@ class ParticleTraj(ctypes.Structure):
                 ("term_state", c_void_p), ("term_state_stride", c_size_t),
                 ("term_obs_others", c_void_p), ("term_obs_others_stride", c_size_t),
                 ("collisions", c_void_p), ("collisions_stride", c_size_t),
-                ("state_live", c_void_p), ("goals_live", c_void_p)]
+                ("state_live", c_void_p), ("goals_live", c_void_p), ("live_record", c_void_p)]
 
 
 class TransitionCols(ctypes.Structure):
@@ -179,6 +179,7 @@ SYMBOLS = {
     "cm3_particle_observe_f64": (ctypes.c_int, [P(ParticleDesc), P(ParticleBufs), c_void_p]),
     "cm3_particle_rollout_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), c_int32, c_void_p]),
     "cm3_particle_rollout_f64": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), c_int32, c_void_p]),
+    "cm3_particle_live_record_applies": (ctypes.c_int, [P(ParticleDesc), c_int32]),
     "cm3_checkers_step": (ctypes.c_int, [P(CheckersDesc), P(CheckersBufs), c_void_p]),
     "cm3_checkers_rollout": (ctypes.c_int, [P(CheckersDesc), P(CheckersTraj), c_int32, c_void_p]),
     "cm3_checkers_reset": (ctypes.c_int, [P(CheckersDesc), P(CheckersBufs), c_void_p, c_void_p]),

@@ -133,10 +133,11 @@ struct KernelVariant {
   int real_bytes;      // 4 / 8 (0: not a template parameter)
   int n, waves, fused, sp, live, tu, early, g;
   int prec;            // actor kernels: 0 float32, 1 bf16, 2 split float16 (-1: not a template parameter)
+  int rec;             // pair step kernel: 1 = the packed-live-record variant
 };
 KernelVariant &last_variant();  // thread-local (util.hip)
 static inline void note_variant(const char *kernel, int real_bytes, int n, int waves, int fused, int sp, int live, int tu,
-                                int early = 0, int g = 0, int prec = -1) {
+                                int early = 0, int g = 0, int prec = -1, int rec = 0) {
   KernelVariant &v = last_variant();
   v.kernel = kernel;
   v.real_bytes = real_bytes;
@@ -149,6 +150,7 @@ static inline void note_variant(const char *kernel, int real_bytes, int n, int w
   v.early = early;
   v.g = g;
   v.prec = prec;
+  v.rec = rec;
 }
 
 #define CM3_HIP_CHECK(expr)                                                                  \

@@ -71,6 +71,7 @@ struct ParticleParams {
   int n_ticks;
   int _pad2;
   size_t st_state, st_goals, st_obs, st_actions, st_reward_n, st_reward, st_done, st_term_state, st_term_obs, st_coll;
+  void *live_record;   // optional (cm3_particle_traj.live_record): the packed live records the REC variant of the pair kernel steps on
   CM3_SPAN_FIELD  // (span build only, common.h: where this launch's per-wave time stamps go)
 };
 
@@ -727,7 +728,15 @@ template <int N> struct PairGeom {
 // (profiles/r02_draw_wave_on_off.txt) it had become a loss in every configuration that used it -- in place 0-6 %, trajectory mode
 // 5-10 % -- and was removed: a fifth wave, two workgroup barriers and an extra store + reload of the action row cost more than the
 // Philox chain they hid once the square roots had left the physics chain.)
-template <typename R, int N, int WAVES, bool FUSED, int SP = kSpPlain, bool LIVE = false, int TU = CM3_PARTICLE_TU>
+// REC (a compile-time variant beside LIVE: the others carry none of it; float32, one launch per tick, in-kernel actions, N <= 4): the
+// live state of an env is ONE 128-byte record (cm3_amd.h, cm3_particle_traj.live_record; kRec* below) and `h_state_in` is the record
+// array.  A wave's initial loads then open EPW consecutive lines of one array instead of lines of five, stage 1 of the action stream is
+// a word of that line instead of ten Philox rounds, and the live stores of the tick go back into the same line.  Everything written to
+// the trajectory slots is unchanged in value, address and store policy.
+// NOTE: in the REC instantiation the first argument is READ AND WRITTEN -- it keeps the `const void *h_state_in` slot of the shared
+// signature (so that it stays a preloaded SGPR pair like state_in), and the live stores go through at32, which drops the const.
+constexpr uint32_t kRecBytes = 128, kRecGoals = 64, kRecMeta = 96, kRecWords = 112;
+template <typename R, int N, int WAVES, bool FUSED, int SP = kSpPlain, bool LIVE = false, bool REC = false, int TU = CM3_PARTICLE_TU>
 __global__ void __launch_bounds__(WAVES * 64)
     k_particle_step_pairs(const void *h_state_in, const void *h_goals_in, const int32_t *h_meta_in, const int32_t *h_episode,
                           const int h_E, const uint32_t h_flags, const int h_E0, const int h_EN, const int h_max_steps,
@@ -741,6 +750,7 @@ __global__ void __launch_bounds__(WAVES * 64)
   // one wave per SIMD the launch time is the length of the executed path: the 64-bit multiplies, adds and compares of
   // size_t indexing were ~8 % of it.
   static_assert(N >= 2, "the pair mapping needs at least two agents");
+  static_assert(!REC || (LIVE && !FUSED && sizeof(R) == 4 && N <= 4), "one 128-byte record holds four float32 agents; per-tick live launches only");
   using V4 = typename Vec<R>::v4;
   using V2 = typename Vec<R>::v2;
   using PG = PairGeom<N>;
@@ -765,25 +775,47 @@ __global__ void __launch_bounds__(WAVES * 64)
 
   CM3_STAMP(0, false);
   // ---- loads (once per launch; the state then lives in registers across the ticks of this launch) -------------
-  const uint32_t row_i = (uint32_t)i * E, row_j = (uint32_t)j * E;
-  V4 si = *at32<const V4>(h_state_in, (row_i + ec) * (uint32_t)sizeof(V4));
-  V4 sj = *at32<const V4>(h_state_in, (row_j + ec) * (uint32_t)sizeof(V4));
-  V2 gl = *at32<const V2>(h_goals_in, (row_i + ec) * (uint32_t)sizeof(V2));
-  const int2 meta = *at32<const int2>(h_meta_in, ec * 8u);
-  int steps = meta.x, collisions = meta.y;
+  [[maybe_unused]] const uint32_t row_i = (uint32_t)i * E, row_j = (uint32_t)j * E;
+  [[maybe_unused]] const uint32_t rec_e = ec * kRecBytes;   // (REC) this env's record
+  V4 si, sj;
+  V2 gl;
+  int steps, collisions;
+  uint32_t episode = 0, aword = 0;
   const bool auto_reset = (h_flags & CM3_FLAG_AUTO_RESET) != 0;
-  const bool gen = (h_flags & CM3_FLAG_GEN_ACTIONS) != 0;
-  uint32_t episode = 0;
-  if (gen || (h_flags & CM3_FLAG_AUTO_RESET)) episode = (uint32_t)*at32<const int32_t>(h_episode, ec * 4u);
-  const uint32_t episode_in = episode;
-  // (after the vector loads are in flight: the scalar fetches complete in their shadow)
-  CM3_FETCH_EARLY(p.state_out, p.goals_out, p.goals_in, p.collisions_tick, p.reward_n, p.reward, p.done, p.obs_others, p.meta_out);
-  if constexpr (LIVE) CM3_FETCH_EARLY(p.state_copy, p.goals_copy);
+  const bool gen = REC || (h_flags & CM3_FLAG_GEN_ACTIONS) != 0;   // (the record variant is launched for in-kernel actions only)
+  if constexpr (REC) {
+    // everything from the env's own line: own state, the other agent's position, own goal, the counters, own stage-1 word
+    si = *at32<const V4>(h_state_in, rec_e + (uint32_t)i * 16u);
+    const V2 pj = *at32<const V2>(h_state_in, rec_e + (uint32_t)j * 16u + 8u);
+    gl = *at32<const V2>(h_state_in, rec_e + kRecGoals + (uint32_t)i * 8u);
+    const int4 tail = *at32<const int4>(h_state_in, rec_e + kRecMeta);
+    aword = *at32<const uint32_t>(h_state_in, rec_e + kRecWords + (uint32_t)i * 4u);
+    sj.x = sj.y = R(0);   // (the other agent's velocity is not read before the post-step exchange)
+    sj.z = pj.x;
+    sj.w = pj.y;
+    steps = tail.x;
+    collisions = tail.y;
+    episode = (uint32_t)tail.z;
+    CM3_FETCH_EARLY(p.collisions_tick, p.reward_n, p.reward, p.done, p.obs_others, p.state_copy, p.goals_copy);
+  } else {
+    si = *at32<const V4>(h_state_in, (row_i + ec) * (uint32_t)sizeof(V4));
+    sj = *at32<const V4>(h_state_in, (row_j + ec) * (uint32_t)sizeof(V4));
+    gl = *at32<const V2>(h_goals_in, (row_i + ec) * (uint32_t)sizeof(V2));
+    const int2 meta = *at32<const int2>(h_meta_in, ec * 8u);
+    steps = meta.x;
+    collisions = meta.y;
+    if (gen || (h_flags & CM3_FLAG_AUTO_RESET)) episode = (uint32_t)*at32<const int32_t>(h_episode, ec * 4u);
+    // (after the vector loads are in flight: the scalar fetches complete in their shadow)
+    CM3_FETCH_EARLY(p.state_out, p.goals_out, p.goals_in, p.collisions_tick, p.reward_n, p.reward, p.done, p.obs_others, p.meta_out);
+    if constexpr (LIVE) CM3_FETCH_EARLY(p.state_copy, p.goals_copy);
+  }
+  [[maybe_unused]] const uint32_t episode_in = episode;
   const uint64_t genv = (uint64_t)(p.env_id_base + (int64_t)ec);
   // stage 1 of the action stream (philox.h): this agent's word of its env's Philox block -- ten rounds that depend on nothing the
   // launch loads, computed while the loads are in flight (until round 3 the whole draw waited for `steps` / `episode`)
-  uint32_t aword = 0;
-  if (gen) aword = pick_word(action_block(p.seed, genv, (uint32_t)(i >> 2)), i & 3);
+  if constexpr (!REC) {
+    if (gen) aword = pick_word(action_block(p.seed, genv, (uint32_t)(i >> 2)), i & 3);
+  }
   const R kDt = R(0.1), kKeep = R(1 - 0.25);
 
   CM3_STAMP(1, true);
@@ -932,9 +964,14 @@ __global__ void __launch_bounds__(WAVES * 64)
       if (lead) {
         if (gen) *at32<int32_t>(actions_t, (e * N + i) * 4u) = act;
         *at32<R>(tick_ptr(p.reward_n, p.st_reward_n, t), (e * N + i) * (uint32_t)sizeof(R)) = rew;
-        *at32<V4>(tick_ptr(p.state_out, p.st_state, t), (row_i + e) * (uint32_t)sizeof(V4)) = si;
-        if (p.goals_out != p.goals_in || was_reset)
-          *at32<V2>(tick_ptr(p.goals_out, p.st_goals, t), (row_i + e) * (uint32_t)sizeof(V2)) = gl;
+        if constexpr (REC) {   // the live state goes back into the env's record (e == ec here)
+          *at32<V4>(h_state_in, rec_e + (uint32_t)i * 16u) = si;
+          if (was_reset) *at32<V2>(h_state_in, rec_e + kRecGoals + (uint32_t)i * 8u) = gl;
+        } else {
+          *at32<V4>(tick_ptr(p.state_out, p.st_state, t), (row_i + e) * (uint32_t)sizeof(V4)) = si;
+          if (p.goals_out != p.goals_in || was_reset)
+            *at32<V2>(tick_ptr(p.goals_out, p.st_goals, t), (row_i + e) * (uint32_t)sizeof(V2)) = gl;
+        }
         if constexpr (LIVE)   // live-state rollout (a compile-time variant: the others carry none of it): the slot gets a copy
           store_obs_vec<SP>(at32<V4>(p.state_copy, (row_i + e) * (uint32_t)sizeof(V4)), si);
         if constexpr (!FUSED) {   // goal slots are SPARSE wherever the goals live in place (live state, or goals_live alone)
@@ -948,7 +985,14 @@ __global__ void __launch_bounds__(WAVES * 64)
         *at32<R>(tick_ptr(p.reward, p.st_reward, t), e * (uint32_t)sizeof(R)) = reward;
         *at32<uint8_t>(tick_ptr(p.done, p.st_done, t), e) = done ? 1 : 0;
         if (p.collisions_tick) *at32<int32_t>(tick_ptr(p.collisions_tick, p.st_coll, t), e * 4u) = collisions_tick;
-        if constexpr (!FUSED) {  // the live counters, once per launch
+        if constexpr (REC) {     // the live counters: one 16-byte store into the record (the stage-1 words behind it stay)
+          int4 m;
+          m.x = steps;
+          m.y = collisions;
+          m.z = (int)episode;
+          m.w = 0;
+          *at32<int4>(h_state_in, rec_e + kRecMeta) = m;
+        } else if constexpr (!FUSED) {  // the live counters, once per launch
           int2 m;
           m.x = steps;
           m.y = collisions;
@@ -1622,6 +1666,59 @@ __global__ void __launch_bounds__(WAVES * 64) k_particle_observe(const ParticleP
   store_obs_others_staged<R, N>(s, &lds_all[wave][0], lane, e0, p.EN, reinterpret_cast<R *>(p.obs_others));
 }
 
+// ---- packed live records (cm3_particle_traj.live_record): pack before the first tick of a rollout call, unpack after its last ------
+// One lane per env, float32, N <= 4.  pack: env buffers -> record, plus the four stage-1 action words of the env (a constant of seed
+// and global env id: what every launch of the plain kernels recomputes); unpack: record -> state_live / goals_live / meta / episode.
+template <int N>
+__global__ void __launch_bounds__(256) k_particle_record_pack(const float4 *state, const float2 *goals, const int2 *meta, const int32_t *episode,
+                                                              uint4 *records, uint32_t E, uint32_t E0, uint32_t EN, int64_t env_id_base,
+                                                              uint64_t seed) {
+  static_assert(N >= 2 && N <= 4, "one record holds up to four agents");
+  const uint32_t e = E0 + blockIdx.x * 256u + threadIdx.x;
+  if (e >= EN) return;
+  float4 s[4];
+  float2 g[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    s[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    g[i] = make_float2(0.f, 0.f);
+    if (i < N) {
+      s[i] = state[(size_t)i * E + e];
+      g[i] = goals[(size_t)i * E + e];
+    }
+  }
+  const int2 m = meta[e];
+  const u32x4 w = action_block(seed, (uint64_t)(env_id_base + (int64_t)e), 0u);
+  uint4 *r = records + (size_t)e * (kRecBytes / 16);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = make_uint4(__float_as_uint(s[i].x), __float_as_uint(s[i].y), __float_as_uint(s[i].z), __float_as_uint(s[i].w));
+  r[4] = make_uint4(__float_as_uint(g[0].x), __float_as_uint(g[0].y), __float_as_uint(g[1].x), __float_as_uint(g[1].y));
+  r[5] = make_uint4(__float_as_uint(g[2].x), __float_as_uint(g[2].y), __float_as_uint(g[3].x), __float_as_uint(g[3].y));
+  r[6] = make_uint4((uint32_t)m.x, (uint32_t)m.y, (uint32_t)episode[e], 0u);
+  r[7] = make_uint4(w.x, w.y, w.z, w.w);
+}
+
+template <int N>
+__global__ void __launch_bounds__(256) k_particle_record_unpack(const uint4 *records, float4 *state, float2 *goals, int2 *meta, int32_t *episode,
+                                                                uint32_t E, uint32_t E0, uint32_t EN) {
+  const uint32_t e = E0 + blockIdx.x * 256u + threadIdx.x;
+  if (e >= EN) return;
+  const uint4 *r = records + (size_t)e * (kRecBytes / 16);
+  const uint4 g01 = r[4], g23 = r[5], m = r[6];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (i < N) {
+      const uint4 v = r[i];
+      state[(size_t)i * E + e] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+      const uint4 gg = i < 2 ? g01 : g23;
+      goals[(size_t)i * E + e] = (i & 1) ? make_float2(__uint_as_float(gg.z), __uint_as_float(gg.w))
+                                         : make_float2(__uint_as_float(gg.x), __uint_as_float(gg.y));
+    }
+  }
+  meta[e] = make_int2((int)m.x, (int)m.y);
+  episode[e] = (int32_t)m.z;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------
 enum ParticleOp { kStep = 0, kReset = 1, kObserve = 2 };
 
@@ -1738,20 +1835,30 @@ template <typename R, int N, int WAVES> static int launch_pairs(const ParticlePa
     const uint32_t xf = cm3_xcd_flags(raw_blocks);
     constexpr int kF32 = sizeof(R) == 4 ? kSpNt : kSpPlain;
     const bool nt = sizeof(R) == 4 && (p.flags & kFlagObsStoreNt);   // streaming-size trajectory (obs_store_nt)
+    const bool rec = p.live_record != nullptr;   // cm3_particle_traj.live_record: the record array takes the place of state_in
+    const void *first = rec ? p.live_record : p.state_in;
 #define CM3_LAUNCH_PAIRS(...)                                                                                               \
   hipLaunchKernelGGL((k_particle_step_pairs<R, N, WAVES, __VA_ARGS__>), dim3(blocks), dim3(WAVES * 64), 0, stream,          \
-                     p.state_in, p.goals_in, p.meta_in, (const int32_t *)p.episode, p.E, p.flags | xf, p.E0, p.EN, p.max_steps,   \
+                     first, p.goals_in, p.meta_in, (const int32_t *)p.episode, p.E, p.flags | xf, p.E0, p.EN, p.max_steps,   \
                      (const int32_t *)p.actions, p)
     // the kernel indexes with 32-bit byte offsets: its largest per-tick array (obs_others) must stay below 4 GiB
     if ((size_t)p.E * PairGeom<N>::SLOTS * 4 * sizeof(R) >= ((size_t)1 << 32))
       return fail(CM3_ERR_INVALID, "the lane-per-pair kernel addresses at most 4 GiB per array: %d envs x %d agents is too large "
                   "(use the default kernel choice)", p.E, N);
     const bool live = p.state_copy != nullptr;   // cm3_particle_traj.state_live (per-tick launches only)
+    if (rec && !(sizeof(R) == 4 && N <= 4 && live && p.n_ticks == 1 && (p.flags & CM3_FLAG_GEN_ACTIONS) &&
+                 (size_t)p.E * kRecBytes < ((size_t)1 << 32)))
+      return fail(CM3_ERR_INVALID, "live records are for per-tick float32 live-state launches with in-kernel actions, n_agents 2..4");
     note_variant("k_particle_step_pairs", (int)sizeof(R), N, WAVES, p.n_ticks > 1, nt ? kF32 : kSpPlain, p.n_ticks == 1 && live,
-                 CM3_PARTICLE_TU);
+                 CM3_PARTICLE_TU, 0, 0, -1, rec);
     if (p.n_ticks > 1) {
       if (nt) CM3_LAUNCH_PAIRS(true, kF32);
       else CM3_LAUNCH_PAIRS(true, kSpPlain);
+    } else if (rec) {
+      if constexpr (sizeof(R) == 4 && N <= 4) {
+        if (nt) CM3_LAUNCH_PAIRS(false, kF32, true, true);
+        else CM3_LAUNCH_PAIRS(false, kSpPlain, true, true);
+      }
     } else if (live) {
       if (nt) CM3_LAUNCH_PAIRS(false, kF32, true);
       else CM3_LAUNCH_PAIRS(false, kSpPlain, true);
@@ -1769,6 +1876,18 @@ template <typename R, int N, int WAVES> static int launch_pairs(const ParticlePa
 
 // Largest batch for which the lane-per-pair mapping is preferred when no per-N entry says otherwise (see launch_n).
 constexpr size_t kPairsMaxEnvs = (size_t)1 << 14;
+// ... and per agent count (the measurements behind the table: launch_n)
+constexpr size_t pair_max_envs(int n) { return n > 8 ? 0 : (n == 2 ? 32768 : (n == 3 ? 24576 : (n == 4 ? 12288 : kPairsMaxEnvs))); }
+// Does a rollout call of this descriptor step on packed live records when it is handed some (cm3_particle_traj.live_record)?  Per-tick
+// float32 launches of the lane-per-pair kernel with in-kernel actions, two to four agents.  (N <= 4: launch_n's lane-per-agent range
+// starts above pair_max_envs, so without a forced mapping the pair kernel runs exactly up to it.)
+static bool live_record_applies(const cm3_particle_desc *d, int real_bytes) {
+  if (real_bytes != 4 || d->n_agents < 2 || d->n_agents > 4 || d->n_envs <= 0) return false;
+  if (!(d->flags & CM3_FLAG_GEN_ACTIONS) || (d->flags & CM3_FLAG_FUSED_TICKS)) return false;
+  if (d->flags & (CM3_FLAG_KERNEL_LANE_PER_ENV | CM3_FLAG_KERNEL_LANE_PER_AGENT)) return false;
+  if ((size_t)d->n_envs * kRecBytes >= ((size_t)1 << 32)) return false;
+  return (d->flags & CM3_FLAG_KERNEL_LANE_PER_PAIR) || (size_t)d->n_envs <= pair_max_envs(d->n_agents);
+}
 
 template <typename R, int N, int WAVES> static int launch_agents(const ParticleParams &p, hipStream_t stream) {
   if constexpr (N >= 2) {
@@ -1873,7 +1992,7 @@ template <typename R, int N> static int launch_n(const ParticleParams &p, Partic
     // positions): `auto` within ~1 % of the best mapping at 88 of 91 (N, E) points.  The two candidates for a move -- N = 2 pair up
     // to 65536, N = 4 agent up to 65536 -- were tried and taken back: on the antipodal config of the bench N = 4 at 65536 envs ran
     // 6.11 us with the agent mapping against 5.70 with lane-per-env; the crossovers depend on how crowded a config is.
-    constexpr size_t kPairMax = N > 8 ? 0 : (N == 2 ? 32768 : (N == 3 ? 24576 : (N == 4 ? 12288 : kPairsMaxEnvs)));
+    constexpr size_t kPairMax = pair_max_envs(N);
     // round 3: N = 8 with two lanes per agent (k_particle_step_agents2; profiles/r03_two_lanes_per_agent.txt) moved its crossover
     // to 2048 envs; the XCD-aware block order (common.h) then sped the pair mapping up most at exactly these sizes
     // (profiles/r03_xcd_block_order.txt; pair / agent, in place): N = 8: 2048 3.42 / 3.74, 4096 4.47 / 3.84 -> agent from 4096;
@@ -1887,6 +2006,8 @@ template <typename R, int N> static int launch_n(const ParticleParams &p, Partic
     //          put the buffers), 2^21 392-412 / 437-466                                -> agent up to 768 K envs (was unbounded)
     //   N = 8: 2^19 110.5 / 99.9, 2^20 222-233 / 278-281 (6.1 vs 4.9 TB/s), 2^21 489-556 / 477-505 -> agent up to 768 K envs
     constexpr size_t kAgentHi = N == 4 || N == 5 ? 40960 : (N == 6 ? 1572864 : (N >= 7 ? 786432 : 0));
+    // (live_record_applies() relies on it: for the agent counts a record holds, the lane-per-agent range lies wholly above the pair range)
+    static_assert(N > 4 || kAgentLo > pair_max_envs(N), "N <= 4: the lane-per-agent range must start above the lane-per-pair range");
     bool pairs = N >= 2 && (size_t)p.E <= kPairMax;
     bool agents = N >= 4 && (size_t)p.E >= kAgentLo && (size_t)p.E <= kAgentHi;
     // both shared-env mappings index with 32-bit byte offsets (obs_others below 4 GiB per tick); beyond that only a forced choice
@@ -1896,6 +2017,7 @@ template <typename R, int N> static int launch_n(const ParticleParams &p, Partic
     if (p.flags & CM3_FLAG_KERNEL_LANE_PER_PAIR) { pairs = true; agents = false; }
     if (N > 8 && pairs) return fail(CM3_ERR_INVALID, "the lane-per-pair kernel needs n_agents in 2..8");
     if (p.flags & CM3_FLAG_KERNEL_LANE_PER_AGENT) agents = true;
+    if (p.live_record && (agents || !pairs)) return fail(CM3_ERR_INVALID, "live records are stepped by the lane-per-pair kernel only");
     if (agents) {
       const size_t waves = ((size_t)p.E + AgentGeom<(N >= 2 ? N : 2)>::EPW - 1) / AgentGeom<(N >= 2 ? N : 2)>::EPW;
 #ifndef CM3_PARTICLE_ILP_TU
@@ -1969,6 +2091,9 @@ static int particle_rollout(const cm3_particle_desc *d, const cm3_particle_traj 
   auto at = [](void *base, size_t stride, int k) -> void * {
     return base ? (void *)((char *)base + stride * (size_t)k) : nullptr;
   };
+  // packed live records are for descriptors they apply to, whatever path the call takes (the fused path has no use for them)
+  CM3_REQUIRE(!t->live_record || live_record_applies(d, (int)sizeof(R)),
+              "rollout: live_record does not apply to this descriptor (see cm3_particle_live_record_applies)");
   if (d->flags & CM3_FLAG_FUSED_TICKS) {
     // ONE launch runs all n_ticks ticks with the state in registers (no per-tick launch, no state re-load).
     // Only possible when no host/policy step is needed between ticks: actions are drawn in-kernel, or all
@@ -2008,6 +2133,25 @@ static int particle_rollout(const cm3_particle_desc *d, const cm3_particle_traj 
     p.flags |= obs_store_nt(t->obs_others_stride, n_ticks);
     return launch<R>(p, d->n_agents, kStep, (hipStream_t)stream);
   }
+  // packed live records: the ticks of this call step on one 128-byte record per env; the env's own buffers are read once before the
+  // first tick and are current again after the last
+  const bool rec = t->live_record != nullptr;
+  const unsigned rec_blocks = rec ? (unsigned)(((d->env_count > 0 ? d->env_count : d->n_envs) + 255) / 256) : 0u;
+  const uint32_t rec_e0 = (uint32_t)d->env_offset, rec_en = (uint32_t)(d->env_count > 0 ? d->env_offset + d->env_count : d->n_envs);
+  if (rec) {
+    CM3_REQUIRE(t->state_live && t->episode, "rollout: live_record needs state_live / goals_live and the episode counters");
+    CM3_REQUIRE(((uintptr_t)t->live_record & (kRecBytes - 1)) == 0, "rollout: live_record must be 128-byte aligned");
+    CM3_REQUIRE(d->env_offset >= 0 && d->env_count >= 0 && (int64_t)d->env_offset + d->env_count <= d->n_envs, "env_offset / env_count");
+#define CM3_RECORD_PACK(NA)                                                                                                        \
+  hipLaunchKernelGGL(k_particle_record_pack<NA>, dim3(rec_blocks), dim3(256), 0, (hipStream_t)stream, (const float4 *)t->state_live, \
+                     (const float2 *)t->goals_live, (const int2 *)t->meta, (const int32_t *)t->episode, (uint4 *)t->live_record,     \
+                     (uint32_t)d->n_envs, rec_e0, rec_en, d->env_id_base, d->seed)
+    if (d->n_agents == 2) CM3_RECORD_PACK(2);
+    else if (d->n_agents == 3) CM3_RECORD_PACK(3);
+    else CM3_RECORD_PACK(4);
+#undef CM3_RECORD_PACK
+    CM3_HIP_CHECK(hipGetLastError());
+  }
   for (int k = 0; k < n_ticks; ++k) {
     cm3_particle_bufs b;
     memset(&b, 0, sizeof(b));
@@ -2035,11 +2179,23 @@ static int particle_rollout(const cm3_particle_desc *d, const cm3_particle_traj 
     if (live) {
       p.state_copy = at(t->state, t->state_stride, k + 1);
       p.goals_copy = at(t->goals, t->goals_stride, k + 1);
+      p.live_record = t->live_record;
     } else if (sparse_goals) {
       p.goals_copy = at(t->goals, t->goals_stride, k + 1);
     }
     rc = launch<R>(p, d->n_agents, kStep, (hipStream_t)stream);
     if (rc != CM3_OK) return rc;
+  }
+  if (rec) {
+#define CM3_RECORD_UNPACK(NA)                                                                                                      \
+  hipLaunchKernelGGL(k_particle_record_unpack<NA>, dim3(rec_blocks), dim3(256), 0, (hipStream_t)stream, (const uint4 *)t->live_record, \
+                     (float4 *)t->state_live, (float2 *)t->goals_live, (int2 *)t->meta, (int32_t *)t->episode, (uint32_t)d->n_envs,  \
+                     rec_e0, rec_en)
+    if (d->n_agents == 2) CM3_RECORD_UNPACK(2);
+    else if (d->n_agents == 3) CM3_RECORD_UNPACK(3);
+    else CM3_RECORD_UNPACK(4);
+#undef CM3_RECORD_UNPACK
+    CM3_HIP_CHECK(hipGetLastError());
   }
   return CM3_OK;
 }
@@ -2095,6 +2251,9 @@ int particle_ilp_launch_agents_f32(const ParticleParams &p, int n_agents, int w,
 #ifndef CM3_NO_ENTRY_POINTS
 extern "C" {
 #ifdef CM3_PARTICLE_F32
+int cm3_particle_live_record_applies(const cm3_particle_desc *d, int32_t real_bytes) {
+  return d && cm3::live_record_applies(d, (int)real_bytes) ? 1 : 0;
+}
 int cm3_particle_step_f32(const cm3_particle_desc *d, const cm3_particle_bufs *b, void *s) {
   return cm3::particle_call<float>(d, b, cm3::kStep, nullptr, s);
 }

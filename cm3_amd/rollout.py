@@ -392,6 +392,10 @@ class ParticleRollout(_Transitions):
         self._graphs = (self._norm_graph, self._graph, self._actor_graph)
         self._norm = self._norm_key = None       # collect_normalized's ReturnsNormalizer and the arguments it was built for
         self._live, self._live_cur = False, env._cur
+        # packed live records (cm3_particle_traj.live_record): one 128-byte line per env that the per-tick random-action live-state
+        # launches of the pair kernel step on (float32, 2..4 agents); allocated once, its address is part of the graphs' key
+        self._record = (torch.zeros(E, 32, dtype=torch.int32, device=dev)
+                        if env.dtype == torch.float32 and 2 <= N <= 4 and self._goals_buf is not None else None)
         # episode-synchronous mode: which envs' episodes have ended since their last reset (carried across collects)
         self._finished = torch.zeros(E, dtype=torch.bool, device=dev)
         self._finished0 = None
@@ -411,7 +415,17 @@ class ParticleRollout(_Transitions):
             self._finished &= ~m
 
     # ---- plumbing ------------------------------------------------------------------------------------
-    def _traj(self, t0=0, live=False, sparse_goals=False):
+    def _record_for(self, flags, live):
+        """The record tensor when the launches of `flags` step on packed live records, else None: live state, and a descriptor the
+        library takes them for (float32, in-kernel actions, a launch per tick, 2..4 agents, the pair kernel steps this batch)."""
+        if not live or self._record is None:
+            return None
+        env = self.env
+        env._desc.flags = flags
+        ok = self._lib.cm3_particle_live_record_applies(ctypes.byref(env._desc), self.state.element_size())
+        return self._record if ok else None
+
+    def _traj(self, t0=0, live=False, sparse_goals=False, record=None):
         """live: per-tick launches step IN PLACE on the env's own state / goals buffers and write every tick's state / goals
         to its slot as a copy (cm3_particle_traj.state_live): a tick then loads lines its predecessor read and overwrote
         instead of a fresh slot that was only ever written -- 0.19 us of 2.83 per tick at C2 (tools/trajectory_gap.py)."""
@@ -421,6 +435,8 @@ class ParticleRollout(_Transitions):
         if live:
             t.state_live = env._state[env._cur].data_ptr()
             t.goals_live = env._goals.data_ptr()
+            if record is not None:
+                t.live_record = record.data_ptr()
         t.state = self.state[t0].data_ptr()
         t.state_stride = N * E * 4 * es
         if self._goals_buf is not None:
@@ -453,10 +469,10 @@ class ParticleRollout(_Transitions):
             t.collisions_stride = E * 4
         return t
 
-    def _enqueue(self, t0, n, flags, stream=None, live=False, sparse_goals=False):
+    def _enqueue(self, t0, n, flags, stream=None, live=False, sparse_goals=False, record=None):
         env = self.env
         env._desc.flags = flags
-        traj = self._traj(t0, live, sparse_goals)
+        traj = self._traj(t0, live, sparse_goals, record)
         stream = env._stream() if stream is None else stream
         fn = getattr(self._lib, "cm3_particle_rollout_" + env._suffix)
         _lib.check(fn(ctypes.byref(env._desc), ctypes.byref(traj), int(n), stream))
@@ -616,9 +632,11 @@ class ParticleRollout(_Transitions):
         mode = self._mode(policy)
         live, sparse = mode.live, mode.sparse
         self._live = live
+        # packed live records: the per-tick random-action launches only (every other mode reads the env's buffers between ticks)
+        record = self._record_for(base | FLAG_GEN_ACTIONS, live) if mode.kind == "random" else None
         # ONE key for every captured graph of this object: the mode, plus the env's buffer parity where the launches hold the
-        # addresses of the env's current buffers (live state; env.step() flips them)
-        key = (mode, env._cur if live else None)
+        # addresses of the env's current buffers (live state; env.step() flips them) and the record's address where they hold that
+        key = (mode, env._cur if live else None, record.data_ptr() if record is not None else None)
         if self._graph_mode is not None and self._graph_mode != key:
             self._drop_graphs()
         self._graph_mode = key
@@ -634,9 +652,9 @@ class ParticleRollout(_Transitions):
             flags = base | FLAG_GEN_ACTIONS
             if self.use_graph:
                 self.n_captures += int(self._graph.graph is None)
-                self._graph.launch(lambda s: self._enqueue(0, self.T, flags, s, live=live, sparse_goals=sparse), stream)
+                self._graph.launch(lambda s: self._enqueue(0, self.T, flags, s, live=live, sparse_goals=sparse, record=record), stream)
             else:
-                self._enqueue(0, self.T, flags, live=live, sparse_goals=sparse)
+                self._enqueue(0, self.T, flags, live=live, sparse_goals=sparse, record=record)
         elif mode.kind == "policy_episode":
             # the whole policy-driven episode in ONE launch (csrc/policy.hip): weights, observation tile and env state stay in
             # LDS / registers for all T ticks; bit-identical to alternating actor / step launches
@@ -697,16 +715,18 @@ class ParticleRollout(_Transitions):
             self._norm_key = key
         self._finished0 = None
         live = self._live = self._wants_live_state()
-        if self._graph_mode is not None and self._graph_mode != (live, live):
+        flags = FLAG_AUTO_RESET | env.kernel_flags | FLAG_GEN_ACTIONS
+        record = self._record_for(flags, live)      # (the live branch steps on packed live records where they apply, as collect does)
+        key_mode = (live, live, record.data_ptr() if record is not None else None)
+        if self._graph_mode is not None and self._graph_mode != key_mode:
             self._drop_graphs()
-        self._graph_mode = (live, live)
+        self._graph_mode = key_mode
         self._goals_sparse, self._goal_src = live, None      # (the live-state launches write a goals slot only where an env restarts)
         # The captured graph bakes in the addresses of env._state[env._cur] / env._obs_others[env._cur] (tick 0 reads them, the
         # slot bookkeeping writes them) -- live or not -- and VecParticleEnv.step() flips env._cur: re-capture after a flip.
         if self._live_cur != env._cur:
             self._drop_graphs()
             self._live_cur = env._cur
-        flags = FLAG_AUTO_RESET | env.kernel_flags | FLAG_GEN_ACTIONS
 
         def enqueue(s):
             pairs, back = self._slot0_pairs(), self._store_back_pairs(live)      # (what _load_slot0 / _store_back copy)
@@ -722,7 +742,7 @@ class ParticleRollout(_Transitions):
                                              (self._goals_buf[0], env._goals, self._goals_buf[self.T])])
                 return
             _copy_pairs(pairs, s)
-            self._enqueue(0, self.T, flags, s, live=live)
+            self._enqueue(0, self.T, flags, s, live=live, record=record)
             _copy_pairs(back, s)
             if world == 1:
                 self._norm.enqueue_fused(s)        # (= enqueue_moments + enqueue_normalize on the own moments, bit for bit)

@@ -49,7 +49,11 @@ extern "C" {
 #define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
                                   Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network);
                                   cm3_checkers_transitions_gather (the Checkers transition export in one launch);
-                                  cm3_checkers_transitions_pack / cm3_checkers_ring_expand (the compact Checkers replay ring).
+                                  cm3_checkers_transitions_pack / cm3_checkers_ring_expand (the compact Checkers replay ring);
+                                  cm3_particle_traj.live_record (appended; NULL = as before) and cm3_particle_live_record_applies.
+                                  NOTE: sizeof(cm3_particle_traj) GREW by 8 bytes (192 -> 200) without a version step: a caller compiled
+                                  against the shorter struct must be recompiled, or the library reads 8 bytes past its struct as
+                                  live_record.  The in-tree binding mirrors the new size (tests/test_abi.py compares every offset).
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -202,12 +206,30 @@ typedef struct cm3_particle_traj {
      the launch runs at the chip's copy rate (profiles/r04_trajectory_stream.txt).  Here the goals live in goals_live (read and, on a
      restart, updated in place) and slot k + 1 of `goals` is written ONLY for the envs re-initialised at tick k: the goals in effect
      at slot t are those of the last written slot <= t (slot 0 is the caller's).  Per-tick launches only. */
+  void *live_record;
+  /* optional, with state_live / goals_live: PACKED LIVE RECORDS, n_envs x 128 bytes, 128-byte aligned, scratch owned by the caller
+     (contents are undefined between calls).  The live state of an env is otherwise spread over five arrays (state, goals, meta,
+     episode and the action stream's per-env block, which every launch recomputes): a wave of the lane-per-pair kernel opens a cold
+     line in each of them at the start of every tick.  With live_record a rollout call packs the live buffers of its envs into one
+     record per env before its first tick, every tick loads from and stores its live state back into that ONE line, and the call
+     unpacks the records into state_live / goals_live / meta / episode after its last tick: the caller's buffers are current after the
+     call exactly as without it, and every trajectory slot gets the same values at the same addresses.  Layout of a record:
+         bytes   0 ..  63   state (vx, vy, px, py) of agents 0..3, 16 bytes each (agents >= n_agents: zero)
+                64 ..  95   goals (x, y) of agents 0..3, 8 bytes each
+                96 ..  99   steps          100 .. 103   collisions          104 .. 107   episode          108 .. 111   zero
+               112 .. 127   the four stage-1 words of the env's action stream (Philox block (seed, global env id, call 0); a constant
+                            of the env: a same-launch reset leaves it alone)
+     Only for descriptors for which cm3_particle_live_record_applies() returns 1 (CM3_ERR_INVALID otherwise). */
 } cm3_particle_traj;
 
 int cm3_particle_rollout_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj, int32_t n_ticks,
                              void *stream);
 int cm3_particle_rollout_f64(const cm3_particle_desc *desc, const cm3_particle_traj *traj, int32_t n_ticks,
                              void *stream);
+/* 1 when a cm3_particle_rollout_* call of this descriptor (flags, n_envs and n_agents as they will be passed) can step on packed
+ * live records (cm3_particle_traj.live_record): float32 (real_bytes == 4), CM3_FLAG_GEN_ACTIONS without CM3_FLAG_FUSED_TICKS,
+ * n_agents in 2..4, and a batch that the lane-per-pair kernel steps (forced, or chosen from n_envs).  0 otherwise. */
+int cm3_particle_live_record_applies(const cm3_particle_desc *desc, int32_t real_bytes);
 
 
 /* ------------------------------------------------------------------------------------------
