@@ -1436,6 +1436,18 @@ static int ck_actor_check(const cm3_actor_checkers_desc *d) {
   return CM3_OK;
 }
 
+// the QMIX agent's descriptor (cm3_qmix_checkers_*, cm3_policy_rollout_checkers_qmix): desc->stage is not read
+static int ck_qmix_check(const cm3_actor_checkers_desc *d) {
+  using namespace ck_actor;
+  CM3_REQUIRE(d, "null desc");
+  CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= 8, "Checkers QMIX agent: n_agents must be in 1..8; got %d", d->n_agents);
+  CM3_REQUIRE(d->conv_f == kConvF && d->n_conv_linear == kLin && d->n_h1 == kH1 && d->n_h2 == kH2 && d->n_actions == kA,
+              "the Checkers QMIX agent's widths are the actor's nn block: conv_f 6 / conv_linear 32 / h1 256 / h2 256 / 5 actions; "
+              "got %d/%d/%d/%d/%d", d->conv_f, d->n_conv_linear, d->n_h1, d->n_h2, d->n_actions);
+  CM3_REQUIRE(d->n_obs == 2, "the Checkers QMIX agent reads 5x5x3 windows (n_obs = 2); got n_obs = %d", d->n_obs);
+  return CM3_OK;
+}
+
 static void ck_actor_weights(CkActorParams &p, const cm3_actor_checkers_weights *wt) {
   p.conv_w = wt->conv_w; p.conv_b = wt->conv_b; p.lin_w = wt->lin_w; p.lin_b = wt->lin_b;
   p.self_w = wt->self_w; p.self_b = wt->self_b; p.w_self_h2 = wt->w_self_h2;
@@ -1531,19 +1543,6 @@ extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm
 }
 
 // ---- QMIX agent (ABI 9, additive): the actor's forward pass with the others branch at every agent count and the greedy head ---------
-namespace cm3 {
-static int ck_qmix_check(const cm3_actor_checkers_desc *d) {
-  using namespace ck_actor;
-  CM3_REQUIRE(d, "null desc");
-  CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= 8, "Checkers QMIX agent: n_agents must be in 1..8; got %d", d->n_agents);
-  CM3_REQUIRE(d->conv_f == kConvF && d->n_conv_linear == kLin && d->n_h1 == kH1 && d->n_h2 == kH2 && d->n_actions == kA,
-              "the Checkers QMIX agent's widths are the actor's nn block: conv_f 6 / conv_linear 32 / h1 256 / h2 256 / 5 actions; "
-              "got %d/%d/%d/%d/%d", d->conv_f, d->n_conv_linear, d->n_h1, d->n_h2, d->n_actions);
-  CM3_REQUIRE(d->n_obs == 2, "the Checkers QMIX agent reads 5x5x3 windows (n_obs = 2); got n_obs = %d", d->n_obs);
-  return CM3_OK;
-}
-}  // namespace cm3
-
 extern "C" int cm3_qmix_checkers_pack(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, void *packed,
                                       void *stream) {
   using namespace cm3;
@@ -1563,6 +1562,14 @@ extern "C" int cm3_qmix_checkers_pack(const cm3_actor_checkers_desc *d, const cm
   ck_actor_weights(p, wt);
   hipLaunchKernelGGL(k_ck_actor_pack, dim3(128), dim3(256), 0, (hipStream_t)stream, p, (float *)packed);
   CM3_HIP_CHECK(hipGetLastError());
+  if (d->n_agents <= 2) {
+    // the others branch as a table for cm3_policy_rollout_checkers_qmix, from the weights just packed: with one or two agents a row's
+    // v_obs_others is ONE normalised cell (N = 1: the agent's own, checkers.py:128-154), 91 possible inputs (k_ck_actor_others_table).
+    // The stand-alone kernels do not read that region.
+    hipLaunchKernelGGL(k_ck_actor_others_table, dim3(2), dim3(512), 0, (hipStream_t)stream, (const float *)packed,
+                       (float *)packed + ck_actor::kPOthTab);
+    CM3_HIP_CHECK(hipGetLastError());
+  }
   return CM3_OK;
 }
 

@@ -78,8 +78,10 @@ __device__ __forceinline__ int actor_sample(const float (&pr)[kA], uint64_t seed
 // Callers issue it before their head's dependent matrix work: the Philox rounds are VALU work that fills the matrix waits.
 constexpr uint32_t kPurposeExplore = 0x20000000u;   // distinct from kAction (0), kReset (bit 31), kPolicy (bit 30)
 
-__device__ __forceinline__ void explore_words(uint64_t seed, uint64_t genv, uint32_t episode, uint32_t steps, int agent,
-                                              uint32_t &w_explore, uint32_t &w_action) {
+// Two stages, like the actor's uniform: stage 1 (explore_block_words: the agent's two words of the env's block) depends on nothing
+// loaded or computed, so the whole-episode Checkers kernel draws it once per LAUNCH; stage 2 (explore_words_from) mixes the
+// episode / step counters in.
+__device__ __forceinline__ uint2 explore_block_words(uint64_t seed, uint64_t genv, int agent) {
   u32x4 ctr;
   ctr.x = (uint32_t)genv;
   ctr.y = (uint32_t)(genv >> 32);
@@ -87,8 +89,16 @@ __device__ __forceinline__ void explore_words(uint64_t seed, uint64_t genv, uint
   ctr.w = kPurposeExplore | ((uint32_t)(agent >> 1) << 24);
   const u32x4 wd = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
   const bool odd = (agent & 1) != 0;
-  w_explore = action_word(odd ? wd.z : wd.x, episode, steps);
-  w_action = action_word(odd ? wd.w : wd.y, episode, steps);
+  return make_uint2(odd ? wd.z : wd.x, odd ? wd.w : wd.y);
+}
+__device__ __forceinline__ void explore_words_from(uint2 block_words, uint32_t episode, uint32_t steps, uint32_t &w_explore,
+                                                   uint32_t &w_action) {
+  w_explore = action_word(block_words.x, episode, steps);
+  w_action = action_word(block_words.y, episode, steps);
+}
+__device__ __forceinline__ void explore_words(uint64_t seed, uint64_t genv, uint32_t episode, uint32_t steps, int agent,
+                                              uint32_t &w_explore, uint32_t &w_action) {
+  explore_words_from(explore_block_words(seed, genv, agent), episode, steps, w_explore, w_action);
 }
 
 // argmax Q with the first index on ties (tf.argmax), replaced with probability eps by a uniform action (alg_qmix.py:177-182,

@@ -24,6 +24,9 @@
 // Trajectories (every array of CheckersRollout, actions and probabilities included) are bit-identical to the alternating launches
 // (tests/test_gpu_actor_checkers.py::test_checkers_policy_rollout_equals_launch_per_tick).  Precision 2 (split float16) only; N = 1
 // (stage 1) or N = 2 (stage 2), the reference's Checkers configurations, reference geometry (3 x 8 band, n_obs 2).
+// The GREEDY instantiations run the QMIX baseline's agent in the actor's place (cm3_policy_rollout_checkers_qmix: the same forward
+// pass, the others table at N = 1 too, argmax + epsilon-greedy instead of softmax + sampling; bit-identical to alternating
+// cm3_qmix_checkers_f32 / cm3_checkers_step launches, tests/test_gpu_qmix_checkers_rollout.py).
 #ifndef CM3_POLICY_CHECKERS_BODY_ONLY   // (tools/probes/ck_policy_timeline.hip includes the two files WITH their entry points first)
 #define CM3_NO_ENTRY_POINTS 1
 #include "checkers.hip"
@@ -139,7 +142,9 @@ __device__ __forceinline__ void ckp_zero_x0_pad(_Float16 *X0, int row) {
 }
 
 // lane g < N of an env: the tail of agent g's X2 row -- v_obs_self (the env's normalised values, cast to float32 like a TF feed and
-// split), the one-hots of a_prev and of the goal -- and, for two agents, the table row of the others branch: the OTHER agent's cell
+// split), the one-hots of a_prev and of the goal -- and the table row of the others branch: the OTHER agent's cell for two agents,
+// the agent's OWN cell for one (what the env's obs_others holds at N = 1: the QMIX agent's others branch reads it; the CM3 actor
+// has no others branch there and never looks the row up)
 template <int N>
 __device__ __forceinline__ void ckp_row_inputs(const CkState<N> &s, const uint8_t (&goal)[N], const int (&aprev)[N], const uint4 *lds_tab,
                                                int g, const CkX3Planes &L, int32_t *sCell, int row0) {
@@ -147,7 +152,7 @@ __device__ __forceinline__ void ckp_row_inputs(const CkState<N> &s, const uint8_
   if (g < N) {
     ckp_zero_x0_pad(L.X0, row0 + g);
     int r = s.r[0], c = s.c[0], ng = s.ng[0], no = s.no[0], gl = goal[0], ap = aprev[0];
-    int orr = s.r[N > 1 ? 1 : 0], occ = s.c[N > 1 ? 1 : 0];
+    int orr = s.r[N > 1 ? 1 : 0], occ = s.c[N > 1 ? 1 : 0];   // (N == 1: the agent's own cell)
 #pragma unroll
     for (int a = 1; a < N; ++a) {
       const bool me = g == a;
@@ -194,7 +199,7 @@ __device__ __forceinline__ void ckp_row_flags(const CkState<N> &s, const uint8_t
   if (g < N) {
     ckp_zero_x0_pad(L.X0, row0 + g);
     int gl = goal[0], ap = aprev[0];
-    int orr = s.r[N > 1 ? 1 : 0], occ = s.c[N > 1 ? 1 : 0];
+    int orr = s.r[N > 1 ? 1 : 0], occ = s.c[N > 1 ? 1 : 0];   // (N == 1: the agent's own cell, as in ckp_row_inputs)
 #pragma unroll
     for (int a = 1; a < N; ++a) {
       const bool me = g == a;
@@ -210,7 +215,8 @@ __device__ __forceinline__ void ckp_row_flags(const CkState<N> &s, const uint8_t
   }
 }
 
-// h2's accumulators start from the others-branch table (two agents; stage 1: zeros): row = the OTHER agent's cell.  A lane's
+// h2's accumulators start from the others-branch table (the actor with two agents, the QMIX agent always; the stage-1 actor: h2's
+// bias): row = sCell, the OTHER agent's cell (N = 1: the agent's own).  A lane's
 // accumulators cover 16 agent rows per tile -- read straight from the table that is 16 scattered 64-byte pieces per load, 128
 // cache-line requests per wave and tick, and cost 1.0 - 1.5 us of a 16.5 us tick.  Instead wave w fetches the eight WHOLE table rows
 // of agent rows [8w, 8w + 8), one coalesced 1 KB request each, STRAIGHT INTO LDS (global_load_lds_dwordx4: wave-uniform LDS base + 16
@@ -222,7 +228,7 @@ __device__ __forceinline__ void ckp_row_flags(const CkState<N> &s, const uint8_t
 // compiler drains the vector-memory counter ahead of every barrier while an LDS-direct load is in flight.
 constexpr int kCkpTabLd = 256 + ck_actor::kLdPad / 2;   // (floats: 8 dwords mod 64 -- the same lane groups read it with 16-byte loads, see kLdHb)
 struct CkpTableHooks {
-  const float *tab;     // NULL: stage 1, no others branch
+  const float *tab;     // NULL: the stage-1 actor, no others branch
   const float *pk;
   const int32_t *sCell;
   float *sT;
@@ -264,7 +270,11 @@ struct CkpTableHooks {
   }
 };
 
-template <int N> __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_policy_rollout(const CkPolicyParams q_arg) {
+// GREEDY: the QMIX agent (networks.Qmix_single_checkers + alg_qmix_checkers.run_actor) instead of the CM3 actor -- the same forward
+// pass with the others table at EVERY agent count (N = 1: the row of the agent's OWN cell, what the env's obs_others holds there) and
+// the head of k_ck_actor_x3<true>: the logits read as Q values, argmax, epsilon-greedy on the words of ck_qmix_words; q.probs receives
+// the raw Q values.  q.stage is not read.
+template <int N, bool GREEDY> __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_policy_rollout(const CkPolicyParams q_arg) {
   using namespace ck_actor;
   constexpr int G = CkpGeom<N>::G, EPW = 64 / N, ENV_WAVES = EPW * G / 64;
   static_assert(ENV_WAVES == 8, "every wave takes part in the env phase");
@@ -304,7 +314,7 @@ template <int N> __global__ void __launch_bounds__(512) __attribute__((amdgpu_wa
   const float *pk = q.packed;
   const size_t rows = (size_t)p.E * N;
   const size_t row_base = (size_t)blockIdx.x * 64;
-  const bool stage2 = q.stage > 1;
+  const bool others_tab = GREEDY || q.stage > 1;
 
   CkConvB b_conv;
 
@@ -346,8 +356,14 @@ template <int N> __global__ void __launch_bounds__(512) __attribute__((amdgpu_wa
   const int el_h = row_l / N, i_h = row_l - el_h * N;
   const size_t e_h = row_h / N;
   const bool head_lane = w < 4 && lane < 16;
+  // stage 1 of the head's draws, once per launch: the actor's sampling word, or the QMIX agent's two exploration words
   uint32_t ublock = 0u;
-  if (head_lane) ublock = actor_block_word(p.seed, (uint64_t)(p.env_id_base + (int64_t)(e_h < (size_t)p.E ? e_h : (size_t)p.E - 1)), i_h);
+  uint2 xblock = make_uint2(0u, 0u);
+  if constexpr (GREEDY) {
+    if (head_lane) xblock = explore_block_words(p.seed, (uint64_t)(p.env_id_base + (int64_t)(e_h < (size_t)p.E ? e_h : (size_t)p.E - 1)), i_h);
+  } else {
+    if (head_lane) ublock = actor_block_word(p.seed, (uint64_t)(p.env_id_base + (int64_t)(e_h < (size_t)p.E ? e_h : (size_t)p.E - 1)), i_h);
+  }
   // zero fill, once: the tail of X2 beyond the concat (43 .. 63) and the lo plane of its one-hots
   for (int idx = tid; idx < 64 * 32; idx += 512) {
     const int r = idx >> 5, k = kLin + (idx & 31);
@@ -402,7 +418,7 @@ template <int N> __global__ void __launch_bounds__(512) __attribute__((amdgpu_wa
     ck_x3_load_conv(pkt, w, lane, b_conv);
     f32x4 acc2[4][kCkBCT];
     CkpTableHooks hooks;
-    hooks.tab = stage2 ? pkt + kPOthTab : nullptr; hooks.pk = pkt; hooks.sCell = sCell; hooks.sT = sT; hooks.w = w; hooks.lane = lane;
+    hooks.tab = others_tab ? pkt + kPOthTab : nullptr; hooks.pk = pkt; hooks.sCell = sCell; hooks.sT = sT; hooks.w = w; hooks.lane = lane;
     ck_x3_self_chain<CkpTableHooks &>(L, pkt, w, lane, b_conv, acc2, hooks);
     if (w < 4) {
       __builtin_amdgcn_s_waitcnt(0);
@@ -411,9 +427,19 @@ template <int N> __global__ void __launch_bounds__(512) __attribute__((amdgpu_wa
         float o[kA], pr[kA];
 #pragma unroll
         for (int a = 0; a < kA; ++a) o[a] = sLG[row_l][a];
-        ck_actor_probs(o, eps_now, pr);
-        const int2 m = sMeta[el_h];
-        const int act = actor_pick(pr, actor_uniform_from(ublock, (uint32_t)m.x, m.y));
+        int act;
+        if constexpr (GREEDY) {   // (ck_qmix_head: Q values as they are, the first index on ties)
+          const int2 m = sMeta[el_h];
+          uint32_t w_explore, w_action;
+          explore_words_from(xblock, (uint32_t)m.x, (uint32_t)m.y, w_explore, w_action);
+          act = epsilon_greedy(o, eps_now, w_explore, w_action);
+#pragma unroll
+          for (int a = 0; a < kA; ++a) pr[a] = o[a];
+        } else {
+          ck_actor_probs(o, eps_now, pr);
+          const int2 m = sMeta[el_h];
+          act = actor_pick(pr, actor_uniform_from(ublock, (uint32_t)m.x, m.y));
+        }
         sAct[row_l] = act;
         if (row_h < rows) {
           ck_tick_ptr(p.actions, p.st_actions, t)[row_h] = act;
@@ -500,7 +526,7 @@ template <int N> __global__ void __launch_bounds__(512) __attribute__((amdgpu_wa
   }
 }
 
-template <int N> static int ckp_launch(const CkPolicyParams &q, hipStream_t s) {
+template <int N, bool GREEDY> static int ckp_launch(const CkPolicyParams &q, hipStream_t s) {
   const size_t rows = (size_t)q.ck.E * N;
   // the step's stores use 32-bit byte offsets (ck_launch): the widest per-env record of any per-tick array bounds E
   size_t widest = (size_t)q.ck.obst_stride;
@@ -508,32 +534,41 @@ template <int N> static int ckp_launch(const CkPolicyParams &q, hipStream_t s) {
   if ((size_t)N * 32 > widest) widest = (size_t)N * 32;
   if ((size_t)q.ck.E * widest >= ((size_t)1 << 32))
     return fail(CM3_ERR_INVALID, "the Checkers step addresses at most 4 GiB per array: %d envs x %d agents is too large", q.ck.E, N);
-  note_variant("k_ck_policy_rollout", 0, N, 8, q.ck.n_ticks > 1, 2, 0, 0, 0, CkpGeom<N>::G);
-  hipLaunchKernelGGL((k_ck_policy_rollout<N>), dim3((unsigned)((rows + 63) / 64)), dim3(512), 0, s, q);
+  note_variant(GREEDY ? "k_ck_policy_rollout_qmix" : "k_ck_policy_rollout", 0, N, 8, q.ck.n_ticks > 1, 2, 0, 0, 0, CkpGeom<N>::G);
+  hipLaunchKernelGGL((k_ck_policy_rollout<N, GREEDY>), dim3((unsigned)((rows + 63) / 64)), dim3(512), 0, s, q);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
 
 }  // namespace cm3
 
-extern "C" int cm3_policy_rollout_checkers(const cm3_checkers_desc *d, const cm3_checkers_traj *t, const cm3_actor_checkers_desc *ad,
-                                           const cm3_actor_checkers_weights *wt, const int32_t *actions_prev0, int32_t *actions_prev_next, float *probs,
-                                           size_t probs_stride, const float *epsilon_dev, const cm3_checkers_bufs *final_obs,
-                                           int32_t n_ticks, void *stream) {
-  using namespace cm3;
+namespace cm3 {
+// the checks and the parameter fill the two entry points share (greedy: the QMIX agent's, cm3_policy_rollout_checkers_qmix): every
+// argument is checked before anything touches the GPU
+static int ckp_rollout(const cm3_checkers_desc *d, const cm3_checkers_traj *t, const cm3_actor_checkers_desc *ad,
+                       const cm3_actor_checkers_weights *wt, const int32_t *actions_prev0, int32_t *actions_prev_next, float *probs,
+                       size_t probs_stride, const float *epsilon_dev, const cm3_checkers_bufs *final_obs, int32_t n_ticks, void *stream,
+                       bool greedy) {
   CM3_REQUIRE(d && t && ad && wt, "null argument");
   CM3_REQUIRE(n_ticks >= 1, "n_ticks must be >= 1");
   CM3_REQUIRE(d->n_agents == 1 || d->n_agents == 2,
-              "the whole-episode Checkers policy rollout covers one or two agents (config_checkers_stage1 / stage2); got %d -- use "
-              "alternating cm3_actor_checkers_f32 / cm3_checkers_step launches", d->n_agents);
-  int rc = ck_actor_check(ad);
+              "the whole-episode Checkers %s rollout covers one or two agents (config_checkers_stage1 / stage2); got %d -- use "
+              "alternating %s / cm3_checkers_step launches", greedy ? "QMIX" : "policy", d->n_agents,
+              greedy ? "cm3_qmix_checkers_f32" : "cm3_actor_checkers_f32");
+  int rc = greedy ? ck_qmix_check(ad) : ck_actor_check(ad);
   if (rc != CM3_OK) return rc;
   CM3_REQUIRE(ad->n_agents == d->n_agents && ad->n_envs == d->n_envs, "actor / env descriptors disagree");
-  CM3_REQUIRE(ad->precision == 2, "the whole-episode Checkers policy rollout runs the split-float16 actor (precision 2)");
-  CM3_REQUIRE((ad->stage > 1) == (d->n_agents > 1), "stage 1 has one agent, stage 2 two (the others branch is a table over the ONE other agent's cell)");
+  if (greedy) {
+    CM3_REQUIRE(ad->precision == 2,
+                "the whole-episode Checkers QMIX rollout runs the split-float16 agent (precision 2); got %d -- precision 0 (float32) runs "
+                "as alternating cm3_qmix_checkers_f32 / cm3_checkers_step launches (the launch-pair path)", ad->precision);
+  } else {
+    CM3_REQUIRE(ad->precision == 2, "the whole-episode Checkers policy rollout runs the split-float16 actor (precision 2)");
+    CM3_REQUIRE((ad->stage > 1) == (d->n_agents > 1), "stage 1 has one agent, stage 2 two (the others branch is a table over the ONE other agent's cell)");
+  }
   CM3_REQUIRE(ad->seed == d->seed && ad->env_id_base == d->env_id_base, "actor and env must share seed and env_id_base");
   CM3_REQUIRE(ad->epsilon >= 0.0f && ad->epsilon <= 1.0f, "epsilon must be in [0,1]");
-  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_checkers_pack once per weight update");
+  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run %s once per weight update", greedy ? "cm3_qmix_checkers_pack" : "cm3_actor_checkers_pack");
   CM3_REQUIRE(!(d->flags & ~CM3_FLAG_AUTO_RESET), "only CM3_FLAG_AUTO_RESET applies: the policy draws the actions, the ticks are fused by definition");
   CM3_REQUIRE(t->actions && (n_ticks == 1 || t->actions_stride != 0), "one action slot per tick is required");
   CM3_REQUIRE(t->episode, "the episode counter is required (it keys the sampling uniforms)");
@@ -553,7 +588,7 @@ extern "C" int cm3_policy_rollout_checkers(const cm3_checkers_desc *d, const cm3
   q.st_probs = probs_stride;
   q.eps = ad->epsilon;
   q.eps_dev = epsilon_dev;
-  q.stage = ad->stage;
+  q.stage = ad->stage;   // (the GREEDY kernel does not read it)
   q.slot0.grid = t->grid; q.slot0.vec = t->vec; q.slot0.obs_others = t->obs_others; q.slot0.obs_self_t = t->obs_self_t;
   q.slot0.obs_self_v = t->obs_self_v;
   q.goals_slot0 = t->goals_slots;
@@ -564,5 +599,21 @@ extern "C" int cm3_policy_rollout_checkers(const cm3_checkers_desc *d, const cm3
     q.final_obs.obs_self_t = final_obs->obs_self_t; q.final_obs.obs_self_v = final_obs->obs_self_v;
     q.final_actions = final_obs->actions;
   }
-  return d->n_agents == 1 ? ckp_launch<1>(q, (hipStream_t)stream) : ckp_launch<2>(q, (hipStream_t)stream);
+  if (greedy) return d->n_agents == 1 ? ckp_launch<1, true>(q, (hipStream_t)stream) : ckp_launch<2, true>(q, (hipStream_t)stream);
+  return d->n_agents == 1 ? ckp_launch<1, false>(q, (hipStream_t)stream) : ckp_launch<2, false>(q, (hipStream_t)stream);
+}
+}  // namespace cm3
+
+extern "C" int cm3_policy_rollout_checkers(const cm3_checkers_desc *d, const cm3_checkers_traj *t, const cm3_actor_checkers_desc *ad,
+                                           const cm3_actor_checkers_weights *wt, const int32_t *actions_prev0, int32_t *actions_prev_next, float *probs,
+                                           size_t probs_stride, const float *epsilon_dev, const cm3_checkers_bufs *final_obs,
+                                           int32_t n_ticks, void *stream) {
+  return cm3::ckp_rollout(d, t, ad, wt, actions_prev0, actions_prev_next, probs, probs_stride, epsilon_dev, final_obs, n_ticks, stream, false);
+}
+
+extern "C" int cm3_policy_rollout_checkers_qmix(const cm3_checkers_desc *d, const cm3_checkers_traj *t, const cm3_actor_checkers_desc *ad,
+                                                const cm3_actor_checkers_weights *wt, const int32_t *actions_prev0, int32_t *actions_prev_next,
+                                                float *q_values, size_t q_stride, const float *epsilon_dev, const cm3_checkers_bufs *final_obs,
+                                                int32_t n_ticks, void *stream) {
+  return cm3::ckp_rollout(d, t, ad, wt, actions_prev0, actions_prev_next, q_values, q_stride, epsilon_dev, final_obs, n_ticks, stream, true);
 }

@@ -138,12 +138,19 @@ class CheckersQmixAgent(object):
             (alg_qmix_checkers.py:90, run_actor :153-182)                  -> actions [E, N] (one launch)
         alg.run_actor(actions_prev, obs_others, obs_self_t, obs_self_v,  CheckersRollout.collect(goals, policy=agent,
             goals, eps, sess)  (train_offpolicy.py:316-317)                epsilon=..): agent and step launches alternate
-                                                                           inside ONE hipGraph
+                                                                           inside ONE hipGraph; with
+                                                                           CheckersRollout(env, policy_mode="episode") the
+                                                                           whole rollout is ONE launch
 
     The network is the CM3 Checkers actor's forward pass (csrc/actor_checkers.hip) with the others branch at every agent count
     and a greedy head.  precision: "f32" (every layer on the exact-f32 MFMA) or "f16x3" (every layer in split float16, the
     actor's precision 2).  Exploration draws come from the particle QMIX agent's stream (keyed with the Checkers env's episode
-    and step counters).  The one-launch rollout kernel runs the CM3 actor: CheckersRollout runs this agent as launch pairs.
+    and step counters).
+
+    CheckersRollout runs this agent as launch pairs under policy_mode "auto" and "tick".  policy_mode="episode" opts in to the
+    one-launch rollout kernel (cm3_policy_rollout_checkers_qmix; enqueue_episode / episode_ok below): "f16x3", one or two agents,
+    agent and env on one seed and env_id_base -- the same bits as the launch pairs.  (The hooks are NOT named like CheckersActor's
+    enqueue_rollout / fused_rollout_ok: "auto" picks the one-launch kernel for whatever carries those names.)
     """
 
     def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0, precision="f32"):
@@ -214,6 +221,25 @@ class CheckersQmixAgent(object):
         d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base, obst_stride)
         s = _lib.current_stream_handle(self.device) if stream is None else stream
         _lib.check(self._lib.cm3_qmix_checkers_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
+
+    def enqueue_episode(self, env_desc, traj, n_envs, obst_stride, n_ticks, epsilon, prev0=None, probs=None, stream=None,
+                        final_obs=None, prev0_next=None):
+        """The whole agent-driven rollout in ONE launch (cm3_policy_rollout_checkers_qmix), the signature of
+        CheckersActor.enqueue_rollout; probs: optional float32 [T, E, N, 5], receives the Q values."""
+        epsilon, eps_dev = _epsilon_args(epsilon)
+        d = self._desc(n_envs, epsilon, env_desc.env_id_base, obst_stride)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_policy_rollout_checkers_qmix(
+            ctypes.byref(env_desc), ctypes.byref(traj), ctypes.byref(d), ctypes.byref(self._wt), _lib.ptr(prev0), _lib.ptr(prev0_next),
+            _lib.ptr(probs), 0 if probs is None else probs[0].numel() * probs.element_size(), eps_dev,
+            None if final_obs is None else ctypes.byref(final_obs), int(n_ticks), s))
+
+    def episode_ok(self, env):
+        """cm3_policy_rollout_checkers_qmix applies: split float16, one or two agents (the env's count), the 3 x 8 band with
+        n_obs 2 and 4-byte padded records, agent and env on one seed and env_id_base (one Philox key)."""
+        same_key = (self.seed & 0xFFFFFFFFFFFFFFFF) == int(env._desc.seed) and self.env_id_base == int(env._desc.env_id_base)
+        return (self.precision == "f16x3" and same_key and env.n == self.n and env.n in (1, 2) and env.K == 5 and env.R == 3
+                and env.C == 8 and env.grid_stride % 4 == 0 and env.obst_stride % 4 == 0)
 
     def act(self, env, epsilon, actions_prev=None, return_q=False):
         """Actions [E, N] int32 for the env's CURRENT observation (alg_qmix_checkers.run_actor); actions_prev None = zeros

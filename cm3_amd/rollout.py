@@ -92,6 +92,37 @@ def _copy_pairs(pairs, stream):
                 d.copy_(s_)
 
 
+def _one_launch_hooks(policy):
+    """(applies(env), enqueue(...)) of the whole-rollout Checkers kernel that runs `policy`, or None.  CheckersActor's pair
+    (fused_rollout_ok / enqueue_rollout) is what policy_mode "auto" looks for; CheckersQmixAgent's (episode_ok /
+    enqueue_episode) runs under policy_mode "episode" only."""
+    if hasattr(policy, "enqueue_rollout"):
+        return policy.fused_rollout_ok, policy.enqueue_rollout
+    if hasattr(policy, "enqueue_episode"):
+        return policy.episode_ok, policy.enqueue_episode
+    return None
+
+
+def _one_launch_refusal(policy, env):
+    """Why the whole-rollout Checkers kernel does not run `policy` on `env`: the first failed condition, in words."""
+    who = type(policy).__name__
+    if _one_launch_hooks(policy) is None:
+        return "%s has no one-launch rollout kernel" % who
+    if getattr(policy, "precision", None) != "f16x3":
+        return ("precision: the one-launch rollout kernel runs the split-float16 network (precision='f16x3'); this %s has "
+                "precision=%r, which runs as launch pairs (policy_mode='tick')" % (who, getattr(policy, "precision", None)))
+    if env.n != policy.n or env.n not in (1, 2):
+        return ("agent count: the one-launch rollout kernel covers one or two agents, the env's and the policy's alike; env has %d, "
+                "%s %d -- other counts run as launch pairs (policy_mode='tick')" % (env.n, who, policy.n))
+    if hasattr(policy, "stage") and (policy.stage > 1) != (env.n > 1):
+        return "agent count: a stage-%d %s does not match an env with %d agent(s)" % (policy.stage, who, env.n)
+    if (policy.seed & 0xFFFFFFFFFFFFFFFF) != int(env._desc.seed) or policy.env_id_base != int(env._desc.env_id_base):
+        return ("seed / env_id_base: the one-launch rollout kernel draws for policy and env under one Philox key; %s has seed %d, "
+                "env_id_base %d, the env seed %d, env_id_base %d" % (who, policy.seed, policy.env_id_base, int(env._desc.seed),
+                                                                      int(env._desc.env_id_base)))
+    return "geometry: the one-launch rollout kernel needs the 3 x 8 band, n_obs 2 and 4-byte padded records"
+
+
 _Mode = collections.namedtuple("_Mode", "kind live sparse")
 
 
@@ -947,14 +978,18 @@ class CheckersRollout(_Transitions):
     def __init__(self, env, n_ticks=None, use_graph=True, fused=False, policy_mode="auto", record_probs=False):
         """policy_mode (collect(policy=<CheckersActor>)): "auto" = the whole rollout in ONE launch (cm3_policy_rollout_checkers)
         wherever that kernel applies (CheckersActor.fused_rollout_ok), else -- and with "tick" -- an actor launch and a step
-        launch per tick inside one hipGraph; the two produce the same bits.  record_probs: keep the mixed probabilities the
-        actions were drawn from, float32 [T, E, N, 5] (self.probs)."""
+        launch per tick inside one hipGraph; the two produce the same bits.  A CheckersQmixAgent runs as launch pairs under
+        "auto" and "tick".  "episode" = the one-launch kernel or an error, for either device policy: cm3_policy_rollout_checkers
+        for the actor, cm3_policy_rollout_checkers_qmix for the QMIX agent (CheckersQmixAgent.episode_ok), same bits as its
+        launch pairs; collect() raises Cm3Error naming the condition that fails (precision, agent count, seed / env_id_base).
+        A host callable or policy=None behaves under "episode" as under "auto".  record_probs: keep the mixed probabilities
+        the actions were drawn from -- the QMIX agent's Q values -- float32 [T, E, N, 5] (self.probs)."""
         self.env = env
         self.T = int(n_ticks or env.max_steps)
         self.use_graph = bool(use_graph)
         self.fused = bool(fused)      # random-action branch in ONE launch (CM3_FLAG_FUSED_TICKS; fast kernel only)
-        if policy_mode not in ("auto", "tick"):
-            raise Cm3Error("policy_mode must be 'auto' or 'tick'")
+        if policy_mode not in ("auto", "episode", "tick"):
+            raise Cm3Error("policy_mode must be 'auto', 'episode' or 'tick'")
         self.policy_mode = policy_mode
         self.auto_reset = bool(env.auto_reset)
         E, N, T, dev = env.E, env.n, self.T, env.device
@@ -1078,8 +1113,9 @@ class CheckersRollout(_Transitions):
         if self._traj_cache is None or self._traj_cache[0] != env._cur:
             self._traj_cache = (env._cur, self._traj(), env._bufs(env._cur))
         _, traj, final = self._traj_cache
-        actor.enqueue_rollout(env._desc, traj, env.E, env.obst_stride, self.T, epsilon, prev0=self.prev0, probs=self.probs,
-                              stream=stream, final_obs=final, prev0_next=prev0_next)
+        _, enqueue = _one_launch_hooks(actor)
+        enqueue(env._desc, traj, env.E, env.obst_stride, self.T, epsilon, prev0=self.prev0, probs=self.probs, stream=stream,
+                final_obs=final, prev0_next=prev0_next)
         env._desc.flags = 0
 
     def _load_slot0(self):
@@ -1103,13 +1139,18 @@ class CheckersRollout(_Transitions):
 
     def collect(self, goals=None, policy=None, epsilon=0.0, reset=None):
         """goals: one-hot [N,2] / [E,N,2] (train_onpolicy.py:287-293); needed whenever the env is reset.
-        policy None = uniform random actions drawn in-kernel; a cm3_amd.actor.CheckersActor = the on-device policy (the whole
-        rollout in one launch where that kernel applies, else actor and step launches alternating inside one hipGraph: policy_mode);
+        policy None = uniform random actions drawn in-kernel; a cm3_amd.actor.CheckersActor or cm3_amd.qmix.CheckersQmixAgent = the
+        on-device policy (the whole rollout in one launch, or policy and step launches alternating inside one hipGraph: policy_mode);
         else policy(actions_prev, obs_others, obs_self_t, obs_self_v, goals) -> [E,N] on the host.  reset: None -> always for an
         episode-synchronous env, only the first time for a continuous (auto-reset) one."""
         env = self.env
         one_launch = (policy is not None and hasattr(policy, "enqueue_rollout") and self.policy_mode == "auto"
                       and policy.fused_rollout_ok(env))
+        if self.policy_mode == "episode" and _is_device_policy(policy):
+            hooks = _one_launch_hooks(policy)
+            if hooks is None or not hooks[0](env):     # (before the env is reset or anything is launched)
+                raise Cm3Error("policy_mode='episode': " + _one_launch_refusal(policy, env))
+            one_launch = True
         if reset is None:
             reset = (not self.auto_reset) or (not self._started)
         # actions_prev of tick 0 (self.prev0; train_onpolicy.py:295,345): zeros after a reset, else the previous rollout's last actions

@@ -48,6 +48,8 @@ extern "C" {
 
 #define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
                                   Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network);
+                                  cm3_policy_rollout_checkers_qmix (the one-launch Checkers rollout driven by that agent; cm3_qmix_checkers_pack
+                                  now also writes the others-branch table behind the packed weights, inside the same allocation);
                                   cm3_checkers_transitions_gather (the Checkers transition export in one launch);
                                   cm3_checkers_transitions_pack / cm3_checkers_ring_expand (the compact Checkers replay ring);
                                   cm3_particle_traj.live_record (appended; NULL = as before) and cm3_particle_live_record_applies.
@@ -554,6 +556,20 @@ int cm3_policy_rollout_checkers(const cm3_checkers_desc *desc, const cm3_checker
                                 const cm3_actor_checkers_weights *weights, const int32_t *actions_prev0, int32_t *actions_prev_next, float *probs,
                                 size_t probs_stride, const float *epsilon_dev, const cm3_checkers_bufs *final_obs,
                                 int32_t n_ticks, void *stream);
+
+/* The same rollout driven by the Checkers QMIX agent (part of ABI 9, additive): per tick networks.Qmix_single_checkers (precision 2),
+ * argmax Q + the epsilon-greedy choice of cm3_qmix_checkers_f32, and Checkers.step -- the QMIX collection loop of
+ * train_offpolicy.py:309-368 without leaving the kernel.  Arguments as for cm3_policy_rollout_checkers, with these differences:
+ * `agent` is validated like cm3_qmix_checkers_f32's descriptor (agent->stage is not read); weights->packed comes from
+ * cm3_qmix_checkers_pack, which for one or two agents also builds the others-branch table (N = 1: a row per cell of the agent
+ * itself, what the env's obs_others holds there); n_agents 1 or 2; precision 2 only -- precision 0 stays on alternating
+ * cm3_qmix_checkers_f32 / cm3_checkers_step launches; agent and env must share seed and env_id_base; q_values: optional float
+ * [n_ticks][E][N][5], the raw Q values, q_stride BYTES between ticks.  Every output equals, bit for bit, what n_ticks x
+ * (cm3_qmix_checkers_f32, cm3_checkers_step) write.  cm3_last_kernel_variant() names it k_ck_policy_rollout_qmix. */
+int cm3_policy_rollout_checkers_qmix(const cm3_checkers_desc *desc, const cm3_checkers_traj *traj, const cm3_actor_checkers_desc *agent,
+                                     const cm3_actor_checkers_weights *weights, const int32_t *actions_prev0, int32_t *actions_prev_next,
+                                     float *q_values, size_t q_stride, const float *epsilon_dev, const cm3_checkers_bufs *final_obs,
+                                     int32_t n_ticks, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Advantage normalisation (build-defined; the reference's advantage, alg_credit.py:334-357, is not normalised).

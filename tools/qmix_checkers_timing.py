@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """us per tick of policy-driven Checkers collection with the QMIX agent (CheckersQmixAgent: an agent launch and a step launch per
 tick inside one hipGraph) next to the CM3 Checkers actor in the same launch mode (CheckersActor, policy_mode="tick"), f32 and f16x3
-each, in one process, at C3 (config_checkers_stage2: 8192 envs x 2 agents): 33-tick continuous rollouts with full trajectory
-storage, epsilon 0.1, random weights of the reference's shapes.  Timed with events over graph replays (collect() replays the
-captured graph), alternating the four policies over several repeats; prints one JSON line.
+each, and the two f16x3 policies once more as ONE launch per rollout (policy_mode="episode": qmix_f16x3_episode,
+cm3_actor_f16x3_episode), in one process, at C3 (config_checkers_stage2: 8192 envs x 2 agents): 33-tick continuous rollouts with
+full trajectory storage, epsilon 0.1, random weights of the reference's shapes.  Timed with events over collect() calls (graph
+replays, or the one launch), alternating the six policies over several repeats; prints one JSON line.
 --agent-only [f32|f16x3]: launch only the QMIX agent at C3, 200 times (for rocprofv3 --kernel-trace --stats)."""
 import json
 import os
@@ -23,12 +24,15 @@ def _policies(dev, only=None):
     from tests import qmix_checkers_ref as QC
     w_actor = AO.init_weights(np.random.default_rng(0), N, stage=2)
     w_qmix = QC.init_weights(np.random.default_rng(1), N)
-    out = {}
+    out = {}                                           # name -> (policy, policy_mode)
     for prec in ("f32", "f16x3"):
         if only is None:
-            out["cm3_actor_%s_tick" % prec] = CheckersActor(w_actor, N, stage=2, device=dev, precision=prec)
+            out["cm3_actor_%s_tick" % prec] = (CheckersActor(w_actor, N, stage=2, device=dev, precision=prec), "tick")
         if only in (None, prec):
-            out["qmix_%s" % prec] = CheckersQmixAgent(w_qmix, N, device=dev, precision=prec)
+            out["qmix_%s" % prec] = (CheckersQmixAgent(w_qmix, N, device=dev, precision=prec), "tick")
+    if only is None:
+        out["qmix_f16x3_episode"] = (out["qmix_f16x3"][0], "episode")
+        out["cm3_actor_f16x3_episode"] = (out["cm3_actor_f16x3_tick"][0], "episode")
     return out
 
 
@@ -49,7 +53,7 @@ def main():
         prec = sys.argv[2] if len(sys.argv) > 2 else "f16x3"
         env = _env(dev, False)
         env.reset(np.eye(2))
-        agent = _policies(dev, only=prec)["qmix_%s" % prec]
+        agent = _policies(dev, only=prec)["qmix_%s" % prec][0]
         for _ in range(200):
             agent.act(env, 0.1)
         torch.cuda.synchronize()
@@ -58,14 +62,14 @@ def main():
     reps, inner = 5, 20
     pols = _policies(dev)
     ros = {}
-    for name, pol in pols.items():
-        ros[name] = CheckersRollout(_env(dev, True), n_ticks=T, use_graph=True, policy_mode="tick")
+    for name, (pol, mode) in pols.items():
+        ros[name] = CheckersRollout(_env(dev, True), n_ticks=T, use_graph=True, policy_mode=mode)
         for _ in range(3):
             ros[name].collect(np.eye(2), policy=pol, epsilon=0.1)
     torch.cuda.synchronize()
     times = {name: [] for name in pols}
     for _ in range(reps):
-        for name, pol in pols.items():
+        for name, (pol, _) in pols.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             for _ in range(inner):
