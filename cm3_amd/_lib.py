@@ -67,16 +67,31 @@ class TransitionCols(ctypes.Structure):
                                         "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
 
 
+# THE list of the 16 columns of a Checkers transition, each with the record of the trajectory it carries, in the field order of both
+# column structs below (kCkColumns in csrc/batch.hip is the same table); rollout.CHECKERS_ORDER and CheckersRollout.ORDER are its names
+CHECKERS_COLUMN_RECORDS = (
+    ("grid", "grid"), ("vec", "vec"), ("obs_others", "obs_others"), ("obs_self_t", "obs_self_t"), ("obs_self_v", "obs_self_v"),
+    ("actions_prev", "actions"), ("actions", "actions"), ("reward", "reward"), ("local_rewards", "local_rewards"), ("next_grid", "grid"),
+    ("next_vec", "vec"), ("next_obs_others", "obs_others"), ("next_obs_self_t", "obs_self_t"), ("next_obs_self_v", "obs_self_v"),
+    ("done", "done"), ("goals", "goals"))
+CHECKERS_COLUMNS = tuple(name for name, _ in CHECKERS_COLUMN_RECORDS)
+
+
 class CheckersTransitionCols(ctypes.Structure):
-    # (the pointer fields carry the names of CheckersRollout.ORDER, in its order)
-    _fields_ = [(n, c_void_p) for n in ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions_prev", "actions", "reward",
-                                        "local_rewards", "next_grid", "next_vec", "next_obs_others", "next_obs_self_t",
-                                        "next_obs_self_v", "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
+    _fields_ = [(n, c_void_p) for n in CHECKERS_COLUMNS] + [("ring_start", c_int64), ("ring_size", c_int64)]
 
 
 class CheckersCompactCols(ctypes.Structure):
     # (cm3_checkers_compact_cols: the same names and order, the columns with the dtypes the trajectory keeps)
     _fields_ = list(CheckersTransitionCols._fields_)
+
+
+def fill_checkers_cols(struct, columns, ring_start=0, ring_size=0):
+    """Either column struct with the device pointers of `columns` (name -> tensor, checked by the caller) and the ring."""
+    for name in CHECKERS_COLUMNS:
+        setattr(struct, name, columns[name].data_ptr())
+    struct.ring_start, struct.ring_size = int(ring_start), int(ring_size)
+    return struct
 
 
 class RowCols(ctypes.Structure):

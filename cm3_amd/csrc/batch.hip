@@ -748,13 +748,112 @@ static int ck_traj_check(const char *entry, const cm3_checkers_traj *traj, const
   return CM3_OK;
 }
 
+// ---- the 16 columns, ONE table: cm3_checkers_transitions_gather, cm3_checkers_transitions_pack and cm3_checkers_ring_expand all read it --
+enum CkRec : uint8_t {   // the record of the trajectory a column carries
+  CKR_GRID, CKR_VEC, CKR_OBS_OTHERS, CKR_OBS_SELF_T, CKR_OBS_SELF_V, CKR_ACTIONS, CKR_REWARD, CKR_LOCAL_REWARDS, CKR_DONE, CKR_GOALS
+};
+// X(field, record, next, prev) in header order.  next: the next_* form (slot t + 1, or the term_* slot behind a done); prev:
+// actions_prev, the actions record one tick back.  (done and goals are their own records: the record is their role.)
+#define CM3_CK_COLUMNS(X)                                                                                                                 \
+  X(grid, CKR_GRID, 0, 0) X(vec, CKR_VEC, 0, 0) X(obs_others, CKR_OBS_OTHERS, 0, 0) X(obs_self_t, CKR_OBS_SELF_T, 0, 0)                   \
+  X(obs_self_v, CKR_OBS_SELF_V, 0, 0) X(actions_prev, CKR_ACTIONS, 0, 1) X(actions, CKR_ACTIONS, 0, 0) X(reward, CKR_REWARD, 0, 0)        \
+  X(local_rewards, CKR_LOCAL_REWARDS, 0, 0) X(next_grid, CKR_GRID, 1, 0) X(next_vec, CKR_VEC, 1, 0) X(next_obs_others, CKR_OBS_OTHERS, 1, 0) \
+  X(next_obs_self_t, CKR_OBS_SELF_T, 1, 0) X(next_obs_self_v, CKR_OBS_SELF_V, 1, 0) X(done, CKR_DONE, 0, 0) X(goals, CKR_GOALS, 0, 0)
+struct CkColumn {
+  const char *name; CkRec rec; bool next, prev;
+  size_t off;           // of the pointer inside cm3_checkers_transition_cols AND cm3_checkers_compact_cols
+};
+#define X(f, rec, next, prev) {#f, rec, next != 0, prev != 0, offsetof(cm3_checkers_transition_cols, f)},
+static const CkColumn kCkColumns[kCkCols] = {CM3_CK_COLUMNS(X)};
+#undef X
+#define X(f, rec, next, prev) && offsetof(cm3_checkers_compact_cols, f) == offsetof(cm3_checkers_transition_cols, f)
+static_assert(sizeof(cm3_checkers_compact_cols) == sizeof(cm3_checkers_transition_cols) CM3_CK_COLUMNS(X) &&
+                  offsetof(cm3_checkers_compact_cols, ring_start) == offsetof(cm3_checkers_transition_cols, ring_start) &&
+                  offsetof(cm3_checkers_compact_cols, ring_size) == offsetof(cm3_checkers_transition_cols, ring_size),
+              "cm3_checkers_compact_cols and cm3_checkers_transition_cols must lay their fields out alike");
+#undef X
+static void *ck_field(const void *cols, const CkColumn &col) {   // the column's pointer in either struct
+  void *p;
+  memcpy(&p, static_cast<const char *>(cols) + col.off, sizeof(p));
+  return p;
+}
+
+// (geometry, record) -> bytes between the env records of a slot, bytes of a dense ring row, the wide export's unit kind and units per row
+struct CkRecord { uint32_t env_stride, row_bytes, kind, upr; };
+static CkRecord ck_record(const CkGeom &g, CkRec rec) {
+  const uint32_t N = g.N;
+  switch (rec) {
+    case CKR_GRID: return {g.grid_stride, g.grid_rec, CKU_I8X2, g.grid_rec / 2};
+    case CKR_VEC: return {16 * N, 16 * N, CKU_I32X2, 2 * N};
+    case CKR_OBS_OTHERS: return {8 * N * g.Lo, 8 * N * g.Lo, CKU_COPY16, N * g.Lo / 2};
+    case CKR_OBS_SELF_T:   // (a row of 75 N doubles at odd N: 8-byte units)
+      return {g.obst_stride, g.obst_rec, (g.obst_rec & 1u) ? CKU_I8 : CKU_I8X2, (g.obst_rec & 1u) ? g.obst_rec : g.obst_rec / 2};
+    case CKR_OBS_SELF_V: return {32 * N, 32 * N, CKU_COPY16, 2 * N};
+    case CKR_ACTIONS: return {4 * N, 4 * N, CKU_COPY4, N};
+    case CKR_REWARD: return {8, 8, CKU_COPY8, 1};
+    case CKR_LOCAL_REWARDS: return {8 * N, 8 * N, CKU_COPY8, N};
+    case CKR_DONE: return {1, 1, CKU_DONE, 1};
+    default: return {N, N, CKU_GOAL, N};   // CKR_GOALS
+  }
+}
+
+// what a launch needs to know of one column (upr / the CKU_* kinds: the wide export; row_bytes / the PK_* kinds: the pack)
 struct CkSpec {
-  const char *name;
-  void *dst;
+  const char *name; void *dst;
   const void *src, *alt;
   size_t slot_stride, alt_stride;
-  uint32_t env_stride, upr, kind, next;
+  uint32_t env_stride, row_bytes, upr, kind, next;
 };
+// (trajectory, record, next) -> where the export and the pack read a column: slot 0 with its slot stride and, for next_*, the term_*
+// array with its own.  Everything else of the spec is the record's; the caller sets the kind where it differs.
+static CkSpec ck_traj_spec(const cm3_checkers_traj *t, const CkColumn &col, const CkRecord &r, void *dst) {
+  CkSpec s = {col.name, dst, nullptr, nullptr, 0, 0, r.env_stride, r.row_bytes, r.upr, r.kind, col.next ? 1u : 0u};
+  auto from = [&](const void *src, size_t stride, const void *alt = nullptr, size_t alt_stride = 0) {
+    s.src = src; s.slot_stride = stride;
+    if (col.next) { s.alt = alt; s.alt_stride = alt_stride; }
+  };
+  switch (col.rec) {
+    case CKR_GRID: from(t->grid, t->grid_slot_stride, t->term_grid, t->term_grid_slot_stride); break;
+    case CKR_VEC: from(t->vec, t->vec_stride, t->term_vec, t->term_vec_stride); break;
+    case CKR_OBS_OTHERS: from(t->obs_others, t->obs_others_stride, t->term_obs_others, t->term_obs_others_stride); break;
+    case CKR_OBS_SELF_T: from(t->obs_self_t, t->obs_self_t_slot_stride, t->term_obs_self_t, t->term_obs_self_t_slot_stride); break;
+    case CKR_OBS_SELF_V: from(t->obs_self_v, t->obs_self_v_stride, t->term_obs_self_v, t->term_obs_self_v_stride); break;
+    case CKR_ACTIONS: from(t->actions, t->actions_stride); break;
+    case CKR_REWARD: from(t->reward, t->reward_stride); break;
+    case CKR_LOCAL_REWARDS: from(t->local_rewards, t->local_rewards_stride); break;
+    case CKR_DONE: from(t->done, t->done_stride); break;
+    default:   // CKR_GOALS: the slot's goal bytes where the trajectory records them, else the live array (stride 0: every tick the same)
+      from(t->goals_slots ? t->goals_slots : t->goals, t->goals_slots ? t->goals_slots_stride : 0);
+  }
+  return s;
+}
+
+// What CkCol and PkCol share, filled from a spec (C = either), behind the check that the column is there ...
+template <typename C> static int ck_col_fill(C &c, const CkSpec &s, bool term, const char *cols_what) {
+  CM3_REQUIRE(s.dst, "%s: column %s is missing", cols_what, s.name);
+  c.src = (const char *)s.src; c.slot_stride = s.slot_stride;
+  c.alt = term ? (const char *)s.alt : nullptr; c.alt_stride = c.alt ? s.alt_stride : 0;
+  c.dst = (char *)s.dst; c.env_stride = s.env_stride; c.kind = s.kind; c.next = s.next;
+  return CM3_OK;
+}
+// ... and, behind the kernel's own alignment checks, the column's workgroups: `work` units (pieces) at per_block of them each
+static int ck_col_blocks(const char *entry, size_t work, size_t per_block, size_t &blocks, uint32_t &blk_end) {
+  blocks += (work + per_block - 1) / per_block;
+  CM3_REQUIRE(blocks < ((size_t)1 << 31), "%s: too many transitions for one launch", entry);
+  blk_end = (uint32_t)blocks;
+  return CM3_OK;
+}
+
+// the ring a column struct names: one that takes the n rows, or (optional) none -- ring_size 0: transition b goes to row b
+static int ring_required(const char *what, int64_t start, int64_t size, int64_t n) {
+  CM3_REQUIRE(size >= 1 && start >= 0 && start < size && n <= size,
+              "%s: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)", what);
+  return CM3_OK;
+}
+static int ring_optional(const char *what, int64_t start, int64_t size, int64_t n) {
+  return size == 0 && start >= 0 ? CM3_OK : ring_required(what, start, size, n);
+}
+
 // One k_ck_transitions_gather launch over the 16 columns of `specs`: `cols_what` / `src_what` name the destination and the source in
 // the error texts.  check_small_copies: the sources of the 8- / 4-byte copy units are checked for the alignment of their loads too (a
 // caller's ring columns; the trajectory export keeps the checks it always had).
@@ -768,19 +867,11 @@ static int ck_gather_launch(const char *entry, const char *cols_what, const char
   bool even = true;
   for (int k = 0; k < kCkCols; ++k) {
     const CkSpec &s = specs[k];
-    CM3_REQUIRE(s.dst, "%s: column %s is missing", cols_what, s.name);
+    CkCol &c = p.col[k];
+    if (int rc = ck_col_fill(c, s, term, cols_what)) return rc;
+    c.upr = s.upr;
     CM3_REQUIRE((uintptr_t)s.dst % ck_dst_bytes(s.kind) == 0, "%s: column %s is not aligned to its %u-byte units", cols_what, s.name,
                 ck_dst_bytes(s.kind));
-    CkCol &c = p.col[k];
-    c.src = (const char *)s.src;
-    c.alt = term ? (const char *)s.alt : nullptr;
-    c.dst = (char *)s.dst;
-    c.slot_stride = s.slot_stride;
-    c.alt_stride = c.alt ? s.alt_stride : 0;
-    c.env_stride = s.env_stride;
-    c.upr = s.upr;
-    c.kind = s.kind;
-    c.next = s.next;
     if (s.kind == CKU_COPY16 || s.kind == CKU_I32X2)
       CM3_REQUIRE(((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride) % (s.kind == CKU_COPY16 ? 16 : 8) == 0,
                   "%s: %s is not aligned to the loads of its units", src_what, s.name);
@@ -790,9 +881,7 @@ static int ck_gather_launch(const char *entry, const char *cols_what, const char
     if (s.kind == CKU_I8X2) even = even && (((uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride | c.env_stride) & 1u) == 0;
     const size_t units = n * s.upr;
     most = units > most ? units : most;
-    blocks += (units + kCkUnitsPerLane * 256 - 1) / (kCkUnitsPerLane * 256);
-    CM3_REQUIRE(blocks < ((size_t)1 << 31), "%s: too many transitions for one launch", entry);
-    p.blk_end[k] = (uint32_t)blocks;
+    if (int rc = ck_col_blocks(entry, units, kCkUnitsPerLane * 256, blocks, p.blk_end[k])) return rc;
   }
   p.done = done;
   p.st_done = st_done;
@@ -927,8 +1016,7 @@ int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle
   p.o_done = out->done;
   p.o_goals = (float *)out->goals;
   p.n = (size_t)n;
-  CM3_REQUIRE(out->ring_size >= 0 && out->ring_start >= 0 && (out->ring_size == 0 || (out->ring_start < out->ring_size && n <= out->ring_size)),
-              "transition columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (int rc = ring_optional("transition columns", out->ring_start, out->ring_size, n)) return rc;
   p.ring_start = (size_t)out->ring_start;
   p.ring_size = (size_t)out->ring_size;
   p.E = (size_t)desc->n_envs;
@@ -951,41 +1039,18 @@ int cm3_checkers_transitions_gather(const cm3_checkers_desc *desc, const cm3_che
   CM3_REQUIRE(out, "checkers_transitions_gather: null out");
   CM3_REQUIRE((tt == nullptr) == (ee == nullptr), "checkers_transitions_gather: tt and ee: both or neither");
   CM3_REQUIRE(n >= 0, "n must be >= 0");
-  CM3_REQUIRE(out->ring_size >= 0 && out->ring_start >= 0 && (out->ring_size == 0 || (out->ring_start < out->ring_size && n <= out->ring_size)),
-              "checkers transition columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (int rc = ring_optional("checkers transition columns", out->ring_start, out->ring_size, n)) return rc;
   if (n == 0) return CM3_OK;      // (before the pointer checks: the columns of an empty batch are null)
   CkGeom geo;
   if (int rc = ck_geometry(desc, true, geo)) return rc;
-  const uint32_t N = geo.N, Lo = geo.Lo, grid_rec = geo.grid_rec, obst_rec = geo.obst_rec, grid_stride = geo.grid_stride,
-                 obst_stride = geo.obst_stride;
   bool term = false;
   if (int rc = ck_traj_check("checkers_transitions_gather", traj, prev0, term)) return rc;
-  const bool obst_odd = (obst_rec & 1u) != 0;   // (a row of 75 N doubles at odd N: 8-byte units)
-  const uint32_t obst_kind = obst_odd ? CKU_I8 : CKU_I8X2, obst_upr = obst_odd ? obst_rec : obst_rec / 2;
-  const CkSpec specs[kCkCols] = {
-      {"grid", out->grid, traj->grid, nullptr, traj->grid_slot_stride, 0, grid_stride, grid_rec / 2, CKU_I8X2, 0},
-      {"vec", out->vec, traj->vec, nullptr, traj->vec_stride, 0, 16 * N, 2 * N, CKU_I32X2, 0},
-      {"obs_others", out->obs_others, traj->obs_others, nullptr, traj->obs_others_stride, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
-      {"obs_self_t", out->obs_self_t, traj->obs_self_t, nullptr, traj->obs_self_t_slot_stride, 0, obst_stride, obst_upr, obst_kind, 0},
-      {"obs_self_v", out->obs_self_v, traj->obs_self_v, nullptr, traj->obs_self_v_stride, 0, 32 * N, 2 * N, CKU_COPY16, 0},
-      {"actions_prev", out->actions_prev, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, N, CKU_PREV, 0},
-      {"actions", out->actions, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, N, CKU_COPY4, 0},
-      {"reward", out->reward, traj->reward, nullptr, traj->reward_stride, 0, 8, 1, CKU_COPY8, 0},
-      {"local_rewards", out->local_rewards, traj->local_rewards, nullptr, traj->local_rewards_stride, 0, 8 * N, N, CKU_COPY8, 0},
-      {"next_grid", out->next_grid, traj->grid, traj->term_grid, traj->grid_slot_stride, traj->term_grid_slot_stride, grid_stride,
-       grid_rec / 2, CKU_I8X2, 1},
-      {"next_vec", out->next_vec, traj->vec, traj->term_vec, traj->vec_stride, traj->term_vec_stride, 16 * N, 2 * N, CKU_I32X2, 1},
-      {"next_obs_others", out->next_obs_others, traj->obs_others, traj->term_obs_others, traj->obs_others_stride,
-       traj->term_obs_others_stride, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 1},
-      {"next_obs_self_t", out->next_obs_self_t, traj->obs_self_t, traj->term_obs_self_t, traj->obs_self_t_slot_stride,
-       traj->term_obs_self_t_slot_stride, obst_stride, obst_upr, obst_kind, 1},
-      {"next_obs_self_v", out->next_obs_self_v, traj->obs_self_v, traj->term_obs_self_v, traj->obs_self_v_stride,
-       traj->term_obs_self_v_stride, 32 * N, 2 * N, CKU_COPY16, 1},
-      {"done", out->done, traj->done, nullptr, traj->done_stride, 0, 1, 1, CKU_DONE, 0},
-      // goals: the slot's goal bytes where the trajectory records them, else the live array (stride 0: the same bytes for every tick)
-      {"goals", out->goals, traj->goals_slots ? traj->goals_slots : traj->goals, nullptr,
-       traj->goals_slots ? traj->goals_slots_stride : 0, 0, N, N, CKU_GOAL, 0},
-  };
+  CkSpec specs[kCkCols];
+  for (int k = 0; k < kCkCols; ++k) {
+    const CkColumn &col = kCkColumns[k];
+    specs[k] = ck_traj_spec(traj, col, ck_record(geo, col.rec), ck_field(out, col));
+    if (col.prev) specs[k].kind = CKU_PREV;
+  }
   return ck_gather_launch("checkers_transitions_gather", "checkers transition columns", "checkers trajectory", false, specs, term, traj->done, traj->done_stride, prev0, tt, ee,
                           (size_t)n, (size_t)desc->n_envs, out->ring_start, out->ring_size, (hipStream_t)stream);
 }
@@ -997,71 +1062,37 @@ int cm3_checkers_transitions_pack(const cm3_checkers_desc *desc, const cm3_check
   CM3_REQUIRE(traj, "checkers_transitions_pack: null traj");
   CM3_REQUIRE(out, "checkers_transitions_pack: null compact columns");
   CM3_REQUIRE(n >= 0, "n must be >= 0");
-  CM3_REQUIRE(out->ring_size >= 1 && out->ring_start >= 0 && out->ring_start < out->ring_size && n <= out->ring_size,
-              "compact checkers columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (int rc = ring_required("compact checkers columns", out->ring_start, out->ring_size, n)) return rc;
   if (n == 0) return CM3_OK;      // (before the pointer checks: nothing is touched)
   CkGeom geo;
   if (int rc = ck_geometry(desc, true, geo)) return rc;
-  const uint32_t N = geo.N, Lo = geo.Lo;
   bool term = false;
   if (int rc = ck_traj_check("checkers_transitions_pack", traj, prev0, term)) return rc;
-  // (CkSpec.upr holds the BYTES of a ring row here)
-  const CkSpec specs[kCkCols] = {
-      {"grid", out->grid, traj->grid, nullptr, traj->grid_slot_stride, 0, geo.grid_stride, geo.grid_rec, PK_COPY, 0},
-      {"vec", out->vec, traj->vec, nullptr, traj->vec_stride, 0, 16 * N, 16 * N, PK_COPY, 0},
-      {"obs_others", out->obs_others, traj->obs_others, nullptr, traj->obs_others_stride, 0, 8 * N * Lo, 8 * N * Lo, PK_COPY, 0},
-      {"obs_self_t", out->obs_self_t, traj->obs_self_t, nullptr, traj->obs_self_t_slot_stride, 0, geo.obst_stride, geo.obst_rec, PK_COPY, 0},
-      {"obs_self_v", out->obs_self_v, traj->obs_self_v, nullptr, traj->obs_self_v_stride, 0, 32 * N, 32 * N, PK_COPY, 0},
-      {"actions_prev", out->actions_prev, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, 4 * N, PK_PREV, 0},
-      {"actions", out->actions, traj->actions, nullptr, traj->actions_stride, 0, 4 * N, 4 * N, PK_COPY, 0},
-      {"reward", out->reward, traj->reward, nullptr, traj->reward_stride, 0, 8, 8, PK_COPY, 0},
-      {"local_rewards", out->local_rewards, traj->local_rewards, nullptr, traj->local_rewards_stride, 0, 8 * N, 8 * N, PK_COPY, 0},
-      {"next_grid", out->next_grid, traj->grid, traj->term_grid, traj->grid_slot_stride, traj->term_grid_slot_stride, geo.grid_stride,
-       geo.grid_rec, PK_COPY, 1},
-      {"next_vec", out->next_vec, traj->vec, traj->term_vec, traj->vec_stride, traj->term_vec_stride, 16 * N, 16 * N, PK_COPY, 1},
-      {"next_obs_others", out->next_obs_others, traj->obs_others, traj->term_obs_others, traj->obs_others_stride,
-       traj->term_obs_others_stride, 8 * N * Lo, 8 * N * Lo, PK_COPY, 1},
-      {"next_obs_self_t", out->next_obs_self_t, traj->obs_self_t, traj->term_obs_self_t, traj->obs_self_t_slot_stride,
-       traj->term_obs_self_t_slot_stride, geo.obst_stride, geo.obst_rec, PK_COPY, 1},
-      {"next_obs_self_v", out->next_obs_self_v, traj->obs_self_v, traj->term_obs_self_v, traj->obs_self_v_stride,
-       traj->term_obs_self_v_stride, 32 * N, 32 * N, PK_COPY, 1},
-      {"done", out->done, traj->done, nullptr, traj->done_stride, 0, 1, 1, PK_DONE, 0},
-      {"goals", out->goals, traj->goals_slots ? traj->goals_slots : traj->goals, nullptr,
-       traj->goals_slots ? traj->goals_slots_stride : 0, 0, N, N, PK_COPY, 0},
-  };
   PkParams p;
   memset(&p, 0, sizeof(p));
   const size_t start = (size_t)out->ring_start, size = (size_t)out->ring_size;
   const size_t rows_a = start + (size_t)n <= size ? (size_t)n : size - start, rows_b = (size_t)n - rows_a;   // before / past the wrap
   size_t blocks = 0, most = 0;
   for (int k = 0; k < kCkCols; ++k) {
-    const CkSpec &s = specs[k];
-    CM3_REQUIRE(s.dst, "compact checkers columns: column %s is missing", s.name);
+    const CkColumn &col = kCkColumns[k];
+    CkSpec s = ck_traj_spec(traj, col, ck_record(geo, col.rec), ck_field(out, col));
+    s.kind = col.prev ? PK_PREV : col.rec == CKR_DONE ? PK_DONE : PK_COPY;
+    PkCol &c = p.col[k];
+    if (int rc = ck_col_fill(c, s, term, "compact checkers columns")) return rc;
     CM3_REQUIRE((uintptr_t)s.dst % 16 == 0, "compact checkers columns: column %s is not aligned to the 16-byte pieces the kernel stores",
                 s.name);
-    PkCol &c = p.col[k];
-    c.src = (const char *)s.src;
-    c.alt = term ? (const char *)s.alt : nullptr;
-    c.dst = (char *)s.dst;
-    c.slot_stride = s.slot_stride;
-    c.alt_stride = c.alt ? s.alt_stride : 0;
-    c.env_stride = s.env_stride;
-    c.rb = s.upr;
-    c.kind = s.kind;
-    c.next = s.next;
-    c.lo_a = start * s.upr;
-    c.hi_a = (start + rows_a) * s.upr;
-    c.hi_b = rows_b * s.upr;
+    c.rb = s.row_bytes;
+    c.lo_a = start * s.row_bytes;
+    c.hi_a = (start + rows_a) * s.row_bytes;
+    c.hi_b = rows_b * s.row_bytes;
     // the granule: what divides the row, every stride and every base (a granule is one naturally aligned load inside one row)
     uintptr_t a = (uintptr_t)c.src | (uintptr_t)c.alt | c.slot_stride | c.alt_stride | c.env_stride | c.rb;
     if (s.kind == PK_PREV) a |= (uintptr_t)prev0;
     c.gran = a % 16 == 0 ? 16u : a % 8 == 0 ? 8u : a % 4 == 0 ? 4u : a % 2 == 0 ? 2u : 1u;
     const size_t pieces = (c.hi_a + 15) / 16 - c.lo_a / 16 + (c.hi_b + 15) / 16;
-    const size_t bytes = size * s.upr;
+    const size_t bytes = size * s.row_bytes;
     most = bytes > most ? bytes : most;
-    blocks += (pieces + kPkPiecesPerLane * 256 - 1) / (kPkPiecesPerLane * 256);
-    CM3_REQUIRE(blocks < ((size_t)1 << 31), "checkers_transitions_pack: too many transitions for one launch");
-    p.blk_end[k] = (uint32_t)blocks;
+    if (int rc = ck_col_blocks("checkers_transitions_pack", pieces, kPkPiecesPerLane * 256, blocks, p.blk_end[k])) return rc;
   }
   p.done = traj->done;
   p.st_done = traj->done_stride;
@@ -1086,43 +1117,21 @@ int cm3_checkers_ring_expand(const cm3_checkers_desc *desc, const cm3_checkers_c
   CM3_REQUIRE(ring, "checkers_ring_expand: null compact columns");
   CM3_REQUIRE(out, "checkers_ring_expand: null out");
   CM3_REQUIRE(n >= 0, "n must be >= 0");
-  CM3_REQUIRE(ring->ring_size >= 1 && ring->ring_start >= 0 && ring->ring_start < ring->ring_size && n <= ring->ring_size,
-              "compact checkers columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
-  CM3_REQUIRE(out->ring_size >= 0 && out->ring_start >= 0 && (out->ring_size == 0 || (out->ring_start < out->ring_size && n <= out->ring_size)),
-              "checkers transition columns: ring_start / ring_size out of range (0 <= ring_start < ring_size, n <= ring_size)");
+  if (int rc = ring_required("compact checkers columns", ring->ring_start, ring->ring_size, n)) return rc;
+  if (int rc = ring_optional("checkers transition columns", out->ring_start, out->ring_size, n)) return rc;
   if (n == 0) return CM3_OK;      // (before the pointer checks: the columns of an empty batch are null)
   CkGeom geo;
   if (int rc = ck_geometry(desc, false, geo)) return rc;
-  const uint32_t N = geo.N, Lo = geo.Lo, grid_rec = geo.grid_rec, obst_rec = geo.obst_rec;
-  const bool obst_odd = (obst_rec & 1u) != 0;
-  const uint32_t obst_kind = obst_odd ? CKU_I8 : CKU_I8X2, obst_upr = obst_odd ? obst_rec : obst_rec / 2;
-  const struct { const char *name; const void *p; } have[kCkCols] = {
-      {"grid", ring->grid}, {"vec", ring->vec}, {"obs_others", ring->obs_others}, {"obs_self_t", ring->obs_self_t},
-      {"obs_self_v", ring->obs_self_v}, {"actions_prev", ring->actions_prev}, {"actions", ring->actions}, {"reward", ring->reward},
-      {"local_rewards", ring->local_rewards}, {"next_grid", ring->next_grid}, {"next_vec", ring->next_vec},
-      {"next_obs_others", ring->next_obs_others}, {"next_obs_self_t", ring->next_obs_self_t}, {"next_obs_self_v", ring->next_obs_self_v},
-      {"done", ring->done}, {"goals", ring->goals}};
-  for (int k = 0; k < kCkCols; ++k) CM3_REQUIRE(have[k].p, "compact checkers columns: column %s is missing", have[k].name);
   // the unit kinds of the export with ONE slot (stride 0) of dense ring rows as their source: row index[b] is the "env", the
   // actions_prev and done a row holds are final (plain copies -- CKU_DONE reads p.done, here the ring's own column)
-  const CkSpec specs[kCkCols] = {
-      {"grid", out->grid, ring->grid, nullptr, 0, 0, grid_rec, grid_rec / 2, CKU_I8X2, 0},
-      {"vec", out->vec, ring->vec, nullptr, 0, 0, 16 * N, 2 * N, CKU_I32X2, 0},
-      {"obs_others", out->obs_others, ring->obs_others, nullptr, 0, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
-      {"obs_self_t", out->obs_self_t, ring->obs_self_t, nullptr, 0, 0, obst_rec, obst_upr, obst_kind, 0},
-      {"obs_self_v", out->obs_self_v, ring->obs_self_v, nullptr, 0, 0, 32 * N, 2 * N, CKU_COPY16, 0},
-      {"actions_prev", out->actions_prev, ring->actions_prev, nullptr, 0, 0, 4 * N, N, CKU_COPY4, 0},
-      {"actions", out->actions, ring->actions, nullptr, 0, 0, 4 * N, N, CKU_COPY4, 0},
-      {"reward", out->reward, ring->reward, nullptr, 0, 0, 8, 1, CKU_COPY8, 0},
-      {"local_rewards", out->local_rewards, ring->local_rewards, nullptr, 0, 0, 8 * N, N, CKU_COPY8, 0},
-      {"next_grid", out->next_grid, ring->next_grid, nullptr, 0, 0, grid_rec, grid_rec / 2, CKU_I8X2, 0},
-      {"next_vec", out->next_vec, ring->next_vec, nullptr, 0, 0, 16 * N, 2 * N, CKU_I32X2, 0},
-      {"next_obs_others", out->next_obs_others, ring->next_obs_others, nullptr, 0, 0, 8 * N * Lo, N * Lo / 2, CKU_COPY16, 0},
-      {"next_obs_self_t", out->next_obs_self_t, ring->next_obs_self_t, nullptr, 0, 0, obst_rec, obst_upr, obst_kind, 0},
-      {"next_obs_self_v", out->next_obs_self_v, ring->next_obs_self_v, nullptr, 0, 0, 32 * N, 2 * N, CKU_COPY16, 0},
-      {"done", out->done, ring->done, nullptr, 0, 0, 1, 1, CKU_DONE, 0},
-      {"goals", out->goals, ring->goals, nullptr, 0, 0, N, N, CKU_GOAL, 0},
-  };
+  CkSpec specs[kCkCols];
+  for (int k = 0; k < kCkCols; ++k) {
+    const CkColumn &col = kCkColumns[k];
+    const CkRecord r = ck_record(geo, col.rec);
+    const void *src = ck_field(ring, col);
+    CM3_REQUIRE(src, "compact checkers columns: column %s is missing", col.name);
+    specs[k] = {col.name, ck_field(out, col), src, nullptr, 0, 0, r.row_bytes, r.row_bytes, r.upr, r.kind, 0};
+  }
   // index NULL: rows 0 .. n - 1 -- the whole-trajectory order b = t E + e with E = n is tick 0, env b
   return ck_gather_launch("checkers_ring_expand", "checkers transition columns", "compact checkers columns", true, specs, false, ring->done, 0, nullptr, nullptr, index,
                           (size_t)n, (size_t)n, out->ring_start, out->ring_size, (hipStream_t)stream);

@@ -8,10 +8,13 @@ Transitions are the columns ParticleRollout / CheckersRollout export (numpy=Fals
 column; adding a whole vectorised rollout is ONE launch (cm3_rows_scatter, or the export kernels of csrc/batch.hip writing ring rows),
 sampling is one gather launch.
 """
+import ctypes
+
 import torch
 
 from . import _lib
 from ._lib import Cm3Error
+from .rollout import CHECKERS_ORDER, check_columns, compact_specs, sample_distinct
 
 
 class RingIndex(object):
@@ -49,11 +52,9 @@ def dual_take(n1, n2, size):
     return half, False, half, False
 
 
-class DeviceReplayBuffer(object):
-    """replay_buffer.Replay_Buffer on the device: capacity `size` transitions, overwrite oldest when full
-    (replay_buffer.py:11-16), sample_batch(size) = everything if len <= size else `size` distinct uniformly
-    (:28-37).  One tensor per column; `add` is ONE launch for all columns (cm3_rows_scatter onto the ring positions),
-    sampling ONE launch (cm3_rows_gather).  There is no host path: the buffer lives on an AMD GPU."""
+class _Ring(object):
+    """What the replay rings share: the ring index with its maxsize / idx / len surface, the stream, and the draw of sample_batch
+    (replay_buffer.py:28-37)."""
 
     def __init__(self, size=int(1e6), device="cuda:0"):
         self.device = _lib.require_gpu(device)
@@ -69,6 +70,20 @@ class DeviceReplayBuffer(object):
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _draw(self, n, generator, everything=False):
+        """int64 [min(n, len)] distinct stored rows, uniformly at random; everything=True (sample_batch): None where len <= n --
+        all of them, in storage order."""
+        if everything and self.len <= n:
+            return None
+        return sample_distinct(self.len, min(int(n), self.len), 1, generator, self.device)[0].to(torch.int64).contiguous()
+
+
+class DeviceReplayBuffer(_Ring):
+    """replay_buffer.Replay_Buffer on the device: capacity `size` transitions, overwrite oldest when full
+    (replay_buffer.py:11-16), sample_batch(size) = everything if len <= size else `size` distinct uniformly
+    (:28-37).  One tensor per column; `add` is ONE launch for all columns (cm3_rows_scatter onto the ring positions),
+    sampling ONE launch (cm3_rows_gather).  There is no host path: the buffer lives on an AMD GPU."""
 
     def _alloc(self, cols):
         if self.cols is None:
@@ -132,19 +147,18 @@ class DeviceReplayBuffer(object):
         return {k: v[:self.len] for k, v in self.cols.items()}
 
     def sample_batch(self, size, generator=None):
-        if self.len <= size:
+        index = self._draw(size, generator, everything=True)
+        if index is None:
             # a COPY: all() hands out views of the ring, which the next add() overwrites in place -- the reference's
             # np.array(self.memory) is a copy, and a learner may still hold the batch when the next chunk is added
             return {k: v.clone() for k, v in self.all().items()}
-        return self.sample_n(size, generator)
+        return self._take(index)
 
     def sample_n(self, n, generator=None):
-        from .rollout import sample_distinct
-        n = min(int(n), self.len)
-        return self._take(sample_distinct(self.len, n, 1, generator, self.device)[0])
+        return self._take(self._draw(n, generator))
 
 
-class CompactCheckersReplayBuffer(object):
+class CompactCheckersReplayBuffer(_Ring):
     """replay_buffer.Replay_Buffer for Checkers transitions with NARROW storage: the ring keeps every column with the dtype the
     trajectory keeps (grid / obs_self_t int8, vec int32, goals the uint8 goal index: 707 B per transition at the reference geometry
     where DeviceReplayBuffer's float64 columns take 3657 B) and only the rows a learner samples are widened.  The surface and the
@@ -157,25 +171,12 @@ class CompactCheckersReplayBuffer(object):
     columns."""
 
     def __init__(self, size=int(1e6), device="cuda:0"):
-        self.device = _lib.require_gpu(device)
-        self.ring = RingIndex(size)
-        self.cols = None
+        super().__init__(size, device)
         self._wide = None        # name -> (row shape, dtype) of the columns sample_batch returns
         self._desc = None
 
-    maxsize = property(lambda self: self.ring.maxsize)
-    idx = property(lambda self: self.ring.idx)
-    len = property(lambda self: self.ring.len)
-
-    def __len__(self):
-        return self.ring.len
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _layout(self, wide):
         """wide: name -> (row shape, dtype) of the reference columns.  Fixes the geometry on first use; later it must agree."""
-        from .rollout import CHECKERS_ORDER
         wide = {k: (tuple(shape), dt) for k, (shape, dt) in wide.items()}
         if self._wide is not None:
             if wide != self._wide:
@@ -191,7 +192,6 @@ class CompactCheckersReplayBuffer(object):
         self._wide, self._desc = wide, d
 
     def _ring(self):
-        from .rollout import compact_specs
         if self.cols is None:
             return {k: torch.zeros((self.maxsize,) + shape, dtype=dt, device=self.device) for k, (shape, dt) in compact_specs(self._wide).items()}
         return self.cols
@@ -216,7 +216,6 @@ class CompactCheckersReplayBuffer(object):
         """cols: the WIDE reference columns (what as_reference_batch(numpy=False) returns), B transitions in order.  They are narrowed
         here; a value that does not survive -- a grid / obs_self_t entry that is no int8, a vec entry that is no int32, goals that are
         not one-hot -- raises Cm3Error and leaves the ring as it was."""
-        from .rollout import CHECKERS_ORDER, compact_specs
         if set(cols) != set(CHECKERS_ORDER):
             raise Cm3Error("a compact Checkers ring takes the 16 columns of CheckersRollout.ORDER, got %s" % (sorted(cols),))
         wide = {k: cols[k].to(self.device) for k in CHECKERS_ORDER}
@@ -249,10 +248,9 @@ class CompactCheckersReplayBuffer(object):
         self.cols = ring
         assert self.ring.plan_add(B) == (skip, start, kept)
 
-    def _expand(self, index, n, out, what):
-        """Rows index[b] (None: 0 .. n - 1) of the ring as the 16 reference columns: ONE launch of cm3_checkers_ring_expand."""
-        import ctypes
-        from .rollout import check_columns
+    def _expand(self, index, out, what):
+        """Rows index[b] (None: everything stored) of the ring as the 16 reference columns: ONE launch of cm3_checkers_ring_expand."""
+        n = self.len if index is None else index.numel()
         if self.cols is None:
             raise Cm3Error("%s: the replay buffer is empty" % what)
         if out is None:
@@ -261,11 +259,8 @@ class CompactCheckersReplayBuffer(object):
             check_columns(self._wide, out, n, self.device, "%s(out=...): pass the dict an earlier call returned for %d transitions" % (what, n))
             out = {k: out[k] for k in self._wide}
         if n:
-            src, dst = _lib.CheckersCompactCols(), _lib.CheckersTransitionCols()
-            for name in self._wide:
-                setattr(src, name, self.cols[name].data_ptr())
-                setattr(dst, name, out[name].data_ptr())
-            src.ring_start, src.ring_size = 0, self.maxsize
+            src = _lib.fill_checkers_cols(_lib.CheckersCompactCols(), self.cols, 0, self.maxsize)
+            dst = _lib.fill_checkers_cols(_lib.CheckersTransitionCols(), out)
             _lib.check(_lib.lib().cm3_checkers_ring_expand(ctypes.byref(self._desc), ctypes.byref(src), _lib.ptr(index), int(n),
                                                            ctypes.byref(dst), self._stream()))
         return out
@@ -273,21 +268,17 @@ class CompactCheckersReplayBuffer(object):
     def all(self):
         """Everything stored, in storage order, as the reference columns: a COPY by nature (the rows are widened) -- unlike
         DeviceReplayBuffer.all(), whose views the next add overwrites."""
-        return self._expand(None, self.len, None, "all")
+        return self._expand(None, None, "all")
 
     def sample_batch(self, size, generator=None, out=None):
         """DeviceReplayBuffer.sample_batch: everything in storage order if len <= size, else `size` distinct rows uniformly (the
         same draws for the same len and generator state).  Fresh tensors, or with out= (a dict an earlier call returned for the same
         row count) those tensors written again: the persistent addresses a captured graph of the consumer needs."""
-        if self.len <= size:
-            return self._expand(None, self.len, out, "sample_batch")
-        return self.sample_n(size, generator, out)
+        index = self._draw(size, generator, everything=True)
+        return self._expand(index, out, "sample_batch" if index is None else "sample_n")
 
     def sample_n(self, n, generator=None, out=None):
-        from .rollout import sample_distinct
-        n = min(int(n), self.len)
-        index = sample_distinct(self.len, n, 1, generator, self.device)[0].to(torch.int64).contiguous()
-        return self._expand(index, n, out, "sample_n")
+        return self._expand(self._draw(n, generator), out, "sample_n")
 
 
 def _cat(a, b):

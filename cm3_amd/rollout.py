@@ -50,9 +50,12 @@ def _is_device_policy(policy):
 
 PARTICLE_ORDER = ("v_global", "obs_others", "v_local", "actions", "reward", "reward_local", "v_global_next",
                   "obs_others_next", "v_local_next", "done", "goals")
-CHECKERS_ORDER = ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "actions_prev", "actions", "reward",
-                  "local_rewards", "next_grid", "next_vec", "next_obs_others", "next_obs_self_t",
-                  "next_obs_self_v", "done", "goals")
+CHECKERS_ORDER = _lib.CHECKERS_COLUMNS
+# Checkers record -> (wide dtype: the reference's columns, trajectory dtype: what the trajectory and a compact ring keep); the goals
+# record is the uint8 goal index, its wide form the one-hot int64 pair (one more dimension of 2)
+_F64, _I32 = (torch.float64,) * 2, (torch.int32,) * 2
+CHECKERS_DTYPES = dict(grid=(torch.float64, torch.int8), vec=(torch.float64, torch.int32), obs_others=_F64, obs_self_t=(torch.float64, torch.int8),
+                       obs_self_v=_F64, actions=_I32, reward=_F64, local_rewards=_F64, done=(torch.bool,) * 2, goals=(torch.int64, torch.uint8))
 
 
 def _valid_from_done(done_u8, finished0=None):
@@ -190,17 +193,11 @@ def check_columns(specs, columns, rows, device, what):
 def compact_specs(specs):
     """The compact form of the Checkers column specs (name -> (row shape, dtype)): every column with the dtype the trajectory keeps --
     grid / obs_self_t int8, vec int32, goals the uint8 goal index instead of the one-hot int64 pair -- the others as they are."""
+    record = dict(_lib.CHECKERS_COLUMN_RECORDS)
     out = {}
     for name, (shape, dt) in specs.items():
-        base = name[5:] if name.startswith("next_") else name
-        if base in ("grid", "obs_self_t"):
-            out[name] = (shape, torch.int8)
-        elif base == "vec":
-            out[name] = (shape, torch.int32)
-        elif base == "goals":
-            out[name] = (shape[:-1], torch.uint8)
-        else:
-            out[name] = (shape, dt)
+        wide, kept = CHECKERS_DTYPES[record[name]]
+        out[name] = (shape[:-1] if record[name] == "goals" else shape, dt if wide == kept else kept)
     return out
 
 
@@ -283,18 +280,23 @@ class _Transitions(object):
         self._gather(None if everything else tt, None if everything else ee, B, cols)
         return _to_numpy(cols) if numpy else cols
 
+    def _ring_chunk(self, what, columns, ring_start, ring_size, specs=None):
+        """What export_into and CheckersRollout.pack_into (`what`: the one called) check before their launch: a continuous collection,
+        a ring that takes its T * E transitions, every column.  Returns the number of transitions."""
+        if not (self.auto_reset and self.kernel_export):
+            raise Cm3Error("%s needs a continuous collection (every transition valid) that the export kernel reads" % what)
+        B, ring_start, ring_size = self.T * self.env.E, int(ring_start), int(ring_size)
+        if not (0 <= ring_start < ring_size and B <= ring_size):
+            raise Cm3Error("%s: ring of %d rows from row %d does not take %d transitions" % (what, ring_size, ring_start, B))
+        self._check_columns(columns, ring_size, what, specs)
+        return B
+
     def export_into(self, columns, ring_start, ring_size):
         """Every transition of the trajectory (continuous collection the export kernel applies to) written straight into the rows
         (ring_start + b) mod ring_size of `columns` -- a dict with the tensors of as_reference_batch(numpy=False), each with ring_size
         rows: export and replay add in ONE launch (DeviceReplayBuffer.add_rollout).  Every column is checked before the launch.
         Returns the number of transitions."""
-        if not (self.auto_reset and self.kernel_export):
-            raise Cm3Error("export_into needs a continuous collection (every transition valid) that the export kernel reads")
-        ring_start, ring_size = int(ring_start), int(ring_size)
-        B = self.T * self.env.E
-        if not (0 <= ring_start < ring_size and B <= ring_size):
-            raise Cm3Error("export_into: ring of %d rows from row %d does not take %d transitions" % (ring_size, ring_start, B))
-        self._check_columns(columns, ring_size, "export_into")
+        B = self._ring_chunk("export_into", columns, ring_start, ring_size)
         self._gather(None, None, B, columns, ring_start, ring_size)
         return B
 
@@ -1253,54 +1255,35 @@ class CheckersRollout(_Transitions):
     def column_specs(self):
         """name -> (row shape, dtype) of the 16 columns of as_reference_batch(numpy=False), in ORDER."""
         env = self.env
-        N, f64, i32 = env.n, torch.float64, torch.int32
-        obs = dict(grid=((env.R, env.C + 1, 2), f64), vec=((N, 4), f64), obs_others=((N, env.Lo), f64),
-                   obs_self_t=((N, env.K, env.K, 3), f64), obs_self_v=((N, 4), f64))
-        specs = dict(obs, actions_prev=((N,), i32), actions=((N,), i32), reward=((), f64), local_rewards=((N,), f64),
-                     done=((), torch.bool), goals=((N, 2), torch.int64))
-        specs.update({"next_" + k: v for k, v in obs.items()})
-        return {name: specs[name] for name in self.ORDER}
-
-    def _gather(self, tt, ee, B, columns, ring_start=0, ring_size=0):
-        """ONE launch of cm3_checkers_transitions_gather (csrc/batch.hip) fills all of `columns` (checked by the caller); integer-valued
-        columns are cast to the reference's float64 (alg_credit_checkers.py:427-444).  as_reference_batch_torch below is the same as a
-        composition of torch operations, ~40 launches: what the kernel is tested against."""
-        env = self.env
-        if self._gather_traj is None:
-            self._gather_traj = self._traj()           # (the trajectory buffers never move)
-        out = _lib.CheckersTransitionCols()
-        for name in self.ORDER:
-            setattr(out, name, columns[name].data_ptr())
-        out.ring_start, out.ring_size = int(ring_start), int(ring_size)
-        _lib.check(self._lib.cm3_checkers_transitions_gather(ctypes.byref(env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr(),
-                                                             _lib.ptr(tt), _lib.ptr(ee), int(B), ctypes.byref(out), env._stream()))
+        N = env.n
+        shapes = dict(grid=(env.R, env.C + 1, 2), vec=(N, 4), obs_others=(N, env.Lo), obs_self_t=(N, env.K, env.K, 3), obs_self_v=(N, 4),
+                      actions=(N,), reward=(), local_rewards=(N,), done=(), goals=(N, 2))
+        return {name: (shapes[rec], CHECKERS_DTYPES[rec][0]) for name, rec in _lib.CHECKERS_COLUMN_RECORDS}
 
     def compact_column_specs(self):
         """name -> (row shape, dtype) of the 16 columns of a compact replay ring (replay.CompactCheckersReplayBuffer), in ORDER: the
         columns of column_specs() with the dtypes the trajectory keeps (707 B per transition at the reference geometry, not 3657)."""
         return compact_specs(self.column_specs())
 
-    def pack_into(self, columns, ring_start, ring_size):
-        """Every transition of the trajectory (continuous collection the export kernel applies to) written into the rows
-        (ring_start + b) mod ring_size of the compact `columns` (compact_column_specs(), ring_size rows each): ONE launch of
-        cm3_checkers_transitions_pack, nothing converted.  Every column is checked before the launch.  Returns the number of
-        transitions."""
-        if not (self.auto_reset and self.kernel_export):
-            raise Cm3Error("pack_into needs a continuous collection (every transition valid) that the export kernel reads")
-        ring_start, ring_size = int(ring_start), int(ring_size)
-        B = self.T * self.env.E
-        if not (0 <= ring_start < ring_size and B <= ring_size):
-            raise Cm3Error("pack_into: ring of %d rows from row %d does not take %d transitions" % (ring_size, ring_start, B))
-        self._check_columns(columns, ring_size, "pack_into", self.compact_column_specs())
-        env = self.env
+    def _export_args(self):
         if self._gather_traj is None:
-            self._gather_traj = self._traj()           # (the trajectory buffers never move)
-        out = _lib.CheckersCompactCols()
-        for name in self.ORDER:
-            setattr(out, name, columns[name].data_ptr())
-        out.ring_start, out.ring_size = ring_start, ring_size
-        _lib.check(self._lib.cm3_checkers_transitions_pack(ctypes.byref(env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr(),
-                                                           B, ctypes.byref(out), env._stream()))
+            self._gather_traj = self._traj()           # (built once: the trajectory buffers never move)
+        return ctypes.byref(self.env._desc), ctypes.byref(self._gather_traj), self.prev0.data_ptr()
+
+    def _gather(self, tt, ee, B, columns, ring_start=0, ring_size=0):
+        """ONE launch of cm3_checkers_transitions_gather (csrc/batch.hip) fills all of `columns` (checked by the caller); integer-valued
+        columns are cast to the reference's float64 (alg_credit_checkers.py:427-444).  as_reference_batch_torch below is the same as a
+        composition of torch operations, ~40 launches: what the kernel is tested against."""
+        out = _lib.fill_checkers_cols(_lib.CheckersTransitionCols(), columns, ring_start, ring_size)
+        _lib.check(self._lib.cm3_checkers_transitions_gather(*self._export_args(), _lib.ptr(tt), _lib.ptr(ee), int(B), ctypes.byref(out),
+                                                             self.env._stream()))
+
+    def pack_into(self, columns, ring_start, ring_size):
+        """export_into for a compact ring: `columns` are those of compact_column_specs(), ring_size rows each.  ONE launch of
+        cm3_checkers_transitions_pack, nothing converted; the same checks before it.  Returns the number of transitions."""
+        B = self._ring_chunk("pack_into", columns, ring_start, ring_size, self.compact_column_specs())
+        out = _lib.fill_checkers_cols(_lib.CheckersCompactCols(), columns, ring_start, ring_size)
+        _lib.check(self._lib.cm3_checkers_transitions_pack(*self._export_args(), B, ctypes.byref(out), self.env._stream()))
         return B
 
     def as_reference_batch_torch(self, tt, ee, numpy=True):
