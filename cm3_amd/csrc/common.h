@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/cm3_amd.h"
+#include "xcd_grid.h"
 
 // Timeline instrumentation for the diagnostic probes under tools/probes only (never defined in the product build).
 #ifdef CM3_STAMPS
@@ -39,21 +40,12 @@ extern __device__ long long *cm3_stamp_buf;
 // G = ceil(blocks / 8) -- every XCD gets work whatever the count (a 256-tile with 128 or 192 blocks would leave XCDs idle: measured
 // +11 .. 18 % on such launches).  The mode travels in the top byte of `flags`: 0 plain order, 1 .. 32 = G of an eighths launch,
 // kXcdTiles = tiles of 256.
-constexpr uint32_t kFlagXcdShift = 24, kXcdTiles = 63u;   // internal launch flag bits
+// (the two constants and the host side -- cm3_xcd_flags(), cm3_xcd_grid() -- live in xcd_grid.h, included above)
 __device__ __forceinline__ uint32_t cm3_xcd_block(uint32_t flags) {
   const uint32_t b = blockIdx.x, v = flags >> kFlagXcdShift;
   const uint32_t tiled = (b & ~255u) | ((b & 7u) << 5) | ((b >> 3) & 31u);
   const uint32_t eighth = (b & 7u) * v + (b >> 3);
   return v == 0u ? b : (v == kXcdTiles ? tiled : eighth);
-}
-// host: the flag bits and the grid for a launch of `blocks` workgroups
-static inline uint32_t cm3_xcd_flags(unsigned blocks) {
-  if (blocks < 64u) return 0u;
-  return (blocks <= 256u ? (blocks + 7u) / 8u : kXcdTiles) << kFlagXcdShift;
-}
-static inline unsigned cm3_xcd_grid(unsigned blocks) {
-  const uint32_t v = cm3_xcd_flags(blocks) >> kFlagXcdShift;
-  return v == 0u ? blocks : (v == kXcdTiles ? (blocks + 255u) / 256u * 256u : 8u * v);
 }
 
 // Kernel-span instrumentation (build variant -DCM3_SPAN_STAMPS -> libcm3_hip_span.so; never defined in the product build):

@@ -16,8 +16,10 @@
 // Arithmetic follows the reference's operation order exactly (compile with -ffp-contract=off):
 // the double instantiation differs from NumPy only in the last ulps of exp/log1p.
 #include "common.h"
+#include "particle_plan.h"
 #include "philox.h"
 #include "thresholds.h"
+#include <type_traits>
 
 // This file is compiled a THIRD time for float32 (build.sh: -DCM3_PARTICLE_ILP_TU with -mllvm -amdgpu-sched-strategy=max-ilp): only the
 // two shared-env step kernels and their launchers, tagged with TU = 1 so that they are distinct symbols.  The max-ILP scheduling
@@ -33,10 +35,8 @@
 namespace cm3 {
 
 struct ParticleParams;
-// launchers of the max-ILP translation unit (float32 only): waves = 1 or kSharedEnvWaves per workgroup; n_agents 2..8
-int particle_ilp_launch_pairs_f32(const ParticleParams &p, int n_agents, int waves_per_wg, hipStream_t stream);
-int particle_ilp_launch_agents_f32(const ParticleParams &p, int n_agents, int waves_per_wg, hipStream_t stream);
-[[maybe_unused]] constexpr size_t kIlpMaxWaves = 16384;
+// launcher of the max-ILP translation unit: the shared-env float32 plans with ilp = 1 (particle_plan.h), n_agents 2..10
+int particle_ilp_launch_f32(const StepPlan &pl, const ParticleParams &p, int n_agents, hipStream_t stream);
 
 struct ParticleParams {
   int E;          // extent of the env axis of every array (row stride of the [N][E][..] arrays)
@@ -191,11 +191,7 @@ template <typename R, typename V4> __device__ __forceinline__ V4 sub4(const V4 &
 // instantiations are byte for byte the code without this feature.  (A first version selected among four flavours at run
 // time: that alone cost 1-3 % on every kernel that carried it -- profiles/r02_base_vs_new_runtime_flavours.txt -- and the
 // write-through flavours it also offered bought nothing, profiles/r02_store_policy_ab.txt.)
-constexpr uint32_t kFlagObsStoreNt = 0x100000u;  // internal launch flag, set by particle_rollout only
-constexpr size_t kWtMinObsBytes = (size_t)3 << 20;
-// N = 8: two lanes per agent up to this many envs per launch (measured crossover, profiles/r03_two_lanes_per_agent.txt) ...
-constexpr size_t kAgents2MaxEnvs = 32768;
-constexpr size_t kAgents2EarlyMaxEnvs = 16384;   // ... with its write-through stores ahead of the reward work up to here
+// (the launch flag kFlagObsStoreNt, the constants kSp* and the size gates kWtMinObsBytes / kAgents2*MaxEnvs: particle_plan.h)
 
 typedef float cm3_f4 __attribute__((ext_vector_type(4)));
 // Store policy of the observation rows, a COMPILE-TIME parameter of the step kernels (kSpPlain kernels are byte for byte the code
@@ -208,7 +204,6 @@ typedef float cm3_f4 __attribute__((ext_vector_type(4)));
 //             during the launch instead.  Measured (profiles/r03_obs_store_write_through.txt, same box, in place): N = 8 at 8192
 //             envs 5.01 -> 4.48 us, 16 384 envs 6.97 -> 5.87; N = 4 at 65 536 envs 6.33 -> 5.76, 262 144 envs 17.9 -> 15.9, 2^22
 //             envs 337 -> 305; and a LOSS where a launch writes little (C2: 0.8 MB, 2.55 -> 2.93 us) or in 4-byte pieces (Checkers).
-constexpr int kSpPlain = 0, kSpNt = 1, kSpWt = 2;
 template <int SP> __device__ __forceinline__ void store_obs_vec(float4 *p, const float4 &v) {
   if constexpr (SP == kSpWt) {
     const cm3_f4 t = {v.x, v.y, v.z, v.w};
@@ -291,7 +286,7 @@ template <typename T, int N> __device__ __forceinline__ void store_row(T *base, 
 // ---- obs_others geometry + LDS-staged store -------------------------------------------------------
 template <typename R, int N> struct ObsGeom {
   static constexpr int NO = N > 1 ? N - 1 : 1;  // "others" per agent (N == 1 stores self, mgs.py:148-151)
-  static constexpr int REC = N * NO * 4;        // reals per env
+  static constexpr int REC = env_obs_reals(N);  // reals per env
   static constexpr int STRIDE = REC + 4;        // +4 reals: spreads consecutive rows over LDS banks
   static constexpr int kBudget = 16384;         // LDS bytes per wave
   static constexpr int rows() {
@@ -713,14 +708,10 @@ template <int N> struct PairGeom {
   static constexpr int SLOTS = N * NO;
   // lanes per agent: its N-1 pair lanes, padded to a power of two where that keeps the group size (N = 3, 4, 5) -- an agent is then
   // a pair / a quad of lanes and its forces come together with DPP quad permutes instead of an LDS shuffle round trip
-  static constexpr int LA = (N >= 3 && N <= 5) ? (N == 3 ? 2 : 4) : NO;
-  static constexpr int pow2ceil(int v) {
-    int r = 1;
-    while (r < v) r <<= 1;
-    return r;
-  }
-  static constexpr int G = pow2ceil(N * LA);
-  static constexpr int EPW = 64 / G;  // envs per wave
+  static constexpr int LA = pair_lanes_per_agent(N);
+  static constexpr int pow2ceil(int v) { return cm3::pow2ceil(v); }
+  static constexpr int G = pair_group_lanes(N);
+  static constexpr int EPW = pair_envs_per_wave(N);  // envs per wave
 };
 
 // (Round 1 gave the workgroup an extra "draw wave" that drew the NEXT launch's actions while the physics waves ran, handing the
@@ -735,7 +726,7 @@ template <int N> struct PairGeom {
 // the trajectory slots is unchanged in value, address and store policy.
 // NOTE: in the REC instantiation the first argument is READ AND WRITTEN -- it keeps the `const void *h_state_in` slot of the shared
 // signature (so that it stays a preloaded SGPR pair like state_in), and the live stores go through at32, which drops the const.
-constexpr uint32_t kRecBytes = 128, kRecGoals = 64, kRecMeta = 96, kRecWords = 112;
+constexpr uint32_t kRecGoals = 64, kRecMeta = 96, kRecWords = 112;   // (kRecBytes = 128: particle_plan.h)
 template <typename R, int N, int WAVES, bool FUSED, int SP = kSpPlain, bool LIVE = false, bool REC = false, int TU = CM3_PARTICLE_TU>
 __global__ void __launch_bounds__(WAVES * 64)
     k_particle_step_pairs(const void *h_state_in, const void *h_goals_in, const int32_t *h_meta_in, const int32_t *h_episode,
@@ -744,7 +735,7 @@ __global__ void __launch_bounds__(WAVES * 64)
   // The leading arguments repeat the fields of `p` that the first loads need: scalar kernel arguments are preloaded into
   // SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count; the first 14 dwords in practice: everything up to and
   // including h_max_steps), so the addresses of the first loads do not wait for a kernarg fetch.
-  // Index and address arithmetic is 32-bit: every array of one tick is below 4 GiB (checked by launch_pairs), so an element is
+  // Index and address arithmetic is 32-bit: every array of one tick is below 4 GiB (checked by plan_launch), so an element is
   // <uniform base pointer> + <32-bit byte offset of the lane>, which the hardware adds itself (global_load/store with a
   // scalar base).  By tools/probes/issue_probe.hip a lone wave issues one VALU instruction per 4 cycles whatever it is, so at
   // one wave per SIMD the launch time is the length of the executed path: the 64-bit multiplies, adds and compares of
@@ -1031,9 +1022,9 @@ __global__ void __launch_bounds__(WAVES * 64)
 // Bit-identical to the other two mappings (same expressions, same summation orders).
 template <int N> struct AgentGeom {
   static constexpr int NO = N - 1;
-  static constexpr int G = PairGeom<N>::pow2ceil(N);
-  static constexpr int EPW = 64 / G;        // envs per wave
-  static constexpr int VPE = N * NO;        // obs vectors per env record
+  static constexpr int G = cm3::pow2ceil(N);
+  static constexpr int EPW = agent_envs_per_wave(N);  // envs per wave
+  static constexpr int VPE = shared_obs_reals(N) / 4;  // obs vectors per env record
 };
 
 template <typename R, int N, int WAVES, bool FUSED, int SP = kSpPlain, bool LIVE = false, int TU = CM3_PARTICLE_TU>
@@ -1044,7 +1035,7 @@ __global__ void __launch_bounds__(WAVES * 64)
   // Leading scalar arguments as in k_particle_step_pairs: they repeat the fields of `p` that the first loads need and are
   // preloaded into SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count), so the first addresses do not wait for a
   // kernarg fetch (worth 7.7 % on the pair kernel at C2, profiles/r02_remaining_round1_tunings_rechecked.txt).  32-bit index
-  // and address arithmetic as in the pair kernel (every per-tick array below 4 GiB, checked by launch_agents).
+  // and address arithmetic as in the pair kernel (every per-tick array below 4 GiB, checked by plan_launch).
   static_assert(N >= 2, "the agent mapping needs at least two agents");
   using V4 = typename Vec<R>::v4;
   using V2 = typename Vec<R>::v2;
@@ -1792,275 +1783,104 @@ static int fill_params(const cm3_particle_desc *d, const cm3_particle_bufs *b, P
   return CM3_OK;
 }
 
-template <typename R, int N, int WAVES>
-static int launch_one(const ParticleParams &p, ParticleOp op, hipStream_t stream) {
-  const unsigned per_block = WAVES * 64;
-  const unsigned blocks = (unsigned)(((size_t)(p.EN - p.E0) + per_block - 1) / per_block);
-  switch (op) {
-    case kStep: {
-      constexpr int kNt = sizeof(R) == 4 ? kSpNt : kSpPlain, kWt = sizeof(R) == 4 ? kSpWt : kSpPlain;
-      const bool nt = sizeof(R) == 4 && (p.flags & kFlagObsStoreNt);   // streaming-size trajectory (obs_store_nt)
-      // a launch that writes >= kWtMinObsBytes of observation rows writes them through (kSpWt; per-tick launches only)
-      const bool wt = sizeof(R) == 4 && (size_t)(p.EN - p.E0) * ObsGeom<R, N>::REC * sizeof(R) >= kWtMinObsBytes && !p.state_copy;
-      note_variant("k_particle_step", (int)sizeof(R), N, WAVES, p.n_ticks > 1,
-                   p.n_ticks > 1 ? (nt ? kNt : kSpPlain) : (wt ? kWt : (nt ? kNt : kSpPlain)), 0, CM3_PARTICLE_TU);
-      if (p.n_ticks > 1) {
-        if (nt) hipLaunchKernelGGL((k_particle_step<R, N, WAVES, true, kNt>), dim3(blocks), dim3(per_block), 0, stream, p);
-        else hipLaunchKernelGGL((k_particle_step<R, N, WAVES, true>), dim3(blocks), dim3(per_block), 0, stream, p);
-      } else {
-        if (wt) hipLaunchKernelGGL((k_particle_step<R, N, WAVES, false, kWt>), dim3(blocks), dim3(per_block), 0, stream, p);
-        else if (nt) hipLaunchKernelGGL((k_particle_step<R, N, WAVES, false, kNt>), dim3(blocks), dim3(per_block), 0, stream, p);
-        else hipLaunchKernelGGL((k_particle_step<R, N, WAVES, false>), dim3(blocks), dim3(per_block), 0, stream, p);
-      }
-      break;
-    }
-    case kReset:
-      note_variant("k_particle_reset", (int)sizeof(R), N, WAVES, 0, kSpPlain, 0, CM3_PARTICLE_TU);
-      hipLaunchKernelGGL((k_particle_reset<R, N, WAVES>), dim3(blocks), dim3(per_block), 0, stream, p);
-      break;
-    case kObserve:
-      note_variant("k_particle_observe", (int)sizeof(R), N, WAVES, 0, kSpPlain, 0, CM3_PARTICLE_TU);
-      hipLaunchKernelGGL((k_particle_observe<R, N, WAVES>), dim3(blocks), dim3(per_block), 0, stream, p);
-      break;
+template <typename R> static StepShape step_shape(const ParticleParams &p, int n_agents) {
+  return StepShape{(int)sizeof(R), n_agents, p.E, p.E0, p.EN, p.n_ticks, p.flags, p.state_copy != nullptr, p.live_record != nullptr};
+}
+
+// what a caller is told when plan_step refuses a launch
+static int refuse(int why, int E, int n) {
+  switch (why) {
+    case kRefusePairAgents: return fail(CM3_ERR_INVALID, "the lane-per-pair kernel needs n_agents in 2..8");
+    case kRefuseAgentAgents: return fail(CM3_ERR_INVALID, "the lane-per-agent kernel needs n_agents >= 2");
+    case kRefusePair4GiB:
+      return fail(CM3_ERR_INVALID, "the lane-per-pair kernel addresses at most 4 GiB per array: %d envs x %d agents is too large "
+                  "(use the default kernel choice)", E, n);
+    case kRefuseAgent4GiB:
+      return fail(CM3_ERR_INVALID, "the lane-per-agent kernel addresses at most 4 GiB per array: %d envs x %d agents is too large", E, n);
+    case kRefuseRecordMapping: return fail(CM3_ERR_INVALID, "live records are stepped by the lane-per-pair kernel only");
+    case kRefuseRecordConditions:
+      return fail(CM3_ERR_INVALID, "live records are for per-tick float32 live-state launches with in-kernel actions, n_agents 2..4");
   }
+  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", n);
+}
+
+// f(std::integral_constant<int, V>) for the V among Vs that a run-time value equals; false when it is none of them
+template <int... Vs, typename F> static bool with_value(int v, F &&f) { return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...); }
+
+// f(std::integral_constant<int, n>) for a run-time agent count in Lo..Hi: the one switch over n_agents
+template <int Lo, int Hi, typename F> static int with_agents(int n, F &&f) {
+  if constexpr (Lo > Hi) return fail(CM3_ERR_INVALID, "n_agents %d unsupported", n);
+  else return n == Lo ? f(std::integral_constant<int, Lo>{}) : with_agents<Lo + 1, Hi>(n, f);
+}
+
+// ONE instantiation of the step kernels.  The leading arguments of the shared-env kernels repeat fields of `p` (preloaded SGPRs); in
+// the REC build the record array takes the place of state_in.
+template <typename R, int N, int MAP, int WAVES, bool FUSED, int SP, bool LIVE, bool REC, bool EARLY>
+static void launch_variant(const StepPlan &pl, const ParticleParams &p, hipStream_t stream) {
+  const dim3 grid(pl.grid_blocks), block(WAVES * 64);
+  [[maybe_unused]] auto shared = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, REC ? (const void *)p.live_record : p.state_in, p.goals_in, p.meta_in,
+                       (const int32_t *)p.episode, p.E, p.flags | pl.xcd_flags, p.E0, p.EN, p.max_steps, (const int32_t *)p.actions, p);
+  };
+  if constexpr (MAP == kMapEnv) hipLaunchKernelGGL((k_particle_step<R, N, WAVES, FUSED, SP>), grid, block, 0, stream, p);
+  else if constexpr (MAP == kMapPairs) shared(k_particle_step_pairs<R, N, WAVES, FUSED, SP, LIVE, REC>);
+  else if constexpr (MAP == kMapAgents) shared(k_particle_step_agents<R, N, WAVES, FUSED, SP, LIVE>);
+  else shared(k_particle_step_agents2<WAVES, SP, LIVE, EARLY>);
+}
+
+// A plan (plan_step) becomes a launch; what cm3_last_kernel_variant() reports comes from the fields the dispatch reads.
+template <typename R, int N> static int launch_step(const StepPlan &pl, const ParticleParams &p, hipStream_t stream) {
+  static const char *const kKernel[] = {"k_particle_step", "k_particle_step_pairs", "k_particle_step_agents", "k_particle_step_agents2"};
+  note_variant(kKernel[pl.map], (int)sizeof(R), N, pl.waves, pl.fused, pl.sp, pl.live, pl.ilp, pl.early, 0, -1, pl.rec);
+  // The plan's fields become template arguments one by one.  A combination is instantiated in this translation unit iff
+  // step_variant_exists says the library has it -- nothing else ever is -- and the max-ILP unit holds the shared-env kernels only.
+  const bool launched = pl.ilp == CM3_PARTICLE_TU &&
+      with_value<kMapEnv, kMapPairs, kMapAgents, kMapAgents2>(pl.map, [&](auto m) {
+      return with_value<1, 4>(pl.waves, [&](auto w) {
+      return with_value<0, 1>(pl.fused, [&](auto f) {
+      return with_value<kSpPlain, kSpNt, kSpWt>(pl.sp, [&](auto s) {
+      return with_value<0, 1>(pl.live, [&](auto l) {
+      return with_value<0, 1>(pl.rec, [&](auto r) {
+      return with_value<0, 1>(pl.early, [&](auto e) {
+        constexpr bool built = step_variant_exists(m, (int)sizeof(R), N, w, f, s, l, r, e) && (CM3_PARTICLE_TU == 0 || m != kMapEnv);
+        if constexpr (built) launch_variant<R, N, m, w, f != 0, s, l != 0, r != 0, e != 0>(pl, p, stream);
+        return built;
+      }); }); }); }); }); }); });
+  if (!launched) return fail(CM3_ERR_INVALID, "no build of %s for this plan in translation unit %d", kKernel[pl.map], CM3_PARTICLE_TU);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
 
-template <typename R, int N, int WAVES> static int launch_pairs(const ParticleParams &p, hipStream_t stream) {
-  if constexpr (N >= 2 && N <= 8) {   // (N (N - 1) pair lanes must fit a wave)
-    const size_t envs_per_block = (size_t)WAVES * PairGeom<N>::EPW;
-    const unsigned raw_blocks = (unsigned)(((size_t)(p.EN - p.E0) + envs_per_block - 1) / envs_per_block);
-    const unsigned blocks = cm3_xcd_grid(raw_blocks);          // XCD-aware block order (common.h)
-    const uint32_t xf = cm3_xcd_flags(raw_blocks);
-    constexpr int kF32 = sizeof(R) == 4 ? kSpNt : kSpPlain;
-    const bool nt = sizeof(R) == 4 && (p.flags & kFlagObsStoreNt);   // streaming-size trajectory (obs_store_nt)
-    const bool rec = p.live_record != nullptr;   // cm3_particle_traj.live_record: the record array takes the place of state_in
-    const void *first = rec ? p.live_record : p.state_in;
-#define CM3_LAUNCH_PAIRS(...)                                                                                               \
-  hipLaunchKernelGGL((k_particle_step_pairs<R, N, WAVES, __VA_ARGS__>), dim3(blocks), dim3(WAVES * 64), 0, stream,          \
-                     first, p.goals_in, p.meta_in, (const int32_t *)p.episode, p.E, p.flags | xf, p.E0, p.EN, p.max_steps,   \
-                     (const int32_t *)p.actions, p)
-    // the kernel indexes with 32-bit byte offsets: its largest per-tick array (obs_others) must stay below 4 GiB
-    if ((size_t)p.E * PairGeom<N>::SLOTS * 4 * sizeof(R) >= ((size_t)1 << 32))
-      return fail(CM3_ERR_INVALID, "the lane-per-pair kernel addresses at most 4 GiB per array: %d envs x %d agents is too large "
-                  "(use the default kernel choice)", p.E, N);
-    const bool live = p.state_copy != nullptr;   // cm3_particle_traj.state_live (per-tick launches only)
-    if (rec && !(sizeof(R) == 4 && N <= 4 && live && p.n_ticks == 1 && (p.flags & CM3_FLAG_GEN_ACTIONS) &&
-                 (size_t)p.E * kRecBytes < ((size_t)1 << 32)))
-      return fail(CM3_ERR_INVALID, "live records are for per-tick float32 live-state launches with in-kernel actions, n_agents 2..4");
-    note_variant("k_particle_step_pairs", (int)sizeof(R), N, WAVES, p.n_ticks > 1, nt ? kF32 : kSpPlain, p.n_ticks == 1 && live,
-                 CM3_PARTICLE_TU, 0, 0, -1, rec);
-    if (p.n_ticks > 1) {
-      if (nt) CM3_LAUNCH_PAIRS(true, kF32);
-      else CM3_LAUNCH_PAIRS(true, kSpPlain);
-    } else if (rec) {
-      if constexpr (sizeof(R) == 4 && N <= 4) {
-        if (nt) CM3_LAUNCH_PAIRS(false, kF32, true, true);
-        else CM3_LAUNCH_PAIRS(false, kSpPlain, true, true);
-      }
-    } else if (live) {
-      if (nt) CM3_LAUNCH_PAIRS(false, kF32, true);
-      else CM3_LAUNCH_PAIRS(false, kSpPlain, true);
-    } else {
-      if (nt) CM3_LAUNCH_PAIRS(false, kF32);
-      else CM3_LAUNCH_PAIRS(false, kSpPlain);
-    }
-#undef CM3_LAUNCH_PAIRS
-    CM3_HIP_CHECK(hipGetLastError());
-    return CM3_OK;
-  } else {
-    return fail(CM3_ERR_INVALID, "the lane-per-pair kernel needs n_agents in 2..8");
-  }
-}
-
-// Largest batch for which the lane-per-pair mapping is preferred when no per-N entry says otherwise (see launch_n).
-constexpr size_t kPairsMaxEnvs = (size_t)1 << 14;
-// ... and per agent count (the measurements behind the table: launch_n)
-constexpr size_t pair_max_envs(int n) { return n > 8 ? 0 : (n == 2 ? 32768 : (n == 3 ? 24576 : (n == 4 ? 12288 : kPairsMaxEnvs))); }
-// Does a rollout call of this descriptor step on packed live records when it is handed some (cm3_particle_traj.live_record)?  Per-tick
-// float32 launches of the lane-per-pair kernel with in-kernel actions, two to four agents.  (N <= 4: launch_n's lane-per-agent range
-// starts above pair_max_envs, so without a forced mapping the pair kernel runs exactly up to it.)
-static bool live_record_applies(const cm3_particle_desc *d, int real_bytes) {
-  if (real_bytes != 4 || d->n_agents < 2 || d->n_agents > 4 || d->n_envs <= 0) return false;
-  if (!(d->flags & CM3_FLAG_GEN_ACTIONS) || (d->flags & CM3_FLAG_FUSED_TICKS)) return false;
-  if (d->flags & (CM3_FLAG_KERNEL_LANE_PER_ENV | CM3_FLAG_KERNEL_LANE_PER_AGENT)) return false;
-  if ((size_t)d->n_envs * kRecBytes >= ((size_t)1 << 32)) return false;
-  return (d->flags & CM3_FLAG_KERNEL_LANE_PER_PAIR) || (size_t)d->n_envs <= pair_max_envs(d->n_agents);
-}
-
-template <typename R, int N, int WAVES> static int launch_agents(const ParticleParams &p, hipStream_t stream) {
-  if constexpr (N >= 2) {
-    const size_t envs_per_block = (size_t)WAVES * AgentGeom<N>::EPW;
-    const unsigned raw_blocks = (unsigned)(((size_t)(p.EN - p.E0) + envs_per_block - 1) / envs_per_block);
-    const unsigned blocks = cm3_xcd_grid(raw_blocks);          // XCD-aware block order (common.h)
-    const uint32_t xf = cm3_xcd_flags(raw_blocks);
-    const bool nt = sizeof(R) == 4 && (p.flags & kFlagObsStoreNt);   // streaming-size trajectory (obs_store_nt)
-#define CM3_LAUNCH_AGENTS(...)                                                                                              \
-  hipLaunchKernelGGL((k_particle_step_agents<R, N, WAVES, __VA_ARGS__>), dim3(blocks), dim3(WAVES * 64), 0, stream,         \
-                     p.state_in, p.goals_in, p.meta_in, (const int32_t *)p.episode, p.E, p.flags | xf, p.E0, p.EN, p.max_steps,   \
-                     (const int32_t *)p.actions, p)
-    // 32-bit byte offsets inside the kernel: the largest per-tick array (obs_others) must stay below 4 GiB
-    if ((size_t)p.E * AgentGeom<N>::VPE * 4 * sizeof(R) >= ((size_t)1 << 32))
-      return fail(CM3_ERR_INVALID, "the lane-per-agent kernel addresses at most 4 GiB per array: %d envs x %d agents is too large", p.E, N);
-    const bool live = p.state_copy != nullptr;   // cm3_particle_traj.state_live (per-tick launches only)
-    constexpr int kNt = sizeof(R) == 4 ? kSpNt : kSpPlain, kWt = sizeof(R) == 4 ? kSpWt : kSpPlain;
-    // a launch that writes >= kWtMinObsBytes of observation rows writes them through (kSpWt; per-tick launches, no slot copies)
-    const bool wt = sizeof(R) == 4 && (size_t)(p.EN - p.E0) * AgentGeom<N>::VPE * 4 * sizeof(R) >= kWtMinObsBytes;
-    if constexpr (N == 8 && sizeof(R) == 4) {
-      // two lanes per agent (k_particle_step_agents2) while a SIMD holds few waves: per-tick launches up to kAgents2MaxEnvs
-      if (p.n_ticks == 1 && (size_t)(p.EN - p.E0) <= kAgents2MaxEnvs) {
-        const unsigned raw2 = (unsigned)(((size_t)(p.EN - p.E0) + (size_t)WAVES * 4 - 1) / ((size_t)WAVES * 4));
-        const unsigned blocks2 = cm3_xcd_grid(raw2);
-        const uint32_t xf2 = cm3_xcd_flags(raw2);
-#define CM3_LAUNCH_AGENTS2(...)                                                                                             \
-  hipLaunchKernelGGL((k_particle_step_agents2<WAVES, __VA_ARGS__>), dim3(blocks2), dim3(WAVES * 64), 0, stream, p.state_in,  \
-                     p.goals_in, p.meta_in, (const int32_t *)p.episode, p.E, p.flags | xf2, p.E0, p.EN, p.max_steps,         \
-                     (const int32_t *)p.actions, p)
-        const bool early = wt && (size_t)(p.EN - p.E0) <= kAgents2EarlyMaxEnvs;
-        note_variant("k_particle_step_agents2", 4, 8, WAVES, 0, wt ? kWt : (nt ? kNt : kSpPlain), live, CM3_PARTICLE_TU, early);
-        if (live) {
-          if (early) CM3_LAUNCH_AGENTS2(kWt, true, true);
-          else if (wt) CM3_LAUNCH_AGENTS2(kWt, true);
-          else if (nt) CM3_LAUNCH_AGENTS2(kNt, true);
-          else CM3_LAUNCH_AGENTS2(kSpPlain, true);
-        } else {
-          if (early) CM3_LAUNCH_AGENTS2(kWt, false, true);
-          else if (wt) CM3_LAUNCH_AGENTS2(kWt);
-          else if (nt) CM3_LAUNCH_AGENTS2(kNt);
-          else CM3_LAUNCH_AGENTS2(kSpPlain);
-        }
-#undef CM3_LAUNCH_AGENTS2
-        CM3_HIP_CHECK(hipGetLastError());
-        return CM3_OK;
-      }
-    }
-    note_variant("k_particle_step_agents", (int)sizeof(R), N, WAVES, p.n_ticks > 1,
-                 p.n_ticks > 1 ? (nt ? kNt : kSpPlain) : (wt ? kWt : (nt ? kNt : kSpPlain)), p.n_ticks == 1 && live, CM3_PARTICLE_TU);
-    if (p.n_ticks > 1) {
-      if (nt) CM3_LAUNCH_AGENTS(true, kNt);
-      else CM3_LAUNCH_AGENTS(true, kSpPlain);
-    } else if (live) {
-      if (wt) CM3_LAUNCH_AGENTS(false, kWt, true);
-      else if (nt) CM3_LAUNCH_AGENTS(false, kNt, true);
-      else CM3_LAUNCH_AGENTS(false, kSpPlain, true);
-    } else {
-      if (wt) CM3_LAUNCH_AGENTS(false, kWt);
-      else if (nt) CM3_LAUNCH_AGENTS(false, kNt);
-      else CM3_LAUNCH_AGENTS(false, kSpPlain);
-    }
-#undef CM3_LAUNCH_AGENTS
-    CM3_HIP_CHECK(hipGetLastError());
-    return CM3_OK;
-  } else {
-    return fail(CM3_ERR_INVALID, "the lane-per-agent kernel needs n_agents >= 2");
-  }
-}
-
-// waves per workgroup of the shared-env mappings at >= 256 waves: one per SIMD of a CU (C2 4 waves 2.61 us per tick, 2 waves 2.96,
-// 8 waves 2.89; profiles/r02_f32_softplus_hw.txt, g.)
-constexpr int kSharedEnvWaves = 4;
-template <typename R, int N> static int launch_n(const ParticleParams &p, ParticleOp op, hipStream_t stream) {
-  if (op == kStep) {
-    // Which mapping for (N, E): measured on MI355X in round 2, after the exact squared-distance thresholds took the square roots
-    // out of every mapping (in place, us per tick, pair / agent / env; profiles/r02_n2345_mapping_sweep_*.txt, r02_n678_mid_sweep.txt,
-    // r02_n8_mapping_sweep.txt, r02_n567_mapping_sweep.txt).  Round 1's rule (pair for N >= 3 up to 16384 envs, agent for N >= 6 between
-    // 6144 and 2^17) had been tuned on N = 4 and N = 8 only and before that change; it left `auto` up to 41 % behind the best kernel:
-    //   N = 3   24576: 4.43 / 5.15 / 4.97   32768: 5.14 / 5.31 / 5.14   65536: 7.7 / 7.6 / 5.8     -> pair to 32768, then env
-    //   N = 4   16384: 5.06 / 5.13 / 6.65   24576: 6.40 / 6.04 / 7.29   32768: 7.85 / 6.42 / 7.67   65536: 12.6 / 9.1 / 8.4
-    //           -> pair to 16384, agent to 49152, then env
-    //   N = 5    8192: 5.14 / 5.33 / 9.73   16384: 7.64 / 6.42 / 10.0   32768: 12.8 / 9.2 / 11.5    65536: 21 / 14.2 / 12.3
-    //           -> pair to 12288, agent to 49152, then env
-    //   N = 6    8192: 5.7 / 6.0 / 13.2     16384: 8.8 / 7.5 / 13.5     65536: 23.6 / 16.3 / 16.7   2^17: - / 26.6 / 23.5
-    //           -> pair to 12288, agent to 65536, then env
-    //   N = 7    6144: 7.1 / 6.4 / 18.5     65536: 41 / 17.9 / 22.6     2^17 .. 2^20: agent = env within 1 %   -> agent 6144 .. 2^17
-    //   N = 8    4096: 6.2 / 6.7 / 23.8      6144: 7.9 / 7.0 / 23.7     2^18: - / 68.9 / 71.1       2^20: - / 286 / 319
-    //           -> pair below 6144, agent from 6144 up (no upper bound)
-    // Crossovers that fall between two measured sizes (12288, 49152) are interpolated, not measured.
-    constexpr size_t kInf = ~(size_t)0;
-    // Re-measured after the executed paths of the pair / agent kernels were shortened (hardware soft-plus, 32-bit addressing, no
-    // spills; tools/mapping_sweep.py, profiles/r02_mapping_sweep_after_path_shortening.txt): the table moved a little --
-    //   N = 2: pair wins by 10 % up to 6144 envs (2.31 / - / 2.56 at 2048), level with env above  -> pair to 6144
-    //   N = 3: pair to 24576 (32768: 4.41 / 4.43 / 4.20)
-    //   N = 4: pair to 12288 (3.80 / 3.88 / 4.70), agent to 40960 (16384: 4.41 / 4.06 / 4.85; 49152: 9.0 / 6.40 / 6.30), then env
-    //   N = 5, 6: agent from 8192 (N = 5: 4.31 / 4.23 / 6.41); N = 5 up to 40960, N = 6 up to 65536, then env
-    //   N = 7, 8: agent from 6144 up, no upper bound (N = 7 at 2^20: - / 218 / 231)
-    // ... and once more on the final build (max-ILP pair / agent kernels; profiles/r02_mapping_sweep_final_build.txt):
-    //   N = 2: pair up to 32768 envs (16384: 2.57 / - / 2.68; 32768: 2.89 / - / 3.01); N = 6: agent from 6144 (4.27 / 4.11);
-    //   N = 7, 8: agent from 4096 (N = 8: 5.12 / 4.57, N = 7: 4.73 / 4.34; at 2048 pair: 3.83 / 4.29)
-    // round 4, after the two-stage action draw shortened every mapping's path: re-swept (profiles/r04_mapping_sweep.txt, merge8
-    // positions): `auto` within ~1 % of the best mapping at 88 of 91 (N, E) points.  The two candidates for a move -- N = 2 pair up
-    // to 65536, N = 4 agent up to 65536 -- were tried and taken back: on the antipodal config of the bench N = 4 at 65536 envs ran
-    // 6.11 us with the agent mapping against 5.70 with lane-per-env; the crossovers depend on how crowded a config is.
-    constexpr size_t kPairMax = pair_max_envs(N);
-    // round 3: N = 8 with two lanes per agent (k_particle_step_agents2; profiles/r03_two_lanes_per_agent.txt) moved its crossover
-    // to 2048 envs; the XCD-aware block order (common.h) then sped the pair mapping up most at exactly these sizes
-    // (profiles/r03_xcd_block_order.txt; pair / agent, in place): N = 8: 2048 3.42 / 3.74, 4096 4.47 / 3.84 -> agent from 4096;
-    // N = 7: 4096 4.12 / 4.31, 6144 5.03 / 4.29 -> agent from 6144; N = 6: 6144 3.86 / 4.14, 8192 4.37 / 4.11 -> agent from 8192
-    // N = 5: 8192 3.86 / 4.02, 12288 4.74 / 4.42 -> agent from 10240 (profiles/r03_mapping_sweep_xcd.txt)
-    // N = 9, 10 (round 4; no pair mapping: N (N - 1) lanes do not fit a wave): lane per agent from 1024 envs (256 waves), as N = 8 above
-    constexpr size_t kAgentLo = N == 4 ? 12289 : (N == 5 ? 10240 : (N == 6 ? 8192 : (N == 7 ? 6144 : (N == 8 ? 4096 : (N > 8 ? 1024 : kInf)))));
-    // round 3, large batches after the write-through observation stores (profiles/r03_mapping_sweep_large.txt; env / agent):
-    //   N = 6: 2^17 17.7 / 17.4, 2^19 66.3 / 62.3, 2^20 125.5 / 121.9, 2^21 290 / 326   -> agent up to 1.5 M envs (was 65536)
-    //   N = 7: 2^19 89 / 80, 2^20 164-170 / 153-217 (the agent mapping is bimodal there: it depends on where the allocator
-    //          put the buffers), 2^21 392-412 / 437-466                                -> agent up to 768 K envs (was unbounded)
-    //   N = 8: 2^19 110.5 / 99.9, 2^20 222-233 / 278-281 (6.1 vs 4.9 TB/s), 2^21 489-556 / 477-505 -> agent up to 768 K envs
-    constexpr size_t kAgentHi = N == 4 || N == 5 ? 40960 : (N == 6 ? 1572864 : (N >= 7 ? 786432 : 0));
-    // (live_record_applies() relies on it: for the agent counts a record holds, the lane-per-agent range lies wholly above the pair range)
-    static_assert(N > 4 || kAgentLo > pair_max_envs(N), "N <= 4: the lane-per-agent range must start above the lane-per-pair range");
-    bool pairs = N >= 2 && (size_t)p.E <= kPairMax;
-    bool agents = N >= 4 && (size_t)p.E >= kAgentLo && (size_t)p.E <= kAgentHi;
-    // both shared-env mappings index with 32-bit byte offsets (obs_others below 4 GiB per tick); beyond that only a forced choice
-    // reaches them (and is refused by their launchers)
-    if ((size_t)p.E * N * (N - 1) * 4 * sizeof(R) >= ((size_t)1 << 32)) pairs = agents = false;
-    if (p.flags & CM3_FLAG_KERNEL_LANE_PER_ENV) pairs = agents = false;
-    if (p.flags & CM3_FLAG_KERNEL_LANE_PER_PAIR) { pairs = true; agents = false; }
-    if (N > 8 && pairs) return fail(CM3_ERR_INVALID, "the lane-per-pair kernel needs n_agents in 2..8");
-    if (p.flags & CM3_FLAG_KERNEL_LANE_PER_AGENT) agents = true;
-    if (p.live_record && (agents || !pairs)) return fail(CM3_ERR_INVALID, "live records are stepped by the lane-per-pair kernel only");
-    if (agents) {
-      const size_t waves = ((size_t)p.E + AgentGeom<(N >= 2 ? N : 2)>::EPW - 1) / AgentGeom<(N >= 2 ? N : 2)>::EPW;
-#ifndef CM3_PARTICLE_ILP_TU
-      if constexpr (sizeof(R) == 4 && N >= 2)
-        if (waves <= kIlpMaxWaves) return particle_ilp_launch_agents_f32(p, N, waves < 256 ? 1 : kSharedEnvWaves, stream);
-#endif
-      if (waves < 256) return launch_agents<R, N, 1>(p, stream);
-      return launch_agents<R, N, kSharedEnvWaves>(p, stream);
-    }
-    if (pairs) {
-      // 4 waves per workgroup (one per SIMD of a CU) measured faster than 1 or 2 from 1024 waves up
-      // (tools/probes/step_timeline.hip: 4.38 vs 4.82 us at E=4096, 6.36 vs 7.32 us at E=16384, stamped build);
-      // below 256 waves single-wave workgroups spread the work over more CUs.
-      constexpr int NP = (N >= 2 && N <= 8) ? N : 2;
-      const size_t waves = ((size_t)p.E + PairGeom<NP>::EPW - 1) / PairGeom<NP>::EPW;
-#ifndef CM3_PARTICLE_ILP_TU
-      if constexpr (sizeof(R) == 4 && N >= 2)
-        if (waves <= kIlpMaxWaves) return particle_ilp_launch_pairs_f32(p, N, waves < 256 ? 1 : kSharedEnvWaves, stream);
-#endif
-      if (waves < 256) return launch_pairs<R, N, 1>(p, stream);
-      return launch_pairs<R, N, kSharedEnvWaves>(p, stream);
-    }
-  }
-  // lane-per-env.  Small batches: one wave per workgroup; large: 4 waves per workgroup (one per SIMD).
-  // measured crossover (N=4): 11.27 vs 11.43 us at 2^17 envs, 20.9 vs 19.7 us at 2^18
-  if ((size_t)p.E <= (size_t)128 * 1024) return launch_one<R, N, 1>(p, op, stream);
-  return launch_one<R, N, 4>(p, op, stream);
+// reset / observe: lane per env, waves per workgroup as the step kernel of that mapping
+template <typename R, int N, int WAVES> static int launch_aux(const ParticleParams &p, ParticleOp op, hipStream_t stream) {
+  const unsigned per_block = WAVES * 64, blocks = (unsigned)(((size_t)(p.EN - p.E0) + per_block - 1) / per_block);
+  note_variant(op == kReset ? "k_particle_reset" : "k_particle_observe", (int)sizeof(R), N, WAVES, 0, kSpPlain, 0, CM3_PARTICLE_TU);
+  if (op == kReset) hipLaunchKernelGGL((k_particle_reset<R, N, WAVES>), dim3(blocks), dim3(per_block), 0, stream, p);
+  else hipLaunchKernelGGL((k_particle_observe<R, N, WAVES>), dim3(blocks), dim3(per_block), 0, stream, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
 }
 
 template <typename R> static int launch(const ParticleParams &p, int n_agents, ParticleOp op, hipStream_t stream) {
-  switch (n_agents) {
-    case 1: return launch_n<R, 1>(p, op, stream);
-    case 2: return launch_n<R, 2>(p, op, stream);
-    case 3: return launch_n<R, 3>(p, op, stream);
-    case 4: return launch_n<R, 4>(p, op, stream);
-    case 5: return launch_n<R, 5>(p, op, stream);
-    case 6: return launch_n<R, 6>(p, op, stream);
-    case 7: return launch_n<R, 7>(p, op, stream);
-    case 8: return launch_n<R, 8>(p, op, stream);
-    case 9: return launch_n<R, 9>(p, op, stream);
-    case 10: return launch_n<R, 10>(p, op, stream);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", n_agents);
+  if (op != kStep)
+    return with_agents<1, CM3_MAX_AGENTS>(n_agents, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      return (size_t)p.E <= kEnvOneWaveMaxEnvs ? launch_aux<R, N, 1>(p, op, stream) : launch_aux<R, N, kEnvWaves>(p, op, stream);
+    });
+  StepPlan pl;
+  if (const int why = plan_step(step_shape<R>(p, n_agents), pl)) return refuse(why, p.E, n_agents);
+  if constexpr (sizeof(R) == 4 && CM3_PARTICLE_TU == 0)
+    if (pl.ilp) return particle_ilp_launch_f32(pl, p, n_agents, stream);
+  return with_agents<1, CM3_MAX_AGENTS>(n_agents, [&](auto n) { return launch_step<R, decltype(n)::value>(pl, p, stream); });
+}
+
+// Does a rollout call of this descriptor step on packed live records when it is handed some (cm3_particle_traj.live_record)?  Where
+// the plan of its per-tick launches does (plan_takes_record): float32, lane per pair, in-kernel actions, two to four agents.
+static bool live_record_applies(const cm3_particle_desc *d, int real_bytes) {
+  // (never beside a flag that forces another mapping -- fill_params refuses two of them, but the rollout asks this first)
+  if (d->n_envs <= 0 || (d->flags & (CM3_FLAG_KERNEL_LANE_PER_ENV | CM3_FLAG_KERNEL_LANE_PER_AGENT))) return false;
+  return plan_takes_record(StepShape{real_bytes, d->n_agents, d->n_envs, 0, d->n_envs, (d->flags & CM3_FLAG_FUSED_TICKS) ? 2 : 1,
+                                     d->flags & ~CM3_FLAG_FUSED_TICKS, true, true});
 }
 
 template <typename R>
@@ -2142,14 +1962,13 @@ static int particle_rollout(const cm3_particle_desc *d, const cm3_particle_traj 
     CM3_REQUIRE(t->state_live && t->episode, "rollout: live_record needs state_live / goals_live and the episode counters");
     CM3_REQUIRE(((uintptr_t)t->live_record & (kRecBytes - 1)) == 0, "rollout: live_record must be 128-byte aligned");
     CM3_REQUIRE(d->env_offset >= 0 && d->env_count >= 0 && (int64_t)d->env_offset + d->env_count <= d->n_envs, "env_offset / env_count");
-#define CM3_RECORD_PACK(NA)                                                                                                        \
-  hipLaunchKernelGGL(k_particle_record_pack<NA>, dim3(rec_blocks), dim3(256), 0, (hipStream_t)stream, (const float4 *)t->state_live, \
-                     (const float2 *)t->goals_live, (const int2 *)t->meta, (const int32_t *)t->episode, (uint4 *)t->live_record,     \
-                     (uint32_t)d->n_envs, rec_e0, rec_en, d->env_id_base, d->seed)
-    if (d->n_agents == 2) CM3_RECORD_PACK(2);
-    else if (d->n_agents == 3) CM3_RECORD_PACK(3);
-    else CM3_RECORD_PACK(4);
-#undef CM3_RECORD_PACK
+    const int packed = with_agents<2, 4>(d->n_agents, [&](auto n) {
+      hipLaunchKernelGGL(k_particle_record_pack<decltype(n)::value>, dim3(rec_blocks), dim3(256), 0, (hipStream_t)stream,
+                         (const float4 *)t->state_live, (const float2 *)t->goals_live, (const int2 *)t->meta, (const int32_t *)t->episode,
+                         (uint4 *)t->live_record, (uint32_t)d->n_envs, rec_e0, rec_en, d->env_id_base, d->seed);
+      return CM3_OK;
+    });
+    if (packed != CM3_OK) return packed;
     CM3_HIP_CHECK(hipGetLastError());
   }
   for (int k = 0; k < n_ticks; ++k) {
@@ -2187,14 +2006,13 @@ static int particle_rollout(const cm3_particle_desc *d, const cm3_particle_traj 
     if (rc != CM3_OK) return rc;
   }
   if (rec) {
-#define CM3_RECORD_UNPACK(NA)                                                                                                      \
-  hipLaunchKernelGGL(k_particle_record_unpack<NA>, dim3(rec_blocks), dim3(256), 0, (hipStream_t)stream, (const uint4 *)t->live_record, \
-                     (float4 *)t->state_live, (float2 *)t->goals_live, (int2 *)t->meta, (int32_t *)t->episode, (uint32_t)d->n_envs,  \
-                     rec_e0, rec_en)
-    if (d->n_agents == 2) CM3_RECORD_UNPACK(2);
-    else if (d->n_agents == 3) CM3_RECORD_UNPACK(3);
-    else CM3_RECORD_UNPACK(4);
-#undef CM3_RECORD_UNPACK
+    const int unpacked = with_agents<2, 4>(d->n_agents, [&](auto n) {
+      hipLaunchKernelGGL(k_particle_record_unpack<decltype(n)::value>, dim3(rec_blocks), dim3(256), 0, (hipStream_t)stream,
+                         (const uint4 *)t->live_record, (float4 *)t->state_live, (float2 *)t->goals_live, (int2 *)t->meta,
+                         (int32_t *)t->episode, (uint32_t)d->n_envs, rec_e0, rec_en);
+      return CM3_OK;
+    });
+    if (unpacked != CM3_OK) return unpacked;
     CM3_HIP_CHECK(hipGetLastError());
   }
   return CM3_OK;
@@ -2205,37 +2023,8 @@ static int particle_rollout(const cm3_particle_desc *d, const cm3_particle_traj 
 
 #ifdef CM3_PARTICLE_ILP_TU
 namespace cm3 {
-template <int N> static int ilp_pairs_n(const ParticleParams &p, int w, hipStream_t s) {
-  return w == 1 ? launch_pairs<float, N, 1>(p, s) : launch_pairs<float, N, kSharedEnvWaves>(p, s);
-}
-template <int N> static int ilp_agents_n(const ParticleParams &p, int w, hipStream_t s) {
-  return w == 1 ? launch_agents<float, N, 1>(p, s) : launch_agents<float, N, kSharedEnvWaves>(p, s);
-}
-int particle_ilp_launch_pairs_f32(const ParticleParams &p, int n_agents, int w, hipStream_t s) {
-  switch (n_agents) {
-    case 2: return ilp_pairs_n<2>(p, w, s);
-    case 3: return ilp_pairs_n<3>(p, w, s);
-    case 4: return ilp_pairs_n<4>(p, w, s);
-    case 5: return ilp_pairs_n<5>(p, w, s);
-    case 6: return ilp_pairs_n<6>(p, w, s);
-    case 7: return ilp_pairs_n<7>(p, w, s);
-    case 8: return ilp_pairs_n<8>(p, w, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", n_agents);
-}
-int particle_ilp_launch_agents_f32(const ParticleParams &p, int n_agents, int w, hipStream_t s) {
-  switch (n_agents) {
-    case 2: return ilp_agents_n<2>(p, w, s);
-    case 3: return ilp_agents_n<3>(p, w, s);
-    case 4: return ilp_agents_n<4>(p, w, s);
-    case 5: return ilp_agents_n<5>(p, w, s);
-    case 6: return ilp_agents_n<6>(p, w, s);
-    case 7: return ilp_agents_n<7>(p, w, s);
-    case 8: return ilp_agents_n<8>(p, w, s);
-    case 9: return ilp_agents_n<9>(p, w, s);
-    case 10: return ilp_agents_n<10>(p, w, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", n_agents);
+int particle_ilp_launch_f32(const StepPlan &pl, const ParticleParams &p, int n_agents, hipStream_t stream) {
+  return with_agents<2, CM3_MAX_AGENTS>(n_agents, [&](auto n) { return launch_step<float, decltype(n)::value>(pl, p, stream); });
 }
 }  // namespace cm3
 #define CM3_NO_ENTRY_POINTS 1

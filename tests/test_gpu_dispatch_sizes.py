@@ -1,6 +1,6 @@
 """GPU: the SIZE-GATED instantiations of the particle step kernels.
 
-`kernel="auto"` (cm3::launch_n, csrc/particle.hip) chooses a build of one template from (N, E): the mapping (lane per pair /
+`kernel="auto"` (cm3::plan_step, csrc/particle_plan.h) chooses a build of one template from (N, E): the mapping (lane per pair /
 per agent / two lanes per agent / per env), waves per workgroup, the observation store policy (plain / non-temporal /
 write-through), the max-ILP translation unit, the early-store variant.  Every crossover of that table is exercised here at one
 size just below and one just above it, and the test ASSERTS WHICH BUILD RAN (cm3_last_kernel_variant, ABI 5) against an
@@ -28,7 +28,7 @@ gpu = pytest.mark.gpu       # (the table-scan test below needs no GPU and also r
 CFG = {2: "particle_stage2_merge.json", 3: "particle_merge8.json", 4: "particle_stage2_cross.json", 5: "particle_merge8.json",
        6: "particle_merge8.json", 7: "particle_merge8.json", 8: "particle_merge8.json", 9: "particle_ring10.json",
        10: "particle_ring10.json"}
-ONE_WAVE_MAX = 128 * 1024          # launch_n: lane-per-env runs one wave per workgroup up to here, four above
+ONE_WAVE_MAX = 128 * 1024          # kEnvOneWaveMaxEnvs: lane-per-env runs one wave per workgroup up to here, four above
 WT_MIN = 3 << 20                   # kWtMinObsBytes
 ILP_MAX_WAVES = 16384              # kIlpMaxWaves
 
@@ -41,7 +41,7 @@ def _pow2ceil(v):
 
 
 def expected_variant(N, E, forced=None):
-    """Restatement of cm3::launch_n / launch_pairs / launch_agents / launch_one for a float32 in-place step launch of E envs
+    """Restatement of cm3::plan_step / plan_launch (csrc/particle_plan.h) for a float32 in-place step launch of E envs
     (n_ticks = 1, no streaming flag): the fields of cm3_last_kernel_variant() that the choice determines."""
     NO = max(N - 1, 1)
     obs_bytes = E * N * NO * 16

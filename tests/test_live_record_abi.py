@@ -23,6 +23,11 @@ def _desc(n_agents, n_envs, flags):
     (4, 4096, GEN, 8, 0), (5, 4096, GEN, 4, 0), (1, 4096, GEN, 4, 0),
     (4, 4096, 0, 4, 0), (4, 4096, GEN | FUSED, 4, 0), (4, 4096, GEN | AGENT, 4, 0), (4, 4096, GEN | ENV, 4, 0),
     (2, 1 << 25, GEN | PAIR, 4, 0),                               # 32-bit byte offsets into the record array
+    # a forced pair mapping whose obs_others reaches 4 GiB (N = 4: from 22 369 622 envs): the record applies where every record
+    # condition holds -- the launch then names the limit -- and nowhere else
+    (4, 23000000, GEN | PAIR, 4, 1), (4, 23000000, PAIR, 4, 0), (4, 23000000, GEN | PAIR | FUSED, 4, 0), (4, 23000000, GEN | PAIR, 8, 0),
+    (8, 23000000, GEN | PAIR, 4, 0), (5, 23000000, GEN | PAIR, 4, 0), (4, 34000000, GEN | PAIR, 4, 0), (3, 100000000, GEN | PAIR, 4, 0),
+    (4, 23000000, GEN, 4, 0), (4, 4096, GEN | PAIR | ENV, 4, 0),
 ])
 def test_live_record_applies(n, e, flags, real, want):
     assert _lib.lib().cm3_particle_live_record_applies(ctypes.byref(_desc(n, e, flags)), real) == want
@@ -30,12 +35,21 @@ def test_live_record_applies(n, e, flags, real, want):
 
 @pytest.mark.parametrize("n,flags,fn", [(5, GEN, "cm3_particle_rollout_f32"), (4, GEN | FUSED, "cm3_particle_rollout_f32"),
                                         (4, GEN, "cm3_particle_rollout_f64"), (4, GEN | FUSED, "cm3_particle_rollout_f64")])
-def test_rollout_refuses_a_record_it_cannot_use(n, flags, fn):
+def test_rollout_refuses_a_record_it_cannot_use(n, flags, fn, e=64):
     h = _lib.lib()
     t = _lib.ParticleTraj()
     for name in ("state", "goals", "obs_others", "actions", "reward_n", "reward", "done", "meta", "episode", "state_live",
                  "goals_live", "live_record"):
         setattr(t, name, 0x1000)          # never dereferenced: the call fails on its arguments
     t.state_stride = t.goals_stride = 64
-    rc = getattr(h, fn)(ctypes.byref(_desc(n, 64, flags)), ctypes.byref(t), 2, None)
+    rc = getattr(h, fn)(ctypes.byref(_desc(n, e, flags)), ctypes.byref(t), 2, None)
     assert rc == -1 and b"live_record" in h.cm3_last_error()
+    assert e == 64 or b"live_record does not apply" in h.cm3_last_error()
+
+
+@pytest.mark.parametrize("n,flags,fn", [(5, GEN, "cm3_particle_rollout_f32"), (4, GEN | FUSED, "cm3_particle_rollout_f32"),
+                                        (4, GEN, "cm3_particle_rollout_f64"), (4, 0, "cm3_particle_rollout_f32"),
+                                        (8, GEN, "cm3_particle_rollout_f32")])
+def test_rollout_refuses_such_a_record_beyond_4_gib_before_any_launch_too(n, flags, fn):
+    """a forced pair mapping whose obs_others reaches 4 GiB: the record is refused first, by name, not the size by the launch"""
+    test_rollout_refuses_a_record_it_cannot_use(n, flags | PAIR, fn, e=23000000)

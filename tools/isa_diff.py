@@ -24,6 +24,7 @@ def kernels(path):
         if not t or t.startswith(('.', ';')):
             continue
         t = re.sub(r'\.LBB\d+_\d+', 'L', t)
+        t = re.sub(r'\.Lpost_getpc\d+', 'P', t)     # (long-branch labels are numbered per FILE: they move with the order kernels are emitted in)
         t = re.sub(r';.*', '', t).strip()
         if t:
             out[name].append(t)

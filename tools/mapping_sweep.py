@@ -2,7 +2,7 @@
 """Which particle step-kernel mapping (lane per env / per ordered pair / per agent) is fastest for (n_agents, n_envs): in-place
 stepping, 33-tick hipGraphs, HIP-event time per launch, the three mappings alternated, best of `reps` rounds.  Run on the GPU box:
     python tools/mapping_sweep.py [N ...]
-Prints one row per (N, E) with the three times, the winner and what `auto` (the library's table in particle.hip, launch_n) takes."""
+Prints one row per (N, E) with the three times, the winner and what `auto` (the library's table in csrc/particle_plan.h, plan_step) takes."""
 import os
 import sys
 

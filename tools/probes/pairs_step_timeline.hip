@@ -30,11 +30,13 @@ int main(int argc, char **argv) {
   d.flags = CM3_FLAG_AUTO_RESET | CM3_FLAG_GEN_ACTIONS;
   cm3::ParticleParams pp;
   cm3::fill_params(&d, &b, cm3::kStep, nullptr, pp);
-  for (int t = 0; t < 50; ++t) cm3::launch_pairs<float, 4, 4>(pp, s);   // mid-episode (tick 50 mod 33 = 17)
+  cm3::StepPlan pl;   // the lane-per-pair build with 4 waves per workgroup, whatever the size
+  cm3::plan_launch(cm3::step_shape<float>(pp, N), cm3::kMapPairs, 4, pl);
+  for (int t = 0; t < 50; ++t) cm3::launch_step<float, 4>(pl, pp, s);   // mid-episode (tick 50 mod 33 = 17)
   hipStreamSynchronize(s);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   hipEventRecord(e0, s);
-  for (int t = 0; t < 330; ++t) cm3::launch_pairs<float, 4, 4>(pp, s);
+  for (int t = 0; t < 330; ++t) cm3::launch_step<float, 4>(pl, pp, s);
   hipEventRecord(e1, s); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   printf("pairs<4> W=4 E=%d: %.3f us per launch (eager back to back; stamped build)\n", E, ms * 1e3 / 330);

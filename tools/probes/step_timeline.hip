@@ -35,13 +35,12 @@ int main(int argc, char **argv) {
   cm3::fill_params(&d, &b, cm3::kStep, nullptr, pp);
   const char *variant[] = {"lane-per-env W=1", "pairs W=1", "pairs W=2", "pairs W=4"};
   for (int v = 0; v < 4; ++v) {
+    // a fixed mapping and workgroup size (the product's plans hold 1 and 4 waves: the 2-wave build is instantiated here)
+    cm3::StepPlan pl;
+    cm3::plan_launch(cm3::step_shape<float>(pp, 4), v == 0 ? cm3::kMapEnv : cm3::kMapPairs, v == 0 ? 1 : 1 << (v - 1), pl);
     auto launch = [&]() {
-      switch (v) {
-        case 0: cm3::launch_one<float, 4, 1>(pp, cm3::kStep, s); break;
-        case 1: cm3::launch_pairs<float, 4, 1>(pp, s); break;
-        case 2: cm3::launch_pairs<float, 4, 2>(pp, s); break;
-        case 3: cm3::launch_pairs<float, 4, 4>(pp, s); break;
-      }
+      if (v == 2) cm3::launch_variant<float, 4, cm3::kMapPairs, 2, false, cm3::kSpPlain, false, false, false>(pl, pp, s);
+      else cm3::launch_step<float, 4>(pl, pp, s);
     };
     const int nw = v == 0 ? waves : (E + 3) / 4;
     for (int t = 0; t < 40; ++t) launch();
