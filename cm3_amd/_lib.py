@@ -67,6 +67,17 @@ class TransitionCols(ctypes.Structure):
                                         "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
 
 
+class EpisodeRouteDesc(ctypes.Structure):
+    # (cm3_episode_route_desc: what cm3_episode_route_plan reads of a collection and of the dual buffer's two rings)
+    _fields_ = [("done", c_void_p), ("collisions", c_void_p), ("valid", c_void_p),
+                ("done_stride", c_size_t), ("collisions_stride", c_size_t), ("valid_stride", c_size_t),
+                ("n_ticks", c_int32), ("n_envs", c_int32), ("pending_depth", c_int32), ("synchronous", c_int32),
+                ("ring_idx", c_int64 * 2), ("ring_size", c_int64 * 2)]
+
+
+ROUTE_BAD, ROUTE_GOOD, ROUTE_PENDING, ROUTE_SKIP = 0, 1, 2, 255      # the values of the plan's `sel`
+
+
 # THE list of the 16 columns of a Checkers transition, each with the record of the trajectory it carries, in the field order of both
 # column structs below (kCkColumns in csrc/batch.hip is the same table); rollout.CHECKERS_ORDER and CheckersRollout.ORDER are its names
 CHECKERS_COLUMN_RECORDS = (
@@ -226,6 +237,12 @@ SYMBOLS = {
     "cm3_rows_scatter": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "cm3_rows_gather": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_void_p]),
     "cm3_rows_tile": (ctypes.c_int, [P(TileCol), c_int32, c_void_p]),
+    "cm3_episode_route_scratch_bytes": (c_size_t, [c_int32, c_int32]),
+    "cm3_episode_route_plan": (ctypes.c_int, [P(EpisodeRouteDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_size_t, c_void_p]),
+    "cm3_episode_route_plan_host": (ctypes.c_int, [P(EpisodeRouteDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cm3_transitions_route_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), c_void_p, c_size_t, c_int64, c_void_p, c_void_p,
+                                                 P(TransitionCols), c_int32, c_void_p]),
     "cm3_actor_checkers_packed_bytes": (c_size_t, []),
     "cm3_actor_checkers_pack": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), c_void_p, c_void_p]),
     "cm3_policy_rollout_checkers": (ctypes.c_int, [P(CheckersDesc), P(CheckersTraj), P(ActorCheckersDesc), P(ActorCheckersWeights),

@@ -102,6 +102,23 @@ struct TransParams {
   size_t n, E;
   size_t ring_start, ring_size;   // ring_size > 0: transition b goes to output row (ring_start + b) mod ring_size (a replay ring), else to row b
   int N, L;
+  static constexpr bool kRouted = false;
+};
+// The ROUTED whole-trajectory export (cm3_transitions_route_f32): transition b goes to row row[b] of column set sel[b] -- the two rings
+// and the pending store of the dual replay buffer -- or nowhere (sel[b] >= n_sets).  A second parameter struct, so that the plain
+// export keeps its kernel arguments, and with them its instruction stream, as they were.
+struct TransOut {
+  float *state, *obs, *reward_n, *reward, *next_state, *next_obs, *goals;
+  int32_t *actions;
+  uint8_t *done;
+};
+struct RouteParams : TransParams {
+  const uint8_t *sel;
+  const int64_t *row;
+  TransOut set[3];
+  uint32_t n_sets;
+  static constexpr const int64_t *tt = nullptr, *ee = nullptr;   // (hides TransParams': the routed export is a whole-trajectory one)
+  static constexpr bool kRouted = true;
 };
 
 template <typename T> __device__ __forceinline__ const T *tick_of(const T *base, size_t stride, int64_t t) {
@@ -125,13 +142,22 @@ struct TransUnit {
   void *dst;
   int bytes;   // 16, 8, 4, 1 (the done byte: written from the value already loaded), 0 (nothing: past the end)
 };
-__device__ __forceinline__ TransUnit trans_unit(const TransParams &p, size_t b_in, int v, int64_t t, size_t e, int N, int NV) {
+// u.dst: `plain` (the launch's one output column) as the plain export always computed it -- the statement the routed build discards
+// is the only one the plain build sees, which keeps its instruction stream -- or `routed`, from the column of the set the
+// transition's sel byte s names
+#define CM3_TRANS_DST(plain, routed) \
+  do { if constexpr (P::kRouted) u.dst = (routed); else u.dst = (plain); } while (0)
+#define CM3_TRANS_SET(field) (s == 0u ? p.set[0].field : s == 1u ? p.set[1].field : p.set[2].field)
+template <typename P> __device__ __forceinline__ TransUnit trans_unit(const P &p, size_t b_in, int v, int64_t t, size_t e, int N, int NV,
+                                                                      uint32_t s = 0u) {
   TransUnit u;
   u.alt = nullptr;
-  size_t b = b_in;                // output row
-  if (p.ring_size) {
-    b = p.ring_start + b_in;
-    b = b >= p.ring_size ? b - p.ring_size : b;
+  size_t b = b_in;                // output row (routed: row[b] already)
+  if constexpr (!P::kRouted) {
+    if (p.ring_size) {
+      b = p.ring_start + b_in;
+      b = b >= p.ring_size ? b - p.ring_size : b;
+    }
   }
   if (v < 2 * N) {
     const bool nxt = v >= N;
@@ -139,7 +165,8 @@ __device__ __forceinline__ TransUnit trans_unit(const TransParams &p, size_t b_i
     const float *src = nxt ? tick_of(p.state, p.st_state, t + 1) : tick_of(p.state, p.st_state, t);
     u.src = reinterpret_cast<const float4 *>(src) + ((size_t)i * p.E + e);
     if (nxt && p.term_state) u.alt = reinterpret_cast<const float4 *>(tick_of(p.term_state, p.st_term_state, t)) + ((size_t)i * p.E + e);
-    u.dst = reinterpret_cast<float4 *>(nxt ? p.o_next_state : p.o_state) + (b * N + i);
+    CM3_TRANS_DST(reinterpret_cast<float4 *>(nxt ? p.o_next_state : p.o_state) + (b * N + i),
+                  reinterpret_cast<float4 *>(nxt ? CM3_TRANS_SET(next_state) : CM3_TRANS_SET(state)) + (b * N + i));
     u.bytes = 16;
     return u;
   }
@@ -150,7 +177,8 @@ __device__ __forceinline__ TransUnit trans_unit(const TransParams &p, size_t b_i
     const float *src = nxt ? tick_of(p.obs, p.st_obs, t + 1) : tick_of(p.obs, p.st_obs, t);
     u.src = reinterpret_cast<const float4 *>(src) + (e * NV + k);
     if (nxt && p.term_obs) u.alt = reinterpret_cast<const float4 *>(tick_of(p.term_obs, p.st_term_obs, t)) + (e * NV + k);
-    u.dst = reinterpret_cast<float4 *>(nxt ? p.o_next_obs : p.o_obs) + (b * NV + k);
+    CM3_TRANS_DST(reinterpret_cast<float4 *>(nxt ? p.o_next_obs : p.o_obs) + (b * NV + k),
+                  reinterpret_cast<float4 *>(nxt ? CM3_TRANS_SET(next_obs) : CM3_TRANS_SET(obs)) + (b * NV + k));
     u.bytes = 16;
     return u;
   }
@@ -158,38 +186,40 @@ __device__ __forceinline__ TransUnit trans_unit(const TransParams &p, size_t b_i
   if (v < N) {   // goals [slot][N][E][2]: the slot that last wrote this env's landmarks (goal_slot), or the only one (stride 0)
     const int64_t gs = p.goal_slot ? (int64_t)tick_of(p.goal_slot, p.st_goal_slot, t)[e] : t;
     u.src = reinterpret_cast<const float2 *>(tick_of(p.goals, p.st_goals, gs)) + ((size_t)v * p.E + e);
-    u.dst = reinterpret_cast<float2 *>(p.o_goals) + (b * N + v);
+    CM3_TRANS_DST(reinterpret_cast<float2 *>(p.o_goals) + (b * N + v), reinterpret_cast<float2 *>(CM3_TRANS_SET(goals)) + (b * N + v));
     u.bytes = 8;
     return u;
   }
   v -= N;
   if (v < N) {
     u.src = tick_of(p.actions, p.st_actions, t) + (e * N + v);
-    u.dst = p.o_actions + (b * N + v);
+    CM3_TRANS_DST(p.o_actions + (b * N + v), CM3_TRANS_SET(actions) + (b * N + v));
     u.bytes = 4;
     return u;
   }
   v -= N;
   if (v < N) {
     u.src = tick_of(p.reward_n, p.st_reward_n, t) + (e * N + v);
-    u.dst = p.o_reward_n + (b * N + v);
+    CM3_TRANS_DST(p.o_reward_n + (b * N + v), CM3_TRANS_SET(reward_n) + (b * N + v));
     u.bytes = 4;
     return u;
   }
   v -= N;
   if (v == 0) {
     u.src = tick_of(p.reward, p.st_reward, t) + e;
-    u.dst = p.o_reward + b;
+    CM3_TRANS_DST(p.o_reward + b, CM3_TRANS_SET(reward) + b);
     u.bytes = 4;
     return u;
   }
   u.src = nullptr;
-  u.dst = p.o_done + b;
+  CM3_TRANS_DST(p.o_done + b, CM3_TRANS_SET(done) + b);
   u.bytes = 1;
   return u;
 }
+#undef CM3_TRANS_DST
+#undef CM3_TRANS_SET
 
-__global__ void __launch_bounds__(256) k_transitions_gather(const TransParams p) {
+template <typename P> __global__ void __launch_bounds__(256) k_transitions_gather(const P p) {
   constexpr int K = 4;
   const int N = p.N, NV = N * p.L / 4;
   const uint32_t U = (uint32_t)(2 * N + 2 * NV + 3 * N + 2);
@@ -200,6 +230,8 @@ __global__ void __launch_bounds__(256) k_transitions_gather(const TransParams p)
     int64_t tt[K];
     int vv[K];
     uint8_t dd[K];
+    [[maybe_unused]] int64_t rr[K];      // routed: the transition's output row and its column set
+    [[maybe_unused]] uint32_t ss[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const size_t g = g0 + (size_t)k * stride, gc = g < total ? g : total - 1;
@@ -231,6 +263,10 @@ __global__ void __launch_bounds__(256) k_transitions_gather(const TransParams p)
       // (tt == NULL: every transition of the trajectory in time-major order, b = t E + e -- no index arrays to build or read)
       tt[k] = p.tt ? p.tt[b] : (int64_t)(small ? (size_t)((uint32_t)b / (uint32_t)p.E) : b / p.E);
       ee[k] = p.tt ? (size_t)p.ee[b] : b - (size_t)tt[k] * p.E;
+      if constexpr (P::kRouted) {   // (requested with everything else of the unit: only the STORE waits for them)
+        rr[k] = p.row[b];
+        ss[k] = p.sel[b];
+      }
     }
     TransUnit u[K];
     uint4 val[K];
@@ -238,7 +274,12 @@ __global__ void __launch_bounds__(256) k_transitions_gather(const TransParams p)
     // their data can be requested: the byte is requested for those alone, every other unit's data in the same round trip
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      u[k] = trans_unit(p, bb[k], vv[k] < 0 ? 0 : vv[k], tt[k], ee[k], N, NV);
+      if constexpr (P::kRouted) {
+        u[k] = trans_unit(p, (size_t)rr[k], vv[k] < 0 ? 0 : vv[k], tt[k], ee[k], N, NV, ss[k]);
+        if (ss[k] >= p.n_sets) { u[k].bytes = 0; u[k].alt = nullptr; }     // skipped: nothing loaded, nothing stored
+      } else {
+        u[k] = trans_unit(p, bb[k], vv[k] < 0 ? 0 : vv[k], tt[k], ee[k], N, NV);
+      }
       if (vv[k] < 0) u[k].bytes = 0;
       dd[k] = 0;
       if (u[k].alt || u[k].bytes == 1) dd[k] = tick_of(p.done, p.st_done, tt[k])[ee[k]];
@@ -902,6 +943,37 @@ static int ck_gather_launch(const char *entry, const char *cols_what, const char
   return CM3_OK;
 }
 
+// ---- host side shared by cm3_transitions_gather_f32 and cm3_transitions_route_f32 --------------------------------------------------
+static int trans_check(const cm3_particle_desc *desc, const cm3_particle_traj *traj) {
+  CM3_REQUIRE(desc->n_agents >= 1 && desc->n_agents <= CM3_MAX_AGENTS, "n_agents out of range");
+  CM3_REQUIRE(traj->state && traj->obs_others && traj->actions && traj->reward_n && traj->reward && traj->done && traj->goals,
+              "trajectory base pointers are required");
+  CM3_REQUIRE((traj->term_state == nullptr) == (traj->term_obs_others == nullptr), "term_state and term_obs_others: both or neither");
+  return CM3_OK;
+}
+static void trans_sources(TransParams &p, const cm3_particle_desc *desc, const cm3_particle_traj *traj, const int32_t *goal_slot,
+                          size_t goal_slot_stride, int64_t n) {
+  p.state = (const float *)traj->state;             p.st_state = traj->state_stride;
+  p.obs = (const float *)traj->obs_others;          p.st_obs = traj->obs_others_stride;
+  p.actions = traj->actions;                        p.st_actions = traj->actions_stride;
+  p.reward_n = (const float *)traj->reward_n;       p.st_reward_n = traj->reward_n_stride;
+  p.reward = (const float *)traj->reward;           p.st_reward = traj->reward_stride;
+  p.done = traj->done;                              p.st_done = traj->done_stride;
+  p.term_state = (const float *)traj->term_state;   p.st_term_state = traj->term_state_stride;
+  p.term_obs = (const float *)traj->term_obs_others; p.st_term_obs = traj->term_obs_others_stride;
+  p.goals = (const float *)traj->goals;             p.st_goals = traj->goals_stride;
+  p.goal_slot = goal_slot;                          p.st_goal_slot = goal_slot_stride;
+  p.n = (size_t)n;
+  p.E = (size_t)desc->n_envs;
+  p.N = desc->n_agents;
+  p.L = 4 * (desc->n_agents > 1 ? desc->n_agents - 1 : 1);
+}
+static unsigned trans_blocks(const TransParams &p) {
+  const size_t units = p.n * (size_t)(2 * p.N + 2 * (p.N * p.L / 4) + 3 * p.N + 2);
+  size_t blocks = (units + 4 * 256 - 1) / (4 * 256);     // four units per lane
+  return (unsigned)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks));
+}
+
 }  // namespace cm3
 
 extern "C" {
@@ -985,25 +1057,13 @@ int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle
   CM3_REQUIRE(desc && traj && out && ((tt == nullptr) == (ee == nullptr)), "null argument (tt and ee: both or neither)");
   CM3_REQUIRE(n >= 0, "n must be >= 0");
   if (n == 0) return CM3_OK;      // (before the pointer checks: the columns of an empty batch are null -- ADVICE r5)
-  CM3_REQUIRE(desc->n_agents >= 1 && desc->n_agents <= CM3_MAX_AGENTS, "n_agents out of range");
-  CM3_REQUIRE(traj->state && traj->obs_others && traj->actions && traj->reward_n && traj->reward && traj->done && traj->goals,
-              "trajectory base pointers are required");
-  CM3_REQUIRE((traj->term_state == nullptr) == (traj->term_obs_others == nullptr), "term_state and term_obs_others: both or neither");
+  if (int rc = trans_check(desc, traj)) return rc;
   CM3_REQUIRE(out->state && out->obs_others && out->actions && out->reward && out->reward_n && out->next_state && out->next_obs_others &&
                   out->done && out->goals,
               "output columns are required");
   TransParams p;
   memset(&p, 0, sizeof(p));
-  p.state = (const float *)traj->state;             p.st_state = traj->state_stride;
-  p.obs = (const float *)traj->obs_others;          p.st_obs = traj->obs_others_stride;
-  p.actions = traj->actions;                        p.st_actions = traj->actions_stride;
-  p.reward_n = (const float *)traj->reward_n;       p.st_reward_n = traj->reward_n_stride;
-  p.reward = (const float *)traj->reward;           p.st_reward = traj->reward_stride;
-  p.done = traj->done;                              p.st_done = traj->done_stride;
-  p.term_state = (const float *)traj->term_state;   p.st_term_state = traj->term_state_stride;
-  p.term_obs = (const float *)traj->term_obs_others; p.st_term_obs = traj->term_obs_others_stride;
-  p.goals = (const float *)traj->goals;             p.st_goals = traj->goals_stride;
-  p.goal_slot = goal_slot;                          p.st_goal_slot = goal_slot_stride;
+  trans_sources(p, desc, traj, goal_slot, goal_slot_stride, n);
   p.tt = tt;
   p.ee = ee;
   p.o_state = (float *)out->state;
@@ -1015,17 +1075,44 @@ int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle
   p.o_next_obs = (float *)out->next_obs_others;
   p.o_done = out->done;
   p.o_goals = (float *)out->goals;
-  p.n = (size_t)n;
   if (int rc = ring_optional("transition columns", out->ring_start, out->ring_size, n)) return rc;
   p.ring_start = (size_t)out->ring_start;
   p.ring_size = (size_t)out->ring_size;
-  p.E = (size_t)desc->n_envs;
-  p.N = desc->n_agents;
-  p.L = 4 * (desc->n_agents > 1 ? desc->n_agents - 1 : 1);
-  const size_t units = (size_t)n * (size_t)(2 * p.N + 2 * (p.N * p.L / 4) + 3 * p.N + 2);
-  size_t blocks = (units + 4 * 256 - 1) / (4 * 256);     // four units per lane
-  blocks = blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks);
-  hipLaunchKernelGGL(k_transitions_gather, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k_transitions_gather<TransParams>, dim3(trans_blocks(p)), dim3(256), 0, (hipStream_t)stream, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+int cm3_transitions_route_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj, const int32_t *goal_slot,
+                              size_t goal_slot_stride, int64_t n, const uint8_t *sel, const int64_t *row,
+                              const cm3_transition_cols *sets, int32_t n_sets, void *stream) {
+  using namespace cm3;
+  CM3_REQUIRE(desc && traj && sets, "transitions_route: null argument");
+  CM3_REQUIRE(n >= 0, "n must be >= 0");
+  CM3_REQUIRE(n_sets >= 1 && n_sets <= 3, "transitions_route: 1..3 column sets");
+  if (n == 0) return CM3_OK;
+  CM3_REQUIRE(sel && row, "transitions_route: sel and row are required");
+  if (int rc = trans_check(desc, traj)) return rc;
+  CM3_REQUIRE(desc->n_envs >= 1 && n % desc->n_envs == 0, "transitions_route: n must be whole ticks (a multiple of n_envs)");
+  RouteParams p;
+  memset(&p, 0, sizeof(p));
+  trans_sources(p, desc, traj, goal_slot, goal_slot_stride, n);
+  p.sel = sel;
+  p.row = row;
+  p.n_sets = (uint32_t)n_sets;
+  for (int k = 0; k < n_sets; ++k) {
+    const cm3_transition_cols &o = sets[k];
+    CM3_REQUIRE(o.state && o.obs_others && o.actions && o.reward && o.reward_n && o.next_state && o.next_obs_others && o.done && o.goals,
+                "transitions_route: column set %d: output columns are required", k);
+    CM3_REQUIRE(((uintptr_t)o.state | (uintptr_t)o.obs_others | (uintptr_t)o.next_state | (uintptr_t)o.next_obs_others) % 16 == 0 &&
+                    (uintptr_t)o.goals % 8 == 0 && ((uintptr_t)o.actions | (uintptr_t)o.reward | (uintptr_t)o.reward_n) % 4 == 0,
+                "transitions_route: column set %d is not aligned to the units the kernel stores", k);
+    TransOut &t = p.set[k];
+    t.state = (float *)o.state; t.obs = (float *)o.obs_others; t.actions = o.actions; t.reward = (float *)o.reward;
+    t.reward_n = (float *)o.reward_n; t.next_state = (float *)o.next_state; t.next_obs = (float *)o.next_obs_others; t.done = o.done;
+    t.goals = (float *)o.goals;
+  }
+  hipLaunchKernelGGL(k_transitions_gather<RouteParams>, dim3(trans_blocks(p)), dim3(256), 0, (hipStream_t)stream, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }

@@ -31,7 +31,7 @@ pids+=($!)
 # Checkers: max-ILP scheduling throughout (C3 4.26 -> 4.16 us per tick; 2^16 .. 2^20 envs within 1 %)
 "${HIPCC}" ${FLAGS} -mllvm -amdgpu-kernarg-preload-count=16 -mllvm -amdgpu-sched-strategy=max-ilp -c "${HERE}/checkers.hip" -o "${OBJ}/checkers.o" &
 pids+=($!)
-for f in util advantage batch; do
+for f in util advantage batch episode_route; do
   "${HIPCC}" ${FLAGS} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -c "${HERE}/${f}.hip" -o "${OBJ}/${f}.o" &
   pids+=($!)
 done
@@ -52,7 +52,7 @@ for p in "${pids[@]}"; do wait "$p"; done
 # the matrix units' diagnostics went to their resource-usage files with the remarks: show what is not a remark
 for f in actor actor_checkers policy policy_f64 policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
 OBJS=("${OBJ}/particle_f32.o" "${OBJ}/particle_f32_ilp.o" "${OBJ}/particle_f64.o" "${OBJ}/checkers.o" "${OBJ}/util.o" "${OBJ}/advantage.o"
-      "${OBJ}/batch.o" "${OBJ}/actor.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_checkers.o")
+      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_checkers.o")
 if [ "${CM3_SKIP_ISA_LINT:-0}" != 1 ]; then
   python3 "${HERE}/../../tools/isa_lint.py" "${OBJS[@]}"     # (the objects of THIS build, not whatever else sits in ${OBJ})
 fi

@@ -293,11 +293,15 @@ class DeviceDualReplayBuffer(object):
     """replay_buffer_dual.Replay_Buffer: memory_1 holds transitions of "bad" episodes, memory_2 the others; a batch
     takes half from each when both have enough, else everything from the smaller one and the remainder from the larger
     (replay_buffer_dual.py:40-63).  `add` splits a whole batch by its flag column on the device: ranks by a prefix sum, ring
-    positions for both memories, one scatter launch per memory -- one host read (the number of bad transitions)."""
+    positions for both memories, one scatter launch per memory -- one host read (the number of bad transitions).
+    `add_rollout` is the reference's own feeding (train_onpolicy.py:300-356): WHOLE episodes, each contiguous and in time order, into
+    the memory its flag at the episode's end names; the tail of an episode that is still running waits in a pending store."""
 
     def __init__(self, size=int(5e4), device="cuda:0"):
         self.mem1 = DeviceReplayBuffer(size, device)
         self.mem2 = DeviceReplayBuffer(size, device)
+        self._carry = None       # continuous add_rollout: the env batch, its pending store (P rows per env) and pend_len [2][E]
+        self._work = {}          # (T, E, P) -> the plan's device buffers
 
     def add(self, cols, is_bad):
         """is_bad: bool [B] per transition (all transitions of an episode carry the episode's flag; particle:
@@ -316,6 +320,109 @@ class DeviceDualReplayBuffer(object):
             pos = torch.where(keep, (rank + mem.ring.idx) % mem.maxsize, torch.full_like(rank, -1))
             mem.add_at(cols, pos.contiguous(), n)
 
+    # ---- whole episodes, straight from the trajectory (csrc/episode_route.hip, k_transitions_gather<RouteParams>) ----------------
+    @property
+    def pending(self):
+        """Transitions add_rollout holds back: those of episodes that were still running at the end of the last chunk (a host read)."""
+        return 0 if self._carry is None or self._carry["zero"] else int(self._carry["pend_len"][0].sum())
+
+    def drop_pending(self):
+        """Forgets the held-back transitions: for a caller that resets the envs between two chunks (their episodes never end), or
+        that goes on with another env batch."""
+        self._carry = None
+
+    def _route_buffers(self, T, E, P):
+        key = (T, E, P)
+        if key not in self._work:
+            dev = self.mem1.device
+            nbytes = int(_lib.lib().cm3_episode_route_scratch_bytes(T, E))
+            if nbytes == 0:
+                raise Cm3Error("add_rollout: %d ticks x %d envs are more than one routing plan takes" % (T, E))
+            self._work = {key: dict(sel=torch.empty(T * E, dtype=torch.uint8, device=dev), row=torch.empty(T * E, dtype=torch.int64, device=dev),
+                                    flush=torch.empty(2, max(P, 1) * E, dtype=torch.int64, device=dev),
+                                    counts=torch.zeros(2, dtype=torch.int64, device=dev),
+                                    scratch=torch.empty(nbytes // 8, dtype=torch.int64, device=dev))}
+        return self._work[key]
+
+    def add_rollout(self, rollout):
+        """All transitions of a ParticleRollout collection (float32, record_collisions=True), as replay_buffer_dual.Replay_Buffer
+        receives them from the reference's trainers: whole episodes.  Episodes are taken in the order (end tick, env index) -- the
+        order in which a host walking `for t: for e:` meets the done bytes; the episode that ends at (t, e) goes, oldest transition
+        first and contiguously, to memory_1 when collisions[t][e] != 0, else to memory_2, each transition one sequential add (wrap at
+        maxsize; when one call adds more than a ring holds the newest survive).
+        Continuous collection: the transitions of an episode still running at the chunk's last tick enter neither ring.  They wait in
+        a PENDING STORE (max_steps rows per env) and are added, in front of the rest of their episode, by the later call in which the
+        episode ends -- so successive calls must collect from the same env batch (checked: the env object and its size);
+        drop_pending() forgets them.  Episode-synchronous collection: only valid transitions exist, an env that has not finished by
+        the last tick counts as ending there with its collision count so far (ParticleRollout.episode_is_bad), nothing pends.
+        Device side: the routing plan (cm3_episode_route_plan: 5 launches), two cm3_rows_scatter that flush pending rows, ONE routed
+        export launch that reads every transition once (no dense copy of the chunk), then ONE host read (the two counts)."""
+        if not (hasattr(rollout, "route_into") and hasattr(rollout, "episode_is_bad")):
+            raise Cm3Error("a dual replay buffer splits by the episodes' flag (scenario.collisions != 0, train_onpolicy.py:356): that is a "
+                           "ParticleRollout's")
+        if not rollout.kernel_export:
+            raise Cm3Error("add_rollout needs a float32 trajectory (the export kernel); use add() with as_reference_batch()")
+        if rollout.collisions is None:
+            raise Cm3Error("the dual buffer's flag needs the per-tick collision counts (record_collisions=True)")
+        if not rollout.collected:
+            raise Cm3Error("add_rollout: nothing collected yet")
+        env, T, dev = rollout.env, rollout.T, self.mem1.device
+        if torch.device(env.device) != dev:
+            raise Cm3Error("add_rollout: the buffer lives on %s, the rollout's envs on %s" % (dev, env.device))
+        E, sync = env.E, not rollout.auto_reset
+        rings = []
+        for mem in (self.mem1, self.mem2):
+            cols = rollout.empty_columns(mem.maxsize, zero=True) if mem.cols is None else mem.cols
+            rollout._check_columns(cols, mem.maxsize, "add_rollout: a ring that add() allocated keeps separate v_local storage; the rings")
+            rings.append(cols)
+        carry = self._carry
+        if sync:
+            P, pend_in, pend_out, sets = 0, None, None, [(rings[0], self.mem1.maxsize), (rings[1], self.mem2.maxsize)]
+            valid = rollout.valid.to(torch.uint8).contiguous()
+        else:
+            if carry is None:
+                # (the pending store is as deep as the longest episode: pend_len[e] + the ticks to env e's next done never exceed it)
+                P = int(env.max_steps)
+                carry = dict(env=env, E=E, P=P, zero=True, store=rollout.empty_columns(P * E, zero=True),
+                             pend_len=[torch.zeros(E, dtype=torch.int32, device=dev), torch.zeros(E, dtype=torch.int32, device=dev)])
+            elif carry["env"] is not env or carry["E"] != E or int(env.max_steps) > carry["P"]:
+                raise Cm3Error("add_rollout: pending transitions belong to another env batch (successive chunks must come from the same "
+                               "envs: %d envs, max_steps <= %d); drop_pending() forgets them" % (carry["E"], carry["P"]))
+            P, valid = carry["P"], None
+            rollout._check_columns(carry["store"], P * E, "add_rollout: the pending store")
+            pend_in, pend_out = carry["pend_len"]
+            sets = [(rings[0], self.mem1.maxsize), (rings[1], self.mem2.maxsize), (carry["store"], P * E)]
+        if (T + P) * E >= 1 << 31:
+            raise Cm3Error("add_rollout: %d ticks and %d pending rows of %d envs are more than one routing plan takes" % (T, P, E))
+        w = self._route_buffers(T, E, P)
+        d = _lib.EpisodeRouteDesc()
+        d.done, d.done_stride = rollout.done.data_ptr(), E
+        d.collisions, d.collisions_stride = rollout.collisions.data_ptr(), E * 4
+        d.valid, d.valid_stride = _lib.ptr(valid), E
+        d.n_ticks, d.n_envs, d.pending_depth, d.synchronous = T, E, P, int(sync)
+        d.ring_idx[0], d.ring_idx[1], d.ring_size[0], d.ring_size[1] = self.mem1.idx, self.mem2.idx, self.mem1.maxsize, self.mem2.maxsize
+        stream = env._stream()
+        # (launch FIRST, keep the rings and advance after, as DeviceReplayBuffer.add_rollout: whatever raises leaves idx / len and the
+        # current pend_len as they were -- the plan writes the new pend_len into the spare array)
+        _lib.check(_lib.lib().cm3_episode_route_plan(ctypes.byref(d), _lib.ptr(pend_in), _lib.ptr(pend_out), w["sel"].data_ptr(),
+                                                     w["row"].data_ptr(), w["flush"].data_ptr(), w["counts"].data_ptr(),
+                                                     w["scratch"].data_ptr(), w["scratch"].numel() * 8, stream))
+        if not sync and not carry["zero"]:
+            # BEFORE the export: it may overwrite pending rows of an env whose next episode starts in this chunk
+            for c in (0, 1):
+                pairs = [(rings[c][k], carry["store"][k]) for k in rings[c] if k not in rollout.ALIASES]
+                _lib.rows_scatter(pairs, P * E, stream, dst_row=w["flush"][c])
+        rollout.route_into(sets, w["sel"], w["row"])
+        n1, n2 = w["counts"].tolist()                     # the one host read
+        self.mem1.cols, self.mem2.cols = rings
+        self.mem1.ring.plan_add(n1)
+        self.mem2.ring.plan_add(n2)
+        if not sync:
+            carry["pend_len"].reverse()
+            carry["zero"] = False
+            self._carry = carry
+        return n1, n2
+
     def sample_batch(self, size, generator=None):
         n1, n2 = len(self.mem1), len(self.mem2)
         k1, all1, k2, all2 = dual_take(n1, n2, size)
@@ -327,7 +434,7 @@ class DeviceDualReplayBuffer(object):
         return _cat(a, b)
 
 
-def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None, **collect_kwargs):
+def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None, whole_episodes=False, **collect_kwargs):
     """The off-policy cadence of alg/train_offpolicy.py:309-356 (the trainer the reference's README routes Checkers to): every
     transition goes into a PERSISTENT replay buffer (:337-346), and every `steps_per_train` env steps (:348) a batch is sampled
     from it (:350) for a training step.  Vectorised: `rollout` (a ParticleRollout / CheckersRollout in continuous mode with
@@ -336,14 +443,21 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
     one batch is sampled -- yielded as device columns; `collect_kwargs` go to
     rollout.collect() (policy=..., epsilon=..., goals=... for Checkers; policy= a ParticleQmixAgent / CheckersQmixAgent is the
     QMIX baseline's collection, train_offpolicy.py:319 / :317 with use_qmix = 1).  The buffer outlives the chunks: old transitions are
-    overwritten only when it is full (replay_buffer.py:11-16)."""
+    overwritten only when it is full (replay_buffer.py:11-16).
+    whole_episodes=True (a DeviceDualReplayBuffer): the chunk goes in through buffer.add_rollout -- whole episodes in the order
+    (end tick, env), each in the memory its flag at its END names, unfinished tails carried to the next chunk: what the reference's
+    class holds.  The default splits every chunk at once by the flag so far (head and tail of an episode may part)."""
     dual = isinstance(buffer, DeviceDualReplayBuffer)
+    if whole_episodes and not dual:
+        raise Cm3Error("whole_episodes=True is the dual replay buffer's feeding (DeviceDualReplayBuffer.add_rollout)")
     if dual and not hasattr(rollout, "episode_is_bad"):
         raise Cm3Error("a dual replay buffer splits by the episodes' flag (scenario.collisions != 0, train_onpolicy.py:356): that is a "
                        "ParticleRollout's; use a DeviceReplayBuffer here")
     for _ in range(int(n_chunks)):
         rollout.collect(**collect_kwargs)
-        if dual:
+        if dual and whole_episodes:
+            buffer.add_rollout(rollout)
+        elif dual:
             # every transition carries the flag of the episode it belongs to: the flag is known at the tick that ENDS the episode
             # (ParticleRollout.episode_is_bad); transitions of episodes still running at the chunk's end take the flag so far
             cols = rollout.as_reference_batch(numpy=False)

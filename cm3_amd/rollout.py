@@ -907,6 +907,34 @@ class ParticleRollout(_Transitions):
                                                         0 if goal_slot is None else env.E * 4, _lib.ptr(tt), _lib.ptr(ee), int(B),
                                                         ctypes.byref(out), env._stream()))
 
+    def route_into(self, sets, sel, row):
+        """Every transition of the trajectory written to row row[b] of the column set sets[sel[b]] (b = t E + e; sel[b] >= len(sets):
+        nowhere) in ONE launch of cm3_transitions_route_f32 -- the routed form of export_into, which DeviceDualReplayBuffer.add_rollout
+        feeds with the plan of cm3_episode_route_plan: the two rings and the pending store.  sets: 1..3 (columns, rows) pairs, each
+        `columns` a dict with the tensors of as_reference_batch(numpy=False) with `rows` rows (checked before the launch); sel uint8
+        and row int64 [T * E] on the device.  row is NOT bounds-checked: derive it from sizes you own.  Works for both collection
+        modes (an episode-synchronous trajectory has no terminal capture: next_* is slot t + 1)."""
+        if not self.kernel_export:
+            raise Cm3Error("route_into needs a float32 trajectory (the export kernel)")
+        env, B = self.env, self.T * self.env.E
+        dev = self.done.device
+        if not 1 <= len(sets) <= 3:
+            raise Cm3Error("route_into: 1..3 column sets")
+        for t, dt, name in ((sel, torch.uint8, "sel"), (row, torch.int64, "row")):
+            if not (torch.is_tensor(t) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == B):
+                raise Cm3Error("route_into: %s must be a contiguous %s tensor of %d elements on %s" % (name, dt, B, dev))
+        out = (_lib.TransitionCols * len(sets))()
+        for k, (columns, rows) in enumerate(sets):
+            self._check_columns(columns, int(rows), "route_into: column set %d" % k)
+            for field, name in self._COLS_FIELDS:
+                setattr(out[k], field, columns[name].data_ptr())
+        traj = self._traj(0)
+        goal_slot = self._goal_slots32()
+        _lib.check(self._lib.cm3_transitions_route_f32(ctypes.byref(env._desc), ctypes.byref(traj), _lib.ptr(goal_slot),
+                                                       0 if goal_slot is None else env.E * 4, int(B), sel.data_ptr(), row.data_ptr(),
+                                                       out, len(sets), env._stream()))
+        return B
+
     def as_reference_batch_torch(self, tt, ee, numpy=True):
         """The same columns as a composition of torch indexing operations (any dtype; what the kernel path is tested against)."""
         tt = torch.as_tensor(tt, device=self.env.device, dtype=torch.long)

@@ -772,6 +772,60 @@ int cm3_rows_scatter(const cm3_row_cols *cols, int64_t n_rows, const int64_t *ds
 /* dst[k][b] = src[k][src_row[b]] (replay_buffer.py:28-37 sample_batch: the sampled transitions as contiguous columns). */
 int cm3_rows_gather(const cm3_row_cols *cols, int64_t n_rows, const int64_t *src_row, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Whole episodes into the dual replay buffer (additive in ABI 9; replay_buffer_dual.py:13-37 fed as train_onpolicy.py:300-356 feeds it)
+ * ---------------------------------------------------------------------------------------- */
+/* A collection of n_ticks ticks over n_envs envs.  Episodes are ordered by (end tick, env index) -- the order in which a host walking
+ * `for t: for e:` meets the done bytes.  The episode that ends at (t, e) is added whole and oldest first, the transitions an earlier
+ * call left in the PENDING STORE in front of this call's, to ring 0 (bad) when collisions[t][e] != 0, else to ring 1 (good); every
+ * transition is one sequential add: row (ring_idx + rank) mod ring_size, rank counted over all adds of the call to that ring, and a
+ * rank below counts - ring_size is skipped (the call itself overwrites it).  synchronous == 0 (continuous collection): the
+ * transitions behind an env's last done wait in the pending store (row k * n_envs + e for transition k of the running episode) and
+ * pend_len[e] counts them.  synchronous != 0: only transitions with valid[t][e] != 0 exist, an episode still open at the last tick
+ * ends there with collisions[n_ticks - 1][e], nothing pends (pend_len, flush_row and pending_depth may be NULL / 0).
+ * (Untagged, as the column structs above; its layout is checked by tests/test_episode_route_abi.py.) */
+typedef struct {
+  const uint8_t *done;          /* uint8 [n_ticks][n_envs], done_stride bytes per tick */
+  const int32_t *collisions;    /* int32 [n_ticks][n_envs], collisions_stride bytes per tick */
+  const uint8_t *valid;         /* optional uint8 [n_ticks][n_envs], valid_stride bytes per tick; NULL: every transition exists */
+  size_t done_stride, collisions_stride, valid_stride;
+  int32_t n_ticks, n_envs;
+  int32_t pending_depth;        /* P: rows per env of the pending store; the caller keeps it >= the longest episode (max_steps) --
+                                   a running episode that outgrows it is NOT kept whole: pend_len saturates at P, the newest
+                                   transitions of the tail take rows P - 1 downwards and the older ones are dropped (sel 255);
+                                   no row >= P is ever named */
+  int32_t synchronous;
+  int64_t ring_idx[2];          /* [0] the bad ring, [1] the good ring: where its next add goes */
+  int64_t ring_size[2];
+} cm3_episode_route_desc;
+#define CM3_ROUTE_BAD 0         /* values of sel */
+#define CM3_ROUTE_GOOD 1
+#define CM3_ROUTE_PENDING 2
+#define CM3_ROUTE_SKIP 255      /* no such transition (valid == 0), or the call itself overwrites it */
+/* Bytes of device scratch cm3_episode_route_plan needs (8-byte aligned); 0 for a shape it refuses. */
+size_t cm3_episode_route_scratch_bytes(int32_t n_ticks, int32_t n_envs);
+/* The routing plan, on the device, in five fixed-shape launches (no host read, no atomics, no workgroup waits for another):
+ *   sel uint8 [T E], row int64 [T E]   transition b = t E + e goes to row[b] of column set sel[b] (ring 0, ring 1, the pending store)
+ *   flush_row int64 [2][P E]           pending row k E + e goes to flush_row[c][k E + e] of ring c; -1: it stays, or is overwritten
+ *   counts int64 [2]                   sequential adds per ring, pending prefixes included: what the caller advances its rings by
+ *   pend_in / pend_out int32 [E]       transitions of each env's running episode in the pending store before / after (may alias)
+ * CM3_ERR_INVALID: null desc / done / collisions / outputs, a shape with (n_ticks + pending_depth) * n_envs >= 2^31, strides smaller
+ * than a row, ring_idx outside [0, ring_size), scratch too small.  Enqueue the two flushes (cm3_rows_scatter with flush_row[c]) BEFORE
+ * cm3_transitions_route_f32: the export may overwrite pending rows of an env whose next episode starts in this chunk. */
+int cm3_episode_route_plan(const cm3_episode_route_desc *desc, const int32_t *pend_in, int32_t *pend_out, uint8_t *sel, int64_t *row,
+                           int64_t *flush_row, int64_t *counts, void *scratch, size_t scratch_bytes, void *stream);
+/* The same plan computed sequentially on the host from HOST arrays (the one arithmetic, csrc/episode_route.h): same validation, same
+ * outputs element for element. */
+int cm3_episode_route_plan_host(const cm3_episode_route_desc *desc, const int32_t *pend_in, int32_t *pend_out, uint8_t *sel,
+                                int64_t *row, int64_t *flush_row, int64_t *counts);
+/* cm3_transitions_gather_f32 with tt == ee == NULL (ALL transitions of ticks [0, n / E), b = t E + e, sparse goal slots included),
+ * routed: ONE launch reads every transition once and writes it to row row[b] of sets[sel[b]]; sel[b] == CM3_ROUTE_SKIP (or any value
+ * >= n_sets) writes nothing.  sets: n_sets (1..3) column sets, ring_start / ring_size unused.  row is NOT bounds-checked (the index
+ * contract above): the caller derives it from sizes it owns, cm3_episode_route_plan does. */
+int cm3_transitions_route_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj, const int32_t *goal_slot,
+                              size_t goal_slot_stride, int64_t n, const uint8_t *sel, const int64_t *row,
+                              const cm3_transition_cols *sets, int32_t n_sets, void *stream);
+
 /* Tiling of per-agent rows into the feeds of the reference's train_step (ABI 6): process_actions / process_global_state
  * (alg/alg_credit.py:406-443, :528-557), the n x n credit repeats (:614-658) and the n x n x l_action counterfactual tiling
  * (:730-751).  Every output column is "destination row r <- source row f(r)":

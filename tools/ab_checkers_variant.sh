@@ -9,5 +9,5 @@ SRC_ID="$(python3 -c 'import sys; sys.path.insert(0, "."); from cm3_amd._lib imp
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function \
   -mllvm -amdgpu-kernarg-preload-count=16 -mllvm -amdgpu-sched-strategy=max-ilp "$@" -c "$H/checkers.hip" -o "$T/checkers_$NAME.o"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/tools/variants/libcm3_hip_$NAME.so" "$O/particle_f32.o" "$O/particle_f32_ilp.o" "$O/particle_f64.o" \
-  "$T/checkers_$NAME.o" "$O/util.o" "$O/advantage.o" "$O/batch.o" "$O/actor.o" "$O/actor_checkers.o" "$O/policy.o"
+  "$T/checkers_$NAME.o" "$O/util.o" "$O/advantage.o" "$O/batch.o" "$O/episode_route.o" "$O/actor.o" "$O/actor_checkers.o" "$O/policy.o"
 echo "built tools/variants/libcm3_hip_$NAME.so"
