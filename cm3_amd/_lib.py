@@ -67,6 +67,12 @@ class TransitionCols(ctypes.Structure):
                                         "done", "goals")] + [("ring_start", c_int64), ("ring_size", c_int64)]
 
 
+class QmixRows(ctypes.Structure):
+    # (cm3_qmix_rows: the transition rows cm3_qmix_particle_rows_f32 reads and the outputs it writes, every output optional)
+    _fields_ = [("obs_others", c_void_p), ("v_obs", c_void_p), ("goals", c_void_p),
+                ("q", c_void_p), ("argmax", c_void_p), ("onehot", c_void_p), ("q_max", c_void_p), ("n_rows", c_int64)]
+
+
 class EpisodeRouteDesc(ctypes.Structure):
     # (cm3_episode_route_desc: what cm3_episode_route_plan reads of a collection and of the dual buffer's two rings)
     _fields_ = [("done", c_void_p), ("collisions", c_void_p), ("valid", c_void_p),
@@ -225,7 +231,10 @@ SYMBOLS = {
     "cm3_qmix_particle_pack": (ctypes.c_int, [P(ActorParticleDesc), P(c_void_p), c_void_p, c_void_p]),
     "cm3_qmix_particle_f32": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(ActorParticleBufs), c_void_p]),
     "cm3_qmix_particle_f64": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(ActorParticleBufs), c_void_p]),
+    "cm3_qmix_particle_rows_f32": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(QmixRows), c_void_p]),
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
+    "cm3_qmix_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64,
+                                              c_void_p]),
     "cm3_transitions_gather_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), c_void_p, c_size_t, c_void_p, c_void_p, c_int64,
                                                   P(TransitionCols), c_void_p]),
     "cm3_checkers_transitions_gather": (ctypes.c_int, [P(CheckersDesc), P(CheckersTraj), c_void_p, c_void_p, c_void_p, c_int64,

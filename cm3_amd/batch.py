@@ -477,3 +477,117 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     call(["policy_op"], feed)
     call(["list_update_target_ops"], {})
     return calls
+
+
+# ---- QMIX (alg_qmix.py:236-380): everything of train_step that is not the mixer ----------------------------------------------
+
+def process_batch_qmix(cols, l_action=5):
+    """Columns of a sampled particle batch (sample_batch() / as_reference_batch(numpy=False)) -> the 13-tuple of
+    alg_qmix.Alg.process_batch (alg_qmix.py:236-285): process_batch above with `done` and `goals` left per time step."""
+    v_global = cols["v_global"]
+    B, N = v_global.shape[0], v_global.shape[1]
+    a1, ao = process_actions(cols["actions"], l_action)
+    return (B, v_global, cols["obs_others"].reshape(B * N, -1), cols["v_local"].reshape(B * N, -1), a1, ao,
+            rep_rows(cols["reward"], N), cols["reward_local"].reshape(B * N),
+            cols["v_global_next"], cols["obs_others_next"].reshape(B * N, -1), cols["v_local_next"].reshape(B * N, -1),
+            cols["done"], cols["goals"])
+
+
+def _row_sum_numpy_order(x):
+    """np.sum(x, axis=1) of a float64 [B, N]: left to right below 8 values, NumPy's eight-accumulator tree over the first 8 and then
+    the rest one by one from 8 on (N <= 15: one block of the pairwise kernel)."""
+    N = x.shape[1]
+    if N > 15:
+        raise ValueError("the row sum follows np.sum up to 15 values per row")
+    c = [x[:, i] for i in range(N)]
+    if N < 8:
+        s, rest = c[0].clone(), c[1:]
+    else:
+        s, rest = ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7])), c[8:]
+    for v in rest:
+        s = s + v
+    return s
+
+
+def qmix_td_target(reward_local, q_tot, done, gamma):
+    """np.sum(reward_local.reshape(B, N), axis=1) + gamma * np.squeeze(q_tot) * (-(done - 1)) (alg_qmix.py:367-369), float64 [B], in
+    NumPy's order and types: the row sum in float64, gamma * q_tot in the type of q_tot (float32 from a session), then float64.  ONE
+    launch of cm3_qmix_td_target_f64 for device tensors, the torch composition otherwise -- the same bits."""
+    B, N = reward_local.shape
+    q = q_tot.reshape(-1)
+    if q.numel() != B or done.numel() != B:
+        raise ValueError("qmix_td_target: %d transitions, %d values of q_tot, %d of done" % (B, q.numel(), done.numel()))
+    if reward_local.is_cuda:
+        from . import _lib
+        if reward_local.dtype not in (torch.float32, torch.float64) or q.dtype not in (torch.float32, torch.float64):
+            raise ValueError("qmix_td_target: reward_local and q_tot must be float32 or float64")
+        r, q = reward_local.contiguous(), q.contiguous()
+        d = done.reshape(-1).contiguous()
+        d = d.view(torch.uint8) if d.dtype == torch.bool else (d != 0).view(torch.uint8)
+        out = torch.empty(B, dtype=torch.float64, device=r.device)
+        _lib.check(_lib.lib().cm3_qmix_td_target_f64(r.data_ptr(), 1 if r.dtype == torch.float64 else 0, N, q.data_ptr(),
+                                                     1 if q.dtype == torch.float64 else 0, d.data_ptr(), float(gamma), out.data_ptr(), B,
+                                                     torch.cuda.current_stream(r.device).cuda_stream))
+        return out
+    gq = q * torch.tensor(gamma, dtype=q.dtype)
+    not_done = -(done.reshape(-1).to(torch.int64) - 1)                              # if true, then 0, else 1 (:367)
+    return _row_sum_numpy_order(reward_local.to(torch.float64)) + gq.to(torch.float64) * not_done
+
+
+def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5):
+    """The data side of the QMIX train_step (alg_qmix.py:338-380) from the columns of a sampled particle batch: builds, in the
+    reference's order, the feed_dict of its four sess.run calls -- ["argmax_Q_target"], ["mixer_target"], ["mixer_op"],
+    ["list_update_target_ops"] -- and returns the list of (ops, feed).  ``run(ops, feed)`` plays sess.run as in train_step_feeds: ops
+    and placeholders are the reference's attribute names (v_state, v_goal_all, actions_1hot, obs_others, v_obs, v_goal, td_target);
+    it returns one tensor per op (None for mixer_op and list_update_target_ops).  The mixer, its target copy and the optimiser step
+    are `run`'s: nothing here evaluates or trains them.
+
+    Without target_agent everything is the torch composition -- the specification, pinned bit for bit to the arrays the REAL
+    train_step fed (tests/golden/trainstep_qmix_particle_n*.npz); it runs on CPU tensors and calls `run` for the argmax.
+    With target_agent (a ParticleQmixAgent holding the Agent_target weights) and CUDA columns, `run` is NOT called for
+    argmax_Q_target (its (ops, feed) entry still appears in the list): the one-hot target actions come from
+    target_agent.greedy_rows in one launch, actions_1hot from one tiling launch, the TD target from cm3_qmix_td_target_f64.
+    The soft update of the agent's target weights -- the agent half of list_update_target_ops -- is left to the caller:
+    ``target_agent.soft_update_from(main_agent, tau)`` after this function returns."""
+    calls = []
+
+    def call(ops, feed, launch=True):
+        calls.append((ops, feed))
+        return run(ops, feed) if launch else None
+
+    vg = cols["v_global"]
+    B, N = vg.shape[0], vg.shape[1]
+    device = target_agent is not None
+    if device and not vg.is_cuda:
+        raise ValueError("qmix_train_step_feeds: target_agent evaluates device columns; call without it for host tensors")
+    rows = lambda x: x.reshape(B * N, -1)                                           # noqa: E731
+    obs_others, v_local = rows(cols["obs_others"]), rows(cols["v_local"])
+    obs_others_next, v_local_next = rows(cols["obs_others_next"]), rows(cols["v_local_next"])
+    goals = cols["goals"]
+    goals_all, goals_self = goals.reshape(B, -1), rows(goals)                       # :344-345
+    state_next, state = cols["v_global_next"].reshape(B, -1), vg.reshape(B, -1)     # :346-347
+    if device:
+        from . import _lib
+        t = _Tiler(vg.device)
+        actions_1hot = t.add(cols["actions"].reshape(-1).to(torch.int32).contiguous(), B * N, int(l_action), torch.int64, _lib.TILE_ONEHOT_I64)
+        t.run()
+    else:
+        actions_1hot = process_actions(cols["actions"], l_action)[0]
+
+    # ---- argmax actions of the target agents, one-hot (:349-356) ----
+    feed = {"obs_others": obs_others_next, "v_obs": v_local_next, "v_goal": goals_self}
+    if device:
+        call(["argmax_Q_target"], feed, launch=False)
+        target_1hot = target_agent.greedy_rows(obs_others_next, v_local_next, goals_self, onehot=True)["onehot"]
+    else:
+        argmax = call(["argmax_Q_target"], feed)[0]
+        target_1hot = torch.nn.functional.one_hot(argmax.reshape(-1).long(), int(l_action))
+    # ---- Q_tot of the target mixer, TD target (:358-369) ----
+    q_tot = call(["mixer_target"], {"v_state": state_next, "v_goal_all": goals_all, "actions_1hot": target_1hot,
+                                    "obs_others": obs_others_next, "v_obs": v_local_next, "v_goal": goals_self})[0]
+    target = qmix_td_target(cols["reward_local"].reshape(B, N), q_tot, cols["done"], gamma)
+    # ---- optimiser step of the main mixer, soft update (:371-380) ----
+    call(["mixer_op"], {"v_state": state, "v_goal_all": goals_all, "actions_1hot": actions_1hot, "obs_others": obs_others,
+                        "v_obs": v_local, "v_goal": goals_self, "td_target": target})
+    call(["list_update_target_ops"], {})
+    return calls

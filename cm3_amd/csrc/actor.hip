@@ -760,6 +760,21 @@ struct QmixParams {
   const float *w[6];      // pack kernel only: h/kernel, h/bias, h2/kernel, h2/bias, out/kernel, out/bias
 };
 
+// The same network over TRANSITION rows (cm3_qmix_particle_rows_f32): row r of three row-major float32 arrays -- the columns
+// obs_others_next / v_local_next / goals of a sampled batch viewed as [B * N, .] -- instead of an env's live buffers; a pure
+// argmax head (alg_qmix.py:98 on the Agent_target weights, train_step :349-356), every output optional.
+struct QmixRowsParams {
+  size_t n_rows;
+  const float *obs_others, *v_obs, *goals;   // [n_rows][L], [n_rows][4], [n_rows][2]
+  float *q;                                  // [n_rows][5]
+  int32_t *argmax;                           // [n_rows]
+  int64_t *onehot;                           // [n_rows][5]: actions_target_1hot (np.zeros(dtype=int))
+  float *q_max;                              // [n_rows]
+  const float *packed;
+};
+template <int N> __device__ __forceinline__ size_t qmix_row_count(const QmixParams &p) { return (size_t)p.E * N; }
+template <int N> __device__ __forceinline__ size_t qmix_row_count(const QmixRowsParams &p) { return p.n_rows; }
+
 template <int N> __global__ void __launch_bounds__(256) k_qmix_pack(const QmixParams p, float *out) {
   using QL = QmixLayout<N>;
   constexpr int K = QL::L + 6;
@@ -787,7 +802,10 @@ template <int N> __global__ void __launch_bounds__(256) k_qmix_pack(const QmixPa
   }
 }
 
-template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle(const QmixParams p) {
+// The body of both kernels: ROWS = false reads an env's live buffers and ends in the epsilon-greedy choice (k_qmix_particle),
+// ROWS = true reads transition rows and ends in the argmax outputs (k_qmix_particle_rows).  Everything between the staging of the
+// inputs and the Q values is one text, so a row's Q values are the same bits in both.
+template <int N, typename RIN, bool ROWS, typename P> __device__ __forceinline__ void qmix_forward(const P &p) {
   using QL = QmixLayout<N>;
   using V4 = typename Vec<RIN>::v4;
   using V2 = typename Vec<RIN>::v2;
@@ -797,17 +815,22 @@ template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle
   __shared__ float h2s[64][QL::HS];
   const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, hi = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t rows = (size_t)p.E * N;
+  const size_t rows = qmix_row_count<N>(p);
   const size_t row_base = (size_t)blockIdx.x * 64;
 
   // the row this lane finishes in the head (row 16w + (l&15); lanes 0..15 write it) and its exploration key
   size_t hr = row_base + 16 * w + col;
   const bool head_ok = hr < rows && hi == 0;
   hr = hr < rows ? hr : rows - 1;
-  const size_t he = hr / N;
-  const int agent = (int)(hr - he * N);
-  const int head_steps = p.meta[2 * he];
-  const uint32_t head_episode = (uint32_t)p.episode[he];
+  size_t he = 0;
+  int agent = 0, head_steps = 0;
+  uint32_t head_episode = 0;
+  if constexpr (!ROWS) {
+    he = hr / N;
+    agent = (int)(hr - he * N);
+    head_steps = p.meta[2 * he];
+    head_episode = (uint32_t)p.episode[he];
+  }
 
   // every global request first: wave 0's input rows, then the lane's weight operands
   V4 in_s, in_o[L / 4];
@@ -815,10 +838,15 @@ template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle
   if (w == 0) {
     const size_t r = row_base + lane;
     const size_t rc = r < rows ? r : rows - 1;
-    const size_t e = rc / N;
-    const int i = (int)(rc - e * N);
-    in_s = reinterpret_cast<const V4 *>(p.state)[(size_t)i * p.E + e];
-    in_g = reinterpret_cast<const V2 *>(p.goals)[(size_t)i * p.E + e];
+    if constexpr (ROWS) {
+      in_s = reinterpret_cast<const V4 *>(p.v_obs)[rc];
+      in_g = reinterpret_cast<const V2 *>(p.goals)[rc];
+    } else {
+      const size_t e = rc / N;
+      const int i = (int)(rc - e * N);
+      in_s = reinterpret_cast<const V4 *>(p.state)[(size_t)i * p.E + e];
+      in_g = reinterpret_cast<const V2 *>(p.goals)[(size_t)i * p.E + e];
+    }
     const V4 *o4 = reinterpret_cast<const V4 *>(reinterpret_cast<const RIN *>(p.obs_others) + rc * L);
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) in_o[k] = o4[k];
@@ -888,8 +916,9 @@ template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle
   }
   __syncthreads();
   // exploration words first: the Philox rounds are VALU work that issues between the head's dependent matrix instructions
-  uint32_t w_explore, w_action;
-  explore_words(p.seed, (uint64_t)(p.env_id_base + (int64_t)he), head_episode, (uint32_t)head_steps, agent, w_explore, w_action);
+  uint32_t w_explore = 0, w_action = 0;
+  if constexpr (!ROWS)
+    explore_words(p.seed, (uint64_t)(p.env_id_base + (int64_t)he), head_episode, (uint32_t)head_steps, agent, w_explore, w_action);
   // ---- head "out": C[action][row] of rows [16w, 16w+16), bias as the start value, one k-ordered chain ----------------------
   float hx[kQH / 4];
 #pragma unroll
@@ -909,14 +938,45 @@ template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle
     __builtin_memcpy(&q[4], &y, 4);
   }
   // argmax (the first index on ties: tf.argmax, alg_qmix.py:98), epsilon-greedy (alg_qmix.py:177-182)
-  const int act = epsilon_greedy(q, p.eps_dev ? *p.eps_dev : p.eps, w_explore, w_action);
-  if (head_ok) {
-    p.actions[hr] = act;
-    if (p.q) {
+  if constexpr (ROWS) {
+    int act;
+    float best;
+    greedy_argmax(q, act, best);
+    if (head_ok) {
+      if (p.q) {
 #pragma unroll
-      for (int a = 0; a < kA; ++a) p.q[hr * kA + a] = q[a];
+        for (int a = 0; a < kA; ++a) p.q[hr * kA + a] = q[a];
+      }
+      if (p.argmax) p.argmax[hr] = act;
+      if (p.q_max) p.q_max[hr] = best;
+      if (p.onehot) {
+        // 40 bytes per row from a 16-byte aligned base: an even row is 16 | 16 | 8 bytes, an odd one 8 | 16 | 16
+        typedef long long i64x2 __attribute__((ext_vector_type(2)));
+        int64_t *row = p.onehot + hr * kA;
+        const int k0 = (int)(hr & 1), k1 = k0 ? 0 : 4;
+        *reinterpret_cast<i64x2 *>(row + k0) = i64x2{act == k0, act == k0 + 1};
+        *reinterpret_cast<i64x2 *>(row + k0 + 2) = i64x2{act == k0 + 2, act == k0 + 3};
+        row[k1] = act == k1;
+      }
+    }
+  } else {
+    const int act = epsilon_greedy(q, p.eps_dev ? *p.eps_dev : p.eps, w_explore, w_action);
+    if (head_ok) {
+      p.actions[hr] = act;
+      if (p.q) {
+#pragma unroll
+        for (int a = 0; a < kA; ++a) p.q[hr * kA + a] = q[a];
+      }
     }
   }
+}
+
+template <int N, typename RIN> __global__ void CM3_MATRIX_KERNEL k_qmix_particle(const QmixParams p) {
+  qmix_forward<N, RIN, false>(p);
+}
+
+template <int N> __global__ void CM3_MATRIX_KERNEL k_qmix_particle_rows(const QmixRowsParams p) {
+  qmix_forward<N, float, true>(p);
 }
 
 template <int N, typename RIN> static int qmix_launch(const QmixParams &p, hipStream_t s) {
@@ -924,6 +984,14 @@ template <int N, typename RIN> static int qmix_launch(const QmixParams &p, hipSt
   const unsigned blocks = (unsigned)((rows + 63) / 64);
   note_variant("k_qmix_particle", (int)sizeof(RIN), N, 4, 0, 0, 0, 0, 0, 0, kPrecF32);
   hipLaunchKernelGGL((k_qmix_particle<N, RIN>), dim3(blocks), dim3(256), 0, s, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+template <int N> static int qmix_rows_launch(const QmixRowsParams &p, hipStream_t s) {
+  const unsigned blocks = (unsigned)((p.n_rows + 63) / 64);
+  note_variant("k_qmix_particle_rows", (int)sizeof(float), N, 4, 0, 0, 0, 0, 0, 0, kPrecF32);
+  hipLaunchKernelGGL((k_qmix_particle_rows<N>), dim3(blocks), dim3(256), 0, s, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
@@ -1170,5 +1238,45 @@ extern "C" int cm3_qmix_particle_f32(const cm3_actor_particle_desc *d, const voi
 extern "C" int cm3_qmix_particle_f64(const cm3_actor_particle_desc *d, const void *packed, const cm3_actor_particle_bufs *b,
                                      void *stream) {
   return cm3::qmix_particle_call<double>(d, packed, b, stream);
+}
+
+extern "C" int cm3_qmix_particle_rows_f32(const cm3_actor_particle_desc *d, const void *packed, const cm3_qmix_rows *r, void *stream) {
+  using namespace cm3;
+  int rc = qmix_check_desc(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(packed, "packed weights are NULL: run cm3_qmix_particle_pack once per weight update");
+  CM3_REQUIRE(r, "null rows");
+  CM3_REQUIRE(r->obs_others && r->v_obs && r->goals, "missing inputs: obs_others, v_obs and goals are all required");
+  CM3_REQUIRE(r->q || r->argmax || r->onehot || r->q_max, "no output requested: set at least one of q, argmax, onehot, q_max");
+  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
+  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
+  CM3_REQUIRE((uintptr_t)r->obs_others % 16 == 0 && (uintptr_t)r->v_obs % 16 == 0 && (uintptr_t)r->goals % 8 == 0,
+              "misaligned inputs: obs_others and v_obs must be 16-byte aligned, goals 8-byte aligned");
+  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0, "misaligned onehot: must be 16-byte aligned");
+  QmixRowsParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_rows = (size_t)r->n_rows;
+  p.obs_others = r->obs_others;
+  p.v_obs = r->v_obs;
+  p.goals = r->goals;
+  p.q = r->q;
+  p.argmax = r->argmax;
+  p.onehot = r->onehot;
+  p.q_max = r->q_max;
+  p.packed = (const float *)packed;
+  hipStream_t s = (hipStream_t)stream;
+  switch (d->n_agents) {
+    case 1: return qmix_rows_launch<1>(p, s);
+    case 2: return qmix_rows_launch<2>(p, s);
+    case 3: return qmix_rows_launch<3>(p, s);
+    case 4: return qmix_rows_launch<4>(p, s);
+    case 5: return qmix_rows_launch<5>(p, s);
+    case 6: return qmix_rows_launch<6>(p, s);
+    case 7: return qmix_rows_launch<7>(p, s);
+    case 8: return qmix_rows_launch<8>(p, s);
+    case 9: return qmix_rows_launch<9>(p, s);
+    case 10: return qmix_rows_launch<10>(p, s);
+  }
+  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
 #endif  // CM3_NO_ENTRY_POINTS

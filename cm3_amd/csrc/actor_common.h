@@ -101,6 +101,18 @@ __device__ __forceinline__ void explore_words(uint64_t seed, uint64_t genv, uint
   explore_words_from(explore_block_words(seed, genv, agent), episode, steps, w_explore, w_action);
 }
 
+// argmax Q with the first index on ties (tf.argmax) and the value there: the greedy half of epsilon_greedy below, on its own
+__device__ __forceinline__ void greedy_argmax(const float (&q)[kA], int &greedy, float &best) {
+  greedy = 0;
+  best = q[0];
+#pragma unroll
+  for (int a = 1; a < kA; ++a) {
+    const bool gt = q[a] > best;
+    greedy = gt ? a : greedy;
+    best = gt ? q[a] : best;
+  }
+}
+
 // argmax Q with the first index on ties (tf.argmax), replaced with probability eps by a uniform action (alg_qmix.py:177-182,
 // alg_qmix_checkers.py:176-181).  eps is compared in double: eps = 1 always explores.
 __device__ __forceinline__ int epsilon_greedy(const float (&q)[kA], float eps, uint32_t w_explore, uint32_t w_action) {

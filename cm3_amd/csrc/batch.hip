@@ -755,6 +755,28 @@ template <typename R> __global__ void __launch_bounds__(256) k_td_target(const R
   }
 }
 
+// The QMIX TD target (alg_qmix.py:367-369): np.sum(reward_local.reshape(n, N), axis=1) + gamma * q_tot * (-(done - 1)).  One thread
+// per transition.  np.sum over a contiguous last axis of N float64 values: left to right below 8 values, from 8 on the pairwise
+// kernel's eight accumulators over the first 8, combined as ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), then the tail one by one.
+template <typename RR, typename RQ> __global__ void __launch_bounds__(256) k_qmix_td_target(const RR *reward, int N, const RQ *q, const uint8_t *done,
+                                                                                             double gamma, double *out, size_t n) {
+  for (size_t b = (size_t)blockIdx.x * 256 + threadIdx.x; b < n; b += (size_t)gridDim.x * 256) {
+    const RR *r = reward + b * (size_t)N;
+    double sum;
+    int i;
+    if (N < 8) {
+      sum = (double)r[0];
+      i = 1;
+    } else {
+      sum = (((double)r[0] + (double)r[1]) + ((double)r[2] + (double)r[3])) + (((double)r[4] + (double)r[5]) + ((double)r[6] + (double)r[7]));
+      i = 8;
+    }
+    for (; i < N; ++i) sum += (double)r[i];
+    const RQ gq = (RQ)gamma * q[b];                    // in q's type: float32(gamma) * float32, or float64
+    out[b] = sum + (double)gq * (double)(done[b] ? 0 : 1);
+  }
+}
+
 // ---- host side shared by the Checkers export, the compact ring's pack and its expansion --------------------------------------------
 struct CkGeom {
   uint32_t N, Lo, grid_rec, obst_rec, grid_stride, obst_stride;   // record sizes and strides in bytes
@@ -991,6 +1013,29 @@ int cm3_td_target_f64(const void *reward, int32_t reward_is_f64, const double *q
   else
     hipLaunchKernelGGL(k_td_target<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float *)reward, q, multiplier,
                        gamma, out, (size_t)n);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+int cm3_qmix_td_target_f64(const void *reward_local, int32_t reward_is_f64, int32_t n_agents, const void *q_tot, int32_t q_is_f64,
+                           const uint8_t *done, double gamma, double *out, int64_t n, void *stream) {
+  using namespace cm3;
+  CM3_REQUIRE(n >= 0, "n must be >= 0");
+  CM3_REQUIRE(n_agents >= 1 && n_agents <= CM3_MAX_AGENTS, "n_agents must be in 1..%d", CM3_MAX_AGENTS);
+  if (n == 0) return CM3_OK;
+  CM3_REQUIRE(reward_local && q_tot && done && out, "qmix_td_target: null argument");
+  size_t blocks = ((size_t)n + 255) / 256;
+  blocks = blocks > 2048 ? 2048 : blocks;
+  const dim3 grid((unsigned)blocks), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (reward_is_f64 && q_is_f64)
+    hipLaunchKernelGGL((k_qmix_td_target<double, double>), grid, block, 0, s, (const double *)reward_local, n_agents, (const double *)q_tot, done, gamma, out, (size_t)n);
+  else if (reward_is_f64)
+    hipLaunchKernelGGL((k_qmix_td_target<double, float>), grid, block, 0, s, (const double *)reward_local, n_agents, (const float *)q_tot, done, gamma, out, (size_t)n);
+  else if (q_is_f64)
+    hipLaunchKernelGGL((k_qmix_td_target<float, double>), grid, block, 0, s, (const float *)reward_local, n_agents, (const double *)q_tot, done, gamma, out, (size_t)n);
+  else
+    hipLaunchKernelGGL((k_qmix_td_target<float, float>), grid, block, 0, s, (const float *)reward_local, n_agents, (const float *)q_tot, done, gamma, out, (size_t)n);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }

@@ -115,6 +115,55 @@ class ParticleQmixAgent(object):
                      epsilon, q, env_id_base=env.env_id_base, dtype=env.dtype)
         return (actions, q) if return_q else actions
 
+    def greedy_rows(self, obs_others, v_obs, goals, q=False, onehot=True, q_max=False):
+        """The network over transition rows with a pure argmax head, ONE launch (cm3_qmix_particle_rows_f32): with the Agent_target
+        weights this is argmax_Q_target of alg_qmix.train_step (alg_qmix.py:349-356) on the columns obs_others_next / v_local_next /
+        goals of a sampled batch.  Inputs: float tensors [..., L], [..., 4], [..., 2] with equal leading shape, made contiguous
+        float32 (a float64 column is rounded, as the reference's tf.float32 placeholders do).  Returns a dict of device tensors over
+        the R = prod(leading shape) rows: "argmax" int32 [R] always; "q" float32 [R, 5], "onehot" int64 [R, 5] (the reference's
+        actions_target_1hot), "q_max" float32 [R] when asked for.  A row's Q values are the bits act() computes for the same
+        inputs."""
+        lead = tuple(v_obs.shape[:-1])
+        if (tuple(obs_others.shape) != lead + (self.L,) or tuple(v_obs.shape) != lead + (4,)
+                or tuple(goals.shape) != lead + (2,)):
+            raise Cm3Error("greedy_rows takes [..., %d], [..., 4] and [..., 2] with equal leading shape, got %s, %s, %s"
+                           % (self.L, tuple(obs_others.shape), tuple(v_obs.shape), tuple(goals.shape)))
+        rows = int(np.prod(lead, dtype=np.int64))
+        if rows <= 0:
+            raise Cm3Error("greedy_rows needs at least one row")
+        stage = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
+        oo, vo, vg = stage(obs_others), stage(v_obs), stage(goals)
+        out = {"argmax": torch.empty(rows, dtype=torch.int32, device=self.device)}
+        if q:
+            out["q"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        if onehot:
+            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
+        if q_max:
+            out["q_max"] = torch.empty(rows, dtype=torch.float32, device=self.device)
+        self.enqueue_rows(rows, oo, vo, vg, **out)
+        return out
+
+    def enqueue_rows(self, n_rows, obs_others, v_obs, goals, q=None, argmax=None, onehot=None, q_max=None, stream=None):
+        """Raw launch of cm3_qmix_particle_rows_f32 on contiguous float32 device tensors; every output is optional, one is required."""
+        r = _lib.QmixRows()
+        r.obs_others, r.v_obs, r.goals = _lib.ptr(obs_others), _lib.ptr(v_obs), _lib.ptr(goals)
+        r.q, r.argmax, r.onehot, r.q_max = _lib.ptr(q), _lib.ptr(argmax), _lib.ptr(onehot), _lib.ptr(q_max)
+        r.n_rows = int(n_rows)
+        d = self._desc(1, 0.0, 0)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_qmix_particle_rows_f32(ctypes.byref(d), self._packed.data_ptr(), ctypes.byref(r), s))
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the six TF-shaped float32 tensors in place, then repack(): the agent half of
+        list_update_target_ops (alg_qmix.py:135-137), for an agent holding the Agent_target weights."""
+        if not isinstance(main, ParticleQmixAgent) or main.n != self.n:
+            raise Cm3Error("soft_update_from: the main agent must be a ParticleQmixAgent for %d agents" % self.n)
+        tau = float(tau)
+        for name in NAMES:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
+        self.repack()
+
 
 # ---- Checkers -------------------------------------------------------------------------------------------------------------------
 # the thirteen variables of networks.Qmix_single_checkers (networks.py:617-637) by the fields of cm3_actor_checkers_weights

@@ -56,6 +56,8 @@ extern "C" {
                                   NOTE: sizeof(cm3_particle_traj) GREW by 8 bytes (192 -> 200) without a version step: a caller compiled
                                   against the shorter struct must be recompiled, or the library reads 8 bytes past its struct as
                                   live_record.  The in-tree binding mirrors the new size (tests/test_abi.py compares every offset).
+                                  cm3_qmix_particle_rows_f32 (the QMIX agent network over transition rows, argmax head) and
+                                  cm3_qmix_td_target_f64 (the QMIX TD target): the data side of alg_qmix.train_step; additive.
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -437,6 +439,30 @@ int cm3_qmix_particle_f32(const cm3_actor_particle_desc *desc, const void *packe
                           void *stream);
 int cm3_qmix_particle_f64(const cm3_actor_particle_desc *desc, const void *packed, const cm3_actor_particle_bufs *bufs,
                           void *stream);
+
+/* The same network over TRANSITION rows (part of ABI 9, additive): what alg_qmix.train_step evaluates with the Agent_target weights
+ * (argmax_Q_target, alg_qmix.py:349-356) on the next observation of every sampled agent row.  Row r comes from three row-major
+ * float32 arrays -- the columns obs_others_next / v_local_next / goals of a sampled batch viewed as [B * N, .] -- and n_rows is any
+ * positive count (not a multiple of n_agents).  The head is a pure argmax (the first index on ties); nothing is drawn.  A row's Q values
+ * are, bit for bit, those cm3_qmix_particle_f32 computes for the same L + 6 inputs.  Every output is optional, at least one is required:
+ *   q       the Q values                                  argmax  the greedy action
+ *   onehot  the reference's actions_target_1hot (int64)     q_max   Q of the greedy action
+ * (Anonymous struct tag, like cm3_episode_route_desc.) */
+typedef struct {
+  const float *obs_others;  /* [n_rows][4*max(N-1,1)], 16-byte aligned */
+  const float *v_obs;       /* [n_rows][4], 16-byte aligned */
+  const float *goals;       /* [n_rows][2],  8-byte aligned */
+  float   *q;               /* optional [n_rows][5] */
+  int32_t *argmax;          /* optional [n_rows] */
+  int64_t *onehot;          /* optional [n_rows][5], 16-byte aligned */
+  float   *q_max;           /* optional [n_rows] */
+  int64_t  n_rows;
+} cm3_qmix_rows;
+/* desc: n_agents 1..10, the widths 64/64/5 and precision 0 are validated; n_envs, epsilon, seed and env_id_base are not read.
+ * packed: from cm3_qmix_particle_pack.  CM3_ERR_INVALID before any launch: null desc / packed / rows, a missing input, no output
+ * requested, n_rows <= 0 or more than 64 * (2^31 - 1), a misaligned input or onehot pointer.  cm3_last_kernel_variant() names the
+ * launch k_qmix_particle_rows<f32,N=..>. */
+int cm3_qmix_particle_rows_f32(const cm3_actor_particle_desc *desc, const void *packed, const cm3_qmix_rows *rows, void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
@@ -855,6 +881,15 @@ int cm3_rows_tile(const cm3_tile_col *cols, int32_t n_cols, void *stream);
  * reward float32 (reward_is_f64 = 0) or float64 [n], q float64 [n], multiplier int64 [n] (0 / 1), out float64 [n]. */
 int cm3_td_target_f64(const void *reward, int32_t reward_is_f64, const double *q, const int64_t *multiplier, double gamma, double *out,
                       int64_t n, void *stream);
+/* out[b] = sum_i reward_local[b][i] + (gamma * q_tot[b]) * (1 - done[b])  (part of ABI 9, additive): the TD target of the QMIX
+ * train_step (alg_qmix.py:367-369), in the order and types NumPy evaluates it with.  The row sum runs in float64 after widening: left
+ * to right for n_agents < 8, NumPy's eight-accumulator tree over the first 8 values and then the rest one by one from 8 on.
+ * gamma * q_tot is computed in the type of q_tot (float32: q_is_f64 = 0, gamma rounded to float32 first -- what a TF session's
+ * float32 result gives; float64: q_is_f64 = 1), widened to float64, multiplied by 1 - done (done: one byte per transition, 0 / 1)
+ * and added.  reward_local float32 (reward_is_f64 = 0) or float64 [n][n_agents], out float64 [n].  One launch, no atomics.
+ * CM3_ERR_INVALID: n < 0, n_agents outside 1..10, a null pointer with n > 0. */
+int cm3_qmix_td_target_f64(const void *reward_local, int32_t reward_is_f64, int32_t n_agents, const void *q_tot, int32_t q_is_f64,
+                           const uint8_t *done, double gamma, double *out, int64_t n, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement and launch plumbing
