@@ -534,7 +534,78 @@ def qmix_td_target(reward_local, q_tot, done, gamma):
     return _row_sum_numpy_order(reward_local.to(torch.float64)) + gq.to(torch.float64) * not_done
 
 
-def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5):
+def process_batch_qmix_checkers(cols, l_action=5):
+    """Columns of a sampled Checkers batch (sample_batch() of either ring / CheckersRollout.as_reference_batch(numpy=False)) -> the
+    18-tuple of alg_qmix_checkers.Alg.process_batch (alg_qmix_checkers.py:234-290; CHECKERS_BATCH_NAMES).  NOT process_batch_checkers,
+    the CM3 learner's: here `reward` is repeated N times, state_env / state_env_next / done are left per time step, and state_agents
+    stays [B, N, 4]."""
+    vec = cols["vec"]
+    B, N = vec.shape[0], vec.shape[1]
+    rows = lambda x: x.reshape(B * N, *x.shape[2:])            # noqa: E731
+    a1, ao = process_actions(cols["actions"], l_action)
+    prev1 = torch.nn.functional.one_hot(cols["actions_prev"].long(), l_action).reshape(B * N, l_action)
+    return (B, cols["grid"], vec, rows(cols["obs_others"]), rows(cols["obs_self_t"]), rows(cols["obs_self_v"]),
+            prev1, a1, ao, rep_rows(cols["reward"], N), cols["local_rewards"].reshape(B * N), cols["next_grid"],
+            cols["next_vec"], rows(cols["next_obs_others"]), rows(cols["next_obs_self_t"]),
+            rows(cols["next_obs_self_v"]), cols["done"], cols["goals"])
+
+
+def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action):
+    """The Checkers form of qmix_train_step_feeds (alg_qmix_checkers.py:342-393)."""
+    calls = []
+
+    def call(ops, feed, launch=True):
+        calls.append((ops, feed))
+        return run(ops, feed) if launch else None
+
+    vec = cols["vec"]
+    B, N = vec.shape[0], vec.shape[1]
+    device = target_agent is not None
+    if device and not vec.is_cuda:
+        raise ValueError("qmix_train_step_feeds: target_agent evaluates device columns; call without it for host tensors")
+    rows = lambda x: x.reshape(B * N, *x.shape[2:])            # noqa: E731
+    obs_others, obs_self_t, obs_self_v = rows(cols["obs_others"]), rows(cols["obs_self_t"]), rows(cols["obs_self_v"])
+    obs_others_next, obs_self_t_next, obs_self_v_next = (rows(cols["next_obs_others"]), rows(cols["next_obs_self_t"]),
+                                                         rows(cols["next_obs_self_v"]))
+    goals = cols["goals"]
+    goals_all, goals_self = goals.reshape(B, -1), rows(goals)                       # :348-349
+    state_agents_next, state_agents = cols["next_vec"].reshape(B, -1), vec.reshape(B, -1)   # :350-351
+    if device:
+        from . import _lib
+        t = _Tiler(vec.device)
+        actions_1hot = t.add(cols["actions"].reshape(-1).to(torch.int32).contiguous(), B * N, int(l_action), torch.int64, _lib.TILE_ONEHOT_I64)
+        actions_prev_1hot = t.add(cols["actions_prev"].reshape(-1).to(torch.int32).contiguous(), B * N, int(l_action), torch.int64,
+                                  _lib.TILE_ONEHOT_I64)
+        t.run()
+    else:
+        actions_1hot = process_actions(cols["actions"], l_action)[0]
+        actions_prev_1hot = torch.nn.functional.one_hot(cols["actions_prev"].long(), int(l_action)).reshape(B * N, int(l_action))
+
+    # ---- argmax actions of the target agents, one-hot (:353-362).  The reference feeds actions_prev : actions_1hot here and in the
+    # mixer_target feed -- the action JUST TAKEN, next to the next_* observations -- not the actions_prev column ----
+    agent_next = {"actions_prev": actions_1hot, "obs_others": obs_others_next, "obs_self_t": obs_self_t_next,
+                  "obs_self_v": obs_self_v_next, "v_goal": goals_self}
+    if device:
+        call(["argmax_Q_target"], dict(agent_next), launch=False)
+        target_1hot = target_agent.greedy_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(B * N),
+                                               goals_self, onehot=True)["onehot"]
+    else:
+        argmax = call(["argmax_Q_target"], dict(agent_next))[0]
+        target_1hot = torch.nn.functional.one_hot(argmax.reshape(-1).long(), int(l_action))
+    # ---- Q_tot of the target mixer, TD target (:364-379; the arithmetic of the particle train_step) ----
+    feed = {"state_env": cols["next_grid"], "v_state": state_agents_next, "v_goal_all": goals_all, "actions_1hot": target_1hot}
+    feed.update(agent_next)
+    q_tot = call(["mixer_target"], feed)[0]
+    target = qmix_td_target(cols["local_rewards"].reshape(B, N), q_tot, cols["done"], gamma)
+    # ---- optimiser step of the main mixer, soft update (:381-393) ----
+    call(["mixer_op"], {"state_env": cols["grid"], "v_state": state_agents, "v_goal_all": goals_all, "actions_1hot": actions_1hot,
+                        "actions_prev": actions_prev_1hot, "obs_others": obs_others, "obs_self_t": obs_self_t,
+                        "obs_self_v": obs_self_v, "v_goal": goals_self, "td_target": target})
+    call(["list_update_target_ops"], {})
+    return calls
+
+
+def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle"):
     """The data side of the QMIX train_step (alg_qmix.py:338-380) from the columns of a sampled particle batch: builds, in the
     reference's order, the feed_dict of its four sess.run calls -- ["argmax_Q_target"], ["mixer_target"], ["mixer_op"],
     ["list_update_target_ops"] -- and returns the list of (ops, feed).  ``run(ops, feed)`` plays sess.run as in train_step_feeds: ops
@@ -548,7 +619,17 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5):
     argmax_Q_target (its (ops, feed) entry still appears in the list): the one-hot target actions come from
     target_agent.greedy_rows in one launch, actions_1hot from one tiling launch, the TD target from cm3_qmix_td_target_f64.
     The soft update of the agent's target weights -- the agent half of list_update_target_ops -- is left to the caller:
-    ``target_agent.soft_update_from(main_agent, tau)`` after this function returns."""
+    ``target_agent.soft_update_from(main_agent, tau)`` after this function returns.
+
+    env="checkers": the same four calls of alg_qmix_checkers.train_step (alg_qmix_checkers.py:342-393) from the columns of a sampled
+    Checkers batch; placeholders state_env, v_state, v_goal_all, actions_1hot, actions_prev, obs_others, obs_self_t, obs_self_v,
+    v_goal, td_target.  In the two TARGET feeds actions_prev is fed actions_1hot (the action just taken, as the reference does),
+    in mixer_op the one-hot actions_prev column.  target_agent: a CheckersQmixAgent holding the Agent_target weights; both one-hot
+    action feeds come from one tiling launch.  Pinned to tests/golden/trainstep_qmix_checkers_n*.npz."""
+    if env == "checkers":
+        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action)
+    if env != "particle":
+        raise ValueError("qmix_train_step_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
     calls = []
 
     def call(ops, feed, launch=True):

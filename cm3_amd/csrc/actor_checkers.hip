@@ -471,10 +471,238 @@ __device__ __forceinline__ void ck_qmix_head(const CkActorParams &p, const float
   }
 }
 
+__device__ __forceinline__ void put_split(_Float16 *h, _Float16 *l, int at, float v);   // (defined with the split-float16 layers below)
+
+// ---- the agent network over TRANSITION rows (cm3_qmix_checkers_rows_f32) -----------------------------------------------------------
+// What alg_qmix_checkers.train_step evaluates with the Agent_target weights (argmax_Q_target, alg_qmix_checkers.py:353-359) on every
+// sampled agent row: the forward pass of k_ck_actor<false, true> / k_ck_actor_x3<true> -- the SAME code behind the staging barrier
+// (float32: a further instantiation of k_ck_actor itself; split float16: k_ck_qmix_rows_x3 calls the device functions k_ck_actor_x3
+// calls), so a row's Q values are the collection kernels' bits -- fed from row-major arrays over R rows instead of an env's buffers,
+// with a pure argmax head (nothing is drawn: no steps / episode / prev_done / epsilon / seed).
+struct CkRowsParams {
+  size_t n_rows;
+  int N, Lo;
+  const void *obs_self_t;                  // WIDE_T: float64 [R][75] (what sample_batch returns), else int8 [R][75]
+  const double *obs_self_v, *obs_others;   // [R][4], [R][Lo]
+  const int32_t *actions_prev;             // [R], 0..4
+  const void *goals;                       // WIDE_G: int64 one-hot [R][2], else the uint8 index [R]
+  float *q;                                // [R][5]
+  int32_t *argmax;                         // [R]
+  int64_t *onehot;                         // [R][5]: actions_target_1hot (np.zeros(dtype=int))
+  float *q_max;                            // [R]
+  const float *packed;
+};
+
+// Where the staged inputs of a row go: the float32 tiles of k_ck_actor or the float16 hi | lo planes of k_ck_actor_x3 (the slots and
+// the values ck_x3_stage_inputs / k_ck_actor's staging write).  ov: v_obs_others, zeros from Lo on.
+struct CkRowsSinkF32 {
+  float *X0, *X2, *XO;
+  static constexpr int kKPad = ck_actor::kKConv;
+  __device__ __forceinline__ void win(int r, int k, float v) const { X0[r * ck_actor::kLdX0 + k] = v; }
+  __device__ __forceinline__ void tail(int r, int k, float v) const { X2[r * ck_actor::kLdX2 + ck_actor::kLin + k] = v; }
+  __device__ __forceinline__ void zero_tail(int r) const {
+    using namespace ck_actor;
+#pragma unroll
+    for (int k = kCat - kLin; k < kKSelf - kLin; ++k) X2[r * kLdX2 + kLin + k] = 0.0f;
+  }
+  __device__ __forceinline__ void others(int r, const float (&ov)[16], int Lo) const {
+    using namespace ck_actor;
+#pragma unroll
+    for (int q = 0; q < kKOth; ++q) {   // input k sits at position 4 (k & 3) + (k >> 2) (see k_ck_actor's staging)
+      const int k = 4 * (q & 3) + (q >> 2);
+      XO[r * kLdXO + q] = k < Lo ? ov[k] : 0.0f;
+    }
+  }
+};
+struct CkRowsSinkX3 {
+  _Float16 *X0, *X2h, *X2l, *XOh, *XOl;
+  static constexpr int kKPad = ck_actor::kKConvX;
+  // (a float64 window value must be exact in float16 here: the window plane has no lo part; the env's are -1 / 0 / 1)
+  __device__ __forceinline__ void win(int r, int k, float v) const { X0[r * ck_actor::kLhX0 + k] = (_Float16)v; }
+  __device__ __forceinline__ void tail(int r, int k, float v) const { put_split(X2h, X2l, r * ck_actor::kLhX2 + ck_actor::kLin + k, v); }
+  __device__ __forceinline__ void zero_tail(int r) const {   // units 32 .. 63 of both planes; the values follow (same wave, program order)
+    using namespace ck_actor;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int q = 0; q < (kKSelfX - kLin) / 8; ++q) {
+      *reinterpret_cast<uint4 *>(X2h + r * kLhX2 + kLin + 8 * q) = z;
+      *reinterpret_cast<uint4 *>(X2l + r * kLhX2 + kLin + 8 * q) = z;
+    }
+  }
+  __device__ __forceinline__ void others(int r, const float (&ov)[16], int Lo) const {
+    using namespace ck_actor;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int q = 0; q < kKOthX / 8; ++q) {
+      *reinterpret_cast<uint4 *>(XOh + r * kLhXO + 8 * q) = z;
+      *reinterpret_cast<uint4 *>(XOl + r * kLhXO + 8 * q) = z;
+    }
+#pragma unroll
+    for (int k = 0; k < 14; ++k)
+      if (k < Lo) put_split(XOh, XOl, r * kLhXO + k, ov[k]);
+  }
+};
+
+// Staging of 64 transition rows by threads tid < 256.  The rows' windows are ONE contiguous span of the input -- 64 x 75 int8 = 300
+// sixteen-byte chunks, or 64 x 75 float64 = 2400 of them -- that starts at a multiple of 16 bytes from the (16-byte aligned) base at
+// every agent count: thread tid requests chunks tid, tid + 256, ... with 16-byte loads, then scatters their elements to the
+// (row, k) slots (one division per chunk: the slot of element j + 1 follows from that of element j).  The last workgroup clamps: a
+// chunk that would cross the end of the array is read as the 16 bytes that END there (elements the chunk before it also delivers are
+// written twice, with the same value), a chunk past the end is not read at all (its address is the span's first chunk); window slots
+// of rows >= n_rows get zeros.  The row's tail (v_obs_self, v_obs_others, a_prev, goal), four lanes per row, is requested as
+// straight-line loads of a CLAMPED row ahead of every LDS write, as in ck_x3_stage_inputs (see there for what dependent round
+// trips cost a lone workgroup).
+template <bool WIDE_T, bool WIDE_G, class SINK>
+__device__ __forceinline__ void ck_rows_stage(const CkRowsParams &p, const SINK &S, int tid, size_t row_base) {
+  using namespace ck_actor;
+  constexpr int EPC = WIDE_T ? 2 : 16;                        // elements per 16-byte chunk
+  constexpr int NCH = 64 * kObs / EPC, Q = (NCH + 255) / 256;   // chunks per workgroup, per thread
+  constexpr int ESZ = WIDE_T ? 8 : 1;
+  static_assert((64 * kObs) % EPC == 0, "a workgroup's span is whole chunks");
+  const size_t rows = p.n_rows;
+  const size_t left = (rows - row_base) * kObs;               // elements from this workgroup's first one to the end of the array
+  const int rem = left < (size_t)(64 * kObs) ? (int)left : 64 * kObs;   // >= 75 > EPC: the grid has no empty workgroup
+  const char *span = reinterpret_cast<const char *>(p.obs_self_t) + row_base * (size_t)(kObs * ESZ);
+  uint4 raw[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int lo = (tid + 256 * q) * EPC;
+    const int at = lo >= rem ? 0 : (lo + EPC <= rem ? lo : rem - EPC);
+    __builtin_memcpy(&raw[q], span + (size_t)at * ESZ, 16);
+  }
+  const int trow = tid >> 2, part = tid & 3;
+  size_t row_t = row_base + trow;
+  row_t = row_t < rows ? row_t : rows - 1;
+  typedef double ck_dbl2 __attribute__((ext_vector_type(2)));
+  ck_dbl2 tv2[2];
+  __builtin_memcpy(&tv2[0], p.obs_self_v + row_t * 4, 16);
+  __builtin_memcpy(&tv2[1], p.obs_self_v + row_t * 4 + 2, 16);
+  constexpr int kLoMax = 14;
+  ck_dbl2 ov2[kLoMax / 2];
+  {
+    const int pairs = p.Lo >> 1;   // >= 1
+    const double *orow = p.obs_others + row_t * p.Lo;
+#pragma unroll
+    for (int j = 0; j < kLoMax / 2; ++j) {
+      const int jc = j < pairs ? j : pairs - 1;
+      __builtin_memcpy(&ov2[j], orow + 2 * jc, 16);
+    }
+  }
+  const int ap = p.actions_prev[row_t];
+  float g0, g1;
+  if constexpr (WIDE_G) {
+    typedef long long ck_i64x2 __attribute__((ext_vector_type(2)));
+    ck_i64x2 gv;
+    __builtin_memcpy(&gv, reinterpret_cast<const int64_t *>(p.goals) + row_t * 2, 16);
+    g0 = (float)gv[0];
+    g1 = (float)gv[1];
+  } else {
+    const int gl = reinterpret_cast<const uint8_t *>(p.goals)[row_t];
+    g0 = gl == 0 ? 1.0f : 0.0f;
+    g1 = gl == 0 ? 0.0f : 1.0f;
+  }
+  // zero fills while the loads are in flight: the k padding of the windows, the padding of the concat tail
+  for (int idx = tid; idx < 64 * (SINK::kKPad - kObs); idx += 256) {
+    const int r = idx / (SINK::kKPad - kObs), k = kObs + idx - r * (SINK::kKPad - kObs);
+    S.win(r, k, 0.0f);
+  }
+  if (part == 2) S.zero_tail(trow);
+  if (part == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) S.tail(trow, k, (float)tv2[k >> 1][k & 1]);
+  } else if (part == 1) {
+#pragma unroll
+    for (int k = 0; k < kA; ++k) S.tail(trow, 4 + k, ap == k ? 1.0f : 0.0f);
+    S.tail(trow, 9, g0);
+    S.tail(trow, 10, g1);
+  } else if (part == 3) {
+    float ov[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) ov[k] = k < kLoMax ? (float)ov2[(k < kLoMax ? k : 0) >> 1][k & 1] : 0.0f;
+    S.others(trow, ov, p.Lo);
+  }
+  // the windows: float64 -> float32 as a tf.float32 placeholder rounds a fed array; int8 -> float32
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int c = tid + 256 * q;
+    if (q + 1 < Q || c < NCH) {
+      const int lo = c * EPC;
+      const bool none = lo >= rem, full = lo + EPC <= rem;
+      const int pos0 = (none || full) ? lo : rem - EPC;
+      int r = pos0 / kObs, k = pos0 - r * kObs;
+#pragma unroll
+      for (int j = 0; j < EPC; ++j) {
+        float v;
+        if constexpr (WIDE_T) {
+          double d;
+          const uint32_t two[2] = {j == 0 ? raw[q].x : raw[q].z, j == 0 ? raw[q].y : raw[q].w};
+          __builtin_memcpy(&d, two, 8);
+          v = (float)d;
+        } else {
+          const uint32_t word = (j >> 2) == 0 ? raw[q].x : ((j >> 2) == 1 ? raw[q].y : ((j >> 2) == 2 ? raw[q].z : raw[q].w));
+          v = (float)(int8_t)(word >> (8 * (j & 3)));
+        }
+        S.win(r, k, none ? 0.0f : v);
+        ++k;
+        if (k == kObs) {
+          k = 0;
+          ++r;
+        }
+      }
+      if (!none && !full) {   // the one chunk that crosses the end of the array: zeros for its elements past the end
+#pragma unroll
+        for (int j = 0; j < EPC; ++j) {
+          const int pos = lo + j;
+          if (pos >= rem) S.win(pos / kObs, pos % kObs, 0.0f);
+        }
+      }
+    }
+  }
+}
+
+// lane l < 16 finishes row 16w + l: argmax with the first index on ties (tf.argmax); every output is optional
+__device__ __forceinline__ void ck_rows_head(const CkRowsParams &p, const float (*sLG)[8], int w, int lane, size_t row_base) {
+  if (lane < 16) {
+    const size_t row = row_base + 16 * w + lane;
+    if (row < p.n_rows) {
+      float q[kA];
+#pragma unroll
+      for (int a = 0; a < kA; ++a) q[a] = sLG[16 * w + lane][a];
+      int act;
+      float best;
+      greedy_argmax(q, act, best);
+      if (p.q) {
+#pragma unroll
+        for (int a = 0; a < kA; ++a) p.q[row * kA + a] = q[a];
+      }
+      if (p.argmax) p.argmax[row] = act;
+      if (p.q_max) p.q_max[row] = best;
+      if (p.onehot) {
+        // 40 bytes per row from a 16-byte aligned base: an even row is 16 | 16 | 8 bytes, an odd one 8 | 16 | 16
+        typedef long long i64x2 __attribute__((ext_vector_type(2)));
+        int64_t *o = p.onehot + row * kA;
+        const int k0 = (int)(row & 1), k1 = k0 ? 0 : 4;
+        *reinterpret_cast<i64x2 *>(o + k0) = i64x2{act == k0, act == k0 + 1};
+        *reinterpret_cast<i64x2 *>(o + k0 + 2) = i64x2{act == k0 + 2, act == k0 + 3};
+        o[k1] = act == k1;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ size_t ck_row_count(const CkActorParams &p) { return (size_t)p.E * p.N; }
+__device__ __forceinline__ size_t ck_row_count(const CkRowsParams &p) { return p.n_rows; }
+__device__ __forceinline__ int ck_stage(const CkActorParams &p) { return p.stage; }
+__device__ __forceinline__ int ck_stage(const CkRowsParams &) { return 2; }   // the others branch at every agent count
+
 // BF16: the two 256 x 256 layers on the bf16 matrix cores (precision = 1, not a parity path); otherwise float32 throughout.
 // GREEDY: the QMIX agent's head (ck_qmix_head) instead of the actor's sampling head (float32 only)
-template <bool BF16, bool GREEDY = false>
-__global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
+// ROWS: the transition-rows form -- cm3_last_kernel_variant() calls it k_ck_qmix_rows -- with P = CkRowsParams, its own staging
+// (ck_rows_stage<WIDE_T, WIDE_G>) and the argmax head (ck_rows_head).  ONE kernel text for both: everything behind the staging
+// barrier is the same code, so a row's Q values are the same bits.  (The body stays IN the kernel: handed to a __device__ function,
+// by reference or by value, the kernel-argument struct made the compiler schedule the existing instantiations differently.)
+template <bool BF16, bool GREEDY = false, bool ROWS = false, bool WIDE_T = false, bool WIDE_G = false, typename P = CkActorParams>
+__global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
   static_assert(!(BF16 && GREEDY), "the QMIX agent has no bf16 build: argmax would flip");
   using namespace ck_actor;
   // H: [64][260] first-layer activations / h2; before that it holds X0 [64][84] and C1 [64][164]
@@ -489,14 +717,21 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int N = p.N;
-  const size_t rows = (size_t)p.E * N;
+  const size_t rows = ck_row_count(p);
   const size_t row_base = (size_t)blockIdx.x * 64;
   const float *pk = p.packed;
+  (void)N;
+  (void)rows;   // (the rows kernel's head counts its rows itself)
   CM3_STAMP(0, false);
 
   float4 b_conv[5];
   load_b0<5, kKConv / 16>(pk + kPConv, 5 * (w >> 1), lane, b_conv);
   // ---- stage the inputs ------------------------------------------------------------------------------------------------
+  if constexpr (ROWS) {
+    CkRowsSinkF32 S;
+    S.X0 = sX0; S.X2 = sX2; S.XO = sXO;
+    ck_rows_stage<WIDE_T, WIDE_G>(p, S, tid, row_base);
+  } else {
   // window bytes -> floats (t_obs_self; values in {-1, 0, 1})
   if ((p.obst_stride & 3) == 0 && (64 % N) == 0) {
     // env records are dword-aligned and the 64 rows are whole envs: read each record as dwords (38 per env at N = 2
@@ -557,6 +792,7 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
     }
     (void)i;
   }
+  }
   CM3_STAMP(1, true);
   __syncthreads();
   CM3_STAMP(2, false);
@@ -609,7 +845,7 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
   zero_tiles(acc2);
   if constexpr (BF16) gemm_tiles_bf16<4>(sHb, kLdHb, pk + kPH2Sb, 4 * w, lane, b_h2b, acc2);
   else gemm_tiles<4, 4, kH1 / 16>(sH, kLdH, 0, pk + kPH2S, 4 * w, lane, b_h2, acc2);
-  const bool stage2 = p.stage > 1;
+  const bool stage2 = ck_stage(p) > 1;
   float bias_oth[4], bias_h2[4];
   load_bias<4>(pk + kPOthB, 4 * w, lane, bias_oth);
   load_bias<4>(pk + kPH2B, 4 * w, lane, bias_h2);
@@ -673,7 +909,8 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const CkActorParams p) {
   }
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
-  if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
+  if constexpr (ROWS) ck_rows_head(p, sLG, w, lane, row_base);
+  else if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
   else ck_actor_head(p, sLG, w, lane, row_base, rows);
   CM3_STAMP(12, true);
 }
@@ -1422,6 +1659,54 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
     }
 }
 
+// split float16: the LDS planes of k_ck_actor_x3, its layers (ck_x3_h2_bias, ck_x3_others, ck_x3_self_chain)
+template <bool WIDE_T, bool WIDE_G>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_qmix_rows_x3(const CkRowsParams p) {
+  using namespace ck_actor;
+  __shared__ __attribute__((aligned(16))) _Float16 sH[kCkX3HBytes / 2];
+  __shared__ __attribute__((aligned(16))) _Float16 sX0[kCkX3X0Bytes / 2];
+  __shared__ __attribute__((aligned(16))) _Float16 sX2[kCkX3X2Bytes / 2];
+  __shared__ __attribute__((aligned(16))) _Float16 sXO[kCkX3XOBytes / 2];
+  __shared__ float sLG[64][8];
+  CkX3Planes L;
+  L.Hh = sH; L.Hl = sH + 64 * kLdHb;
+  L.X0 = sX0; L.C1h = sH; L.C1l = sH + 64 * kLhC1;
+  L.X2h = sX2; L.X2l = sX2 + 64 * kLhX2; L.XOh = sXO; L.XOl = sXO + 64 * kLhXO;
+  L.LG = sLG;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t row_base = (size_t)blockIdx.x * 64;
+  const float *pk = p.packed;
+  CkConvB b_conv;
+  ck_x3_load_conv(pk, w, lane, b_conv);
+  if (w < 4) {
+    CkRowsSinkX3 S;
+    S.X0 = L.X0; S.X2h = L.X2h; S.X2l = L.X2l; S.XOh = L.XOh; S.XOl = L.XOl;
+    ck_rows_stage<WIDE_T, WIDE_G>(p, S, tid, row_base);
+  }
+  __syncthreads();
+  f32x4 acc2[4][kCkBCT];
+  ck_x3_h2_bias(pk, w, lane, acc2);
+  ck_x3_others(L, pk, w, lane, acc2);
+  ck_x3_self_chain(L, pk, w, lane, b_conv, acc2);
+  if (w < 4) {
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    ck_rows_head(p, sLG, w, lane, row_base);
+  }
+}
+
+template <bool WIDE_T, bool WIDE_G> static int ck_rows_launch(const CkRowsParams &p, int precision, hipStream_t s) {
+  const dim3 grid((unsigned)((p.n_rows + 63) / 64));
+  // (g: 1 = float64 windows, 2 = one-hot goals, 3 = both)
+  note_variant(precision == 2 ? "k_ck_qmix_rows_x3" : "k_ck_qmix_rows", 4, p.N, precision == 2 ? 8 : 4, 0, 0, 0, 0, 0,
+               (WIDE_T ? 1 : 0) + (WIDE_G ? 2 : 0), precision);
+  if (precision == 2) hipLaunchKernelGGL((k_ck_qmix_rows_x3<WIDE_T, WIDE_G>), grid, dim3(512), 0, s, p);
+  else hipLaunchKernelGGL((k_ck_actor<false, false, true, WIDE_T, WIDE_G, CkRowsParams>), grid, dim3(256), 0, s, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
 #endif  // CM3_NO_ENTRY_POINTS
 
 static int ck_actor_check(const cm3_actor_checkers_desc *d) {
@@ -1592,5 +1877,48 @@ extern "C" int cm3_qmix_checkers_f32(const cm3_actor_checkers_desc *d, const cm3
   else hipLaunchKernelGGL((k_ck_actor<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
+}
+// ---- the QMIX agent network over transition rows (ABI 9, additive) ------------------------------------------------------------------
+extern "C" int cm3_qmix_checkers_rows_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                          const cm3_qmix_checkers_rows *r, void *stream) {
+  using namespace cm3;
+  int rc = ck_qmix_check(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(d->precision == 0 || d->precision == 2,
+              "the Checkers QMIX agent runs at precision 0 (float32) or 2 (split float16); got %d (bf16 is not a parity path: argmax "
+              "would flip)", d->precision);
+  CM3_REQUIRE(wt, "null weights");
+  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_qmix_checkers_pack once per weight update");
+  CM3_REQUIRE(r, "null rows");
+  CM3_REQUIRE(r->obs_self_t && r->obs_self_v && r->obs_others && r->actions_prev && r->goals,
+              "missing inputs: obs_self_t, obs_self_v, obs_others, actions_prev and goals are all required");
+  CM3_REQUIRE(r->q || r->argmax || r->onehot || r->q_max, "no output requested: set at least one of q, argmax, onehot, q_max");
+  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
+  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
+  CM3_REQUIRE((r->obs_self_t_f64 == 0 || r->obs_self_t_f64 == 1) && (r->goals_onehot == 0 || r->goals_onehot == 1),
+              "form flags must be 0 or 1; got obs_self_t_f64 = %d, goals_onehot = %d", r->obs_self_t_f64, r->goals_onehot);
+  CM3_REQUIRE((uintptr_t)r->obs_self_t % 16 == 0 && (uintptr_t)r->obs_self_v % 16 == 0 && (uintptr_t)r->obs_others % 16 == 0 &&
+                  (uintptr_t)r->actions_prev % 4 == 0 && (r->goals_onehot == 0 || (uintptr_t)r->goals % 16 == 0),
+              "misaligned inputs: obs_self_t, obs_self_v, obs_others (and one-hot goals) must be 16-byte aligned, actions_prev 4-byte");
+  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0 && (uintptr_t)r->q % 4 == 0 && (uintptr_t)r->argmax % 4 == 0 && (uintptr_t)r->q_max % 4 == 0,
+              "misaligned outputs: onehot must be 16-byte aligned, q, argmax and q_max 4-byte");
+  CkRowsParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_rows = (size_t)r->n_rows;
+  p.N = d->n_agents;
+  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
+  p.obs_self_t = r->obs_self_t;
+  p.obs_self_v = r->obs_self_v;
+  p.obs_others = r->obs_others;
+  p.actions_prev = r->actions_prev;
+  p.goals = r->goals;
+  p.q = r->q;
+  p.argmax = r->argmax;
+  p.onehot = r->onehot;
+  p.q_max = r->q_max;
+  p.packed = (const float *)wt->packed;
+  hipStream_t s = (hipStream_t)stream;
+  if (r->obs_self_t_f64) return r->goals_onehot ? ck_rows_launch<true, true>(p, d->precision, s) : ck_rows_launch<true, false>(p, d->precision, s);
+  return r->goals_onehot ? ck_rows_launch<false, true>(p, d->precision, s) : ck_rows_launch<false, false>(p, d->precision, s);
 }
 #endif  // CM3_NO_ENTRY_POINTS

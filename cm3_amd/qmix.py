@@ -16,7 +16,8 @@ ignored, so ``{v.name: sess.run(v)}`` of either scope loads unchanged.  The netw
 (a float64 env's observation is rounded to float32 as the inputs are staged, as the reference's tf.float32 placeholders do).
 
 Exploration draws come from the build's own Philox stream (csrc/actor.hip, kPurposeExplore): the same law as the reference's
-np.random calls, not the same numbers.  The mixer and the learner stay on the reference's side.
+np.random calls, not the same numbers.  The mixer and the learner stay on the reference's side; both agents
+serve a learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from.
 """
 import ctypes
 
@@ -200,6 +201,10 @@ class CheckersQmixAgent(object):
     one-launch rollout kernel (cm3_policy_rollout_checkers_qmix; enqueue_episode / episode_ok below): "f16x3", one or two agents,
     agent and env on one seed and env_id_base -- the same bits as the launch pairs.  (The hooks are NOT named like CheckersActor's
     enqueue_rollout / fused_rollout_ok: "auto" picks the one-launch kernel for whatever carries those names.)
+
+    For a learner: greedy_rows evaluates the network on the rows of a sampled batch (argmax_Q_target of the reference's train_step,
+    one launch, no draws), soft_update_from moves an Agent_target copy towards the main agent; cm3_amd.batch.qmix_train_step_feeds(
+    env="checkers", target_agent=...) builds every feed of train_step around them.  The mixer stays the caller's.
     """
 
     def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0, precision="f32"):
@@ -306,3 +311,76 @@ class CheckersQmixAgent(object):
         self.enqueue(env.E, s["obs_self_t_raw"], env.obst_stride, s["obs_self_v"], s["obs_others"], env._goals, prev,
                      env._steps, env._episode, actions, epsilon, q, env_id_base=env._desc.env_id_base)
         return (actions, q) if return_q else actions
+
+    def greedy_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, q=False, onehot=True, q_max=False):
+        """The network over transition rows with a pure argmax head, ONE launch (cm3_qmix_checkers_rows_f32): with the Agent_target
+        weights this is argmax_Q_target of alg_qmix_checkers.train_step (alg_qmix_checkers.py:353-359) on the columns
+        next_obs_self_t / next_obs_self_v / next_obs_others / actions / goals of a sampled batch (the reference feeds the action just
+        taken as actions_prev next to the next observation).  Inputs share a leading shape [...]: obs_self_t [..., 5, 5, 3] or
+        [..., 75]; obs_self_v [..., 4]; obs_others [..., Lo]; actions_prev [...] (0..4); goals a one-hot [..., 2] or an index [...].
+        The form follows from the dtype: int8 windows and uint8 index goals go in as they are (what the trajectory and the compact
+        ring keep); everything else is made float64 windows / int64 one-hot goals (no copy for the columns sample_batch returns).
+        At precision "f16x3" float64 windows must hold float16-exact values (the env's are -1 / 0 / 1): the window plane is one
+        float16 plane, as in the collection kernel.  Returns a dict of device tensors over the R = prod(leading shape) rows:
+        "argmax" int32 [R] always; "q" float32 [R, 5], "onehot" int64 [R, 5] (the reference's actions_target_1hot), "q_max" float32
+        [R] when asked for.  A row's Q values are the bits act() computes for the same inputs at the same precision."""
+        lead = tuple(obs_self_v.shape[:-1])
+        win = tuple(obs_self_t.shape)
+        index_goals = tuple(goals.shape) == lead
+        if (win not in (lead + (5, 5, 3), lead + (75,)) or tuple(obs_self_v.shape) != lead + (4,)
+                or tuple(obs_others.shape) != lead + (self.Lo,) or tuple(actions_prev.shape) != lead
+                or not (index_goals or tuple(goals.shape) == lead + (2,))):
+            raise Cm3Error("greedy_rows takes [..., 5, 5, 3] (or [..., 75]), [..., 4], [..., %d], [...] and [..., 2] (or [...]) with "
+                           "equal leading shape, got %s, %s, %s, %s, %s" % (self.Lo, win, tuple(obs_self_v.shape),
+                                                                             tuple(obs_others.shape), tuple(actions_prev.shape),
+                                                                             tuple(goals.shape)))
+        rows = int(np.prod(lead, dtype=np.int64))
+        if rows <= 0:
+            raise Cm3Error("greedy_rows needs at least one row")
+        stage = lambda t, dt: t.to(device=self.device, dtype=dt).contiguous()      # noqa: E731
+        ot = stage(obs_self_t, torch.int8 if obs_self_t.dtype == torch.int8 else torch.float64)
+        if index_goals:
+            vg = (stage(goals, torch.uint8) if goals.dtype == torch.uint8
+                  else torch.nn.functional.one_hot(goals.to(self.device).long(), 2).contiguous())
+        else:
+            vg = stage(goals, torch.int64)
+        out = {"argmax": torch.empty(rows, dtype=torch.int32, device=self.device)}
+        if q:
+            out["q"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        if onehot:
+            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
+        if q_max:
+            out["q_max"] = torch.empty(rows, dtype=torch.float32, device=self.device)
+        self.enqueue_rows(rows, ot, stage(obs_self_v, torch.float64), stage(obs_others, torch.float64),
+                          stage(actions_prev, torch.int32), vg, **out)
+        return out
+
+    def enqueue_rows(self, n_rows, obs_self_t, obs_self_v, obs_others, actions_prev, goals, q=None, argmax=None, onehot=None,
+                     q_max=None, stream=None):
+        """Raw launch of cm3_qmix_checkers_rows_f32 on contiguous device tensors: obs_self_t int8 or float64 [R, 75], obs_self_v /
+        obs_others float64, actions_prev int32 [R], goals uint8 [R] or int64 [R, 2]; every output is optional, one is required."""
+        if obs_self_t.dtype not in (torch.int8, torch.float64) or goals.dtype not in (torch.uint8, torch.int64):
+            raise Cm3Error("enqueue_rows reads int8 or float64 windows and uint8 index or int64 one-hot goals, not %s / %s"
+                           % (obs_self_t.dtype, goals.dtype))
+        r = _lib.QmixCheckersRows()
+        r.obs_self_t, r.obs_self_v, r.obs_others = _lib.ptr(obs_self_t), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
+        r.actions_prev, r.goals = _lib.ptr(actions_prev), _lib.ptr(goals)
+        r.obs_self_t_f64 = 1 if obs_self_t.dtype == torch.float64 else 0
+        r.goals_onehot = 1 if goals.dtype == torch.int64 else 0
+        r.q, r.argmax, r.onehot, r.q_max = _lib.ptr(q), _lib.ptr(argmax), _lib.ptr(onehot), _lib.ptr(q_max)
+        r.n_rows = int(n_rows)
+        d = self._desc(1, 0.0, 0, 75 * self.n)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_qmix_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the thirteen TF-shaped float32 tensors in place, then repack(): the agent half of
+        list_update_target_ops (alg_qmix_checkers.py:128-130), for an agent holding the Agent_target weights."""
+        if not isinstance(main, CheckersQmixAgent) or main.n != self.n or main.precision != self.precision:
+            raise Cm3Error("soft_update_from: the main agent must be a CheckersQmixAgent for %d agents at precision %r"
+                           % (self.n, self.precision))
+        tau = float(tau)
+        for short in CK_NAMES:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[short].copy_(tau * main.w[short].to(self.device) + (1.0 - tau) * self.w[short])
+        self.repack()

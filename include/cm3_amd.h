@@ -58,6 +58,8 @@ extern "C" {
                                   live_record.  The in-tree binding mirrors the new size (tests/test_abi.py compares every offset).
                                   cm3_qmix_particle_rows_f32 (the QMIX agent network over transition rows, argmax head) and
                                   cm3_qmix_td_target_f64 (the QMIX TD target): the data side of alg_qmix.train_step; additive.
+                                  cm3_qmix_checkers_rows_f32 (the Checkers QMIX agent network over transition rows, argmax head): the
+                                  data side of alg_qmix_checkers.train_step; additive.
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -566,6 +568,46 @@ int cm3_qmix_checkers_pack(const cm3_actor_checkers_desc *desc, const cm3_actor_
 /* Reads ONLY weights->packed (written by cm3_qmix_checkers_pack). */
 int cm3_qmix_checkers_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
                           const cm3_actor_checkers_bufs *bufs, void *stream);
+
+/* The same network over TRANSITION rows (part of ABI 9, additive): what alg_qmix_checkers.train_step evaluates with the Agent_target
+ * weights (argmax_Q_target, alg_qmix_checkers.py:353-359) on every sampled agent row.  Row r comes from five row-major arrays over
+ * n_rows rows -- the columns next_obs_self_t / next_obs_self_v / next_obs_others / actions / goals of a sampled batch viewed as
+ * [B * N, .] (the reference feeds the action just taken as actions_prev there) -- and n_rows is any positive count (not a multiple of
+ * n_agents).  The head is a pure argmax (the first index on ties); nothing is drawn: no steps, episode, prev_done, epsilon or seed.
+ * A row's Q values are, bit for bit, those cm3_qmix_checkers_f32 computes for the same inputs at the same precision.
+ *   obs_self_t   obs_self_t_f64 = 0: int8 [n_rows][75] (what the trajectory and the compact ring keep);
+ *                obs_self_t_f64 = 1: float64 [n_rows][75] (what sample_batch of either ring returns), rounded to float32 as a
+ *                tf.float32 placeholder rounds a fed array.  At precision 2 the window plane is ONE float16 plane, as in the collection
+ *                kernel: float64 windows must then hold float16-exact values (the env's are -1 / 0 / 1).
+ *   goals        goals_onehot = 0: the uint8 index [n_rows] (0 or 1); goals_onehot = 1: the int64 one-hot pair [n_rows][2], each of
+ *                its two values converted to float as it is.
+ * Alignment the staging relies on (checked): obs_self_t (both forms), obs_self_v, obs_others, one-hot goals and onehot 16 bytes;
+ * actions_prev, q, argmax and q_max 4 bytes; index goals none.  No load touches a byte past n_rows rows of any input.
+ * Every output is optional, at least one is required:
+ *   q       the Q values                                  argmax  the greedy action
+ *   onehot  the reference's actions_target_1hot (int64)     q_max   Q of the greedy action
+ * Rows at or past n_rows are not written.  (Anonymous struct tag, like cm3_qmix_rows.) */
+typedef struct {
+  const void    *obs_self_t;    /* [n_rows][75] int8 or float64 (obs_self_t_f64), 16-byte aligned */
+  const double  *obs_self_v;    /* [n_rows][4], 16-byte aligned */
+  const double  *obs_others;    /* [n_rows][2*max(N-1,1)], 16-byte aligned */
+  const int32_t *actions_prev;  /* [n_rows], 0..4 */
+  const void    *goals;         /* [n_rows] uint8, or [n_rows][2] int64 (goals_onehot; then 16-byte aligned) */
+  int32_t  obs_self_t_f64;      /* 0 / 1 */
+  int32_t  goals_onehot;        /* 0 / 1 */
+  float   *q;                   /* optional [n_rows][5] */
+  int32_t *argmax;              /* optional [n_rows] */
+  int64_t *onehot;              /* optional [n_rows][5], 16-byte aligned */
+  float   *q_max;               /* optional [n_rows] */
+  int64_t  n_rows;
+} cm3_qmix_checkers_rows;
+/* desc: validated like cm3_qmix_checkers_f32's (n_agents 1..8, the widths, n_obs 2) plus precision 0 or 2; n_envs, epsilon, seed,
+ * env_id_base, stage and obs_self_t_stride are not read.  Reads ONLY weights->packed (cm3_qmix_checkers_pack).  CM3_ERR_INVALID before
+ * any launch: null desc / weights / rows / weights->packed, a missing input, no output requested, n_rows <= 0 or more than
+ * 64 * (2^31 - 1), a form flag other than 0 / 1, a misaligned pointer.  cm3_last_kernel_variant() names the launch
+ * k_ck_qmix_rows<f32,N=..,g=F,..> or k_ck_qmix_rows_x3<..> with F = obs_self_t_f64 + 2 * goals_onehot. */
+int cm3_qmix_checkers_rows_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
+                               const cm3_qmix_checkers_rows *rows, void *stream);
 
 /* A whole POLICY-DRIVEN Checkers rollout in ONE launch (ABI 7; csrc/policy_checkers.hip): per tick the actor above (precision 2),
  * epsilon-mixed sampling and Checkers.step with the actions just drawn -- train_onpolicy.py:309-347 / train_offpolicy.py:309-368 without
