@@ -233,6 +233,8 @@ SYMBOLS = {
                                               c_void_p]),
     "cm3_policy_rollout_f64": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), P(ActorParticleDesc),
                                               P(ActorParticleWeights), c_void_p, c_size_t, c_int32, c_void_p]),
+    "cm3_policy_rollout_qmix_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), P(ActorParticleDesc), c_void_p, c_void_p,
+                                                   c_size_t, c_void_p, c_int32, c_void_p]),
     "cm3_policy_force_row_tiles": (ctypes.c_int, [c_int32]),
     "cm3_qmix_particle_packed_bytes": (c_size_t, [c_int32]),
     "cm3_qmix_particle_pack": (ctypes.c_int, [P(ActorParticleDesc), P(c_void_p), c_void_p, c_void_p]),

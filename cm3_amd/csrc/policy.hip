@@ -27,6 +27,23 @@
 // What the physics reads back is never that rounded tile: in float64 the rows' pre-step state lives in the double exchange slots
 // `ns` and their goals in `gd` (see the kernel), so an f64 episode is bit-identical to alternating cm3_actor_particle_f64 and
 // cm3_particle_step_f64 launches.
+//
+// QMIX mode (k_policy_rollout<N, kPrecF32, 4, float, true>, float32 build only; cm3_policy_rollout_qmix_f32): the QMIX baseline's
+// agent network (networks.Qmix_single_particle, k_qmix_particle in actor.hip) and its epsilon-greedy choice in the CM3 actor's
+// place; everything from "physics of agent i" to the closing barrier is the same text.  What differs:
+//   * LDS: qmix_forward's tiles xs[64][K1+1], h1s[64][66], h2s[64][66] (QmixLayout<N>) instead of the actor's tables, 38 - 43 KB;
+//   * row tiles: RT = 4 only -- 64 rows per workgroup, wave w owns rows 16w .. 16w+15, part 0 (lanes 0..15) writes;
+//     cm3_policy_force_row_tiles does not apply (no 32- or 16-row build of this mode exists);
+//   * weights: every lane's operands of the three layers (cm3_qmix_particle_pack's buffer) are loaded ONCE per launch and stay in
+//     registers for all ticks, ~55 VGPRs next to the 16 accumulators;
+//   * per tick: the three layers of qmix_forward -- the same matrix instruction, k grouping and start values, so every Q value
+//     is the same k-ordered chain and the same bits as k_qmix_particle's -- then epsilon-greedy on the exploration words of
+//     (seed, global env id, the row's episode, its pre-step steps, agent): what k_qmix_particle reads from meta / episode at that
+//     tick, also after a same-tick reset.  Three barriers per tick: after "h", after "h2", the closing one;
+//   * the input tile's columns: concat(others[L], self[4], goal[2], 0, 0) instead of self, goal, others -- the env phase reaches
+//     the tile through three column offsets (kXSelf / kXGoal / kXOth); the two zero pads are written once per launch;
+//   * q.probs receives the raw Q values, epsilon comes from q.eps_dev when given (read once at entry).
+// Bit-identical to alternating cm3_qmix_particle_f32 and cm3_particle_step_f32 launches (tests/test_gpu_qmix_particle_episode.py).
 #define CM3_NO_ENTRY_POINTS 1
 #if !defined(CM3_PARTICLE_F32) && !defined(CM3_PARTICLE_F64)
 #define CM3_PARTICLE_F32 1
@@ -52,7 +69,93 @@ struct PolicyParams {
   size_t st_probs;
   float eps;
   int stage;
+  const float *eps_dev;   // QMIX mode, optional: epsilon read at entry instead of eps
 };
+
+// ---- QMIX mode: the three layers of qmix_forward (actor.hip) once more, as device functions of this kernel.  A COPY, not a shared
+// text: with the layers of qmix_forward moved into these functions, every k_qmix_particle / k_qmix_particle_rows build came out with
+// another instruction schedule (up to 12 instructions more, 650 - 1060 differing lines per kernel), so qmix_forward keeps its text and
+// the rollout has its own.  What must stay equal between the two is what the bits rest on: v_mfma_f32_16x16x4_f32, k = 4s .. 4s+3
+// per step in ascending s, and the start values (bias as C for "h" and "out", zero then + b2 for "h2").
+template <int N> struct QmixW {
+  float a1[QmixLayout<N>::S1P], bw[16], wo[16];   // layer-1 A operands, layer-2 B operands, the head's A operands of this lane
+  float4 b1;                                      // units 16w + 4 (l>>4) + 0..3
+  float b2;                                       // unit 16w + (l&15)
+  float4 bo;                                      // actions 4 (l>>4) + 0..3
+};
+template <int N> __device__ __forceinline__ void qmix_load_w(const float *packed, int w, int lane, QmixW<N> &k) {
+  using QL = QmixLayout<N>;
+  const int col = lane & 15, hi = lane >> 4;
+  const float4 *src = reinterpret_cast<const float4 *>(packed + QL::kW1) + (size_t)(w * 64 + lane) * (QL::S1P / 4);
+#pragma unroll
+  for (int s4 = 0; s4 < QL::S1P / 4; ++s4) {
+    const float4 v = src[s4];
+    k.a1[4 * s4 + 0] = v.x; k.a1[4 * s4 + 1] = v.y; k.a1[4 * s4 + 2] = v.z; k.a1[4 * s4 + 3] = v.w;
+  }
+  const float4 *s2 = reinterpret_cast<const float4 *>(packed + QL::kW2) + (size_t)(w * 64 + lane) * 4;
+  const float4 *so = reinterpret_cast<const float4 *>(packed + QL::kWo) + (size_t)lane * 4;
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) {
+    const float4 v = s2[s4], u = so[s4];
+    k.bw[4 * s4 + 0] = v.x; k.bw[4 * s4 + 1] = v.y; k.bw[4 * s4 + 2] = v.z; k.bw[4 * s4 + 3] = v.w;
+    k.wo[4 * s4 + 0] = u.x; k.wo[4 * s4 + 1] = u.y; k.wo[4 * s4 + 2] = u.z; k.wo[4 * s4 + 3] = u.w;
+  }
+  k.b1 = reinterpret_cast<const float4 *>(packed + QL::kB1)[4 * w + hi];
+  k.b2 = packed[QL::kB2 + 16 * w + col];
+  k.bo = reinterpret_cast<const float4 *>(packed + QL::kBo)[hi];
+}
+// layer "h": units [16w, 16w+16) for all 64 rows, C[unit][row]
+template <int N> __device__ __forceinline__ void qmix_layer_h(const QmixW<N> &k, const float (*xs)[QmixLayout<N>::XW],
+                                                              float (*h1s)[QmixLayout<N>::HS], int w, int lane) {
+  const int col = lane & 15, hi = lane >> 4;
+  f32x4 c[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) c[t] = f32x4{k.b1.x, k.b1.y, k.b1.z, k.b1.w};
+#pragma unroll
+  for (int s = 0; s < QmixLayout<N>::S1; ++s)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) c[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(k.a1[s], xs[16 * t + col][4 * s + hi], c[t], 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    *reinterpret_cast<float2 *>(&h1s[16 * t + col][16 * w + 4 * hi]) = make_float2(relu_f32(c[t][0]), relu_f32(c[t][1]));
+    *reinterpret_cast<float2 *>(&h1s[16 * t + col][16 * w + 4 * hi + 2]) = make_float2(relu_f32(c[t][2]), relu_f32(c[t][3]));
+  }
+}
+// layer "h2": columns [16w, 16w+16), C[row][unit]
+template <int N> __device__ __forceinline__ void qmix_layer_h2(const QmixW<N> &k, const float (*h1s)[QmixLayout<N>::HS],
+                                                               float (*h2s)[QmixLayout<N>::HS], int w, int lane) {
+  const int col = lane & 15, hi = lane >> 4;
+  f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int s = 0; s < kQH / 4; ++s)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1s[16 * t + col][4 * s + hi], k.bw[s], acc[t], 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) h2s[16 * t + 4 * hi + reg][16 * w + col] = relu_f32(acc[t][reg] + k.b2);
+}
+// head "out": C[action][row] of rows [16w, 16w+16), one k-ordered chain; lanes 0..15 end with all five Q values of their row
+template <int N> __device__ __forceinline__ void qmix_head_q(const QmixW<N> &k, const float (*h2s)[QmixLayout<N>::HS], int w, int lane,
+                                                             float (&q)[kA]) {
+  const int col = lane & 15, hi = lane >> 4;
+  float hx[kQH / 4];
+#pragma unroll
+  for (int s = 0; s < kQH / 4; ++s) hx[s] = h2s[16 * w + col][4 * s + hi];
+  f32x4 acc = f32x4{k.bo.x, k.bo.y, k.bo.z, k.bo.w};
+#pragma unroll
+  for (int s = 0; s < kQH / 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k.wo[s], hx[s], acc, 0, 0, 0);
+#pragma unroll
+  for (int a = 0; a < 4; ++a) q[a] = acc[a];
+  // action 4 of the row sits in register 0 of the lane 16 further on (see actor_head_probs)
+  uint32_t x;
+  __builtin_memcpy(&x, &q[0], 4);
+  const auto sw = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+  const uint32_t y = sw[1];
+  __builtin_memcpy(&q[4], &y, 4);
+}
 
 // RT = 16-row tiles per workgroup: 4 (64 agent rows) where that already gives every CU several workgroups; 2 or 1 for smaller
 // batches, so that two or more workgroups share a CU and one's matrix-core phases run under the other's physics / LDS staging
@@ -62,14 +165,32 @@ struct PolicyParams {
 // R = the env's real (PolicyReal of the translation unit).  R = double: the physics reads its own and the other agents' pre-step
 // state from `ns` (double, written at the end of every tick) and the goals from `gd`, never from the float32 input tile; the
 // wave's post-step exchange goes through the same `ns` slots.  +3 KB of LDS at 64 rows, the per-env reductions by shuffles.
-template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL k_policy_rollout(const PolicyParams q) {
+// Element [r][c] of the rollout's input tile: the actor's (lds.xs) or the QMIX mode's (q_xs), whose rows differ in width.  A function
+// of the two declarations, called where the tile is touched -- not a pointer variable set once, not a lambda: with either, the float32
+// actor builds of two, four and eight agents came out with permuted registers or a commuted operand.
+template <bool QMIX, typename A, typename B> __device__ __forceinline__ float &policy_tile(A actor_xs, B &qmix_xs, int r, int c) {
+  if constexpr (QMIX) return qmix_xs[r][c];
+  else return actor_xs[r][c];
+}
+#define XS(r, c) policy_tile<QMIX>(lds.xs, q_xs, r, c)   // (inside k_policy_rollout only; undefined after it)
+// QMIX: the QMIX agent's network and epsilon-greedy choice instead of the CM3 actor (see the head of this file)
+template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ void CM3_MATRIX_KERNEL k_policy_rollout(const PolicyParams q) {
   using G = ActorGeom<N, BF16, RT>;
+  using QL = QmixLayout<N>;
   using V4 = typename Vec<R>::v4;
   using V2 = typename Vec<R>::v2;
   constexpr bool F64 = sizeof(R) == 8;
+  static_assert(!QMIX || (RT == 4 && !F64 && BF16 == kPrecF32), "QMIX mode: 64-row workgroups, float32 env, float32 network");
   constexpr int L = G::L, NO = N > 1 ? N - 1 : 1;
+  // the input tile's columns: the actor reads (self, goal, others), the QMIX agent concat(others, self, goal, 0, 0)
+  constexpr int kXSelf = QMIX ? L : 0, kXGoal = kXSelf + 4, kXOth = QMIX ? 0 : 6;
   const ParticleParams &p = q.p;
+  // (every mode declares both sets of LDS arrays and uses one: an array without a use is not allocated -- see the LDS sizes in
+  // policy.resource_usage.txt, 38 - 43 KB per workgroup in QMIX mode)
   CM3_ACTOR_LDS_RT(N, BF16, RT, lds);
+  __shared__ float q_xs[64][QL::XW];
+  __shared__ __attribute__((aligned(16))) float q_h1s[64][QL::HS];
+  __shared__ float q_h2s[64][QL::HS];
   __shared__ __attribute__((aligned(16))) V4 ns[16 * RT];  // post-step (vx, vy, px, py) of every row, exchanged inside a wave
   __shared__ __attribute__((aligned(16))) V2 gd[F64 ? 16 * RT : 1];   // float64: the rows' goals (float32 reads them from the tile)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -105,9 +226,14 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
   // (the W2 slice first: it keeps its registers for the whole launch, and requested after the table copy the register allocator
   // parked the copy in those very registers -- a wait for the tables, a move, and only then the slice's requests)
   ActorB<N, BF16> b;
-  actor_load_b<N, BF16>(q.packed, w, lane, b);
   ActorTabRegs<N> tab;
-  actor_tables_fetch<N>(q.packed, tid, tab);
+  QmixW<N> qw;
+  if constexpr (QMIX) {
+    qmix_load_w<N>(q.packed, w, lane, qw);   // the lane's operands of all three layers, for the whole launch
+  } else {
+    actor_load_b<N, BF16>(q.packed, w, lane, b);
+    actor_tables_fetch<N>(q.packed, tid, tab);
+  }
   const int2 meta = reinterpret_cast<const int2 *>(p.meta_in)[e];
   const bool auto_reset = (p.flags & CM3_FLAG_AUTO_RESET) != 0;
   uint32_t episode = (uint32_t)p.episode[e];
@@ -120,17 +246,29 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) o0[k] = o4[k];
   }
-  const uint32_t ublock = actor_block_word(p.seed, genv, i);   // stage 1 of the sampling uniforms: once per launch (actor_common.h)
+  // stage 1 of the actor's sampling uniforms, once per launch (actor_common.h); QMIX mode: epsilon, read once
+  uint32_t ublock = 0;
+  uint2 xblock = make_uint2(0u, 0u);
+  float q_eps = 0.0f;
+  if constexpr (QMIX) {
+    q_eps = q.eps_dev ? *q.eps_dev : q.eps;
+  } else {
+    ublock = actor_block_word(p.seed, genv, i);
+  }
   int steps = meta.x, collisions = meta.y;
   const uint32_t episode_in = episode;
-  actor_tables_store<N, BF16, RT>(lds, tid, tab);
+  if constexpr (!QMIX) actor_tables_store<N, BF16, RT>(lds, tid, tab);
   if (part0) {
-    lds.xs[rl][0] = (float)s0.x; lds.xs[rl][1] = (float)s0.y; lds.xs[rl][2] = (float)s0.z; lds.xs[rl][3] = (float)s0.w;
-    lds.xs[rl][4] = (float)g0.x; lds.xs[rl][5] = (float)g0.y;
+    XS(rl, kXSelf + 0) = (float)s0.x; XS(rl, kXSelf + 1) = (float)s0.y; XS(rl, kXSelf + 2) = (float)s0.z; XS(rl, kXSelf + 3) = (float)s0.w;
+    XS(rl, kXGoal + 0) = (float)g0.x; XS(rl, kXGoal + 1) = (float)g0.y;
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) {
-      lds.xs[rl][6 + 4 * k + 0] = (float)o0[k].x; lds.xs[rl][6 + 4 * k + 1] = (float)o0[k].y;
-      lds.xs[rl][6 + 4 * k + 2] = (float)o0[k].z; lds.xs[rl][6 + 4 * k + 3] = (float)o0[k].w;
+      XS(rl, kXOth + 4 * k + 0) = (float)o0[k].x; XS(rl, kXOth + 4 * k + 1) = (float)o0[k].y;
+      XS(rl, kXOth + 4 * k + 2) = (float)o0[k].z; XS(rl, kXOth + 4 * k + 3) = (float)o0[k].w;
+    }
+    if constexpr (QMIX) {   // the two zero pads of the last k-step: once per launch, the env phase never writes them
+      XS(rl, L + 6) = 0.0f;
+      XS(rl, L + 7) = 0.0f;
     }
     if constexpr (F64) {
       ns[rl] = s0;
@@ -139,9 +277,12 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
   }
   __syncthreads();
   CM3_STAMP(14, true);    // tables, weights and the input tile are in
+  // QMIX mode draws stage 1 of its exploration words here, behind the barrier (drawn ahead of it, next to the entry's loads, the
+  // one-agent build reserved 52 bytes of scratch per lane that no instruction touched)
+  if constexpr (QMIX) xblock = explore_block_words(p.seed, genv, i);
   ActorHeadB hb;
   ActorFirstB<N> f1;
-  if constexpr (!F64) {
+  if constexpr (!F64 && !QMIX) {
     actor_head_load(lds.wout, lane, hb);      // output-layer operands of this lane, once per launch
     actor_first_b<N, float>(&lds.ws_self[0][0], &lds.ws_oth[0][0], w, lane, q.stage > 1, f1);  // ... and its first-layer operands
                                               // (round 4: they were re-read from LDS every tick)
@@ -155,21 +296,37 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
     // float64: the operands of the first layer and the head are read from the LDS tables every tick (the float32 build holds them
     // for the whole launch): their 40 (N = 4) to 56 (N = 8) registers are what the double physics and the re-initialisation's
     // double transcendentals need -- held, every f64 build spilled (20 - 340 bytes of scratch per lane)
-    if constexpr (F64) actor_first_b<N, float>(&lds.ws_self[0][0], &lds.ws_oth[0][0], w, lane, q.stage > 1, f1);
-    actor_mlp<N, BF16, RT>(lds, b, f1, w, lane, q.stage > 1);
+    if constexpr (QMIX) {
+      qmix_layer_h<N>(qw, q_xs, q_h1s, w, lane);
+      __syncthreads();
+      qmix_layer_h2<N>(qw, q_h1s, q_h2s, w, lane);
+      __syncthreads();
+    } else {
+      if constexpr (F64) actor_first_b<N, float>(&lds.ws_self[0][0], &lds.ws_oth[0][0], w, lane, q.stage > 1, f1);
+      actor_mlp<N, BF16, RT>(lds, b, f1, w, lane, q.stage > 1);
+    }
     if (row_wave) {   // (wave-uniform; no workgroup barrier inside)
     // The head, the physics and the stores of the rows are the part of the tick only this wave can do while its workgroup waits at
     // the closing barrier: it goes first on its SIMD, ahead of the matrix phases of the workgroup that shares the CU (measured,
     // same box, three alternating rounds: 4.31 -> 4.15 us per tick at 4 096 x 4, 45.1 -> 44.6 at 65 536 x 4; levels 1, 2, 3 are
     // the same, raising the priority for the WHOLE tick loses the gain; profiles/r04_policy_head.txt)
     __builtin_amdgcn_s_setprio(2);
-    float pr[kA];
-    const float u = actor_uniform_from(ublock, episode, steps);
-    if constexpr (F64) actor_head_load(lds.wout, lane, hb);
-    actor_head_probs(lds.h2s, hb, wr, lane, q.eps, pr);
-    // (the head leaves the row's probabilities in lanes 0..15 only; lanes 16..63 repeat the physics of lane l & 15 and get its
+    float pr[kA];   // the row's probabilities; QMIX mode: its raw Q values
+    int act;
+    // (either head leaves the row's values in lanes 0..15 only; lanes 16..63 repeat the physics of lane l & 15 and get its
     // action so that they take the same branches -- nothing they compute is stored: see the exchange slot below)
-    const int act = bcast_row0(actor_pick(pr, u));
+    if constexpr (QMIX) {
+      // exploration words first: the Philox mixing is VALU work that issues between the head's dependent matrix instructions
+      uint32_t w_explore, w_action;
+      explore_words_from(xblock, episode, (uint32_t)steps, w_explore, w_action);
+      qmix_head_q<N>(qw, q_h2s, wr, lane, pr);
+      act = bcast_row0(epsilon_greedy(pr, q_eps, w_explore, w_action));
+    } else {
+      const float u = actor_uniform_from(ublock, episode, steps);
+      if constexpr (F64) actor_head_load(lds.wout, lane, hb);
+      actor_head_probs(lds.h2s, hb, wr, lane, q.eps, pr);
+      act = bcast_row0(actor_pick(pr, u));
+    }
     CM3_STAMP(7, false);
 
     // ---- physics of agent i (environment.py:81-123), lanes of part 0 ------------------------------------------------------
@@ -179,8 +336,8 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
       si = ns[rl];
       gl = gd[rl];
     } else {
-      si.x = lds.xs[rl][0]; si.y = lds.xs[rl][1]; si.z = lds.xs[rl][2]; si.w = lds.xs[rl][3];
-      gl.x = lds.xs[rl][4]; gl.y = lds.xs[rl][5];
+      si.x = XS(rl, kXSelf + 0); si.y = XS(rl, kXSelf + 1); si.z = XS(rl, kXSelf + 2); si.w = XS(rl, kXSelf + 3);
+      gl.x = XS(rl, kXGoal + 0); gl.y = XS(rl, kXGoal + 1);
     }
     R ux = R(0), uy = R(0);
     if (act == 1) ux = R(-1);
@@ -196,7 +353,7 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
       if constexpr (F64)
         contact_force<R>(si.z - ns[rj].z, si.w - ns[rj].w, f_x, f_y);
       else
-        contact_force<R>(si.z - lds.xs[rj][2], si.w - lds.xs[rj][3], f_x, f_y);
+        contact_force<R>(si.z - XS(rj, kXSelf + 2), si.w - XS(rj, kXSelf + 3), f_x, f_y);
       Fx = f_x + Fx;
       Fy = f_y + Fy;
     }
@@ -359,11 +516,11 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
         (void)j;
         const V4 d = sub4<R, V4>(other(k), si);
         if (row_ok) o[k] = d;
-        lds.xs[rl][6 + 4 * k + 0] = (float)d.x; lds.xs[rl][6 + 4 * k + 1] = (float)d.y;
-        lds.xs[rl][6 + 4 * k + 2] = (float)d.z; lds.xs[rl][6 + 4 * k + 3] = (float)d.w;
+        XS(rl, kXOth + 4 * k + 0) = (float)d.x; XS(rl, kXOth + 4 * k + 1) = (float)d.y;
+        XS(rl, kXOth + 4 * k + 2) = (float)d.z; XS(rl, kXOth + 4 * k + 3) = (float)d.w;
       }
-      lds.xs[rl][0] = (float)si.x; lds.xs[rl][1] = (float)si.y; lds.xs[rl][2] = (float)si.z; lds.xs[rl][3] = (float)si.w;
-      lds.xs[rl][4] = (float)gl.x; lds.xs[rl][5] = (float)gl.y;
+      XS(rl, kXSelf + 0) = (float)si.x; XS(rl, kXSelf + 1) = (float)si.y; XS(rl, kXSelf + 2) = (float)si.z; XS(rl, kXSelf + 3) = (float)si.w;
+      XS(rl, kXGoal + 0) = (float)gl.x; XS(rl, kXGoal + 1) = (float)gl.y;
       if constexpr (F64) gd[rl] = gl;   // (ns[rl] already holds si: the post-step store above, or the reset's)
     }
     CM3_STAMP(11, false);
@@ -382,6 +539,7 @@ template <int N, int BF16, int RT, typename R> __global__ void CM3_MATRIX_KERNEL
   }
   CM3_STAMP(15, true);    // last store acknowledged
 }
+#undef XS
 
 template <int N, int RT> static int policy_launch_rt(const PolicyParams &q, int prec, hipStream_t s) {
   using R = PolicyReal;
@@ -439,6 +597,18 @@ template <int N> static int policy_launch(const PolicyParams &q, int prec, hipSt
   return policy_launch_rt<N, 4>(q, prec, s);
 }
 
+#ifdef CM3_PARTICLE_F32
+// QMIX mode: 64-row workgroups at every batch size (the only build; cm3_policy_force_row_tiles is not consulted)
+template <int N> static int policy_qmix_launch(const PolicyParams &q, hipStream_t s) {
+  const size_t rows = (size_t)q.p.E * N;
+  const unsigned blocks = (unsigned)((rows + 63) / 64);
+  note_variant("k_policy_rollout_qmix", (int)sizeof(float), N, 4, q.p.n_ticks > 1, kPrecF32, 0, 0, 0, 4);
+  hipLaunchKernelGGL((k_policy_rollout<N, kPrecF32, 4, float, true>), dim3(blocks), dim3(256), 0, s, q);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+#endif
+
 }  // namespace cm3
 
 #ifdef CM3_PARTICLE_F32
@@ -451,23 +621,19 @@ extern "C" int cm3_policy_force_row_tiles(int32_t row_tiles) {
 #endif
 
 namespace cm3 {
-// cm3_policy_rollout_f32 / _f64: the same validation and launch, PolicyReal of this translation unit
-static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_traj *t, const cm3_actor_particle_desc *ad,
-                               const cm3_actor_particle_weights *wt, float *probs, size_t probs_stride, int32_t n_ticks,
-                               void *stream) {
-  CM3_REQUIRE(d && t && ad && wt, "null argument");
+// the checks on the env descriptor, the tick count and the two descriptors' agreement that every entry point of this file makes first
+static int policy_check_env(const cm3_particle_desc *d, const cm3_actor_particle_desc *ad, int32_t n_ticks) {
   CM3_REQUIRE(n_ticks >= 1, "n_ticks must be >= 1");
   CM3_REQUIRE(d->n_agents == 1 || d->n_agents == 2 || d->n_agents == 4 || d->n_agents == 8,
               "the fused policy rollout needs n_agents in {1, 2, 4, 8} (whole envs per 16-row wave tile); got %d",
               d->n_agents);
   CM3_REQUIRE(ad->n_agents == d->n_agents && ad->n_envs == d->n_envs, "actor / env descriptors disagree");
   CM3_REQUIRE(!(d->flags & CM3_FLAG_GEN_ACTIONS), "the policy draws the actions: CM3_FLAG_GEN_ACTIONS is meaningless here");
-  int rc = actor_check_desc(ad);
-  if (rc != CM3_OK) return rc;
-  CM3_REQUIRE(ad->seed == d->seed && ad->env_id_base == d->env_id_base,
-              "actor and env must share seed and env_id_base (one Philox key; the streams differ by purpose bits)");
-  CM3_REQUIRE(ad->epsilon >= 0.0f && ad->epsilon <= 1.0f, "epsilon must be in [0,1]");
-  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_particle_pack once per weight update");
+  return CM3_OK;
+}
+
+// the trajectory checks and the parameter fill every entry point of this file shares: q.p, the strides, q.obs_in
+static int policy_fill(const cm3_particle_desc *d, const cm3_particle_traj *t, int32_t n_ticks, PolicyParams &q) {
   CM3_REQUIRE(t->state && t->goals && t->obs_others && t->actions && t->reward_n && t->reward && t->done && t->meta &&
                   t->episode,
               "trajectory base pointers are required");
@@ -493,9 +659,8 @@ static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_tr
   CM3_REQUIRE(d->env_offset == 0 && d->env_count == 0, "the fused policy rollout covers the whole batch");
   cm3_particle_desc dd = *d;
   dd.flags &= CM3_FLAG_AUTO_RESET;
-  PolicyParams q;
   memset(&q, 0, sizeof(q));
-  rc = fill_params(&dd, &b, kStep, nullptr, q.p);
+  int rc = fill_params(&dd, &b, kStep, nullptr, q.p);
   if (rc != CM3_OK) return rc;
   q.p.n_ticks = n_ticks;
   q.p.st_state = t->state_stride;
@@ -509,6 +674,25 @@ static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_tr
   q.p.st_term_obs = t->term_obs_others_stride;
   q.p.st_coll = t->collisions_stride;
   q.obs_in = t->obs_others;
+  return CM3_OK;
+}
+
+// cm3_policy_rollout_f32 / _f64: the same validation and launch, PolicyReal of this translation unit
+static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_traj *t, const cm3_actor_particle_desc *ad,
+                               const cm3_actor_particle_weights *wt, float *probs, size_t probs_stride, int32_t n_ticks,
+                               void *stream) {
+  CM3_REQUIRE(d && t && ad && wt, "null argument");
+  int rc = policy_check_env(d, ad, n_ticks);
+  if (rc != CM3_OK) return rc;
+  rc = actor_check_desc(ad);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(ad->seed == d->seed && ad->env_id_base == d->env_id_base,
+              "actor and env must share seed and env_id_base (one Philox key; the streams differ by purpose bits)");
+  CM3_REQUIRE(ad->epsilon >= 0.0f && ad->epsilon <= 1.0f, "epsilon must be in [0,1]");
+  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_particle_pack once per weight update");
+  PolicyParams q;
+  rc = policy_fill(d, t, n_ticks, q);
+  if (rc != CM3_OK) return rc;
   q.packed = (const float *)wt->packed;
   q.probs = probs;
   q.st_probs = probs_stride;
@@ -532,6 +716,40 @@ extern "C" int cm3_policy_rollout_f32(const cm3_particle_desc *d, const cm3_part
                                       const cm3_actor_particle_desc *ad, const cm3_actor_particle_weights *wt,
                                       float *probs, size_t probs_stride, int32_t n_ticks, void *stream) {
   return cm3::policy_rollout_call(d, t, ad, wt, probs, probs_stride, n_ticks, stream);
+}
+#endif
+#ifdef CM3_PARTICLE_F32
+// The QMIX agent's one-launch rollout: desc / traj / n_ticks checked as cm3_policy_rollout_f32 checks them, the agent as
+// cm3_qmix_particle_f32 checks it; every failure returns before anything touches the device.
+extern "C" int cm3_policy_rollout_qmix_f32(const cm3_particle_desc *d, const cm3_particle_traj *t, const cm3_actor_particle_desc *ad,
+                                           const void *packed, float *q_values, size_t q_stride, const float *epsilon_dev,
+                                           int32_t n_ticks, void *stream) {
+  using namespace cm3;
+  CM3_REQUIRE(d && t && ad, "null argument");
+  int rc = policy_check_env(d, ad, n_ticks);
+  if (rc != CM3_OK) return rc;
+  rc = qmix_check_desc(ad);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(ad->seed == d->seed && ad->env_id_base == d->env_id_base,
+              "agent and env must share seed and env_id_base (one Philox key; the streams differ by purpose bits)");
+  CM3_REQUIRE(ad->epsilon >= 0.0f && ad->epsilon <= 1.0f, "epsilon must be in [0,1]");
+  CM3_REQUIRE(packed, "packed weights are NULL: run cm3_qmix_particle_pack once per weight update");
+  PolicyParams q;
+  rc = policy_fill(d, t, n_ticks, q);
+  if (rc != CM3_OK) return rc;
+  q.packed = (const float *)packed;
+  q.probs = q_values;
+  q.st_probs = q_stride;
+  q.eps = ad->epsilon;
+  q.eps_dev = epsilon_dev;
+  hipStream_t s = (hipStream_t)stream;
+  switch (d->n_agents) {
+    case 1: return policy_qmix_launch<1>(q, s);
+    case 2: return policy_qmix_launch<2>(q, s);
+    case 4: return policy_qmix_launch<4>(q, s);
+    case 8: return policy_qmix_launch<8>(q, s);
+  }
+  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
 #endif
 #ifdef CM3_PARTICLE_F64

@@ -42,10 +42,17 @@ def _canon(name):
 
 
 class ParticleQmixAgent(object):
-    # the one-launch episode and fused per-tick kernels run the CM3 actor: ParticleRollout keeps this agent on launch pairs
+    """episode_kernel=True opts this agent in to the one-launch rollout (cm3_policy_rollout_qmix_f32: the network, the epsilon-greedy
+    choice and the env step of every tick in ONE launch, the same bits as the launch pairs): ParticleRollout then runs it under
+    policy_mode "episode" and, where it is eligible and measured faster, "auto" (episode_ok / episode_refusal / enqueue_episode
+    below).  The default agent runs as launch pairs in every mode, exactly as before."""
+    # ParticleRollout's fused=True / fused_policy_tick=True kernels run the CM3 actor, and so does policy_mode="episode" unless the
+    # agent was built with episode_kernel=True
     fused_kernels = False
+    EPISODE_AGENTS = (1, 2, 4, 8)        # whole envs per 16-row wave tile
 
-    def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0):
+    def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0, episode_kernel=False):
+        self.episode_kernel = bool(episode_kernel)
         self.device = _lib.require_gpu(device)
         self.n = int(n_agents)
         if not 1 <= self.n <= _lib.MAX_AGENTS:
@@ -115,6 +122,38 @@ class ParticleQmixAgent(object):
         self.enqueue(env.E, env._obs_others[cur], env._state[cur], env._goals, env._meta, env._episode, actions,
                      epsilon, q, env_id_base=env.env_id_base, dtype=env.dtype)
         return (actions, q) if return_q else actions
+
+    def episode_refusal(self, env):
+        """Why cm3_policy_rollout_qmix_f32 does not run this agent on `env` -- the first failed condition, in words -- or None when it
+        does: a float32 env, n_agents in {1, 2, 4, 8}, the agent's count equal to the env's, agent and env on one seed (one Philox
+        key; the env's env_id_base is passed on by the launch)."""
+        if env.dtype != torch.float32:
+            return ("float32 env: the one-launch QMIX rollout has no float64 build; this env is %s and runs as launch pairs "
+                    "(policy_mode='tick')" % (env.dtype,))
+        if env.n not in self.EPISODE_AGENTS:
+            return ("agent count: the one-launch QMIX rollout covers n_agents in {1, 2, 4, 8} (whole envs per 16-row wave tile); the "
+                    "env has %d -- other counts run as launch pairs (policy_mode='tick')" % env.n)
+        if env.n != self.n:
+            return "agent count: QMIX agent built for %d agents, env has %d" % (self.n, env.n)
+        if (self.seed & 0xFFFFFFFFFFFFFFFF) != (int(env.seed) & 0xFFFFFFFFFFFFFFFF):
+            return ("seed: the one-launch QMIX rollout draws for agent and env under one Philox key; the agent has seed %d, the env "
+                    "seed %d" % (self.seed, int(env.seed)))
+        return None
+
+    def episode_ok(self, env):
+        """cm3_policy_rollout_qmix_f32 applies to this agent on `env` (see episode_refusal)."""
+        return self.episode_refusal(env) is None
+
+    def enqueue_episode(self, env_desc, traj, n_envs, n_ticks, epsilon, q_values=None, stream=None):
+        """The whole agent-driven rollout in ONE launch (cm3_policy_rollout_qmix_f32) on a float32 env's descriptor and a
+        cm3_particle_traj; q_values: optional float32 [T, E, N, 5], receives the raw Q values of every tick.  epsilon: a float, or a
+        float32 device tensor of one element that the launch reads itself."""
+        epsilon, eps_dev = _epsilon_args(epsilon)
+        d = self._desc(n_envs, epsilon, env_desc.env_id_base)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_policy_rollout_qmix_f32(
+            ctypes.byref(env_desc), ctypes.byref(traj), ctypes.byref(d), self._packed.data_ptr(), _lib.ptr(q_values),
+            0 if q_values is None else q_values[0].numel() * q_values.element_size(), eps_dev, int(n_ticks), s))
 
     def greedy_rows(self, obs_others, v_obs, goals, q=False, onehot=True, q_max=False):
         """The network over transition rows with a pure argmax head, ONE launch (cm3_qmix_particle_rows_f32): with the Agent_target

@@ -384,6 +384,8 @@ class ParticleRollout(_Transitions):
         #   "auto"     (default, round 3) "episode" whenever the fused kernel applies -- n_agents in {1, 2, 4, 8} (float64 envs: 1, 2, 4),
         #              actor.seed == env.seed (one Philox key) -- else "tick".  fused=True / fused_policy_tick=True
         #              still force their modes.
+        # A ParticleQmixAgent runs as launch pairs in every mode unless it was built with episode_kernel=True: then "episode" and,
+        # where eligible, "auto" run ITS one-launch rollout (kind qmix_episode in _mode); fused / fused_policy_tick stay refused.
         if policy_mode not in ("auto", "episode", "tick"):
             raise Cm3Error("policy_mode must be 'auto', 'episode' or 'tick'")
         self.policy_mode = policy_mode
@@ -602,7 +604,13 @@ class ParticleRollout(_Transitions):
           kind    random_fused | random            the reference's random-action branch, all ticks in one launch / a launch per tick
                   policy_episode                   on-device actor, the whole episode in ONE launch (csrc/policy.hip)
                   policy_fused_tick | policy_tick  on-device actor, one fused launch / an actor + a step launch per tick
-                                                   (a policy with fused_kernels = False, the QMIX agent: policy_tick only)
+                                                   (a policy with fused_kernels = False, the QMIX agent: policy_tick only ...
+                  qmix_episode                     ... unless it was built with episode_kernel=True: the QMIX agent's whole rollout
+                                                   in ONE launch (csrc/policy.hip, QMIX mode).  policy_mode="episode" runs it or
+                                                   raises with the first failed condition (float32 env, n_agents in {1, 2, 4, 8},
+                                                   policy.n == env.n, policy.seed == env.seed); "auto" runs it where eligible (it
+                                                   was faster at every measured size), launch pairs otherwise; "tick" is launch
+                                                   pairs; fused=True / fused_policy_tick=True are refused as for the default agent)
                   host_policy                      a Python callable per tick
           live    per-tick step launches step IN PLACE on the env's buffers and copy every tick's state to its slot -- only while a
                   tick's state is small (<= 1 MiB: the slot copy is extra write traffic, the gain is load latency: C2 2.87 -> 2.74 us)
@@ -621,11 +629,22 @@ class ParticleRollout(_Transitions):
         elif not dev_policy:
             kind = "host_policy"
         elif not getattr(policy, "fused_kernels", True):
-            # an agent the one-launch kernels do not run (ParticleQmixAgent: they evaluate the CM3 actor): launch pairs only
-            if self.fused or self.fused_policy_tick or self.policy_mode == "episode":
+            # an agent the CM3 actor's one-launch kernels do not run (ParticleQmixAgent): launch pairs, unless the agent opted in to
+            # its own one-launch rollout (episode_kernel=True: cm3_policy_rollout_qmix_f32, the same bits as the pairs)
+            opted = bool(getattr(policy, "episode_kernel", False))
+            if self.fused or self.fused_policy_tick or (self.policy_mode == "episode" and not opted):
                 raise Cm3Error("%s runs as an agent launch plus a step launch per tick: policy_mode='episode', fused=True and "
                                "fused_policy_tick=True run the CM3 actor" % type(policy).__name__)
             kind = "policy_tick"
+            if opted and self.policy_mode != "tick":
+                # "auto" takes the one launch wherever it is eligible: at every measured size its slowest round beat the pairs'
+                # fastest round of the same run -- C2 3.55 against 8.00 us per tick, C5 12.75 against 17.06, 65 536 x 4 36.7 against
+                # 40.6 (profiles/r18_qmix_particle_episode.txt) -- so there is no size rule, unlike the f64 N = 8 case below
+                why = policy.episode_refusal(env)
+                if why is None:
+                    kind = "qmix_episode"
+                elif self.policy_mode == "episode":
+                    raise Cm3Error("policy_mode='episode': " + why)
         else:
             episode_ok = env.n in (1, 2, 4, 8) and same_key and not self.fused_policy_tick
             # "auto" leaves float64 envs of eight agents to the launch pairs: measured at C5 (8192 x 8, f16x3) the f64 one-launch
@@ -697,6 +716,11 @@ class ParticleRollout(_Transitions):
             fn = _policy_rollout_entry(self._lib, env.dtype)
             _lib.check(fn(ctypes.byref(env._desc), ctypes.byref(traj), ctypes.byref(ad), ctypes.byref(policy._wt), None, 0, self.T,
                           stream))
+        elif mode.kind == "qmix_episode":
+            # the QMIX agent's whole rollout in ONE launch (csrc/policy.hip, QMIX mode; no graph): bit-identical to alternating
+            # agent / step launches.  epsilon: a float or a 0-dim float32 device tensor, read by the launch
+            env._desc.flags = base & FLAG_AUTO_RESET
+            policy.enqueue_episode(env._desc, self._traj(0), env.E, self.T, epsilon, stream=stream)
         elif mode.kind == "policy_fused_tick":
             if self.use_graph:      # epsilon is a by-value argument of these launches: part of the graph's key
                 self._actor_graph.launch(policy, epsilon, lambda s: self._enqueue_fused_policy_ticks(policy, epsilon, base, s),

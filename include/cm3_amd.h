@@ -48,6 +48,7 @@ extern "C" {
 
 #define CM3_ABI_VERSION 9   /* 9: ADDED cm3_qmix_particle_packed_bytes / _pack / _f32 / _f64 (the QMIX agent network; additive).
                                   Also part of 9, additive: cm3_qmix_checkers_pack / _f32 (the Checkers QMIX agent network);
+                                  cm3_policy_rollout_qmix_f32 (the one-launch particle rollout driven by the particle QMIX agent);
                                   cm3_policy_rollout_checkers_qmix (the one-launch Checkers rollout driven by that agent; cm3_qmix_checkers_pack
                                   now also writes the others-branch table behind the packed weights, inside the same allocation);
                                   cm3_checkers_transitions_gather (the Checkers transition export in one launch);
@@ -483,6 +484,25 @@ int cm3_policy_rollout_f32(const cm3_particle_desc *desc, const cm3_particle_tra
 int cm3_policy_rollout_f64(const cm3_particle_desc *desc, const cm3_particle_traj *traj,
                            const cm3_actor_particle_desc *actor_desc, const cm3_actor_particle_weights *weights,
                            float *probs, size_t probs_stride, int32_t n_ticks, void *stream);
+/* The same one-launch rollout driven by the QMIX agent (part of ABI 9, additive; float32 envs): for every tick the agent network and
+ * its epsilon-greedy choice (as cm3_qmix_particle_f32) followed by the env step (as cm3_particle_step_f32).  CONTRACT: every output --
+ * the trajectory slots, actions, rewards, done, per-tick collisions, the terminal captures, meta / episode, and q_values -- equals,
+ * bit for bit, what n_ticks x (cm3_qmix_particle_f32, cm3_particle_step_f32) write.
+ *   desc, traj, n_ticks   validated as cm3_policy_rollout_f32 validates them (AUTO_RESET honoured, GEN_ACTIONS rejected)
+ *   agent                 validated as cm3_qmix_particle_f32 validates it (64/64/5, precision 0; n_h1_others and stage are not read);
+ *                         n_agents equal in both descriptors and in {1,2,4,8}; agent->seed == desc->seed and agent->env_id_base ==
+ *                         desc->env_id_base (policy and env draw under one Philox key)
+ *   packed                from cm3_qmix_particle_pack, non-NULL
+ *   q_values              optional: the raw Q values per tick, float [n_ticks][E][N][5], q_stride bytes between ticks (the unit of
+ *                         probs_stride)
+ *   epsilon_dev           optional device float, read once at launch INSTEAD of agent->epsilon
+ * Every failure returns CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device.  Workgroups are 64 rows
+ * at every batch size: cm3_policy_force_row_tiles does not apply.  cm3_last_kernel_variant() names the launch
+ * k_policy_rollout_qmix<f32,N=..>. */
+int cm3_policy_rollout_qmix_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj,
+                                const cm3_actor_particle_desc *agent, const void *packed,
+                                float *q_values, size_t q_stride, const float *epsilon_dev,
+                                int32_t n_ticks, void *stream);
 /* Test / measurement knob (ABI 6): 16-row tiles per workgroup of cm3_policy_rollout_f32 and _f64 -- 1, 2 or 4 forces that build of the
  * kernel for every later launch of the process, 0 gives the choice back to the library's rule (by batch size).  Results do not
  * depend on it (tests/test_gpu_actor.py forces each build on one batch).  Initial value: the environment's CM3_POLICY_RT, read
