@@ -73,6 +73,13 @@ class QmixRows(ctypes.Structure):
                 ("q", c_void_p), ("argmax", c_void_p), ("onehot", c_void_p), ("q_max", c_void_p), ("n_rows", c_int64)]
 
 
+class ActorRows(ctypes.Structure):
+    # (cm3_actor_rows: the transition rows cm3_actor_particle_rows_f32 reads, its optional outputs and the key of the rows draw)
+    _fields_ = [("obs_others", c_void_p), ("v_obs", c_void_p), ("goals", c_void_p),
+                ("probs", c_void_p), ("actions", c_void_p), ("onehot", c_void_p), ("epsilon_dev", c_void_p),
+                ("n_rows", c_int64), ("row_id_base", c_int64), ("draw", c_uint32), ("_pad", c_uint32)]
+
+
 class QmixCheckersRows(ctypes.Structure):
     # (cm3_qmix_checkers_rows: the transition rows cm3_qmix_checkers_rows_f32 reads, the two form flags and the optional outputs)
     _fields_ = [("obs_self_t", c_void_p), ("obs_self_v", c_void_p), ("obs_others", c_void_p), ("actions_prev", c_void_p),
@@ -227,6 +234,7 @@ SYMBOLS = {
     "cm3_actor_particle_pack": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), c_void_p, c_void_p]),
     "cm3_actor_particle_f32": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorParticleBufs),
                                               c_void_p]),
+    "cm3_actor_particle_rows_f32": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorRows), c_void_p]),
     "cm3_policy_rollout_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), P(ActorParticleDesc),
                                               P(ActorParticleWeights), c_void_p, c_size_t, c_int32, c_void_p]),
     "cm3_actor_particle_f64": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorParticleBufs),

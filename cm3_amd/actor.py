@@ -79,6 +79,7 @@ class ParticleActor(object):
         self.L = 4 * max(self.n - 1, 1)
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
+        self.rows_draw = 0          # launch counter of the rows stream (sample_rows)
         src = {_canon(k): v for k, v in weights.items()}
         shapes = {"w_self": (6, H1_SELF), "b_self": (H1_SELF,), "w_self_h2": (H1_SELF, H2), "b_h2": (H2,),
                   "w_out": (H2, N_ACTIONS), "b_out": (N_ACTIONS,)}
@@ -142,6 +143,73 @@ class ParticleActor(object):
         self.enqueue(env.E, env._obs_others[cur], env._state[cur], env._goals, env._meta, env._episode, actions,
                      epsilon, probs, env_id_base=env.env_id_base, dtype=env.dtype)
         return (actions, probs) if return_probs else actions
+
+    # ---- the actor over the rows of a sampled batch (cm3_actor_particle_rows_f32): the two evaluations of alg_credit.train_step ----
+    def enqueue_rows(self, n_rows, obs_others, v_obs, goals, epsilon, probs=None, actions=None, onehot=None, draw=0, row_id_base=0,
+                     stream=None):
+        """Raw launch of cm3_actor_particle_rows_f32 on contiguous float32 device tensors; every output is optional, one is
+        required.  epsilon: a float, or a one-element float32 device tensor the launch reads itself.  (seed, row_id_base + row,
+        draw) key the row's uniform; nothing is drawn when actions and onehot are both None."""
+        r = _lib.ActorRows()
+        r.obs_others, r.v_obs, r.goals = _lib.ptr(obs_others), _lib.ptr(v_obs), _lib.ptr(goals)
+        r.probs, r.actions, r.onehot = _lib.ptr(probs), _lib.ptr(actions), _lib.ptr(onehot)
+        epsilon, r.epsilon_dev = _epsilon_args(epsilon)
+        r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base), int(draw) & 0xFFFFFFFF
+        d = self._desc(1, epsilon, 0)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_actor_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def _stage_rows(self, what, obs_others, v_obs, goals):
+        """(rows, obs_others, v_obs, goals) contiguous float32 on the actor's device from [..., L], [..., 4], [..., 2] with equal
+        leading shape (a float64 column is rounded, as the reference's tf.float32 placeholders do)."""
+        lead = tuple(v_obs.shape[:-1])
+        if (tuple(obs_others.shape) != lead + (self.L,) or tuple(v_obs.shape) != lead + (4,)
+                or tuple(goals.shape) != lead + (2,)):
+            raise Cm3Error("%s takes [..., %d], [..., 4] and [..., 2] with equal leading shape, got %s, %s, %s"
+                           % (what, self.L, tuple(obs_others.shape), tuple(v_obs.shape), tuple(goals.shape)))
+        rows = int(np.prod(lead, dtype=np.int64))
+        if rows <= 0:
+            raise Cm3Error("%s needs at least one row" % what)
+        stage = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
+        return rows, stage(obs_others), stage(v_obs), stage(goals)
+
+    def probs_rows(self, obs_others, v_obs, goals, epsilon):
+        """The mixed probabilities float32 [R, 5] over the R = prod(leading shape) rows, ONE launch: the reference's
+        sess.run(self.probs, ...) of train_step (alg_credit.py:121, fetched at :708 / :729) on the columns obs_others / v_local /
+        goals of a sampled batch.  Nothing is drawn.  A row's probabilities are the bits act() computes for the same inputs."""
+        rows, oo, vo, vg = self._stage_rows("probs_rows", obs_others, v_obs, goals)
+        probs = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        self.enqueue_rows(rows, oo, vo, vg, epsilon, probs=probs)
+        return probs
+
+    def sample_rows(self, obs_others, v_obs, goals, epsilon, probs=False, onehot=False, draw=None):
+        """Actions sampled from the mixed probabilities over transition rows, ONE launch: with the Policy_target weights this is
+        action_samples_target of train_step (alg_credit.py:128, run_actor_target :272-287) on obs_others_next / v_local_next /
+        goals.  Returns a dict of device tensors: "actions" int32 [R] always; "probs" float32 [R, 5] and "onehot" int64 [R, 5] when
+        asked for.  The uniforms are the build's own rows stream keyed (seed, row, draw): draw=None takes the actor's counter
+        self.rows_draw and advances it, so successive calls draw afresh; an explicit draw reproduces a call (and leaves the
+        counter alone)."""
+        rows, oo, vo, vg = self._stage_rows("sample_rows", obs_others, v_obs, goals)
+        out = {"actions": torch.empty(rows, dtype=torch.int32, device=self.device)}
+        if probs:
+            out["probs"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        if onehot:
+            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
+        if draw is None:
+            draw, self.rows_draw = self.rows_draw, (self.rows_draw + 1) & 0xFFFFFFFF
+        self.enqueue_rows(rows, oo, vo, vg, epsilon, draw=draw, **out)
+        return out
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the actor half of
+        list_update_target_ops (alg_credit.py:186-194, run at :775), for an actor holding the Policy_target weights."""
+        if not isinstance(main, ParticleActor) or main.n != self.n or main.stage != self.stage:
+            raise Cm3Error("soft_update_from: the main actor must be a ParticleActor for %d agents at stage %d" % (self.n, self.stage))
+        tau = float(tau)
+        for name in self.w:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
+        self.repack()
 
 
 _CK_NAMES = {

@@ -319,7 +319,7 @@ def _rep_n(x, n):
 
 
 def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=True, use_V=True, l_action=5, device_tiling=True,
-                     static=None):
+                     static=None, target_actor=None, actor=None):
     """The data movement of the reference's train_step on the device: builds, in the reference's order, the feed_dict of
     every sess.run -- TD targets, the n x n credit repeats (alg_credit.py:614-658) and the n x n x l_action counterfactual
     tiling (:730-751; Checkers twin alg_credit_checkers.py:590-760) -- from the columns of
@@ -330,13 +330,26 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     for optimiser ops).  Returns the list of (ops, feed) in call order.  Pure gathers / repeats plus the float64 TD
     arithmetic: bit-identical to the arrays the REAL train_step feeds (tests/golden/trainstep_*.npz, recorded by
     oracle/gen_golden_trainstep.py from the reference code itself under a recording session).
-    static: this minibatch's entry of phase_static_feeds() -- the static feeds then cost no launch here."""
+    static: this minibatch's entry of phase_static_feeds() -- the static feeds then cost no launch here.
+
+    target_actor / actor (particle env, CUDA columns): ParticleActors holding the Policy_target / Policy_main weights.  With
+    target_actor, `run` is NOT called for ["action_samples_target"] (its (ops, feed) entry still appears in the list): the samples
+    come from target_actor.sample_rows(obs_others_next, v_local_next, goals, epsilon) in one launch -- the build's own rows stream,
+    equal to tf.multinomial in law only -- and go on through the same one-hot paths.  With actor, the same
+    holds for ["probs"], from actor.probs_rows(obs_others, v_local, goals, epsilon).  epsilon: a float, or the one-element float32
+    device tensor the actors accept.  The soft update of the target actor -- the actor half of list_update_target_ops -- is left to
+    the caller: ``target_actor.soft_update_from(actor, tau)`` after this function returns.  With both None nothing changes."""
     checkers = env == "checkers"
     calls = []
+    if target_actor is not None or actor is not None:
+        if checkers:
+            raise ValueError("train_step_feeds: target_actor / actor are particle actors; the Checkers actor has no rows kernel")
+        if not cols["v_global"].is_cuda:
+            raise ValueError("train_step_feeds: target_actor / actor evaluate device columns; call without them for host tensors")
 
-    def call(ops, feed):
+    def call(ops, feed, launch=True):
         calls.append((ops, feed))
-        return run(ops, feed)
+        return run(ops, feed) if launch else None
 
     if checkers:
         (n_steps, state_env, state_agents, obs_others, obs_self_t, obs_self_v, actions_prev_1hot, actions_1hot,
@@ -390,6 +403,9 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     # ---- Q_n(s, a): target actions a', TD target, optimiser step (alg_credit.py:574-612) ----
     if checkers:      # run_actor_target(actions_1hot, obs_others_next, ...) (alg_credit_checkers.py:551)
         acts = call(["action_samples_target"], actor_feed(obs_others_next, obs_self_t_next, obs_self_v_next, actions_1hot))[0]
+    elif target_actor is not None:
+        call(["action_samples_target"], actor_feed(obs_others_next, v_local_next), launch=False)
+        acts = target_actor.sample_rows(obs_others_next, v_local_next, goals_self, epsilon)["actions"]
     else:
         acts = call(["action_samples_target"], actor_feed(obs_others_next, v_local_next))[0]
     a_next_rep = None
@@ -446,17 +462,25 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
 
     # ---- policy: probabilities + counterfactual Q for every action (:704-757) ----
     pol_obs = (obs_self_t, obs_self_v, actions_prev_1hot) if checkers else (v_local,)
+
+    def fetch_probs():
+        feed = actor_feed(obs_others, *pol_obs)
+        if actor is None:
+            return call(["probs"], feed)[0]
+        call(["probs"], feed, launch=False)
+        return actor.probs_rows(obs_others, v_local, goals_self, epsilon)
+
     rep_a = lambda x: rep_rows(x, l_action)                                         # noqa: E731
     eye = torch.eye(l_action, dtype=f64, device=one.device)                         # self.actions = np.eye(l_action)
     if N == 1:                      # stage 1: Q(s, a = every action, g)
-        probs = call(["probs"], actor_feed(obs_others, *pol_obs))[0]
+        probs = fetch_probs()
         feed = {"v_state_one_agent": rep_a(one), "v_goal": rep_a(goals_self), "action_one": eye.repeat(n_steps, 1),
                 "v_state_other_agents": others, "action_others": actions_others_1hot}
         if checkers:
             feed = with_env(feed, rep_a(state_env), rep_a(obs_self_t), rep_a(obs_self_v))
         q_cf = call(["Q_global"], feed)[0].reshape(n_steps, l_action)
     elif use_Q_credit:
-        probs = rep_rows(call(["probs"], actor_feed(obs_others, *pol_obs))[0], N)
+        probs = rep_rows(fetch_probs(), N)
         if S is None:
             feed = {"v_state_one_agent": rep_a(s_n_rep), "v_goal": rep_a(goals_self_rep),
                     "action_one": eye.repeat(N * N * n_steps, 1), "v_state_m": rep_a(s_m_rep),

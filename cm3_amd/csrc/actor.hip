@@ -612,10 +612,39 @@ __device__ __forceinline__ int bcast_row0(int v) {
   return (int)x;
 }
 
+// The same network over TRANSITION rows (cm3_actor_particle_rows_f32): row r of three row-major float32 arrays -- the columns
+// obs_others / v_local / goals of a sampled batch viewed as [B * N, .] -- instead of an env's live buffers: what
+// alg_credit.train_step evaluates twice per minibatch, the target actor with sampling (action_samples_target, alg_credit.py:128,
+// run_actor_target :272-287) and the main actor forward only (probs, :121).  Every output optional.
+struct ActorRowsParams {
+  size_t n_rows;
+  int stage;
+  float eps;
+  int bf16;                                  // precision of the second layer, as ActorParams::bf16
+  uint32_t draw;                             // the caller's launch counter: counter word 2 of the rows stream
+  uint64_t row_id_base, seed;
+  const float *obs_others, *v_obs, *goals;   // [n_rows][L], [n_rows][4], [n_rows][2]
+  float *probs;                              // [n_rows][5] mixed probabilities
+  int32_t *actions;                          // [n_rows]
+  int64_t *onehot;                           // [n_rows][5]: the sampled action, the form of cm3_qmix_rows.onehot
+  const float *eps_dev;
+  const float *packed;
+};
+template <int N> __device__ __forceinline__ size_t actor_row_count(const ActorParams &p) { return (size_t)p.E * N; }
+template <int N> __device__ __forceinline__ size_t actor_row_count(const ActorRowsParams &p) { return p.n_rows; }
+
+// ONE kernel template for both: ROWS = false (the defaults: k_actor_particle<N, PREC, RIN>) reads an env's live buffers and draws from
+// the policy stream keyed by the env's counters; ROWS = true with P = ActorRowsParams reads transition rows and draws from the rows
+// stream -- cm3_last_kernel_variant() calls that instantiation k_actor_particle_rows.  Everything between the staging of the inputs
+// and the mixed probabilities is one text, so a row's probabilities are the same bits in both.  The body stays IN the kernel, as
+// k_ck_actor's does: moved into a __device__ function over the parameter struct (the form of qmix_forward) it compiled to other
+// instruction streams for the collection kernel -- all 60 instantiations with the struct by reference, 24 by value (register
+// numbers, an address fold) -- while with the two defaulted template parameters every existing instantiation is the parent's
+// stream, instruction for instruction.
 // RIN = real of the env buffers the kernel reads: float, or double for a float64 env -- rounded to float32 (round to nearest even)
 // as the input tile is staged, which is what the reference's tf.float32 placeholders do to its float64 observations
 // (alg_credit.py:96-111).  Everything after the staging is the same code for both.
-template <int N, int PREC, typename RIN> __global__ void CM3_MATRIX_KERNEL k_actor_particle(const ActorParams p) {
+template <int N, int PREC, typename RIN, bool ROWS = false, typename P = ActorParams> __global__ void CM3_MATRIX_KERNEL k_actor_particle(const P p) {
   using G = ActorGeom<N, PREC>;
   using V4 = typename Vec<RIN>::v4;
   using V2 = typename Vec<RIN>::v2;
@@ -623,7 +652,7 @@ template <int N, int PREC, typename RIN> __global__ void CM3_MATRIX_KERNEL k_act
   CM3_ACTOR_LDS(N, PREC, lds);
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t rows = (size_t)p.E * N;
+  const size_t rows = actor_row_count<N>(p);
   const size_t row_base = (size_t)blockIdx.x * 64;
   CM3_STAMP(0, false);
 
@@ -631,10 +660,15 @@ template <int N, int PREC, typename RIN> __global__ void CM3_MATRIX_KERNEL k_act
   size_t hr = row_base + 16 * w + (lane & 15);
   const bool head_ok = hr < rows && (lane >> 4) == 0;
   hr = hr < rows ? hr : rows - 1;
-  const size_t he = hr / N;
-  const int hi_agent = (int)(hr - he * N);
-  const int head_steps = p.meta[2 * he];
-  const uint32_t head_episode = (uint32_t)p.episode[he];
+  size_t he = 0;
+  int hi_agent = 0, head_steps = 0;
+  uint32_t head_episode = 0;
+  if constexpr (!ROWS) {
+    he = hr / N;
+    hi_agent = (int)(hr - he * N);
+    head_steps = p.meta[2 * he];
+    head_episode = (uint32_t)p.episode[he];
+  }
 
   // Kernel entry: every global request first (tables, wave 0's input rows, the W2 slice), then the LDS stores.
   // Measured and REJECTED in round 2 (tools/probes/actor_timeline.hip, 16 384 rows, same box, three repeats):
@@ -650,11 +684,16 @@ template <int N, int PREC, typename RIN> __global__ void CM3_MATRIX_KERNEL k_act
   V2 in_g;
   {
     const size_t r = row_base + lane;
-    const size_t rc = r < rows ? r : rows - 1;
-    const size_t e = rc / N;
-    const int i = (int)(rc - e * N);
-    in_s = reinterpret_cast<const V4 *>(p.state)[(size_t)i * p.E + e];
-    in_g = reinterpret_cast<const V2 *>(p.goals)[(size_t)i * p.E + e];
+    const size_t rc = r < rows ? r : rows - 1;   // (tail rows read the last row: clamped loads, nothing stored)
+    if constexpr (ROWS) {
+      in_s = reinterpret_cast<const V4 *>(p.v_obs)[rc];
+      in_g = reinterpret_cast<const V2 *>(p.goals)[rc];
+    } else {
+      const size_t e = rc / N;
+      const int i = (int)(rc - e * N);
+      in_s = reinterpret_cast<const V4 *>(p.state)[(size_t)i * p.E + e];
+      in_g = reinterpret_cast<const V2 *>(p.goals)[(size_t)i * p.E + e];
+    }
     const V4 *o4 = reinterpret_cast<const V4 *>(reinterpret_cast<const RIN *>(p.obs_others) + rc * L);
 #pragma unroll
     for (int k = 0; k < L / 4; ++k) in_o[k] = o4[k];
@@ -684,14 +723,30 @@ template <int N, int PREC, typename RIN> __global__ void CM3_MATRIX_KERNEL k_act
   actor_mlp<N, PREC, 4>(lds, b, f1, w, lane, p.stage > 1);
   float pr[kA];
   // the uniform first: its Philox rounds are VALU work that can issue between the head's dependent MFMAs
-  const float u = actor_uniform(p.seed, (uint64_t)(p.env_id_base + (int64_t)he), head_episode, head_steps, hi_agent);
-  actor_head_probs(lds.h2s, hb, w, lane, p.eps_dev ? *p.eps_dev : p.eps, pr);
-  const int act = actor_pick(pr, u);
-  if (head_ok) {
-    p.actions[hr] = act;
-    if (p.probs) {
+  if constexpr (ROWS) {
+    const bool draws = p.actions != nullptr || p.onehot != nullptr;   // (the probs fetch draws nothing: uniform over the launch)
+    float u = 0.0f;
+    if (draws) u = rows_uniform(p.seed, p.row_id_base + (uint64_t)hr, p.draw);
+    actor_head_probs(lds.h2s, hb, w, lane, p.eps_dev ? *p.eps_dev : p.eps, pr);
+    const int act = actor_pick(pr, u);
+    if (head_ok) {
+      if (p.probs) {
 #pragma unroll
-      for (int a = 0; a < kA; ++a) p.probs[hr * kA + a] = pr[a];
+        for (int a = 0; a < kA; ++a) p.probs[hr * kA + a] = pr[a];
+      }
+      if (p.actions) p.actions[hr] = act;
+      if (p.onehot) onehot_row_store(p.onehot, hr, act);
+    }
+  } else {
+    const float u = actor_uniform(p.seed, (uint64_t)(p.env_id_base + (int64_t)he), head_episode, head_steps, hi_agent);
+    actor_head_probs(lds.h2s, hb, w, lane, p.eps_dev ? *p.eps_dev : p.eps, pr);
+    const int act = actor_pick(pr, u);
+    if (head_ok) {
+      p.actions[hr] = act;
+      if (p.probs) {
+#pragma unroll
+        for (int a = 0; a < kA; ++a) p.probs[hr * kA + a] = pr[a];
+      }
     }
   }
   CM3_STAMP(7, true);
@@ -707,6 +762,19 @@ template <int N, typename RIN> static int actor_launch(const ActorParams &p, hip
     hipLaunchKernelGGL((k_actor_particle<N, kPrecBf16, RIN>), dim3(blocks), dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL((k_actor_particle<N, kPrecF32, RIN>), dim3(blocks), dim3(256), 0, s, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
+template <int N> static int actor_rows_launch(const ActorRowsParams &p, hipStream_t s) {
+  const unsigned blocks = (unsigned)((p.n_rows + 63) / 64);
+  note_variant("k_actor_particle_rows", (int)sizeof(float), N, 4, 0, 0, 0, 0, 0, 0, p.bf16);
+  if (p.bf16 == kPrecF16x3)
+    hipLaunchKernelGGL((k_actor_particle<N, kPrecF16x3, float, true, ActorRowsParams>), dim3(blocks), dim3(256), 0, s, p);
+  else if (p.bf16 == kPrecBf16)
+    hipLaunchKernelGGL((k_actor_particle<N, kPrecBf16, float, true, ActorRowsParams>), dim3(blocks), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL((k_actor_particle<N, kPrecF32, float, true, ActorRowsParams>), dim3(blocks), dim3(256), 0, s, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
@@ -949,15 +1017,7 @@ template <int N, typename RIN, bool ROWS, typename P> __device__ __forceinline__
       }
       if (p.argmax) p.argmax[hr] = act;
       if (p.q_max) p.q_max[hr] = best;
-      if (p.onehot) {
-        // 40 bytes per row from a 16-byte aligned base: an even row is 16 | 16 | 8 bytes, an odd one 8 | 16 | 16
-        typedef long long i64x2 __attribute__((ext_vector_type(2)));
-        int64_t *row = p.onehot + hr * kA;
-        const int k0 = (int)(hr & 1), k1 = k0 ? 0 : 4;
-        *reinterpret_cast<i64x2 *>(row + k0) = i64x2{act == k0, act == k0 + 1};
-        *reinterpret_cast<i64x2 *>(row + k0 + 2) = i64x2{act == k0 + 2, act == k0 + 3};
-        row[k1] = act == k1;
-      }
+      if (p.onehot) onehot_row_store(p.onehot, hr, act);
     }
   } else {
     const int act = epsilon_greedy(q, p.eps_dev ? *p.eps_dev : p.eps, w_explore, w_action);
@@ -1154,6 +1214,57 @@ extern "C" int cm3_actor_particle_f32(const cm3_actor_particle_desc *d, const cm
 extern "C" int cm3_actor_particle_f64(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
                                       const cm3_actor_particle_bufs *b, void *stream) {
   return cm3::actor_particle_call<double>(d, wt, b, stream);
+}
+
+// The actor over transition rows (part of ABI 9, additive): validated like cm3_actor_particle_f32, n_envs / env_id_base not read
+extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
+                                           const cm3_actor_rows *r, void *stream) {
+  using namespace cm3;
+  int rc = actor_check_desc(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(wt, "null weights");
+  CM3_REQUIRE(r, "null rows");
+  CM3_REQUIRE(d->epsilon >= 0.0f && d->epsilon <= 1.0f, "epsilon must be in [0,1]");
+  CM3_REQUIRE(d->precision >= 0 && d->precision <= 2, "precision must be 0 (float32), 1 (bf16 second layer) or 2 (split float16)");
+  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_particle_pack once per weight update");
+  CM3_REQUIRE(r->obs_others && r->v_obs && r->goals, "missing inputs: obs_others, v_obs and goals are all required");
+  CM3_REQUIRE(r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
+  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
+  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
+  CM3_REQUIRE((uintptr_t)r->obs_others % 16 == 0 && (uintptr_t)r->v_obs % 16 == 0 && (uintptr_t)r->goals % 8 == 0,
+              "misaligned inputs: obs_others and v_obs must be 16-byte aligned, goals 8-byte aligned");
+  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0, "misaligned onehot: must be 16-byte aligned");
+  ActorRowsParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_rows = (size_t)r->n_rows;
+  p.stage = d->stage;
+  p.eps = d->epsilon;
+  p.eps_dev = r->epsilon_dev;
+  p.bf16 = d->precision;
+  p.draw = r->draw;
+  p.row_id_base = (uint64_t)r->row_id_base;
+  p.seed = d->seed;
+  p.obs_others = r->obs_others;
+  p.v_obs = r->v_obs;
+  p.goals = r->goals;
+  p.probs = r->probs;
+  p.actions = r->actions;
+  p.onehot = r->onehot;
+  p.packed = (const float *)wt->packed;
+  hipStream_t s = (hipStream_t)stream;
+  switch (d->n_agents) {
+    case 1: return actor_rows_launch<1>(p, s);
+    case 2: return actor_rows_launch<2>(p, s);
+    case 3: return actor_rows_launch<3>(p, s);
+    case 4: return actor_rows_launch<4>(p, s);
+    case 5: return actor_rows_launch<5>(p, s);
+    case 6: return actor_rows_launch<6>(p, s);
+    case 7: return actor_rows_launch<7>(p, s);
+    case 8: return actor_rows_launch<8>(p, s);
+    case 9: return actor_rows_launch<9>(p, s);
+    case 10: return actor_rows_launch<10>(p, s);
+  }
+  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
 
 // ---- QMIX agent (ABI 9) ------------------------------------------------------------------------------------------------------

@@ -101,6 +101,35 @@ __device__ __forceinline__ void explore_words(uint64_t seed, uint64_t genv, uint
   explore_words_from(explore_block_words(seed, genv, agent), episode, steps, w_explore, w_action);
 }
 
+// ---- the draw of the actor over TRANSITION rows (k_actor_particle<.., ROWS = true> in actor.hip): a sampled batch has no env, episode or step
+// behind it, so its uniforms come from a Philox block of their own purpose, keyed by the row alone: counter (row id lo, row id hi,
+// draw, kPurposeRows), key = seed, word .x -- row id = the caller's 64-bit row_id_base + the row's index, draw = a 32-bit counter the
+// caller advances once per launch.  ONE stage (no action_word mix): nothing of the counter is loaded, all of it is known at entry.
+// kPurposeRows is bit 28 of counter word 3 and nothing else.  No other stream can produce that word: the reset stream always sets
+// bit 31, the policy stream bit 30, the exploration stream bit 29, and what they and the action stream (purpose 0) OR in below is
+// `call << 24` with call = agent >> 2 (action, policy: at most 2 with CM3_MAX_AGENTS = 10, bits 24..25) or agent >> 1 (explore: at
+// most 4, bits 24..26): bit 28 would take 64 (32) agents.
+constexpr uint32_t kPurposeRows = 0x10000000u;
+__device__ __forceinline__ float rows_uniform(uint64_t seed, uint64_t row_id, uint32_t draw) {
+  u32x4 ctr;
+  ctr.x = (uint32_t)row_id;
+  ctr.y = (uint32_t)(row_id >> 32);
+  ctr.z = draw;
+  ctr.w = kPurposeRows;
+  return (float)u01(philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32)).x);
+}
+
+// One row of an int64 [rows][5] one-hot array (the reference's np.zeros(dtype=int) forms: actions_target_1hot, action_one):
+// 40 bytes per row from a 16-byte aligned base -- an even row is 16 | 16 | 8 bytes, an odd one 8 | 16 | 16
+__device__ __forceinline__ void onehot_row_store(int64_t *onehot, size_t hr, int act) {
+  typedef long long i64x2 __attribute__((ext_vector_type(2)));
+  int64_t *row = onehot + hr * kA;
+  const int k0 = (int)(hr & 1), k1 = k0 ? 0 : 4;
+  *reinterpret_cast<i64x2 *>(row + k0) = i64x2{act == k0, act == k0 + 1};
+  *reinterpret_cast<i64x2 *>(row + k0 + 2) = i64x2{act == k0 + 2, act == k0 + 3};
+  row[k1] = act == k1;
+}
+
 // argmax Q with the first index on ties (tf.argmax) and the value there: the greedy half of epsilon_greedy below, on its own
 __device__ __forceinline__ void greedy_argmax(const float (&q)[kA], int &greedy, float &best) {
   greedy = 0;

@@ -61,6 +61,8 @@ extern "C" {
                                   cm3_qmix_td_target_f64 (the QMIX TD target): the data side of alg_qmix.train_step; additive.
                                   cm3_qmix_checkers_rows_f32 (the Checkers QMIX agent network over transition rows, argmax head): the
                                   data side of alg_qmix_checkers.train_step; additive.
+                                  cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
+                                  actions, the two actor evaluations of alg_credit.train_step); additive.
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -419,6 +421,39 @@ int cm3_actor_particle_f32(const cm3_actor_particle_desc *desc, const cm3_actor_
  * float32 roundings of those buffers.  probs stays float32. */
 int cm3_actor_particle_f64(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
                            const cm3_actor_particle_bufs *bufs, void *stream);
+
+/* The same actor over TRANSITION rows (part of ABI 9, additive): what alg_credit.train_step evaluates twice per minibatch -- the
+ * Policy_target weights with sampling (action_samples_target, alg_credit.py:128, run_actor_target :272-287) on obs_others_next /
+ * v_local_next / goals, and the Policy_main weights forward only (probs, :121) on obs_others / v_local / goals.  Row r comes from
+ * three row-major float32 arrays -- the batch columns viewed as [B * N, .] -- and n_rows is any positive count (not a multiple of
+ * n_agents).  A row's mixed probabilities are, bit for bit, those cm3_actor_particle_f32 computes for the same L + 6 inputs at the
+ * same stage and precision.  Every output is optional, at least one is required:
+ *   probs    the mixed probabilities (1 - eps) softmax + eps / 5
+ *   actions  the sampled action: the inverse CDF in action order, as cm3_actor_particle_f32 picks, at the row's uniform
+ *   onehot   the sampled action as int64 one-hot rows, the form of cm3_qmix_rows.onehot
+ * The uniform of row r is (float)((word + 0.5) 2^-32) of word .x of the Philox4x32-10 block with counter (row id lo, row id hi, draw,
+ * 0x10000000) and key seed, where row id = row_id_base + r (64 bit): a purpose of its own in counter word 3, so these draws meet no
+ * other stream of the build.  The caller advances `draw` once per launch; equal (seed, row id, draw) reproduce a draw.  With actions
+ * and onehot both NULL nothing is drawn.  (Anonymous struct tag, like cm3_qmix_rows.) */
+typedef struct {
+  const float *obs_others;  /* [n_rows][4*max(N-1,1)], 16-byte aligned */
+  const float *v_obs;       /* [n_rows][4], 16-byte aligned */
+  const float *goals;       /* [n_rows][2],  8-byte aligned */
+  float   *probs;           /* optional [n_rows][5] */
+  int32_t *actions;         /* optional [n_rows] */
+  int64_t *onehot;          /* optional [n_rows][5], 16-byte aligned */
+  const float *epsilon_dev; /* optional device float: read at launch INSTEAD of desc->epsilon */
+  int64_t  n_rows;
+  int64_t  row_id_base;
+  uint32_t draw;
+  uint32_t _pad;
+} cm3_actor_rows;
+/* desc is validated as for cm3_actor_particle_f32 (n_agents 1..10, the widths 64/128/64/5, precision 0..2, epsilon in [0,1]); stage
+ * and seed are read, n_envs and env_id_base are not.  CM3_ERR_INVALID before any launch: null desc / weights / rows, weights->packed
+ * NULL, a missing input, no output requested, n_rows <= 0 or more than 64 * (2^31 - 1), a misaligned input or onehot pointer.
+ * cm3_last_kernel_variant() names the launch k_actor_particle_rows<f32,N=..,...>. */
+int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
+                                const cm3_actor_rows *rows, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * On-device QMIX agent (ABI 9): networks.Qmix_single_particle (networks.py:581-594) + the epsilon-greedy choice of
