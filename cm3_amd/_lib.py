@@ -87,6 +87,15 @@ class QmixCheckersRows(ctypes.Structure):
                 ("q", c_void_p), ("argmax", c_void_p), ("onehot", c_void_p), ("q_max", c_void_p), ("n_rows", c_int64)]
 
 
+class ActorCheckersRows(ctypes.Structure):
+    # (cm3_actor_checkers_rows: the transition rows cm3_actor_checkers_rows_f32 reads -- the inputs and form flags of QmixCheckersRows --,
+    # its optional outputs and the key of the rows draw)
+    _fields_ = [("obs_self_t", c_void_p), ("obs_self_v", c_void_p), ("obs_others", c_void_p), ("actions_prev", c_void_p),
+                ("goals", c_void_p), ("obs_self_t_f64", c_int32), ("goals_onehot", c_int32),
+                ("probs", c_void_p), ("actions", c_void_p), ("onehot", c_void_p), ("epsilon_dev", c_void_p),
+                ("n_rows", c_int64), ("row_id_base", c_uint64), ("draw", c_uint32), ("_pad", c_uint32)]
+
+
 class EpisodeRouteDesc(ctypes.Structure):
     # (cm3_episode_route_desc: what cm3_episode_route_plan reads of a collection and of the dual buffer's two rings)
     _fields_ = [("done", c_void_p), ("collisions", c_void_p), ("valid", c_void_p),
@@ -278,6 +287,7 @@ SYMBOLS = {
                                                         P(CheckersBufs), c_int32, c_void_p]),
     "cm3_actor_checkers_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersBufs),
                                               c_void_p]),
+    "cm3_actor_checkers_rows_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersRows), c_void_p]),
     "cm3_qmix_checkers_pack": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), c_void_p, c_void_p]),
     "cm3_qmix_checkers_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersBufs), c_void_p]),
     "cm3_qmix_checkers_rows_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(QmixCheckersRows), c_void_p]),

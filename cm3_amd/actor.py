@@ -220,6 +220,34 @@ _CK_NAMES = {
 CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2 = 6, 32, 256, 256
 
 
+def stage_checkers_rows(what, device, Lo, obs_self_t, obs_self_v, obs_others, actions_prev, goals):
+    """(rows, obs_self_t, obs_self_v, obs_others, actions_prev, goals) contiguous on `device`, in the forms the Checkers rows kernels
+    read (cm3_actor_checkers_rows_f32, cm3_qmix_checkers_rows_f32), from inputs with equal leading shape [...]: obs_self_t
+    [..., 5, 5, 3] or [..., 75]; obs_self_v [..., 4]; obs_others [..., Lo]; actions_prev [...] (0..4); goals a one-hot [..., 2] or an
+    index [...].  int8 windows and uint8 index goals go in as they are (what the trajectory and the compact ring keep); everything
+    else becomes float64 windows / int64 one-hot goals (no copy for the columns sample_batch returns)."""
+    lead = tuple(obs_self_v.shape[:-1])
+    win = tuple(obs_self_t.shape)
+    index_goals = tuple(goals.shape) == lead
+    if (win not in (lead + (5, 5, 3), lead + (75,)) or tuple(obs_self_v.shape) != lead + (4,)
+            or tuple(obs_others.shape) != lead + (Lo,) or tuple(actions_prev.shape) != lead
+            or not (index_goals or tuple(goals.shape) == lead + (2,))):
+        raise Cm3Error("%s takes [..., 5, 5, 3] (or [..., 75]), [..., 4], [..., %d], [...] and [..., 2] (or [...]) with equal "
+                       "leading shape, got %s, %s, %s, %s, %s" % (what, Lo, win, tuple(obs_self_v.shape), tuple(obs_others.shape),
+                                                                  tuple(actions_prev.shape), tuple(goals.shape)))
+    rows = int(np.prod(lead, dtype=np.int64))
+    if rows <= 0:
+        raise Cm3Error("%s needs at least one row" % what)
+    stage = lambda t, dt: t.to(device=device, dtype=dt).contiguous()      # noqa: E731
+    ot = stage(obs_self_t, torch.int8 if obs_self_t.dtype == torch.int8 else torch.float64)
+    if index_goals:
+        vg = (stage(goals, torch.uint8) if goals.dtype == torch.uint8
+              else torch.nn.functional.one_hot(goals.to(device).long(), 2).contiguous())
+    else:
+        vg = stage(goals, torch.int64)
+    return rows, ot, stage(obs_self_v, torch.float64), stage(obs_others, torch.float64), stage(actions_prev, torch.int32), vg
+
+
 class CheckersActor(object):
     """The reference's Checkers policy evaluated on the device.
 
@@ -249,6 +277,7 @@ class CheckersActor(object):
         self.Lo = 2 * max(self.n - 1, 1)
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
+        self.rows_draw = 0          # launch counter of the rows stream (sample_rows)
         src = {_canon(k): v for k, v in weights.items()}
         cat = CK_CONV_LIN + 4 + N_ACTIONS + 2
         shapes = {"conv_w": (3, 3, 3, CK_CONV_F), "conv_b": (CK_CONV_F,), "lin_w": (25 * CK_CONV_F, CK_CONV_LIN),
@@ -342,3 +371,69 @@ class CheckersActor(object):
         self.enqueue(env.E, s["obs_self_t_raw"], env.obst_stride, s["obs_self_v"], s["obs_others"], env._goals, prev,
                      env._steps, env._episode, actions, epsilon, probs, env_id_base=env._desc.env_id_base)
         return (actions, probs) if return_probs else actions
+
+    # ---- the actor over the rows of a sampled batch (cm3_actor_checkers_rows_f32): the two evaluations of
+    # alg_credit_checkers.train_step ----
+    def enqueue_rows(self, n_rows, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon, probs=None, actions=None,
+                     onehot=None, draw=0, row_id_base=0, stream=None):
+        """Raw launch of cm3_actor_checkers_rows_f32 on contiguous device tensors: obs_self_t int8 or float64 [R, 75], obs_self_v /
+        obs_others float64, actions_prev int32 [R], goals uint8 [R] or int64 [R, 2]; every output is optional, one is required.
+        epsilon: a float, or a one-element float32 device tensor the launch reads itself.  (seed, row_id_base + row, draw) key the
+        row's uniform; nothing is drawn when actions and onehot are both None."""
+        if obs_self_t.dtype not in (torch.int8, torch.float64) or goals.dtype not in (torch.uint8, torch.int64):
+            raise Cm3Error("enqueue_rows reads int8 or float64 windows and uint8 index or int64 one-hot goals, not %s / %s"
+                           % (obs_self_t.dtype, goals.dtype))
+        r = _lib.ActorCheckersRows()
+        r.obs_self_t, r.obs_self_v, r.obs_others = _lib.ptr(obs_self_t), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
+        r.actions_prev, r.goals = _lib.ptr(actions_prev), _lib.ptr(goals)
+        r.obs_self_t_f64 = 1 if obs_self_t.dtype == torch.float64 else 0
+        r.goals_onehot = 1 if goals.dtype == torch.int64 else 0
+        r.probs, r.actions, r.onehot = _lib.ptr(probs), _lib.ptr(actions), _lib.ptr(onehot)
+        epsilon, r.epsilon_dev = _epsilon_args(epsilon)
+        r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF
+        d = self._desc(1, epsilon, 0, 75 * self.n)
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_actor_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def probs_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon):
+        """The mixed probabilities float32 [R, 5] over the R = prod(leading shape) rows, ONE launch: the reference's
+        sess.run(self.probs, ...) of train_step (alg_credit_checkers.py:107-113) on the columns obs_self_t / obs_self_v / obs_others /
+        actions_prev / goals of a sampled batch (input forms: stage_checkers_rows).  Nothing is drawn.  At precision "f16x3" float64
+        windows must hold float16-exact values (the env's are -1 / 0 / 1).  A row's probabilities are the bits act() computes for
+        the same inputs at the same precision."""
+        rows, ot, ov, oo, ap, vg = stage_checkers_rows("probs_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
+                                                       actions_prev, goals)
+        probs = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        self.enqueue_rows(rows, ot, ov, oo, ap, vg, epsilon, probs=probs)
+        return probs
+
+    def sample_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon, probs=False, onehot=False, draw=None):
+        """Actions sampled from the mixed probabilities over transition rows, ONE launch: with the Policy_target weights this is
+        action_samples_target of train_step (alg_credit_checkers.py:117, run_actor_target :255-260, called at :551) on
+        next_obs_self_t / next_obs_self_v / next_obs_others / actions / goals (the reference feeds the action just taken as
+        actions_prev there).  Returns a dict of device tensors: "actions" int32 [R] always; "probs" float32 [R, 5] and "onehot" int64
+        [R, 5] when asked for.  The uniforms are the build's own rows stream keyed (seed, row, draw): draw=None takes the actor's
+        counter self.rows_draw and advances it, so successive calls draw afresh; an explicit draw reproduces a call (and leaves the
+        counter alone)."""
+        rows, ot, ov, oo, ap, vg = stage_checkers_rows("sample_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
+                                                       actions_prev, goals)
+        out = {"actions": torch.empty(rows, dtype=torch.int32, device=self.device)}
+        if probs:
+            out["probs"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        if onehot:
+            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
+        if draw is None:
+            draw, self.rows_draw = self.rows_draw, (self.rows_draw + 1) & 0xFFFFFFFF
+        self.enqueue_rows(rows, ot, ov, oo, ap, vg, epsilon, draw=draw, **out)
+        return out
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the actor half of
+        list_update_target_ops (alg_credit_checkers.py:72, run at :773), for an actor holding the Policy_target weights."""
+        if not isinstance(main, CheckersActor) or main.n != self.n or main.stage != self.stage:
+            raise Cm3Error("soft_update_from: the main actor must be a CheckersActor for %d agents at stage %d" % (self.n, self.stage))
+        tau = float(tau)
+        for name in self.w:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
+        self.repack()

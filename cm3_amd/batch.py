@@ -332,19 +332,26 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     oracle/gen_golden_trainstep.py from the reference code itself under a recording session).
     static: this minibatch's entry of phase_static_feeds() -- the static feeds then cost no launch here.
 
-    target_actor / actor (particle env, CUDA columns): ParticleActors holding the Policy_target / Policy_main weights.  With
-    target_actor, `run` is NOT called for ["action_samples_target"] (its (ops, feed) entry still appears in the list): the samples
-    come from target_actor.sample_rows(obs_others_next, v_local_next, goals, epsilon) in one launch -- the build's own rows stream,
-    equal to tf.multinomial in law only -- and go on through the same one-hot paths.  With actor, the same
-    holds for ["probs"], from actor.probs_rows(obs_others, v_local, goals, epsilon).  epsilon: a float, or the one-element float32
-    device tensor the actors accept.  The soft update of the target actor -- the actor half of list_update_target_ops -- is left to
-    the caller: ``target_actor.soft_update_from(actor, tau)`` after this function returns.  With both None nothing changes."""
+    target_actor / actor (CUDA columns): device actors holding the Policy_target / Policy_main weights -- ParticleActors for the
+    particle env, CheckersActors for env="checkers" (an actor of the other env's class is refused).  With target_actor, `run` is NOT
+    called for ["action_samples_target"] (its (ops, feed) entry still appears in the list): the samples come in one launch from
+    target_actor.sample_rows(obs_others_next, v_local_next, goals, epsilon), on Checkers from
+    target_actor.sample_rows(next_obs_self_t, next_obs_self_v, next_obs_others, cols["actions"], goals, epsilon) (the reference
+    feeds the action just taken as actions_prev there, alg_credit_checkers.py:551) -- the build's own rows stream, equal to
+    tf.multinomial in law only -- and go on through the same one-hot paths.  With actor, the same holds for
+    ["probs"], from actor.probs_rows(obs_others, v_local, goals, epsilon), on Checkers from
+    actor.probs_rows(obs_self_t, obs_self_v, obs_others, cols["actions_prev"], goals, epsilon).  epsilon: a float, or the one-element
+    float32 device tensor the actors accept.  The soft update of the target actor -- the actor half of list_update_target_ops -- is
+    left to the caller: ``target_actor.soft_update_from(actor, tau)`` after this function returns.  With both None nothing changes."""
     checkers = env == "checkers"
     calls = []
     if target_actor is not None or actor is not None:
-        if checkers:
-            raise ValueError("train_step_feeds: target_actor / actor are particle actors; the Checkers actor has no rows kernel")
-        if not cols["v_global"].is_cuda:
+        from .actor import CheckersActor
+        for a in (target_actor, actor):
+            if a is not None and isinstance(a, CheckersActor) != checkers:
+                raise ValueError("train_step_feeds: env=%r takes %s as target_actor / actor, got a %s"
+                                 % (env, "CheckersActors" if checkers else "ParticleActors", type(a).__name__))
+        if not cols["obs_others"].is_cuda:
             raise ValueError("train_step_feeds: target_actor / actor evaluate device columns; call without them for host tensors")
 
     def call(ops, feed, launch=True):
@@ -402,7 +409,13 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
 
     # ---- Q_n(s, a): target actions a', TD target, optimiser step (alg_credit.py:574-612) ----
     if checkers:      # run_actor_target(actions_1hot, obs_others_next, ...) (alg_credit_checkers.py:551)
-        acts = call(["action_samples_target"], actor_feed(obs_others_next, obs_self_t_next, obs_self_v_next, actions_1hot))[0]
+        feed = actor_feed(obs_others_next, obs_self_t_next, obs_self_v_next, actions_1hot)
+        if target_actor is None:
+            acts = call(["action_samples_target"], feed)[0]
+        else:
+            call(["action_samples_target"], feed, launch=False)
+            acts = target_actor.sample_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(-1), goals_self,
+                                            epsilon)["actions"]
     elif target_actor is not None:
         call(["action_samples_target"], actor_feed(obs_others_next, v_local_next), launch=False)
         acts = target_actor.sample_rows(obs_others_next, v_local_next, goals_self, epsilon)["actions"]
@@ -468,6 +481,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         if actor is None:
             return call(["probs"], feed)[0]
         call(["probs"], feed, launch=False)
+        if checkers:
+            return actor.probs_rows(obs_self_t, obs_self_v, obs_others, cols["actions_prev"].reshape(-1), goals_self, epsilon)
         return actor.probs_rows(obs_others, v_local, goals_self, epsilon)
 
     rep_a = lambda x: rep_rows(x, l_action)                                         # noqa: E731

@@ -336,7 +336,12 @@ __device__ __forceinline__ void store_relu(float *O, int ldo, int rt0, int ct0, 
 
 // ---- precision = 1: the two 256 x 256 layers (86 % of the FLOPs) on v_mfma_f32_16x16x32_bf16, f32 accumulation ----------
 // first-layer activations rounded to bf16 on their way to LDS
-template <int RT, int CT>
+// OWNER (the three bf16 helpers): the kernel-argument struct of the calling kernel, part of the helper's identity and nothing else.
+// The collection kernel k_ck_actor<true> is the only caller of its instantiations, and the compiler specialises them for that one
+// caller's arguments (its LDS array, the row stride) before it inlines them; a second kernel calling the SAME instantiations -- the
+// bf16 rows form -- ends that and the collection kernel compiles to another instruction stream (other address arithmetic, other
+// registers).  With the owner in the template arguments every kernel family keeps helpers of its own.
+template <int RT, int CT, typename OWNER = void>
 __device__ __forceinline__ void store_relu_bf16(__bf16 *O, int ldo, int rt0, int ct0, const float (&bias)[CT], int lane,
                                                 const f32x4 (&acc)[RT][CT]) {
   const int col = lane & 15, hi = lane >> 4;
@@ -350,14 +355,14 @@ __device__ __forceinline__ void store_relu_bf16(__bf16 *O, int ldo, int rt0, int
   }
 }
 
-template <int CT> __device__ __forceinline__ void load_b0_bf16(const float *Bp, int ct0, int lane, uint4 (&b0)[CT]) {
+template <int CT, typename OWNER = void> __device__ __forceinline__ void load_b0_bf16(const float *Bp, int ct0, int lane, uint4 (&b0)[CT]) {
 #pragma unroll
   for (int c = 0; c < CT; ++c) b0[c] = (reinterpret_cast<const uint4 *>(Bp) + ((size_t)(ct0 + c) * 8) * 64 + lane)[0];
 }
 
 // acc[t][c] += A[64 rows][256] x B[256][16 (ct0 + c) .. +16]: A[i = l & 15][k = 32 s + 8 (l >> 4) + q] one ds_read_b128 per
 // row tile and k-step, B one 16-byte load per column tile and k-step (next step requested before this step's MFMAs)
-template <int CT>
+template <int CT, typename OWNER = void>
 __device__ __forceinline__ void gemm_tiles_bf16(const __bf16 *A, int lda, const float *Bp, int ct0, int lane,
                                                 const uint4 (&b0)[CT], f32x4 (&acc)[4][CT]) {
   const int col = lane & 15, hi = lane >> 4;
@@ -552,8 +557,9 @@ struct CkRowsSinkX3 {
 // of rows >= n_rows get zeros.  The row's tail (v_obs_self, v_obs_others, a_prev, goal), four lanes per row, is requested as
 // straight-line loads of a CLAMPED row ahead of every LDS write, as in ck_x3_stage_inputs (see there for what dependent round
 // trips cost a lone workgroup).
-template <bool WIDE_T, bool WIDE_G, class SINK>
-__device__ __forceinline__ void ck_rows_stage(const CkRowsParams &p, const SINK &S, int tid, size_t row_base) {
+// P: CkRowsParams, or the actor's CkActorRowsParams below (the same input fields).
+template <bool WIDE_T, bool WIDE_G, class SINK, class P>
+__device__ __forceinline__ void ck_rows_stage(const P &p, const SINK &S, int tid, size_t row_base) {
   using namespace ck_actor;
   constexpr int EPC = WIDE_T ? 2 : 16;                        // elements per 16-byte chunk
   constexpr int NCH = 64 * kObs / EPC, Q = (NCH + 255) / 256;   // chunks per workgroup, per thread
@@ -690,16 +696,65 @@ __device__ __forceinline__ void ck_rows_head(const CkRowsParams &p, const float 
   }
 }
 
+// ---- the ACTOR over transition rows (cm3_actor_checkers_rows_f32) ---------------------------------------------------------------------
+// What alg_credit_checkers.train_step evaluates twice per minibatch: the Policy_target weights with sampling (action_samples_target,
+// alg_credit_checkers.py:551, run_actor_target) and the Policy_main weights forward only (probs, :107-113).  The inputs and the staging
+// are the QMIX rows form's above; `stage` is live (stage 1: no others branch; stage 2: the others branch at every agent count, N = 1
+// with Lo = 2 included); the head is the collection kernels' ck_actor_probs + actor_pick at the row's uniform of the rows stream
+// (rows_uniform, actor_common.h).  A struct of its own: CkRowsParams and the kernels that take it stay as they are.
+struct CkActorRowsParams {
+  size_t n_rows;
+  int N, Lo, stage;
+  float eps;
+  uint32_t draw;                           // the caller's launch counter: counter word 2 of the rows stream
+  uint64_t row_id_base, seed;
+  const void *obs_self_t;                  // WIDE_T: float64 [R][75], else int8 [R][75]
+  const double *obs_self_v, *obs_others;   // [R][4], [R][Lo]
+  const int32_t *actions_prev;             // [R], 0..4
+  const void *goals;                       // WIDE_G: int64 one-hot [R][2], else the uint8 index [R]
+  const float *eps_dev;                    // optional: epsilon read from the device at launch
+  float *probs;                            // [R][5] mixed probabilities
+  int32_t *actions;                        // [R]
+  int64_t *onehot;                         // [R][5]: the sampled action, the form of CkRowsParams::onehot
+  const float *packed;
+};
+
+// lane l < 16 finishes row 16w + l on the same logits as ck_actor_head, through the same ck_actor_probs; every output is optional
+// and nothing is drawn when neither actions nor onehot is asked for
+__device__ __forceinline__ void ck_rows_head(const CkActorRowsParams &p, const float (*sLG)[8], int w, int lane, size_t row_base) {
+  if (lane < 16) {
+    const size_t row = row_base + 16 * w + lane;
+    if (row < p.n_rows) {
+      float o[kA], pr[kA];
+#pragma unroll
+      for (int a = 0; a < kA; ++a) o[a] = sLG[16 * w + lane][a];
+      ck_actor_probs(o, p.eps_dev ? *p.eps_dev : p.eps, pr);
+      if (p.probs) {
+#pragma unroll
+        for (int a = 0; a < kA; ++a) p.probs[row * kA + a] = pr[a];
+      }
+      if (p.actions != nullptr || p.onehot != nullptr) {
+        const int act = actor_pick(pr, rows_uniform(p.seed, p.row_id_base + (uint64_t)row, p.draw));
+        if (p.actions) p.actions[row] = act;
+        if (p.onehot) onehot_row_store(p.onehot, row, act);
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ size_t ck_row_count(const CkActorParams &p) { return (size_t)p.E * p.N; }
 __device__ __forceinline__ size_t ck_row_count(const CkRowsParams &p) { return p.n_rows; }
+__device__ __forceinline__ size_t ck_row_count(const CkActorRowsParams &p) { return p.n_rows; }
 __device__ __forceinline__ int ck_stage(const CkActorParams &p) { return p.stage; }
 __device__ __forceinline__ int ck_stage(const CkRowsParams &) { return 2; }   // the others branch at every agent count
+__device__ __forceinline__ int ck_stage(const CkActorRowsParams &p) { return p.stage; }
 
 // BF16: the two 256 x 256 layers on the bf16 matrix cores (precision = 1, not a parity path); otherwise float32 throughout.
 // GREEDY: the QMIX agent's head (ck_qmix_head) instead of the actor's sampling head (float32 only)
-// ROWS: the transition-rows form -- cm3_last_kernel_variant() calls it k_ck_qmix_rows -- with P = CkRowsParams, its own staging
-// (ck_rows_stage<WIDE_T, WIDE_G>) and the argmax head (ck_rows_head).  ONE kernel text for both: everything behind the staging
-// barrier is the same code, so a row's Q values are the same bits.  (The body stays IN the kernel: handed to a __device__ function,
+// ROWS: the transition-rows form with its own staging (ck_rows_stage<WIDE_T, WIDE_G>) and the head of its parameter struct
+// (ck_rows_head): P = CkRowsParams is the QMIX agent network with the argmax head -- cm3_last_kernel_variant() calls it
+// k_ck_qmix_rows --, P = CkActorRowsParams the actor with the sampling head (k_ck_actor_rows; float32 and bf16).  ONE kernel text
+// for all: everything behind the staging barrier is the same code, so a row's Q values / probabilities are the same bits.  (The body stays IN the kernel: handed to a __device__ function,
 // by reference or by value, the kernel-argument struct made the compiler schedule the existing instantiations differently.)
 template <bool BF16, bool GREEDY = false, bool ROWS = false, bool WIDE_T = false, bool WIDE_G = false, typename P = CkActorParams>
 __global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
@@ -831,8 +886,8 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
     zero_tiles(acc);
     gemm_tiles<4, 4, kKSelf / 16>(sX2, kLdX2, 0, pk + kPSelf, 4 * w, lane, b_self, acc);
     if constexpr (BF16) {
-      load_b0_bf16<4>(pk + kPH2Sb, 4 * w, lane, b_h2b);
-      store_relu_bf16<4, 4>(sHb, kLdHb, 0, 4 * w, bias, lane, acc);
+      load_b0_bf16<4, P>(pk + kPH2Sb, 4 * w, lane, b_h2b);
+      store_relu_bf16<4, 4, P>(sHb, kLdHb, 0, 4 * w, bias, lane, acc);
     } else {
       load_b0<4, kH1 / 16>(pk + kPH2S, 4 * w, lane, b_h2);
       store_relu<4, 4>(sH, kLdH, 0, 4 * w, bias, lane, acc);
@@ -843,7 +898,7 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
   // ---- h2 = relu(branch_self W_self_h2 + branch_others W_others_h2 + b) -------------------------------------------------------
   f32x4 acc2[4][4];
   zero_tiles(acc2);
-  if constexpr (BF16) gemm_tiles_bf16<4>(sHb, kLdHb, pk + kPH2Sb, 4 * w, lane, b_h2b, acc2);
+  if constexpr (BF16) gemm_tiles_bf16<4, P>(sHb, kLdHb, pk + kPH2Sb, 4 * w, lane, b_h2b, acc2);
   else gemm_tiles<4, 4, kH1 / 16>(sH, kLdH, 0, pk + kPH2S, 4 * w, lane, b_h2, acc2);
   const bool stage2 = ck_stage(p) > 1;
   float bias_oth[4], bias_h2[4];
@@ -874,8 +929,8 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
         }
       }
       if constexpr (BF16) {
-        load_b0_bf16<4>(pk + kPH2Ob, 4 * w, lane, b_h2b);
-        store_relu_bf16<4, 4>(sHb, kLdHb, 0, 4 * w, bias_oth, lane, acc);
+        load_b0_bf16<4, P>(pk + kPH2Ob, 4 * w, lane, b_h2b);
+        store_relu_bf16<4, 4, P>(sHb, kLdHb, 0, 4 * w, bias_oth, lane, acc);
       } else {
         load_b0<4, kH1 / 16>(pk + kPH2O, 4 * w, lane, b_h2);
         store_relu<4, 4>(sH, kLdH, 0, 4 * w, bias_oth, lane, acc);
@@ -883,7 +938,7 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
     }
     __syncthreads();
     CM3_STAMP(8, false);
-    if constexpr (BF16) gemm_tiles_bf16<4>(sHb, kLdHb, pk + kPH2Ob, 4 * w, lane, b_h2b, acc2);
+    if constexpr (BF16) gemm_tiles_bf16<4, P>(sHb, kLdHb, pk + kPH2Ob, 4 * w, lane, b_h2b, acc2);
     else gemm_tiles<4, 4, kH1 / 16>(sH, kLdH, 0, pk + kPH2O, 4 * w, lane, b_h2, acc2);
     load_b0<1, kH2 / 16>(pk + kPOut, 0, lane, b_out);
     CM3_STAMP(9, true);
@@ -1707,6 +1762,55 @@ template <bool WIDE_T, bool WIDE_G> static int ck_rows_launch(const CkRowsParams
   return CM3_OK;
 }
 
+// the actor over transition rows in split float16: k_ck_actor_x3's layers behind the rows staging, the others branch by p.stage
+template <bool WIDE_T, bool WIDE_G>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_actor_rows_x3(const CkActorRowsParams p) {
+  using namespace ck_actor;
+  __shared__ __attribute__((aligned(16))) _Float16 sH[kCkX3HBytes / 2];
+  __shared__ __attribute__((aligned(16))) _Float16 sX0[kCkX3X0Bytes / 2];
+  __shared__ __attribute__((aligned(16))) _Float16 sX2[kCkX3X2Bytes / 2];
+  __shared__ __attribute__((aligned(16))) _Float16 sXO[kCkX3XOBytes / 2];
+  __shared__ float sLG[64][8];
+  CkX3Planes L;
+  L.Hh = sH; L.Hl = sH + 64 * kLdHb;
+  L.X0 = sX0; L.C1h = sH; L.C1l = sH + 64 * kLhC1;
+  L.X2h = sX2; L.X2l = sX2 + 64 * kLhX2; L.XOh = sXO; L.XOl = sXO + 64 * kLhXO;
+  L.LG = sLG;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t row_base = (size_t)blockIdx.x * 64;
+  const float *pk = p.packed;
+  CkConvB b_conv;
+  ck_x3_load_conv(pk, w, lane, b_conv);
+  if (w < 4) {
+    CkRowsSinkX3 S;
+    S.X0 = L.X0; S.X2h = L.X2h; S.X2l = L.X2l; S.XOh = L.XOh; S.XOl = L.XOl;
+    ck_rows_stage<WIDE_T, WIDE_G>(p, S, tid, row_base);
+  }
+  __syncthreads();
+  f32x4 acc2[4][kCkBCT];
+  ck_x3_h2_bias(pk, w, lane, acc2);
+  if (p.stage > 1) ck_x3_others(L, pk, w, lane, acc2);
+  ck_x3_self_chain(L, pk, w, lane, b_conv, acc2);
+  if (w < 4) {
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    ck_rows_head(p, sLG, w, lane, row_base);
+  }
+}
+
+template <bool WIDE_T, bool WIDE_G> static int ck_actor_rows_launch(const CkActorRowsParams &p, int precision, hipStream_t s) {
+  const dim3 grid((unsigned)((p.n_rows + 63) / 64));
+  // (g: 1 = float64 windows, 2 = one-hot goals, 3 = both)
+  note_variant(precision == 2 ? "k_ck_actor_rows_x3" : "k_ck_actor_rows", 4, p.N, precision == 2 ? 8 : 4, 0, 0, 0, 0, 0,
+               (WIDE_T ? 1 : 0) + (WIDE_G ? 2 : 0), precision);
+  if (precision == 2) hipLaunchKernelGGL((k_ck_actor_rows_x3<WIDE_T, WIDE_G>), grid, dim3(512), 0, s, p);
+  else if (precision == 1) hipLaunchKernelGGL((k_ck_actor<true, false, true, WIDE_T, WIDE_G, CkActorRowsParams>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((k_ck_actor<false, false, true, WIDE_T, WIDE_G, CkActorRowsParams>), grid, dim3(256), 0, s, p);
+  CM3_HIP_CHECK(hipGetLastError());
+  return CM3_OK;
+}
+
 #endif  // CM3_NO_ENTRY_POINTS
 
 static int ck_actor_check(const cm3_actor_checkers_desc *d) {
@@ -1920,5 +2024,56 @@ extern "C" int cm3_qmix_checkers_rows_f32(const cm3_actor_checkers_desc *d, cons
   hipStream_t s = (hipStream_t)stream;
   if (r->obs_self_t_f64) return r->goals_onehot ? ck_rows_launch<true, true>(p, d->precision, s) : ck_rows_launch<true, false>(p, d->precision, s);
   return r->goals_onehot ? ck_rows_launch<false, true>(p, d->precision, s) : ck_rows_launch<false, false>(p, d->precision, s);
+}
+
+// ---- the CM3 actor over transition rows (ABI 9, additive): every argument is checked before anything touches the GPU ------------------
+extern "C" int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                           const cm3_actor_checkers_rows *r, void *stream) {
+  using namespace cm3;
+  int rc = ck_actor_check(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(wt, "null weights");
+  CM3_REQUIRE(r, "null rows");
+  CM3_REQUIRE(d->precision >= 0 && d->precision <= 2,
+              "precision must be 0 (float32), 1 (bf16 256x256 layers) or 2 (split float16); got %d", d->precision);
+  CM3_REQUIRE(d->stage == 1 || d->stage == 2, "stage must be 1 (self branch only) or 2 (+ others branch); got %d", d->stage);
+  CM3_REQUIRE(d->epsilon >= 0.0f && d->epsilon <= 1.0f, "epsilon must be in [0,1]");
+  CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_checkers_pack once per weight update");
+  CM3_REQUIRE(r->obs_self_t && r->obs_self_v && r->obs_others && r->actions_prev && r->goals,
+              "missing inputs: obs_self_t, obs_self_v, obs_others, actions_prev and goals are all required");
+  CM3_REQUIRE(r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
+  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
+  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
+  CM3_REQUIRE((r->obs_self_t_f64 == 0 || r->obs_self_t_f64 == 1) && (r->goals_onehot == 0 || r->goals_onehot == 1),
+              "form flags must be 0 or 1; got obs_self_t_f64 = %d, goals_onehot = %d", r->obs_self_t_f64, r->goals_onehot);
+  CM3_REQUIRE((uintptr_t)r->obs_self_t % 16 == 0 && (uintptr_t)r->obs_self_v % 16 == 0 && (uintptr_t)r->obs_others % 16 == 0 &&
+                  (uintptr_t)r->actions_prev % 4 == 0 && (r->goals_onehot == 0 || (uintptr_t)r->goals % 16 == 0),
+              "misaligned inputs: obs_self_t, obs_self_v, obs_others (and one-hot goals) must be 16-byte aligned, actions_prev 4-byte");
+  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0 && (uintptr_t)r->probs % 4 == 0 && (uintptr_t)r->actions % 4 == 0,
+              "misaligned outputs: onehot must be 16-byte aligned, probs and actions 4-byte");
+  CkActorRowsParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_rows = (size_t)r->n_rows;
+  p.N = d->n_agents;
+  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
+  p.stage = d->stage;
+  p.eps = d->epsilon;
+  p.eps_dev = r->epsilon_dev;
+  p.draw = r->draw;
+  p.row_id_base = r->row_id_base;
+  p.seed = d->seed;
+  p.obs_self_t = r->obs_self_t;
+  p.obs_self_v = r->obs_self_v;
+  p.obs_others = r->obs_others;
+  p.actions_prev = r->actions_prev;
+  p.goals = r->goals;
+  p.probs = r->probs;
+  p.actions = r->actions;
+  p.onehot = r->onehot;
+  p.packed = (const float *)wt->packed;
+  hipStream_t s = (hipStream_t)stream;
+  if (r->obs_self_t_f64)
+    return r->goals_onehot ? ck_actor_rows_launch<true, true>(p, d->precision, s) : ck_actor_rows_launch<true, false>(p, d->precision, s);
+  return r->goals_onehot ? ck_actor_rows_launch<false, true>(p, d->precision, s) : ck_actor_rows_launch<false, false>(p, d->precision, s);
 }
 #endif  // CM3_NO_ENTRY_POINTS

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import Cm3Error
-from .actor import _epsilon_args
+from .actor import _epsilon_args, stage_checkers_rows
 
 H, N_ACTIONS = 64, 5
 # the six tensors of cm3_qmix_particle_pack, in its order
@@ -363,26 +363,8 @@ class CheckersQmixAgent(object):
         float16 plane, as in the collection kernel.  Returns a dict of device tensors over the R = prod(leading shape) rows:
         "argmax" int32 [R] always; "q" float32 [R, 5], "onehot" int64 [R, 5] (the reference's actions_target_1hot), "q_max" float32
         [R] when asked for.  A row's Q values are the bits act() computes for the same inputs at the same precision."""
-        lead = tuple(obs_self_v.shape[:-1])
-        win = tuple(obs_self_t.shape)
-        index_goals = tuple(goals.shape) == lead
-        if (win not in (lead + (5, 5, 3), lead + (75,)) or tuple(obs_self_v.shape) != lead + (4,)
-                or tuple(obs_others.shape) != lead + (self.Lo,) or tuple(actions_prev.shape) != lead
-                or not (index_goals or tuple(goals.shape) == lead + (2,))):
-            raise Cm3Error("greedy_rows takes [..., 5, 5, 3] (or [..., 75]), [..., 4], [..., %d], [...] and [..., 2] (or [...]) with "
-                           "equal leading shape, got %s, %s, %s, %s, %s" % (self.Lo, win, tuple(obs_self_v.shape),
-                                                                             tuple(obs_others.shape), tuple(actions_prev.shape),
-                                                                             tuple(goals.shape)))
-        rows = int(np.prod(lead, dtype=np.int64))
-        if rows <= 0:
-            raise Cm3Error("greedy_rows needs at least one row")
-        stage = lambda t, dt: t.to(device=self.device, dtype=dt).contiguous()      # noqa: E731
-        ot = stage(obs_self_t, torch.int8 if obs_self_t.dtype == torch.int8 else torch.float64)
-        if index_goals:
-            vg = (stage(goals, torch.uint8) if goals.dtype == torch.uint8
-                  else torch.nn.functional.one_hot(goals.to(self.device).long(), 2).contiguous())
-        else:
-            vg = stage(goals, torch.int64)
+        rows, ot, ov, oo, ap, vg = stage_checkers_rows("greedy_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
+                                                       actions_prev, goals)
         out = {"argmax": torch.empty(rows, dtype=torch.int32, device=self.device)}
         if q:
             out["q"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
@@ -390,8 +372,7 @@ class CheckersQmixAgent(object):
             out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
         if q_max:
             out["q_max"] = torch.empty(rows, dtype=torch.float32, device=self.device)
-        self.enqueue_rows(rows, ot, stage(obs_self_v, torch.float64), stage(obs_others, torch.float64),
-                          stage(actions_prev, torch.int32), vg, **out)
+        self.enqueue_rows(rows, ot, ov, oo, ap, vg, **out)
         return out
 
     def enqueue_rows(self, n_rows, obs_self_t, obs_self_v, obs_others, actions_prev, goals, q=None, argmax=None, onehot=None,

@@ -63,6 +63,8 @@ extern "C" {
                                   data side of alg_qmix_checkers.train_step; additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
+                                  cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
+                                  alg_credit_checkers.train_step); additive.
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -663,6 +665,49 @@ typedef struct {
  * k_ck_qmix_rows<f32,N=..,g=F,..> or k_ck_qmix_rows_x3<..> with F = obs_self_t_f64 + 2 * goals_onehot. */
 int cm3_qmix_checkers_rows_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
                                const cm3_qmix_checkers_rows *rows, void *stream);
+
+/* The Checkers ACTOR over TRANSITION rows (part of ABI 9, additive): what alg_credit_checkers.train_step evaluates twice per
+ * minibatch -- the Policy_target weights with sampling (action_samples_target, alg_credit_checkers.py:551, run_actor_target) on
+ * next_obs_self_t / next_obs_self_v / next_obs_others / actions / goals (the reference feeds the action just taken as actions_prev
+ * there), and the Policy_main weights forward only (probs, :107-113) on obs_self_t / obs_self_v / obs_others / actions_prev / goals.
+ * The five inputs, the two form flags and the alignment rules are those of cm3_qmix_checkers_rows above (at precision 2 float64
+ * windows must hold float16-exact values); n_rows is any positive count; no load touches a byte past n_rows rows of any input.
+ * The network is cm3_actor_checkers_f32's: desc->stage IS read (1: no others branch, obs_others is staged but not contracted; 2: the
+ * others branch at every agent count, N = 1 with its 2 values included), weights->packed comes from cm3_actor_checkers_pack, precision
+ * 0, 1 or 2.  A row's mixed probabilities are, bit for bit, those cm3_actor_checkers_f32 computes for the same inputs at the same
+ * stage and precision with prev_done = NULL.  Every output is optional, at least one is required:
+ *   probs    the mixed probabilities (1 - eps) softmax + eps / 5
+ *   actions  the sampled action: the inverse CDF in action order, as cm3_actor_checkers_f32 picks, at the row's uniform
+ *   onehot   the sampled action as int64 one-hot rows, the form of cm3_qmix_checkers_rows.onehot
+ * The uniform of row r is that of cm3_actor_rows: word .x of the Philox4x32-10 block with counter (row id lo, row id hi, draw,
+ * 0x10000000) and key desc->seed, row id = row_id_base + r (64 bit).  The caller advances `draw` once per launch; equal (seed, row id,
+ * draw) reproduce a draw.  With actions and onehot both NULL nothing is drawn.  Rows at or past n_rows are not written.
+ * (Anonymous struct tag, like cm3_qmix_checkers_rows.) */
+typedef struct {
+  const void    *obs_self_t;    /* [n_rows][75] int8 or float64 (obs_self_t_f64), 16-byte aligned */
+  const double  *obs_self_v;    /* [n_rows][4], 16-byte aligned */
+  const double  *obs_others;    /* [n_rows][2*max(N-1,1)], 16-byte aligned */
+  const int32_t *actions_prev;  /* [n_rows], 0..4 */
+  const void    *goals;         /* [n_rows] uint8, or [n_rows][2] int64 (goals_onehot; then 16-byte aligned) */
+  int32_t  obs_self_t_f64;      /* 0 / 1 */
+  int32_t  goals_onehot;        /* 0 / 1 */
+  float   *probs;               /* optional [n_rows][5] */
+  int32_t *actions;             /* optional [n_rows] */
+  int64_t *onehot;              /* optional [n_rows][5], 16-byte aligned */
+  const float *epsilon_dev;     /* optional device float: read at launch INSTEAD of desc->epsilon */
+  int64_t  n_rows;
+  uint64_t row_id_base;
+  uint32_t draw;
+  uint32_t _pad;
+} cm3_actor_checkers_rows;
+/* desc: validated like cm3_actor_checkers_f32's (n_agents 1..8, the widths, n_obs 2, epsilon in [0,1]) plus precision 0 / 1 / 2 and
+ * stage 1 / 2; stage, epsilon and seed are read, n_envs, env_id_base and obs_self_t_stride are not.  CM3_ERR_INVALID before any launch:
+ * null desc / weights / rows / weights->packed, a missing input, no output requested, n_rows <= 0 or more than 64 * (2^31 - 1), a
+ * form flag other than 0 / 1, a misaligned pointer (inputs as above; onehot 16 bytes, probs and actions 4).
+ * cm3_last_kernel_variant() names the launch k_ck_actor_rows<f32,N=..,g=F,..,prec=P> or k_ck_actor_rows_x3<..> with
+ * F = obs_self_t_f64 + 2 * goals_onehot. */
+int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
+                                const cm3_actor_checkers_rows *rows, void *stream);
 
 /* A whole POLICY-DRIVEN Checkers rollout in ONE launch (ABI 7; csrc/policy_checkers.hip): per tick the actor above (precision 2),
  * epsilon-mixed sampling and Checkers.step with the actions just drawn -- train_onpolicy.py:309-347 / train_offpolicy.py:309-368 without

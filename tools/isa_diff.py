@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Compares the instruction streams of selected kernels between two hipcc -S outputs (labels and comments normalised).  A kernel
 runs from its symbol to its .Lfunc_end label -- NOT to the first s_endpgm: kernels with an early-returning wave (the draw wave)
-have several.  Usage: isa_diff.py base.s new.s 'base-substring=new-substring' ..."""
+have several.  Usage: isa_diff.py base.s new.s 'base-substring=new-substring' ...
+       isa_diff.py base.s new.s --all     every kernel (a symbol whose body ends a program) present under the SAME name in both: one
+                                          summary line, one line per kernel whose stream differs, the names only one side has"""
 import difflib
 import re
 import sys
@@ -31,8 +33,24 @@ def kernels(path):
     return out
 
 
+def compare_all(b, n):
+    """(data symbols of the namespace match the pattern too: only bodies with an s_endpgm are kernels)"""
+    b, n = ({k: v for k, v in d.items() if 's_endpgm' in v} for d in (b, n))
+    both = sorted(set(b) & set(n))
+    changed = [k for k in both if b[k] != n[k]]
+    print("kernels: base %d, new %d, in both %d, identical %d, CHANGED %d" % (len(b), len(n), len(both), len(both) - len(changed), len(changed)))
+    for k in changed:
+        print("  CHANGED %s: base %d new %d instr" % (k, len(b[k]), len(n[k])))
+    for label, only in (("only in base", sorted(set(b) - set(n))), ("only in new", sorted(set(n) - set(b)))):
+        for k in only:
+            print("  %s: %s (%d instr)" % (label, k, len((b if k in b else n)[k])))
+    return len(changed)
+
+
 def main():
     b, n = kernels(sys.argv[1]), kernels(sys.argv[2])
+    if sys.argv[3:] == ["--all"]:
+        sys.exit(1 if compare_all(b, n) else 0)
     for spec in sys.argv[3:]:
         bs, ns = spec.split('=')
         kb = [k for k in b if bs in k]
