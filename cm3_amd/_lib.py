@@ -4,6 +4,7 @@ The reference names a "thin C-ABI/cffi layer"; cffi is not installed in this ima
 stdlib ``ctypes`` is used.  There is NO CPU fallback: if the HIP library is missing or fails to
 load, importing anything that computes raises ``Cm3Error`` loudly.
 """
+import contextlib
 import ctypes
 import os
 
@@ -272,6 +273,8 @@ SYMBOLS = {
     "cm3_rows_scatter": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_int64, c_int64, c_void_p]),
     "cm3_rows_gather": (ctypes.c_int, [P(RowCols), c_int64, c_void_p, c_void_p]),
     "cm3_rows_tile": (ctypes.c_int, [P(TileCol), c_int32, c_void_p]),
+    "cm3_rows_force_index_width": (ctypes.c_int, [c_int32]),
+    "cm3_rows_last_index_width": (ctypes.c_int, []),
     "cm3_episode_route_scratch_bytes": (c_size_t, [c_int32, c_int32]),
     "cm3_episode_route_plan": (ctypes.c_int, [P(EpisodeRouteDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_size_t, c_void_p]),
@@ -444,6 +447,22 @@ def rows_gather(pairs, n_rows, src_row, stream):
     for k in range(0, len(pairs), 16):
         rc = row_cols(pairs[k:k + 16])
         check(lib().cm3_rows_gather(ctypes.byref(rc), int(n_rows), ptr(src_row), stream))
+
+
+@contextlib.contextmanager
+def force_rows_index_width(bits):
+    """Inside the block every row / export / tiling launch takes the index width `bits` (cm3_rows_force_index_width: 64, or 0 for the
+    rule); on exit the rule decides again.  Process-wide: for tests of the wide builds, not for concurrent use."""
+    check(lib().cm3_rows_force_index_width(int(bits)))
+    try:
+        yield
+    finally:
+        check(lib().cm3_rows_force_index_width(0))
+
+
+def rows_last_index_width():
+    """32 / 64: the index width the most recent row / export / tiling launch of this thread took; 0 before any."""
+    return int(lib().cm3_rows_last_index_width())
 
 
 def current_stream_handle(device):

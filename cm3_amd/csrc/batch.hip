@@ -9,11 +9,26 @@
 //   cm3_rows_gather              the columns of sampled transitions out of a ring (replay_buffer.py:28-37) -- all columns in one launch.
 // Pure byte movement: HBM-bound, no arithmetic, no matrix cores.  A wave copies whole rows with 16-byte (or 8- / 4- / 1-byte, by the
 // row size) units, consecutive lanes on consecutive units, so that the side with contiguous rows is fully coalesced.
+#include <atomic>
+
 #include "common.h"
+#include "rows_index_width.h"
 
 namespace cm3 {
 
 constexpr int kMaxRowCols = 16;
+
+// The index width of the five kernels that exist in two (rows_index_width.h).  cm3_rows_force_index_width(64) sends every launch to the
+// wide build (tests: the wide instantiations at small shapes); each launcher records what it chose for cm3_rows_last_index_width().
+// A thread-local of its own: cm3_last_kernel_variant() must not change across calls that export.
+static std::atomic<int> g_rows_force_bits{0};       // 0: the rule decides; 64: wide
+static thread_local int t_rows_last_bits = 0;
+static bool rows_forced_wide() { return g_rows_force_bits.load(std::memory_order_relaxed) == 64; }
+static bool rows_take_narrow(bool rule_narrow) {
+  const bool narrow = rule_narrow && !rows_forced_wide();
+  t_rows_last_bits = narrow ? 32 : 64;
+  return narrow;
+}
 
 struct RowCols {
   int n;
@@ -77,9 +92,8 @@ static int rows_copy(const cm3_row_cols *cols, int64_t n_rows, const int64_t *ds
     const size_t units = (size_t)n_rows * (c.row_bytes[k] / c.unit[k]);
     most = units > most ? units : most;
   }
-  size_t blocks = (most + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
-  if (most + blocks * 256 < (size_t)1 << 32)
+  const size_t blocks = rows_copy_blocks(most);
+  if (rows_take_narrow(rows_stride_index_narrow(most, blocks)))
     hipLaunchKernelGGL(k_rows_copy<uint32_t>, dim3((unsigned)blocks, (unsigned)c.n), dim3(256), 0, s, c, (size_t)n_rows, dst_row, src_row,
                        ring_start, ring_size);
   else
@@ -219,12 +233,13 @@ template <typename P> __device__ __forceinline__ TransUnit trans_unit(const P &p
 #undef CM3_TRANS_DST
 #undef CM3_TRANS_SET
 
-template <typename P> __global__ void __launch_bounds__(256) k_transitions_gather(const P p) {
-  constexpr int K = 4;
+// (WIDE: `small` is a compile-time false -- the 64-bit divisions at any size, launched only under cm3_rows_force_index_width(64))
+template <typename P, bool WIDE = false> __global__ void __launch_bounds__(256) k_transitions_gather(const P p) {
+  constexpr int K = kTransUnitsPerLane;
   const int N = p.N, NV = N * p.L / 4;
   const uint32_t U = (uint32_t)(2 * N + 2 * NV + 3 * N + 2);
   const size_t total = p.n * U, stride = (size_t)gridDim.x * blockDim.x;
-  const bool small = total + (size_t)K * stride < ((size_t)1 << 32);
+  const bool small = WIDE ? false : trans_index_small(total, stride);
   for (size_t g0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g0 < total; g0 += (size_t)K * stride) {
     size_t bb[K], ee[K];
     int64_t tt[K];
@@ -333,7 +348,6 @@ enum CkUnitKind : uint32_t {
   CKU_GOAL      // goal byte -> int64 one-hot pair (16 B)
 };
 constexpr int kCkCols = 16;
-constexpr int kCkUnitsPerLane = 4;
 
 struct CkCol {
   const char *src;      // slot 0 of the source array
@@ -489,7 +503,6 @@ enum PkKind : uint32_t {
   PK_PREV,      // actions_prev: actions[t - 1] (zeros behind a done under terminal capture), prev0 at t = 0
   PK_DONE       // done[t][e] != 0
 };
-constexpr int kPkPiecesPerLane = 4;
 
 struct PkCol {
   const char *src, *alt;
@@ -957,7 +970,7 @@ static int ck_gather_launch(const char *entry, const char *cols_what, const char
   p.ring_size = (size_t)ring_size;
   p.term = term ? 1 : 0;
   p.pair16 = even ? 1 : 0;
-  if (most + kCkUnitsPerLane * 256 < (size_t)1 << 32)     // (32-bit unit arithmetic: a 64-bit division per unit costs more than the copy)
+  if (rows_take_narrow(ck_gather_index_narrow(most)))     // (32-bit unit arithmetic: a 64-bit division per unit costs more than the copy)
     hipLaunchKernelGGL(k_ck_transitions_gather<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
   else
     hipLaunchKernelGGL(k_ck_transitions_gather<size_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
@@ -990,15 +1003,32 @@ static void trans_sources(TransParams &p, const cm3_particle_desc *desc, const c
   p.N = desc->n_agents;
   p.L = 4 * (desc->n_agents > 1 ? desc->n_agents - 1 : 1);
 }
-static unsigned trans_blocks(const TransParams &p) {
-  const size_t units = p.n * (size_t)(2 * p.N + 2 * (p.N * p.L / 4) + 3 * p.N + 2);
-  size_t blocks = (units + 4 * 256 - 1) / (4 * 256);     // four units per lane
-  return (unsigned)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks));
+static size_t trans_units(const TransParams &p) { return p.n * (size_t)(2 * p.N + 2 * (p.N * p.L / 4) + 3 * p.N + 2); }
+// One k_transitions_gather launch, four units per lane: the build whose `small` the kernel decides, or the wide one when forced
+template <typename P> static void trans_launch(const P &p, hipStream_t stream) {
+  const size_t units = trans_units(p), blocks = trans_blocks_for(units);
+  if (rows_forced_wide()) {
+    rows_take_narrow(false);
+    hipLaunchKernelGGL((k_transitions_gather<P, true>), dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  } else {
+    rows_take_narrow(trans_index_small(units, blocks * kRowsLanes));      // (what every lane of the launch will find)
+    hipLaunchKernelGGL((k_transitions_gather<P>), dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  }
 }
 
 }  // namespace cm3
 
 extern "C" {
+int cm3_rows_force_index_width(int32_t bits) {
+  using namespace cm3;
+  // (32 is refused on purpose: a narrow build above its limit would write out of range)
+  CM3_REQUIRE(bits == 0 || bits == 64, "rows_force_index_width: 0 (the rule decides) or 64; got %d", (int)bits);
+  g_rows_force_bits.store(bits, std::memory_order_relaxed);
+  return CM3_OK;
+}
+
+int cm3_rows_last_index_width(void) { return cm3::t_rows_last_bits; }
+
 int cm3_td_target_f64(const void *reward, int32_t reward_is_f64, const double *q, const int64_t *multiplier, double gamma, double *out,
                       int64_t n, void *stream) {
   using namespace cm3;
@@ -1071,9 +1101,8 @@ int cm3_rows_tile(const cm3_tile_col *cols, int32_t n_cols, void *stream) {
     most = total > most ? total : most;
   }
   if (most == 0) return CM3_OK;
-  size_t blocks = (most + 255) / 256;
-  blocks = blocks > 2048 ? 2048 : blocks;
-  if (most + blocks * 256 < (size_t)1 << 32)
+  const size_t blocks = rows_tile_blocks(most);
+  if (rows_take_narrow(rows_stride_index_narrow(most, blocks)))
     hipLaunchKernelGGL(k_rows_tile<uint32_t>, dim3((unsigned)blocks, (unsigned)n_cols), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(k_rows_tile<size_t>, dim3((unsigned)blocks, (unsigned)n_cols), dim3(256), 0, (hipStream_t)stream, a);
@@ -1123,7 +1152,7 @@ int cm3_transitions_gather_f32(const cm3_particle_desc *desc, const cm3_particle
   if (int rc = ring_optional("transition columns", out->ring_start, out->ring_size, n)) return rc;
   p.ring_start = (size_t)out->ring_start;
   p.ring_size = (size_t)out->ring_size;
-  hipLaunchKernelGGL(k_transitions_gather<TransParams>, dim3(trans_blocks(p)), dim3(256), 0, (hipStream_t)stream, p);
+  trans_launch(p, (hipStream_t)stream);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
@@ -1157,7 +1186,7 @@ int cm3_transitions_route_f32(const cm3_particle_desc *desc, const cm3_particle_
     t.reward_n = (float *)o.reward_n; t.next_state = (float *)o.next_state; t.next_obs = (float *)o.next_obs_others; t.done = o.done;
     t.goals = (float *)o.goals;
   }
-  hipLaunchKernelGGL(k_transitions_gather<RouteParams>, dim3(trans_blocks(p)), dim3(256), 0, (hipStream_t)stream, p);
+  trans_launch(p, (hipStream_t)stream);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
@@ -1234,7 +1263,7 @@ int cm3_checkers_transitions_pack(const cm3_checkers_desc *desc, const cm3_check
   p.ring_size = size;
   p.term = term ? 1 : 0;
   // (32-bit byte offsets into a ring column whenever the largest column fits, the slack of a last workgroup included)
-  if (most + 32 * kPkPiecesPerLane * 256 < (size_t)1 << 32 && 2 * size < (size_t)1 << 32)
+  if (rows_take_narrow(ck_pack_index_narrow(most, size)))
     hipLaunchKernelGGL(k_ck_transitions_pack<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(k_ck_transitions_pack<size_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);

@@ -309,6 +309,11 @@ class DeviceDualReplayBuffer(object):
         dev = self.mem1.device
         bad = torch.as_tensor(is_bad, device=dev).bool()
         B = bad.numel()
+        # (before anything is launched or advanced: flags that do not match the rows would be ranked against other rows' positions)
+        rows = {k: int(v.shape[0]) for k, v in cols.items()}
+        if any(n != B for n in rows.values()):
+            raise Cm3Error("add: %d flags for columns of %s rows (one flag per transition, in the columns' order)"
+                           % (B, sorted(set(rows.values()))))
         if B == 0:
             return
         n1 = int(bad.sum())            # the one host read
@@ -459,7 +464,8 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
             buffer.add_rollout(rollout)
         elif dual:
             # every transition carries the flag of the episode it belongs to: the flag is known at the tick that ENDS the episode
-            # (ParticleRollout.episode_is_bad); transitions of episodes still running at the chunk's end take the flag so far
+            # (ParticleRollout.episode_is_bad); transitions of episodes still running at the chunk's end take the flag so far.
+            # One flag per EXPORTED row, in the export's order (an episode-synchronous export holds the valid transitions only)
             cols = rollout.as_reference_batch(numpy=False)
             buffer.add({k: v.contiguous() for k, v in cols.items()}, _transition_flags(rollout))
         elif rollout.auto_reset and rollout.kernel_export and hasattr(buffer, "add_rollout"):
@@ -471,11 +477,17 @@ def off_policy_batches(rollout, buffer, n_chunks, batch_size=128, generator=None
 
 
 def _transition_flags(rollout):
-    """bool [T * E] in the order of as_reference_batch() of a continuous collection (time-major): transition (t, e) is "bad" when the
-    episode it belongs to has collided by its end inside this chunk -- or by the chunk's last tick, for an episode that runs on."""
+    """One bool per row of as_reference_batch(), in its order (time-major).  Continuous collection: [T * E], transition (t, e) is
+    "bad" when the episode it belongs to has collided by its end inside this chunk -- or by the chunk's last tick, for an episode that
+    runs on.  Episode-synchronous collection: one per VALID transition (valid_indices()), the flag of its env's one episode
+    (episode_is_bad(): at the tick that ends it, or the count so far for an env still running at the last tick) -- the rule of
+    DeviceDualReplayBuffer.add_rollout's synchronous mode."""
     coll = rollout.collisions                       # int32 [T, E]: scenario.collisions after every tick (before a same-launch reset)
     if coll is None:
         raise Cm3Error("the dual buffer's flag needs the per-tick collision counts (record_collisions=True)")
+    if not rollout.auto_reset:
+        _, ee = rollout.valid_indices()
+        return rollout.episode_is_bad()[ee]
     done = rollout.done.bool()
     T = coll.shape[0]
     bad_at_end = (coll != 0)

@@ -65,6 +65,8 @@ extern "C" {
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
                                   alg_credit_checkers.train_step); additive.
+                                  cm3_rows_force_index_width / cm3_rows_last_index_width (the 64-bit index builds of the row, export
+                                  and tiling kernels at any size: tests); additive.
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
                                7 (round 6): REMOVED cm3_particle_rollout_chains_f32 / _f64 (sub-batch chains on several streams: a tested,
                                measured regression since round 2 -- profiles/r02_chains_diag.txt; tools/chains_diag.py reproduces it
@@ -939,6 +941,17 @@ int cm3_rows_scatter(const cm3_row_cols *cols, int64_t n_rows, const int64_t *ds
                      void *stream);
 /* dst[k][b] = src[k][src_row[b]] (replay_buffer.py:28-37 sample_batch: the sampled transitions as contiguous columns). */
 int cm3_rows_gather(const cm3_row_cols *cols, int64_t n_rows, const int64_t *src_row, void *stream);
+/* Index width of the data-movement kernels that exist in two: cm3_rows_scatter / cm3_rows_gather, cm3_rows_tile,
+ * cm3_checkers_transitions_gather / cm3_checkers_ring_expand, cm3_checkers_transitions_pack, cm3_transitions_gather_f32 /
+ * cm3_transitions_route_f32.  Each launcher takes 32-bit unit arithmetic while every index a lane forms stays below 2^32 (the rules:
+ * csrc/rows_index_width.h), else its 64-bit build.  bits = 64: every such launch takes the 64-bit build whatever its size (tests run
+ * the wide instantiations at small shapes; results are identical, the launch is slower); bits = 0, the initial value: the rule
+ * decides.  Anything else is CM3_ERR_INVALID -- 32 on purpose: a narrow build above its limit would write out of range.
+ * Process-wide (one relaxed atomic load per launch). */
+int cm3_rows_force_index_width(int32_t bits);
+/* 32 or 64: what the most recent of those launches of THIS thread took; 0 before any.  (Not part of cm3_last_kernel_variant(), which
+ * these launchers leave alone.) */
+int cm3_rows_last_index_width(void);
 
 /* ------------------------------------------------------------------------------------------
  * Whole episodes into the dual replay buffer (additive in ABI 9; replay_buffer_dual.py:13-37 fed as train_onpolicy.py:300-356 feeds it)

@@ -436,3 +436,52 @@ def test_off_policy_cadence_with_the_dual_buffer():
     assert np.array_equal(flag, want) and want.any() and (~want).any()
     assert len(dual.mem1) + len(dual.mem2) == 2 * 40 * 128
     ro.close()
+
+
+def test_off_policy_dual_buffer_flags_of_an_episode_synchronous_rollout():
+    """for an episode-synchronous rollout the export holds the VALID transitions only, while the flags handed to
+    DeviceDualReplayBuffer.add were one per (tick, env) -- misaligned with the rows, both rings advanced by counts that included
+    invalid ticks, len overcounted and sample_batch returned rows never written.  max_steps = 33 in a 40-tick trajectory: every env
+    has at least 7 invalid ticks.  Expected contents from a host walk (tests/dual_ref.py) over done / collisions / valid."""
+    import numpy as np
+    from cm3_amd import Cm3Error
+    from cm3_amd.particle import VecParticleEnv
+    from cm3_amd.replay import DeviceDualReplayBuffer, off_policy_batches
+    from cm3_amd.rollout import ParticleRollout
+    from tests.dual_ref import BAD, DualModel
+    T, E = 40, 128
+    env = VecParticleEnv(load_cfg("particle_stage2_cross.json"), 4, 0.2, 33, E, device=DEV, dtype=torch.float32, auto_reset=False, seed=11)
+    ro = ParticleRollout(env, n_ticks=T, record_collisions=True, use_graph=False)
+    dual = DeviceDualReplayBuffer(size=T * E * 2, device=DEV)
+    batches = list(off_policy_batches(ro, dual, 1, batch_size=64, generator=torch.Generator(device=DEV).manual_seed(0)))
+    assert len(batches) == 1 and batches[0]["reward"].shape[0] == 64
+    done, coll, valid = ro.done.bool().cpu().numpy(), ro.collisions.cpu().numpy(), ro.valid.cpu().numpy()
+    assert valid.shape == (T, E) and ((~valid).sum(0) >= 7).all()
+    # the host walk: every env's one episode, its class read at the tick that ends it (or at the last tick); a transition's token
+    # is t * E + e, so ascending tokens of a class are its transitions in time-major order
+    model = DualModel((T * E, T * E), E, 0)
+    model.add_chunk(done, coll, valid, sync=True)
+    bad = np.zeros(T * E, bool)
+    for cls, toks in model.episodes:
+        bad[toks] = cls == BAD
+    bad = bad.reshape(T, E)
+    n_valid = int(valid.sum())
+    assert sum(len(toks) for _, toks in model.episodes) == n_valid
+    print("valid %d of %d, bad %d, good %d" % (n_valid, T * E, int((bad & valid).sum()), int((~bad & valid).sum())))
+    assert (bad & valid).any() and (~bad & valid).any()                          # both flags occur
+    assert len(dual.mem1) + len(dual.mem2) == n_valid
+    assert (len(dual.mem1), len(dual.mem2)) == (int((bad & valid).sum()), int((~bad & valid).sum()))
+    for mem, pick in ((dual.mem1, bad & valid), (dual.mem2, ~bad & valid)):
+        tt, ee = (torch.as_tensor(a, device=DEV) for a in np.nonzero(pick))      # (row-major nonzero: time-major)
+        want = ro.as_reference_batch_torch(tt, ee, numpy=False)
+        got = mem.all()
+        assert set(got) == set(want)
+        for k in want:
+            assert got[k].shape == want[k].shape and torch.equal(got[k], want[k]), k
+    # a flag count that does not match the rows is refused before anything is launched or advanced
+    state = [(m.idx, m.len) for m in (dual.mem1, dual.mem2)]
+    cols = ro.as_reference_batch(numpy=False)
+    with pytest.raises(Cm3Error):
+        dual.add(cols, torch.zeros(T * E, dtype=torch.bool, device=DEV))
+    assert [(m.idx, m.len) for m in (dual.mem1, dual.mem2)] == state
+    ro.close()
