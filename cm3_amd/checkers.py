@@ -12,6 +12,10 @@
 Value parity is exact.  Integer-valued arrays come back as integer tensors (grid / obs_self_t int8,
 vec int32); ``.double()`` gives the reference's float64 arrays bit for bit.  The live state on the
 device is compact (64-bit collected mask + one packed word per agent), see csrc/checkers.hip.
+
+Compared with the reference's recorded outputs or the oracle, bit for bit, on both the multi-lane fast kernel and the generic one: the
+reference configs (1 and 2 agents) and, on the 3 x 8 band, every agent count 3..8 on start-column and in-band start cells
+(tests/test_gpu_checkers_band_agents.py); the one-launch policy rollouts (csrc/policy_checkers.hip) stay at N <= 2 by construction.
 """
 import ctypes
 

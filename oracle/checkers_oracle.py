@@ -309,9 +309,16 @@ class VecCheckersOracle(object):
             self.mask = np.where(fresh, self.mask | (np.uint64(1) << bit), self.mask)
             self.count[e, i, colour] += fresh.astype(np.int64)
             local[:, i] = penalty + rew
-        total = local[:, 0].copy()
-        for i in range(1, N):
-            total = total + local[:, i]
+        # np.sum(local_rewards) of checkers.py:248 on a length-N vector: left to right below eight elements, eight
+        # accumulators folded pairwise at exactly eight.  Spelled out so no axis reduction's blocking decides it.
+        assert N <= 8
+        if N == 8:
+            l = [local[:, i] for i in range(8)]
+            total = ((l[0] + l[1]) + (l[2] + l[3])) + ((l[4] + l[5]) + (l[6] + l[7]))
+        else:
+            total = local[:, 0].copy()
+            for i in range(1, N):
+                total = total + local[:, i]
         self.steps = self.steps + 1
         popcnt = np.array([bin(int(m)).count("1") for m in self.mask]) if E <= 4096 else _popcount64(self.mask)
         if N == 1:

@@ -131,9 +131,14 @@ def record_particle(ns, cfg_name, n_agents, prob_random, seed, n_episodes, polic
 # ------------------------------------------------------------------------------------------
 # checkers
 # ------------------------------------------------------------------------------------------
-def record_checkers(ns, cfg_name, seed, n_episodes, policy, scripts=None, goals_list=None):
-    cfg = load_cfg(cfg_name)
+def record_checkers(ns, cfg_name, seed, n_episodes, policy, scripts=None, goals_list=None, config_override=None):
+    """config_override: dict(n_agents=N, init={...}) given inline instead of a config file (cfg_name is then only a label in
+    ``meta``).  goals_list: explicit one-hot [N,2] goals per episode -- required above two agents, where the training loop's
+    ``np.eye(N)`` (train_onpolicy.py:293) is no [N,2] goal array."""
+    cfg = config_override if config_override is not None else load_cfg(cfg_name)
     N = cfg['n_agents']
+    if N > 2 and goals_list is None:
+        raise ValueError("more than two agents need explicit [N,2] one-hot goals")
     init = cfg['init']
     env = H.make_reference_checkers_env(ns, init, N, MAX_STEPS)
     rs = np.random.RandomState(seed)
@@ -157,6 +162,7 @@ def record_checkers(ns, cfg_name, seed, n_episodes, policy, scripts=None, goals_
     for ep in range(Ep):
         if goals_list is not None:
             goals = np.array(goals_list[ep])
+            assert goals.shape == (N, 2) and np.array_equal(goals.sum(axis=1), np.ones(N))
         elif N == 1:
             goals = np.array([[1, 0]]) if rs.randint(2) == 0 else np.array([[0, 1]])   # train_onpolicy.py:288-291
         else:
@@ -229,6 +235,20 @@ def checkers_scripts_stage1():
     return scripts, goals
 
 
+def checkers_band_config(n_agents, cells):
+    """3 x 8 band, n_obs 2 (the reference geometry) with ``n_agents`` agents on the given distinct (row, column) start cells;
+    column 8 is the start column right of the band."""
+    assert len(cells) == n_agents == len(set(cells))
+    assert all(0 <= r < 3 and 0 <= c <= 8 for r, c in cells)
+    return dict(n_agents=n_agents, init=dict(n_rows=3, n_columns=8, n_obs=2, agents_r=[r for r, _ in cells],
+                                             agents_c=[c for _, c in cells]))
+
+
+def onehot_goals(seed, n_episodes, n_agents):
+    idx = np.random.RandomState(seed).randint(0, 2, (n_episodes, n_agents))
+    return [np.eye(2, dtype=np.int64)[idx[ep]].tolist() for ep in range(n_episodes)]
+
+
 # ------------------------------------------------------------------------------------------
 def main():
     ns = H.load_reference()
@@ -287,6 +307,14 @@ def main():
     s1, g1 = checkers_scripts_stage1()
     fixtures['checkers_stage1_script'] = record_checkers(ns, 'checkers_stage1.json', 0, len(s1), 'script',
                                                          scripts=s1, goals_list=g1)
+    # --- the 3 x 8 band above two agents: start column (N = 3) and in-band starts (N = 5, 8: more agents than rows) --------
+    for n, seed, n_ep, cells in (
+            (3, 12351, 4, [(0, 8), (1, 8), (2, 8)]),
+            (5, 12352, 3, [(0, 8), (2, 8), (1, 5), (0, 2), (2, 0)]),
+            (8, 12353, 2, [(1, 8), (0, 7), (2, 7), (1, 4), (0, 3), (2, 3), (1, 0), (0, 0)])):
+        fixtures['checkers_band_n%d_uniform' % n] = record_checkers(
+            ns, 'band_n%d' % n, seed, n_ep, 'uniform', goals_list=onehot_goals(seed + 1000, n_ep, n),
+            config_override=checkers_band_config(n, cells))
     total = 0
     for name, arrs in fixtures.items():
         if only and not name.startswith(only):

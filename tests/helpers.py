@@ -26,6 +26,23 @@ def load_cfg(name):
         return json.load(f)
 
 
+def band_init(n_agents, seed=None):
+    """The reference geometry (3 x 8 band, n_obs 2) with ``n_agents`` distinct start cells: the first cells of a seeded
+    permutation of the 27 cells of band plus start column (column 8), or, with no seed, the start column top to bottom."""
+    if seed is None:
+        assert n_agents <= 3
+        cells = [8 + 9 * r for r in range(n_agents)]
+    else:
+        cells = np.random.default_rng(seed).permutation(27)[:n_agents]
+    return dict(n_rows=3, n_columns=8, n_obs=2, agents_r=[int(c) // 9 for c in cells], agents_c=[int(c) % 9 for c in cells])
+
+
+def left_biased_actions(rng, shape, lo=-1, hi=7, p_left=0.3):
+    """Actions in lo..hi-1 (out-of-range ones included), 30 % overwritten with "left" so that episodes collect many cells."""
+    acts = rng.integers(lo, hi, shape)
+    return np.where(rng.random(shape) < p_left, 3, acts)
+
+
 def particle_transition_columns(g, ep):
     """The reference's 11 transition columns of episode ``ep`` of a particle golden fixture -> (columns, T, N)."""
     T = int(g["ep_len"][ep])

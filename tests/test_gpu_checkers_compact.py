@@ -10,18 +10,19 @@ import torch
 
 from oracle import actor_checkers_oracle as AO
 from tests import qmix_checkers_ref as QC
-from tests.helpers import load_cfg
+from tests.helpers import band_init, load_cfg
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 PACK, EXPAND, GATHER, SCATTER = ("cm3_checkers_transitions_pack", "cm3_checkers_ring_expand", "cm3_checkers_transitions_gather",
                                  "cm3_rows_scatter")
 GENERIC = dict(n_agents=3, init=dict(n_rows=5, n_columns=6, n_obs=1, agents_r=[0, 2, 4], agents_c=[6, 6, 6]))   # 81-byte windows, unpadded
+BAND_N4 = dict(n_agents=4, init=band_init(4, 44))     # 3 x 8 band, in-band start cells, 4-byte padded 300-byte windows: the fast kernels above two agents
 
 
 def _env(case, E, auto_reset, seed=12341, max_steps=7):
     from cm3_amd.checkers import VecCheckersEnv
-    cfg = GENERIC if case == "generic" else load_cfg("checkers_stage%d.json" % (1 if case == "n1" else 2))
+    cfg = {"generic": GENERIC, "band_n4": BAND_N4}.get(case) or load_cfg("checkers_stage%d.json" % (1 if case == "n1" else 2))
     env = VecCheckersEnv(cfg["init"], cfg["n_agents"], max_steps, E, device=DEV, seed=seed, auto_reset=auto_reset,
                          padded_records=(False if case == "generic" else None))
     N = cfg["n_agents"]
@@ -110,7 +111,7 @@ def _gens(seed):
 # (policy-driven collection for n1 and n2: the CM3 Checkers actor is built for the reference geometry's 5 x 5 windows, not for the
 # generic case's 3 x 3 ones.  What the pack kernel reads does not depend on who chose the actions: the generic case covers the
 # 3-agent, unpadded 81-byte records, the policy cases the carried prev0 and the one-launch rollout's buffers.)
-@pytest.mark.parametrize("case,policy", [(c, p) for c in ("n1", "n2") for p in ("random", "auto")] + [("generic", "random")])
+@pytest.mark.parametrize("case,policy", [(c, p) for c in ("n1", "n2") for p in ("random", "auto")] + [("generic", "random"), ("band_n4", "random")])
 def test_compact_ring_equals_the_wide_ring(case, policy, spy):
     """Four chunks of 960 transitions into rings of 2500 (the third wraps) and of 500 (every chunk exceeds the ring): after every
     add the compact ring, widened, IS the wide ring; sampling from both with generators seeded alike returns the same 16 columns."""

@@ -10,12 +10,13 @@ import torch
 
 from oracle import actor_checkers_oracle as AO
 from tests import qmix_checkers_ref as QC
-from tests.helpers import load_cfg
+from tests.helpers import band_init, load_cfg
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ENTRY = "cm3_checkers_transitions_gather"
 GENERIC = dict(n_agents=3, init=dict(n_rows=5, n_columns=6, n_obs=1, agents_r=[0, 2, 4], agents_c=[6, 6, 6]))   # 81-byte windows: 8-byte units
+BAND_N4 = dict(n_agents=4, init=band_init(4, 44))     # 3 x 8 band, in-band start cells, 4-byte padded 300-byte windows: the fast kernels above two agents
 
 
 def _same(a, b, names=None):
@@ -28,7 +29,7 @@ def _same(a, b, names=None):
 
 def _env(case, E, auto_reset, seed=12341, max_steps=7):
     from cm3_amd.checkers import VecCheckersEnv
-    cfg = GENERIC if case == "generic" else load_cfg("checkers_stage%d.json" % (1 if case == "n1" else 2))
+    cfg = {"generic": GENERIC, "band_n4": BAND_N4}.get(case) or load_cfg("checkers_stage%d.json" % (1 if case == "n1" else 2))
     env = VecCheckersEnv(cfg["init"], cfg["n_agents"], max_steps, E, device=DEV, seed=seed, auto_reset=auto_reset,
                          padded_records=(False if case == "generic" else None))
     N = cfg["n_agents"]
@@ -71,7 +72,7 @@ def spy(monkeypatch):
 
 
 CASES = [(c, a, p) for c in ("n1", "n2") for a in (False, True) for p in ("random", "tick", "auto")] + \
-        [("generic", False, "random"), ("generic", True, "random")]
+        [("generic", False, "random"), ("generic", True, "random"), ("band_n4", False, "random"), ("band_n4", True, "random")]
 
 
 @pytest.mark.parametrize("case,auto_reset,policy", CASES)

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle.checkers_oracle import CheckersEnvOracle, VecCheckersOracle
-from tests.helpers import golden_names, load_golden
+from tests.helpers import band_init, golden_names, left_biased_actions, load_golden
 
 NAMES = golden_names("checkers_")
 
@@ -117,3 +117,45 @@ def test_masked_restart_equals_reset():
         want = fresh.reset(a.goal)
         for x, y, z in zip(out, want, b.outputs()):
             assert np.array_equal(x[sel], y[sel]) and np.array_equal(x[~sel], z[~sel])
+
+
+def _dense_outputs(envs, outs):
+    """Per-env tuples of the dense oracle stacked the way VecCheckersOracle returns them."""
+    grid = np.stack([o[0][0] for o in outs])
+    vec = np.stack([np.array(o[0][1]) for o in outs])
+    oo, ot, ov = (np.stack([np.array(o[k]) for o in outs]) for k in (1, 2, 3))
+    return grid, vec, oo, ot, ov
+
+
+@pytest.mark.parametrize("N", range(3, 9))
+def test_vector_oracle_equals_dense_oracle_on_the_band(N):
+    """3 x 8 / n_obs 2 band, 3..8 agents, start column and in-band start cells, random goals per agent, 33 ticks of left-biased
+    actions in -1..6: every output of reset and step of the compact vector oracle is value-equal in float64 to the dense oracle
+    (env/checkers.py line by line).  At N = 8 ``total`` is np.sum's pairwise order (checkers.py:248), not left to right."""
+    layouts = ([None] if N == 3 else []) + [100 * N + k for k in range(3)]
+    E = 8
+    for seed in layouts:
+        init = band_init(N, seed)
+        rng = np.random.default_rng(7000 + N if seed is None else seed)
+        goal_idx = rng.integers(0, 2, (E, N))
+        args = (3, 8, 2, init["agents_r"], init["agents_c"], N, 33)
+        vec_env = VecCheckersOracle(*args, n_envs=E)
+        dense = [CheckersEnvOracle(*args) for _ in range(E)]
+        got = vec_env.reset(goal_idx)
+        want = _dense_outputs(dense, [d.reset(np.eye(2)[goal_idx[e]]) for e, d in enumerate(dense)])
+        for x, y in zip(got, want):
+            assert x.dtype == np.float64 and np.array_equal(x, y), (N, seed, "reset")
+        live = np.ones(E, bool)                               # a dense env is not stepped past its own done
+        for t in range(33):
+            acts = left_biased_actions(rng, (E, N))
+            got = vec_env.step(acts)
+            outs = [dense[e].step(acts[e]) if live[e] else None for e in range(E)]
+            idx = np.flatnonzero(live)
+            want = _dense_outputs(dense, [outs[e] for e in idx])
+            for x, y in zip(got[:5], want):
+                assert np.array_equal(x[idx], y), (N, seed, t)
+            assert np.array_equal(got[5][idx], np.array([outs[e][4] for e in idx], dtype=np.float64)), (N, seed, t, "total")
+            assert np.array_equal(got[6][idx], np.array([outs[e][5] for e in idx], dtype=np.float64)), (N, seed, t, "local")
+            assert np.array_equal(got[7][idx], np.array([outs[e][6] for e in idx])), (N, seed, t, "done")
+            live &= ~got[7]
+        assert not live.any()
