@@ -48,11 +48,17 @@ done
 "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_PARTICLE_F64 -Rpass-analysis=kernel-resource-usage -c "${HERE}/policy.hip" -o "${OBJ}/policy_f64.o" 2> "${OBJ}/policy_f64.resource_usage.txt" \
   || { grep -v "remark:" "${OBJ}/policy_f64.resource_usage.txt" >&2; exit 1; } &
 pids+=($!)
+# ... and for the agent counts whose 16-row tiles are padded (3, 5, 6, 7, 9, 10; float32 envs): 54 builds of the kernel in a unit of
+# their own, beside the others (policy.hip: policy_partial_launch), with the same flags as the float32 build
+"${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_PARTICLE_F32 -DCM3_POLICY_PARTIAL_TILES -Rpass-analysis=kernel-resource-usage -c "${HERE}/policy.hip" -o "${OBJ}/policy_partial.o" 2> "${OBJ}/policy_partial.resource_usage.txt" \
+  || { grep -v "remark:" "${OBJ}/policy_partial.resource_usage.txt" >&2; exit 1; } &
+pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
 # the matrix units' diagnostics went to their resource-usage files with the remarks: show what is not a remark
-for f in actor actor_checkers policy policy_f64 policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
+for f in actor actor_checkers policy policy_f64 policy_partial policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
 OBJS=("${OBJ}/particle_f32.o" "${OBJ}/particle_f32_ilp.o" "${OBJ}/particle_f64.o" "${OBJ}/checkers.o" "${OBJ}/util.o" "${OBJ}/advantage.o"
-      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_checkers.o")
+      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_partial.o"
+      "${OBJ}/policy_checkers.o")
 if [ "${CM3_SKIP_ISA_LINT:-0}" != 1 ]; then
   python3 "${HERE}/../../tools/isa_lint.py" "${OBJS[@]}"     # (the objects of THIS build, not whatever else sits in ${OBJ})
 fi

@@ -19,6 +19,11 @@
 // Arithmetic per agent is the reference's operation order, so trajectories are bit-identical to the unfused path
 // (tests/test_gpu_actor.py::test_fused_policy_rollout_equals_launch_per_tick).
 //
+// Agent counts: a wave's 16-row tile holds 16 / N whole envs (policy_tiles.h).  N in {1, 2, 4, 8} fill it; N in {3, 5, 6, 7, 9, 10}
+// leave pad rows that nobody owns -- float32 envs and the CM3 actor only, built in a translation unit of their own (build.sh compiles
+// this file a third time with -DCM3_POLICY_PARTIAL_TILES; see policy_partial_launch).  Same bits as the launch pairs
+// (tests/test_gpu_policy_partial_tiles.py).
+//
 // float64 envs (VecParticleEnv(dtype=torch.float64), the reference-precision mode): build.sh compiles this file twice, with
 // -DCM3_PARTICLE_F32 and -DCM3_PARTICLE_F64, and PolicyReal below is the real of the env side -- state, contact chain,
 // integration, reward / collision / reached, re-initialisation and every trajectory store.  The network is float32 in both (the
@@ -48,8 +53,12 @@
 #if !defined(CM3_PARTICLE_F32) && !defined(CM3_PARTICLE_F64)
 #define CM3_PARTICLE_F32 1
 #endif
+#if defined(CM3_PARTICLE_F32) && !defined(CM3_POLICY_PARTIAL_TILES)
+#define CM3_POLICY_ENTRY_F32 1   // the translation unit that holds the float32 entry points (see policy_partial_launch)
+#endif
 #include "particle.hip"
 #include "actor.hip"
+#include "policy_tiles.h"
 #include <stdlib.h>
 #include <atomic>
 
@@ -208,17 +217,45 @@ template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ voi
   // depend on the placement.
   const int wr = RT == 2 ? ((w + 2 * (int)((blockIdx.x >> 8) & 1u)) & 3) : w;
   const bool row_wave = wr < RT;
-  const int rl = row_wave ? 16 * wr + (lane & 15) : (lane & 15);
-  const bool part0 = (lane >> 4) == 0 && row_wave;
-  size_t r = row_base + rl;
-  const bool row_ok = r < rows;
-  r = row_ok ? r : rows - 1;
-  const size_t e = r / N;
-  const int i = (int)(r - e * N);
-  const int env_lane0 = (lane & 15) - i;  // lane (within the wave's part 0) of agent 0 of this env
+  // N in {1, 2, 4, 8}: a tile is 16 / N whole envs, no row is padded, and a row behind the batch repeats the last one.
+  // Other N (policy_tiles.h): a tile holds 16 / N whole envs in its first rows_used rows; a lane whose row is a pad row, or whose
+  // env lies behind the batch, owns nothing (row_ok false) and MIRRORS ROW 0 OF ITS TILE as lanes 16..63 mirror lane l & 15 --
+  // rl, i and env_lane0 are row 0's, so every row it reads (rl - i + j, the per-env shuffles) is a row of its own tile, and
+  // (e, i) is a pair of the batch for its entry loads.  `tile_store` guards every LDS store of a row: pad lanes store nothing.
+  int rl_, i_, env_lane0_;
+  size_t r_, e_;
+  bool row_ok_, part0_;
+  if constexpr (policy_tile_is_dense(N)) {
+    rl_ = row_wave ? 16 * wr + (lane & 15) : (lane & 15);
+    part0_ = (lane >> 4) == 0 && row_wave;
+    r_ = row_base + rl_;
+    row_ok_ = r_ < rows;
+    r_ = row_ok_ ? r_ : rows - 1;
+    e_ = r_ / N;
+    i_ = (int)(r_ - e_ * N);
+    env_lane0_ = (lane & 15) - i_;  // lane (within the wave's part 0) of agent 0 of this env
+  } else {
+    (void)rows;
+    (void)row_base;
+    part0_ = (lane >> 4) == 0 && row_wave;
+    const int wt = row_wave ? wr : 0;
+    const PolicyTileRow tr = policy_tile_row(policy_tile_of(blockIdx.x, wt, RT), lane & 15, N, E);
+    rl_ = 16 * wt + tr.local_row;
+    row_ok_ = tr.owns;
+    e_ = tr.env;
+    i_ = tr.agent;
+    r_ = e_ * N + (size_t)i_;
+    env_lane0_ = tr.local_row - tr.agent;
+  }
+  const int rl = rl_, i = i_, env_lane0 = env_lane0_;
+  const size_t r = r_, e = e_;
+  const bool row_ok = row_ok_, part0 = part0_;
   const uint64_t genv = (uint64_t)(p.env_id_base + (int64_t)e);
   const bool writer = row_ok && part0;
   const bool head_lane = writer && i == 0;
+  bool tile_store_ = part0;   // who stores row rl of `ns` and of the input tile
+  if constexpr (!policy_tile_is_dense(N)) tile_store_ = writer;
+  const bool tile_store = tile_store_;
 
   // ---- once per launch: weights, live counters, the input tile ---------------------------------------------------------
   // every global request of the entry first (tables, the wave's W2 slice, counters, the rows' state / goals / observation), the
@@ -258,7 +295,20 @@ template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ voi
   int steps = meta.x, collisions = meta.y;
   const uint32_t episode_in = episode;
   if constexpr (!QMIX) actor_tables_store<N, BF16, RT>(lds, tid, tab);
-  if (part0) {
+  if constexpr (!policy_tile_is_dense(N)) {
+    // the rows nobody owns: zeros once per launch, in the input tile and in `ns`, so that the hidden planes of the pad rows and what
+    // a pad lane of an empty tile computes never depend on what the LDS held before (no owned row's value depends on them either
+    // way: the rows of a matrix product are independent)
+    if (part0 && !row_ok) {
+      const int pad = 16 * wr + (lane & 15);
+#pragma unroll
+      for (int c = 0; c < 6 + L; ++c) XS(pad, c) = 0.0f;
+      V4 zero;
+      zero.x = zero.y = zero.z = zero.w = R(0);
+      ns[pad] = zero;
+    }
+  }
+  if (tile_store) {
     XS(rl, kXSelf + 0) = (float)s0.x; XS(rl, kXSelf + 1) = (float)s0.y; XS(rl, kXSelf + 2) = (float)s0.z; XS(rl, kXSelf + 3) = (float)s0.w;
     XS(rl, kXGoal + 0) = (float)g0.x; XS(rl, kXGoal + 1) = (float)g0.y;
 #pragma unroll
@@ -369,7 +419,7 @@ template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ voi
     // but this way nothing a copy computes is ever stored.  Round 5 found what made copies differ: a packed multiply of the contact
     // chain returning a wrong low half in lanes 48..63 under a co-resident matrix wave, profiles/r05_policy_fault.txt)
     if constexpr (F64) wave_lds_sync();   // float64: every lane has read the pre-step rows from `ns` before they are overwritten
-    if (part0) ns[rl] = si;
+    if (tile_store) ns[rl] = si;
     wave_lds_sync();  // the other agents of this env live in the same wave
     V4 oth[NO];
     if constexpr (!F64) {
@@ -482,7 +532,7 @@ template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ voi
       steps = 0;
       collisions = 0;
       was_reset = true;
-      if (part0) ns[rl] = si;
+      if (tile_store) ns[rl] = si;
       wave_lds_sync();
     }
     if (!F64 && auto_reset && __any(done)) {  // fresh episodes in this wave: the observation is that of the reset states
@@ -495,7 +545,7 @@ template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ voi
 
     CM3_STAMP(10, false);
     // ---- trajectory stores + the LDS tile of the next tick ---------------------------------------------------------------------
-    if (part0) {
+    if (tile_store) {
       if (row_ok) {   // every per-row store of the tick in ONE exec region (the action, its probabilities and the reward used to have
                       // regions of their own further up: ~6 scalar instructions and a branch each on the row waves' path)
         tick_ptr(p.actions, p.st_actions, t)[r] = act;
@@ -543,8 +593,7 @@ template <int N, int BF16, int RT, typename R, bool QMIX = false> __global__ voi
 
 template <int N, int RT> static int policy_launch_rt(const PolicyParams &q, int prec, hipStream_t s) {
   using R = PolicyReal;
-  const size_t rows = (size_t)q.p.E * N;
-  const unsigned blocks = (unsigned)((rows + 16 * RT - 1) / (16 * RT));
+  const unsigned blocks = policy_blocks((size_t)q.p.E, N, RT);   // (N in {1, 2, 4, 8}: ceil(E N / (16 RT)), as ever)
   note_variant("k_policy_rollout", (int)sizeof(R), N, 4, q.p.n_ticks > 1, prec, 0, 0, 0, RT);
   if (prec == kPrecF16x3)
     hipLaunchKernelGGL((k_policy_rollout<N, kPrecF16x3, RT, R>), dim3(blocks), dim3(256), 0, s, q);
@@ -582,13 +631,21 @@ static int policy_rt_override() {
   return v;
 }
 template <int N> static int policy_launch(const PolicyParams &q, int prec, hipStream_t s) {
-  const size_t rows = (size_t)q.p.E * N, wg64 = (rows + 63) / 64;
+  // (counted in tiles: ceil(tiles / 4) 64-row workgroups, which is ceil(E N / 64) where no row is padded.  The thresholds below were
+  // measured at N in {1, 2, 4, 8}; the other agent counts inherit them untuned, with the one exception further down -- profiles/r21_policy_partial_tiles.txt)
+  const size_t wg64 = (policy_tiles((size_t)q.p.E, N) + 3) / 4;
   int rt = wg64 > kPolicyCus ? 4 : (wg64 > kPolicyCus / 2 ? 2 : 1);
   // One or two ticks per launch (the launch-per-tick mode): the entry -- 58 KB of tables and weight slice per workgroup through the
   // CU's L1 path -- is as long as the tick, so the larger workgroup wins one step earlier (N = 4, one tick per launch, RT = 4 / 2 / 1:
   // 1024 envs 8.34 / 7.50 / 6.75, 2048 envs 8.46 / 7.43 / 8.47, 4096 envs 8.72 / 9.71 / 14.2, 8192 envs 11.8 / 16.6 / 24.5 us;
   // tools/probes/policy_tick_tiles.sh, profiles/r04_policy_head.txt)
   if (q.p.n_ticks <= 2) rt = wg64 >= kPolicyCus ? 4 : (wg64 >= kPolicyCus / 2 ? 2 : 1);
+  // Nine and ten agents at f16x3: the 64-row build needs 80 - 88 KB of LDS and 256 registers, ONE workgroup per CU at one wave per
+  // SIMD, and two 32-row workgroups per CU beat it at every size swept -- us per tick at RT = 4 / 2, slowest round of RT = 2 below
+  // the fastest of RT = 4 in each: N = 9 at 4096 envs 19.6 / 18.1, at 16384 envs 77.8 / 69.9; N = 10 at 4096 envs 24.0 / 21.7, at
+  // 16384 envs 94.7 / 84.0 (profiles/r21_policy_partial_tiles.txt).  Only what was swept: float32 / bf16 and the one-tick launches
+  // of these agent counts keep the inherited rule.
+  if (N >= 9 && prec == kPrecF16x3 && q.p.n_ticks > 2 && rt == 4) rt = 2;
   if (const int v = policy_rt_override()) rt = v;
   switch (rt) {
     case 1: return policy_launch_rt<N, 1>(q, prec, s);
@@ -597,7 +654,25 @@ template <int N> static int policy_launch(const PolicyParams &q, int prec, hipSt
   return policy_launch_rt<N, 4>(q, prec, s);
 }
 
-#ifdef CM3_PARTICLE_F32
+// The agent counts whose tiles are padded -- 3, 5, 6, 7, 9, 10; float32 envs and the CM3 actor only: 6 x 3 precisions x 3 row-tile
+// counts = 54 builds of the kernel -- are a translation unit of their own, so that they compile beside the others instead of
+// behind them: build.sh compiles this file once more with -DCM3_POLICY_PARTIAL_TILES, which emits this one function and nothing else.
+int policy_partial_launch(int n_agents, const PolicyParams &q, int prec, hipStream_t s);
+#ifdef CM3_POLICY_PARTIAL_TILES
+int policy_partial_launch(int n_agents, const PolicyParams &q, int prec, hipStream_t s) {
+  switch (n_agents) {
+    case 3: return policy_launch<3>(q, prec, s);
+    case 5: return policy_launch<5>(q, prec, s);
+    case 6: return policy_launch<6>(q, prec, s);
+    case 7: return policy_launch<7>(q, prec, s);
+    case 9: return policy_launch<9>(q, prec, s);
+    case 10: return policy_launch<10>(q, prec, s);
+  }
+  return fail(CM3_ERR_INVALID, "n_agents %d has no padded-tile build", n_agents);
+}
+#endif
+
+#ifdef CM3_POLICY_ENTRY_F32
 // QMIX mode: 64-row workgroups at every batch size (the only build; cm3_policy_force_row_tiles is not consulted)
 template <int N> static int policy_qmix_launch(const PolicyParams &q, hipStream_t s) {
   const size_t rows = (size_t)q.p.E * N;
@@ -611,7 +686,8 @@ template <int N> static int policy_qmix_launch(const PolicyParams &q, hipStream_
 
 }  // namespace cm3
 
-#ifdef CM3_PARTICLE_F32
+#ifndef CM3_POLICY_PARTIAL_TILES   // (every entry point below: the other two translation units of this file)
+#ifdef CM3_POLICY_ENTRY_F32
 extern "C" int cm3_policy_force_row_tiles(int32_t row_tiles) {
   using namespace cm3;
   CM3_REQUIRE(row_tiles == 0 || row_tiles == 1 || row_tiles == 2 || row_tiles == 4, "row_tiles must be 0 (rule), 1, 2 or 4; got %d", row_tiles);
@@ -622,11 +698,17 @@ extern "C" int cm3_policy_force_row_tiles(int32_t row_tiles) {
 
 namespace cm3 {
 // the checks on the env descriptor, the tick count and the two descriptors' agreement that every entry point of this file makes first
-static int policy_check_env(const cm3_particle_desc *d, const cm3_actor_particle_desc *ad, int32_t n_ticks) {
+// padded_tiles: the entry has the builds whose 16-row tiles hold 16 / n_agents whole envs and pad rows (cm3_policy_rollout_f32)
+static int policy_check_env(const cm3_particle_desc *d, const cm3_actor_particle_desc *ad, int32_t n_ticks, bool padded_tiles) {
   CM3_REQUIRE(n_ticks >= 1, "n_ticks must be >= 1");
-  CM3_REQUIRE(d->n_agents == 1 || d->n_agents == 2 || d->n_agents == 4 || d->n_agents == 8,
-              "the fused policy rollout needs n_agents in {1, 2, 4, 8} (whole envs per 16-row wave tile); got %d",
-              d->n_agents);
+  if (padded_tiles)
+    CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= CM3_MAX_AGENTS,
+                "the fused policy rollout needs n_agents in 1..%d (16 / n_agents whole envs per 16-row wave tile); got %d",
+                CM3_MAX_AGENTS, d->n_agents);
+  else
+    CM3_REQUIRE(d->n_agents == 1 || d->n_agents == 2 || d->n_agents == 4 || d->n_agents == 8,
+                "the fused policy rollout needs n_agents in {1, 2, 4, 8} (whole envs per 16-row wave tile); got %d",
+                d->n_agents);
   CM3_REQUIRE(ad->n_agents == d->n_agents && ad->n_envs == d->n_envs, "actor / env descriptors disagree");
   CM3_REQUIRE(!(d->flags & CM3_FLAG_GEN_ACTIONS), "the policy draws the actions: CM3_FLAG_GEN_ACTIONS is meaningless here");
   return CM3_OK;
@@ -682,7 +764,8 @@ static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_tr
                                const cm3_actor_particle_weights *wt, float *probs, size_t probs_stride, int32_t n_ticks,
                                void *stream) {
   CM3_REQUIRE(d && t && ad && wt, "null argument");
-  int rc = policy_check_env(d, ad, n_ticks);
+  constexpr bool kPadded = sizeof(PolicyReal) == 4;   // float32 envs: every n_agents; float64: the dense tiles only
+  int rc = policy_check_env(d, ad, n_ticks, kPadded);
   if (rc != CM3_OK) return rc;
   rc = actor_check_desc(ad);
   if (rc != CM3_OK) return rc;
@@ -707,18 +790,19 @@ static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_tr
     case 4: return policy_launch<4>(q, bf16, s);
     case 8: return policy_launch<8>(q, bf16, s);
   }
+  if constexpr (kPadded) return policy_partial_launch(d->n_agents, q, bf16, s);   // 3, 5, 6, 7, 9, 10: their own translation unit
   return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
 }  // namespace cm3
 
-#ifdef CM3_PARTICLE_F32
+#ifdef CM3_POLICY_ENTRY_F32
 extern "C" int cm3_policy_rollout_f32(const cm3_particle_desc *d, const cm3_particle_traj *t,
                                       const cm3_actor_particle_desc *ad, const cm3_actor_particle_weights *wt,
                                       float *probs, size_t probs_stride, int32_t n_ticks, void *stream) {
   return cm3::policy_rollout_call(d, t, ad, wt, probs, probs_stride, n_ticks, stream);
 }
 #endif
-#ifdef CM3_PARTICLE_F32
+#ifdef CM3_POLICY_ENTRY_F32
 // The QMIX agent's one-launch rollout: desc / traj / n_ticks checked as cm3_policy_rollout_f32 checks them, the agent as
 // cm3_qmix_particle_f32 checks it; every failure returns before anything touches the device.
 extern "C" int cm3_policy_rollout_qmix_f32(const cm3_particle_desc *d, const cm3_particle_traj *t, const cm3_actor_particle_desc *ad,
@@ -726,7 +810,7 @@ extern "C" int cm3_policy_rollout_qmix_f32(const cm3_particle_desc *d, const cm3
                                            int32_t n_ticks, void *stream) {
   using namespace cm3;
   CM3_REQUIRE(d && t && ad, "null argument");
-  int rc = policy_check_env(d, ad, n_ticks);
+  int rc = policy_check_env(d, ad, n_ticks, false);
   if (rc != CM3_OK) return rc;
   rc = qmix_check_desc(ad);
   if (rc != CM3_OK) return rc;
@@ -759,3 +843,4 @@ extern "C" int cm3_policy_rollout_f64(const cm3_particle_desc *d, const cm3_part
   return cm3::policy_rollout_call(d, t, ad, wt, probs, probs_stride, n_ticks, stream);
 }
 #endif
+#endif   // !CM3_POLICY_PARTIAL_TILES

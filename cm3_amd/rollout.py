@@ -128,6 +128,21 @@ def _one_launch_refusal(policy, env):
 
 _Mode = collections.namedtuple("_Mode", "kind live sparse")
 
+# ParticleRollout(partial_tiles=True), policy_mode="auto": per agent count with padded tiles, the largest batch (envs) up to which the
+# one-launch rollout was measured faster than the launch pairs -- "auto" takes the one launch up to there and the pairs beyond (see
+# ParticleRollout._mode; 0 would mean never).  Measured at f16x3 on one MI355X, profiles/r21_policy_partial_tiles.txt.
+#   3, 5, 6, 7 agents: faster at 1024, 4096, 16384 and 65536 envs (the largest measured; 33.5 / 46.7, 64.4 / 84.6, 96.6 / 105.1,
+#                       99.5 / 118.5 us per tick there: the one launch's slowest round / the pairs' fastest round)
+#   9 agents:           faster at 1024, 4096 (18.4 / 26.0) and 8192 (35.8 / 40.5), NOT at 16384 (69.9 against 69.3)
+#   10 agents:          faster at 1024 and 4096 (21.9 / 27.6); 8192 is a tie (42.9 / 43.0, inside the arm-to-arm spread) and 16384 a
+#                       loss (84.0 against 79.9): the bound stays at 4096
+PARTIAL_TILES_AUTO = {3: 65536, 5: 65536, 6: 65536, 7: 65536, 9: 8192, 10: 4096}
+
+
+def partial_tiles_auto(n_agents, n_envs):
+    """Does policy_mode="auto" of ParticleRollout(partial_tiles=True) take the one launch at this padded-tile shape?"""
+    return n_envs <= PARTIAL_TILES_AUTO.get(n_agents, 0)
+
 
 def _policy_rollout_entry(lib, dtype):
     """cm3_policy_rollout_f32 / _f64 (the one-launch policy kernel) by the env's real."""
@@ -367,7 +382,7 @@ class ParticleRollout(_Transitions):
     """
 
     def __init__(self, env, n_ticks=None, use_graph=True, fused=False, record_collisions=True,
-                 fused_policy_tick=False, live_state=None, policy_mode="auto", sparse_goals=None):
+                 fused_policy_tick=False, live_state=None, policy_mode="auto", sparse_goals=None, partial_tiles=False):
         self.env = env
         self.T = int(n_ticks or env.max_steps)
         self.use_graph = bool(use_graph)
@@ -376,7 +391,7 @@ class ParticleRollout(_Transitions):
         self.fused = bool(fused)
         # fused_policy_tick: policy-driven collection with ONE launch per tick -- actor forward pass, sampling and env step of
         # a tick in one cm3_policy_rollout_f32 launch (n_ticks = 1) instead of an actor launch followed by a step launch;
-        # bit-identical to both other policy modes (n_agents in {1, 2, 4, 8})
+        # bit-identical to both other policy modes (float32 envs: any n_agents; float64 envs: n_agents in {1, 2, 4, 8})
         self.fused_policy_tick = bool(fused_policy_tick)
         # policy_mode: how collect(policy=<device actor>) launches (all three are bit-identical, tests/test_gpu_actor.py):
         #   "episode"  the whole policy-driven episode in ONE launch (csrc/policy.hip) -- the fastest (C2: 5.6 vs 10.6 us per tick);
@@ -389,6 +404,13 @@ class ParticleRollout(_Transitions):
         if policy_mode not in ("auto", "episode", "tick"):
             raise Cm3Error("policy_mode must be 'auto', 'episode' or 'tick'")
         self.policy_mode = policy_mode
+        # partial_tiles (opt-in): policy_mode "episode" and "auto" also consider the one-launch kernel at n_agents 3, 5, 6, 7, 9, 10
+        # -- 16-row wave tiles that hold 16 // n_agents whole envs and pad rows (csrc/policy_tiles.h); CM3 actor, float32 envs,
+        # actor.seed == env.seed; the same bits as the launch pairs (tests/test_gpu_policy_partial_tiles.py).  "episode" then runs
+        # it at every such n_agents, "auto" where PARTIAL_TILES_AUTO says it was measured faster.  Without the keyword those agent
+        # counts run as launch pairs and "episode" refuses them, as ever.  (fused=True / fused_policy_tick=True call the same
+        # entry and need no keyword.)
+        self.partial_tiles = bool(partial_tiles)
         # live_state: None = by size (see collect); True / False force stepping in place on the env's buffers with slot copies /
         # chaining the ticks through the slots.  Identical trajectories either way (tests/test_gpu_rollout.py).
         self.live_state = live_state
@@ -646,13 +668,23 @@ class ParticleRollout(_Transitions):
                 elif self.policy_mode == "episode":
                     raise Cm3Error("policy_mode='episode': " + why)
         else:
-            episode_ok = env.n in (1, 2, 4, 8) and same_key and not self.fused_policy_tick
+            dense = env.n in (1, 2, 4, 8)
+            # partial_tiles=True: the padded-tile builds of the kernel -- float32 envs only (no float64 build of them exists)
+            padded = self.partial_tiles and not dense and env.dtype == torch.float32 and 1 <= env.n <= 10
+            episode_ok = (dense or padded) and same_key and not self.fused_policy_tick
             # "auto" leaves float64 envs of eight agents to the launch pairs: measured at C5 (8192 x 8, f16x3) the f64 one-launch
             # episode runs 40.8 us per tick against 33.5 (its 64-row build needs 83.7 KB of LDS: one workgroup per CU;
             # profiles/r07_policy_f64.txt).  policy_mode="episode" still runs it.
             auto_ok = episode_ok and not (env.dtype == torch.float64 and env.n == 8)
+            # ... and a padded-tile agent count goes to the one launch only where PARTIAL_TILES_AUTO holds it (the criterion of
+            # profiles/r18_qmix_particle_episode.txt: its slowest round beat the pairs' fastest round of the same run;
+            # profiles/r21_policy_partial_tiles.txt).  policy_mode="episode" runs the kernel at every such count.
+            auto_ok = auto_ok and (dense or partial_tiles_auto(env.n, env.E))
             if self.fused or (self.policy_mode == "episode" and episode_ok) or (self.policy_mode == "auto" and auto_ok):
                 kind = "policy_episode"
+            elif self.policy_mode == "episode" and self.partial_tiles:
+                raise Cm3Error("policy_mode='episode' with partial_tiles=True needs a float32 env where n_agents is outside "
+                               "{1, 2, 4, 8} (the padded-tile builds are float32 only), n_agents <= 10 and actor.seed == env.seed")
             elif self.policy_mode == "episode":
                 raise Cm3Error("policy_mode='episode' needs n_agents in {1, 2, 4, 8} and actor.seed == env.seed")
             else:

@@ -510,15 +510,18 @@ int cm3_qmix_particle_rows_f32(const cm3_actor_particle_desc *desc, const void *
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
  * state resident in LDS / registers.  Same trajectory layout and flags as cm3_particle_rollout_f32 (AUTO_RESET honoured;
  * GEN_ACTIONS rejected: the policy draws the actions, written to traj->actions).  probs (optional) receives the mixed
- * probabilities per tick, float [n_ticks][E][N][5] with probs_stride bytes between ticks.  n_agents in {1,2,4,8};
- * actor_desc and desc must agree on n_envs / n_agents / seed / env_id_base.  Bit-identical to alternating
- * cm3_actor_particle_f32 and cm3_particle_step_f32 launches. */
+ * probabilities per tick, float [n_ticks][E][N][5] with probs_stride bytes between ticks.  n_agents 1..10: a wave owns a 16-row
+ * tile that holds 16 / n_agents whole envs, so n_agents in {3,5,6,7,9,10} leave 1 .. 7 rows of every tile unused (builds of their
+ * own; same results, fewer envs per workgroup).  actor_desc and desc must agree on n_envs / n_agents / seed / env_id_base.
+ * Bit-identical to alternating cm3_actor_particle_f32 and cm3_particle_step_f32 launches.  cm3_last_kernel_variant() names the
+ * launch k_policy_rollout<f32,N=..,..g=<row tiles per workgroup>..>. */
 int cm3_policy_rollout_f32(const cm3_particle_desc *desc, const cm3_particle_traj *traj,
                            const cm3_actor_particle_desc *actor_desc, const cm3_actor_particle_weights *weights,
                            float *probs, size_t probs_stride, int32_t n_ticks, void *stream);
 /* The same one-launch episode on a float64 env (ABI 8): trajectory arrays float64 as for cm3_particle_rollout_f64, the physics,
  * rewards and re-initialisation in float64 (the operation order and contact-skip threshold of cm3_particle_step_f64), the network
- * float32 on the float32 roundings of each tick's observation.  probs stays float32.  Same validation as the _f32 entry.
+ * float32 on the float32 roundings of each tick's observation.  probs stays float32.  Same validation as the _f32 entry, except
+ * n_agents in {1,2,4,8}: the padded-tile builds exist for float32 envs only.
  * Bit-identical to alternating cm3_actor_particle_f64 and cm3_particle_step_f64 launches. */
 int cm3_policy_rollout_f64(const cm3_particle_desc *desc, const cm3_particle_traj *traj,
                            const cm3_actor_particle_desc *actor_desc, const cm3_actor_particle_weights *weights,
