@@ -779,10 +779,6 @@ template <int N> static int actor_rows_launch(const ActorRowsParams &p, hipStrea
   return CM3_OK;
 }
 
-}  // namespace cm3
-
-namespace cm3 {
-
 // ---- QMIX agent network (ABI 9): networks.Qmix_single_particle (networks.py:581-594) + the epsilon-greedy choice of
 // alg_qmix.run_actor (alg_qmix.py:160-184), for all E*N agent rows in one launch.
 //   concat(o_others[L], o_self[4], goal[2]) -> dense 64 relu ("h") -> dense 64 relu ("h2") -> dense 5 ("out"): Q values, no softmax
@@ -1072,25 +1068,11 @@ static int qmix_check_desc(const cm3_actor_particle_desc *d) {
   return CM3_OK;
 }
 
-static size_t qmix_floats_for(int n) {
-  switch (n) {
-    case 1: return QmixLayout<1>::kTotal;
-    case 2: return QmixLayout<2>::kTotal;
-    case 3: return QmixLayout<3>::kTotal;
-    case 4: return QmixLayout<4>::kTotal;
-    case 5: return QmixLayout<5>::kTotal;
-    case 6: return QmixLayout<6>::kTotal;
-    case 7: return QmixLayout<7>::kTotal;
-    case 8: return QmixLayout<8>::kTotal;
-    case 9: return QmixLayout<9>::kTotal;
-    case 10: return QmixLayout<10>::kTotal;
-  }
-  return 0;
+static size_t qmix_floats_for(int n) {   // (0 for an agent count outside 1..10)
+  bool hit;
+  return agent_dispatch_1_to_10(n, hit, [](auto k) { return (size_t)QmixLayout<k()>::kTotal; });
 }
 
-}  // namespace cm3
-
-namespace cm3 {
 static int actor_check_desc(const cm3_actor_particle_desc *d) {
   CM3_REQUIRE(d, "null desc");
   CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= CM3_MAX_AGENTS, "n_agents must be in 1..%d", CM3_MAX_AGENTS);
@@ -1099,21 +1081,23 @@ static int actor_check_desc(const cm3_actor_particle_desc *d) {
               d->n_h1_others, d->n_h2, d->n_actions);
   return CM3_OK;
 }
-template <int N> static size_t packed_floats() { return (size_t)PackLayout<N>::kTotal; }
-static size_t packed_floats_for(int n) {
-  switch (n) {
-    case 1: return packed_floats<1>();
-    case 2: return packed_floats<2>();
-    case 3: return packed_floats<3>();
-    case 4: return packed_floats<4>();
-    case 5: return packed_floats<5>();
-    case 6: return packed_floats<6>();
-    case 7: return packed_floats<7>();
-    case 8: return packed_floats<8>();
-    case 9: return packed_floats<9>();
-    case 10: return packed_floats<10>();
-  }
-  return 0;
+static size_t packed_floats_for(int n) {   // (0 for an agent count outside 1..10)
+  bool hit;
+  return agent_dispatch_1_to_10(n, hit, [](auto k) { return (size_t)PackLayout<k()>::kTotal; });
+}
+
+// What the two transition-rows entries (cm3_actor_particle_rows_f32, cm3_qmix_particle_rows_f32) ask of their rows struct, in the
+// order the checks fire: R = cm3_actor_rows or cm3_qmix_rows (the same input fields); the outputs differ, so "one is set" and its
+// text come from the entry.
+template <typename R> static int particle_rows_check(const R *r, bool any_output, const char *no_output) {
+  CM3_REQUIRE(r->obs_others && r->v_obs && r->goals, "missing inputs: obs_others, v_obs and goals are all required");
+  CM3_REQUIRE(any_output, "%s", no_output);
+  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
+  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
+  CM3_REQUIRE((uintptr_t)r->obs_others % 16 == 0 && (uintptr_t)r->v_obs % 16 == 0 && (uintptr_t)r->goals % 8 == 0,
+              "misaligned inputs: obs_others and v_obs must be 16-byte aligned, goals 8-byte aligned");
+  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0, "misaligned onehot: must be 16-byte aligned");
+  return CM3_OK;
 }
 template <int N> static int pack_launch(const ActorParams &p, float *out, hipStream_t s) {
   hipLaunchKernelGGL((k_actor_pack<N>), dim3(32), dim3(256), 0, s, p, out);
@@ -1142,19 +1126,7 @@ extern "C" int cm3_actor_particle_pack(const cm3_actor_particle_desc *d, const c
   p.w_oth = wt->w_others; p.b_oth = wt->b_others; p.w_oth_h2 = wt->w_others_h2;
   p.b_h2 = wt->b_h2; p.w_out = wt->w_out; p.b_out = wt->b_out;
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return pack_launch<1>(p, (float *)packed, s);
-    case 2: return pack_launch<2>(p, (float *)packed, s);
-    case 3: return pack_launch<3>(p, (float *)packed, s);
-    case 4: return pack_launch<4>(p, (float *)packed, s);
-    case 5: return pack_launch<5>(p, (float *)packed, s);
-    case 6: return pack_launch<6>(p, (float *)packed, s);
-    case 7: return pack_launch<7>(p, (float *)packed, s);
-    case 8: return pack_launch<8>(p, (float *)packed, s);
-    case 9: return pack_launch<9>(p, (float *)packed, s);
-    case 10: return pack_launch<10>(p, (float *)packed, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch_1_to_10(d->n_agents, [&](auto n) { return pack_launch<n()>(p, (float *)packed, s); });
 }
 
 namespace cm3 {
@@ -1189,19 +1161,7 @@ static int actor_particle_call(const cm3_actor_particle_desc *d, const cm3_actor
   p.probs = b->probs;
   p.packed = (const float *)wt->packed;
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return actor_launch<1, RIN>(p, s);
-    case 2: return actor_launch<2, RIN>(p, s);
-    case 3: return actor_launch<3, RIN>(p, s);
-    case 4: return actor_launch<4, RIN>(p, s);
-    case 5: return actor_launch<5, RIN>(p, s);
-    case 6: return actor_launch<6, RIN>(p, s);
-    case 7: return actor_launch<7, RIN>(p, s);
-    case 8: return actor_launch<8, RIN>(p, s);
-    case 9: return actor_launch<9, RIN>(p, s);
-    case 10: return actor_launch<10, RIN>(p, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch_1_to_10(d->n_agents, [&](auto n) { return actor_launch<n(), RIN>(p, s); });
 }
 }  // namespace cm3
 
@@ -1227,13 +1187,8 @@ extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, con
   CM3_REQUIRE(d->epsilon >= 0.0f && d->epsilon <= 1.0f, "epsilon must be in [0,1]");
   CM3_REQUIRE(d->precision >= 0 && d->precision <= 2, "precision must be 0 (float32), 1 (bf16 second layer) or 2 (split float16)");
   CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_particle_pack once per weight update");
-  CM3_REQUIRE(r->obs_others && r->v_obs && r->goals, "missing inputs: obs_others, v_obs and goals are all required");
-  CM3_REQUIRE(r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
-  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
-  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
-  CM3_REQUIRE((uintptr_t)r->obs_others % 16 == 0 && (uintptr_t)r->v_obs % 16 == 0 && (uintptr_t)r->goals % 8 == 0,
-              "misaligned inputs: obs_others and v_obs must be 16-byte aligned, goals 8-byte aligned");
-  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0, "misaligned onehot: must be 16-byte aligned");
+  rc = particle_rows_check(r, r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
+  if (rc != CM3_OK) return rc;
   ActorRowsParams p;
   memset(&p, 0, sizeof(p));
   p.n_rows = (size_t)r->n_rows;
@@ -1252,19 +1207,7 @@ extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, con
   p.onehot = r->onehot;
   p.packed = (const float *)wt->packed;
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return actor_rows_launch<1>(p, s);
-    case 2: return actor_rows_launch<2>(p, s);
-    case 3: return actor_rows_launch<3>(p, s);
-    case 4: return actor_rows_launch<4>(p, s);
-    case 5: return actor_rows_launch<5>(p, s);
-    case 6: return actor_rows_launch<6>(p, s);
-    case 7: return actor_rows_launch<7>(p, s);
-    case 8: return actor_rows_launch<8>(p, s);
-    case 9: return actor_rows_launch<9>(p, s);
-    case 10: return actor_rows_launch<10>(p, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch_1_to_10(d->n_agents, [&](auto n) { return actor_rows_launch<n()>(p, s); });
 }
 
 // ---- QMIX agent (ABI 9) ------------------------------------------------------------------------------------------------------
@@ -1284,19 +1227,7 @@ extern "C" int cm3_qmix_particle_pack(const cm3_actor_particle_desc *d, const fl
     p.w[k] = tensors[k];
   }
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return qmix_pack_launch<1>(p, (float *)packed, s);
-    case 2: return qmix_pack_launch<2>(p, (float *)packed, s);
-    case 3: return qmix_pack_launch<3>(p, (float *)packed, s);
-    case 4: return qmix_pack_launch<4>(p, (float *)packed, s);
-    case 5: return qmix_pack_launch<5>(p, (float *)packed, s);
-    case 6: return qmix_pack_launch<6>(p, (float *)packed, s);
-    case 7: return qmix_pack_launch<7>(p, (float *)packed, s);
-    case 8: return qmix_pack_launch<8>(p, (float *)packed, s);
-    case 9: return qmix_pack_launch<9>(p, (float *)packed, s);
-    case 10: return qmix_pack_launch<10>(p, (float *)packed, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch_1_to_10(d->n_agents, [&](auto n) { return qmix_pack_launch<n()>(p, (float *)packed, s); });
 }
 
 namespace cm3 {
@@ -1325,19 +1256,7 @@ static int qmix_particle_call(const cm3_actor_particle_desc *d, const void *pack
   p.q = b->probs;
   p.packed = (const float *)packed;
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return qmix_launch<1, RIN>(p, s);
-    case 2: return qmix_launch<2, RIN>(p, s);
-    case 3: return qmix_launch<3, RIN>(p, s);
-    case 4: return qmix_launch<4, RIN>(p, s);
-    case 5: return qmix_launch<5, RIN>(p, s);
-    case 6: return qmix_launch<6, RIN>(p, s);
-    case 7: return qmix_launch<7, RIN>(p, s);
-    case 8: return qmix_launch<8, RIN>(p, s);
-    case 9: return qmix_launch<9, RIN>(p, s);
-    case 10: return qmix_launch<10, RIN>(p, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch_1_to_10(d->n_agents, [&](auto n) { return qmix_launch<n(), RIN>(p, s); });
 }
 }  // namespace cm3
 
@@ -1357,13 +1276,8 @@ extern "C" int cm3_qmix_particle_rows_f32(const cm3_actor_particle_desc *d, cons
   if (rc != CM3_OK) return rc;
   CM3_REQUIRE(packed, "packed weights are NULL: run cm3_qmix_particle_pack once per weight update");
   CM3_REQUIRE(r, "null rows");
-  CM3_REQUIRE(r->obs_others && r->v_obs && r->goals, "missing inputs: obs_others, v_obs and goals are all required");
-  CM3_REQUIRE(r->q || r->argmax || r->onehot || r->q_max, "no output requested: set at least one of q, argmax, onehot, q_max");
-  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
-  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
-  CM3_REQUIRE((uintptr_t)r->obs_others % 16 == 0 && (uintptr_t)r->v_obs % 16 == 0 && (uintptr_t)r->goals % 8 == 0,
-              "misaligned inputs: obs_others and v_obs must be 16-byte aligned, goals 8-byte aligned");
-  CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0, "misaligned onehot: must be 16-byte aligned");
+  rc = particle_rows_check(r, r->q || r->argmax || r->onehot || r->q_max, "no output requested: set at least one of q, argmax, onehot, q_max");
+  if (rc != CM3_OK) return rc;
   QmixRowsParams p;
   memset(&p, 0, sizeof(p));
   p.n_rows = (size_t)r->n_rows;
@@ -1376,18 +1290,6 @@ extern "C" int cm3_qmix_particle_rows_f32(const cm3_actor_particle_desc *d, cons
   p.q_max = r->q_max;
   p.packed = (const float *)packed;
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return qmix_rows_launch<1>(p, s);
-    case 2: return qmix_rows_launch<2>(p, s);
-    case 3: return qmix_rows_launch<3>(p, s);
-    case 4: return qmix_rows_launch<4>(p, s);
-    case 5: return qmix_rows_launch<5>(p, s);
-    case 6: return qmix_rows_launch<6>(p, s);
-    case 7: return qmix_rows_launch<7>(p, s);
-    case 8: return qmix_rows_launch<8>(p, s);
-    case 9: return qmix_rows_launch<9>(p, s);
-    case 10: return qmix_rows_launch<10>(p, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch_1_to_10(d->n_agents, [&](auto n) { return qmix_rows_launch<n()>(p, s); });
 }
 #endif  // CM3_NO_ENTRY_POINTS

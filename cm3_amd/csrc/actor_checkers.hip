@@ -481,8 +481,8 @@ __device__ __forceinline__ void put_split(_Float16 *h, _Float16 *l, int at, floa
 // ---- the agent network over TRANSITION rows (cm3_qmix_checkers_rows_f32) -----------------------------------------------------------
 // What alg_qmix_checkers.train_step evaluates with the Agent_target weights (argmax_Q_target, alg_qmix_checkers.py:353-359) on every
 // sampled agent row: the forward pass of k_ck_actor<false, true> / k_ck_actor_x3<true> -- the SAME code behind the staging barrier
-// (float32: a further instantiation of k_ck_actor itself; split float16: k_ck_qmix_rows_x3 calls the device functions k_ck_actor_x3
-// calls), so a row's Q values are the collection kernels' bits -- fed from row-major arrays over R rows instead of an env's buffers,
+// (a further instantiation of k_ck_actor itself in float32, of k_ck_actor_x3 in split float16), so a row's Q values are the
+// collection kernels' bits -- fed from row-major arrays over R rows instead of an env's buffers,
 // with a pure argmax head (nothing is drawn: no steps / episode / prev_done / epsilon / seed).
 struct CkRowsParams {
   size_t n_rows;
@@ -1617,34 +1617,58 @@ struct CkQmixHooks : CkNoHooks {
   }
 };
 
-template <bool GREEDY = false>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_actor_x3(const CkActorParams p) {
+// the planes of the split-float16 forward pass over a kernel's five LDS arrays
+__device__ __forceinline__ CkX3Planes ck_x3_planes(_Float16 *sH, _Float16 *sX0, _Float16 *sX2, _Float16 *sXO, float (*sLG)[8]) {
+  using namespace ck_actor;
+  CkX3Planes L;
+  L.Hh = sH; L.Hl = sH + 64 * kLdHb;
+  L.X0 = sX0; L.C1h = sH; L.C1l = sH + 64 * kLhC1;
+  L.X2h = sX2; L.X2l = sX2 + 64 * kLhX2; L.XOh = sXO; L.XOl = sXO + 64 * kLhXO;
+  L.LG = sLG;
+  return L;
+}
+
+// ONE kernel text for every split-float16 form, with k_ck_actor's template parameters (no BF16): the defaults are the env form --
+// the actor's sampling head, or with GREEDY the QMIX agent's epsilon-greedy head on words drawn through CkQmixHooks -- and
+// ROWS = true the transition-rows form behind ck_rows_stage<WIDE_T, WIDE_G>, with the head of its parameter struct (ck_rows_head):
+// P = CkRowsParams is the QMIX agent network with the argmax head and the others branch at every agent count
+// (cm3_last_kernel_variant() calls it k_ck_qmix_rows_x3), P = CkActorRowsParams the actor with the sampling head and the others
+// branch by p.stage (k_ck_actor_rows_x3).  Everything behind the staging barrier -- ck_x3_h2_bias, ck_x3_others, ck_x3_self_chain --
+// is the same code, so a row's logits are the same bits in all of them.  The body stays IN the kernel, as k_ck_actor's does.
+template <bool GREEDY = false, bool ROWS = false, bool WIDE_T = false, bool WIDE_G = false, typename P = CkActorParams>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_actor_x3(const P p) {
+  static_assert(!(GREEDY && ROWS), "the rows forms take their head from the parameter struct");
   using namespace ck_actor;
   __shared__ __attribute__((aligned(16))) _Float16 sH[kCkX3HBytes / 2];
   __shared__ __attribute__((aligned(16))) _Float16 sX0[kCkX3X0Bytes / 2];
   __shared__ __attribute__((aligned(16))) _Float16 sX2[kCkX3X2Bytes / 2];
   __shared__ __attribute__((aligned(16))) _Float16 sXO[kCkX3XOBytes / 2];
   __shared__ float sLG[64][8];
-  CkX3Planes L;
-  L.Hh = sH; L.Hl = sH + 64 * kLdHb;
-  L.X0 = sX0; L.C1h = sH; L.C1l = sH + 64 * kLhC1;
-  L.X2h = sX2; L.X2l = sX2 + 64 * kLhX2; L.XOh = sXO; L.XOl = sXO + 64 * kLhXO;
-  L.LG = sLG;
+  const CkX3Planes L = ck_x3_planes(sH, sX0, sX2, sXO, sLG);
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t rows = (size_t)p.E * p.N;
+  const size_t rows = ck_row_count(p);
   const size_t row_base = (size_t)blockIdx.x * 64;
   const float *pk = p.packed;
+  (void)rows;   // (the rows forms' staging and head count their rows themselves)
   CM3_STAMP(0, false);
   CkConvB b_conv;
   ck_x3_load_conv(pk, w, lane, b_conv);
-  if (w < 4) ck_x3_stage_inputs(p, L, tid, row_base, rows);
+  if (w < 4) {
+    if constexpr (ROWS) {
+      CkRowsSinkX3 S;
+      S.X0 = L.X0; S.X2h = L.X2h; S.X2l = L.X2l; S.XOh = L.XOh; S.XOl = L.XOl;
+      ck_rows_stage<WIDE_T, WIDE_G>(p, S, tid, row_base);
+    } else {
+      ck_x3_stage_inputs(p, L, tid, row_base, rows);
+    }
+  }
   CM3_STAMP(1, true);
   __syncthreads();
   CM3_STAMP(2, false);
   f32x4 acc2[4][kCkBCT];
   ck_x3_h2_bias(pk, w, lane, acc2);
-  if (p.stage > 1) ck_x3_others(L, pk, w, lane, acc2);
+  if (ck_stage(p) > 1) ck_x3_others(L, pk, w, lane, acc2);
   uint32_t w_explore = 0u, w_action = 0u;
   if constexpr (GREEDY) {
     CkQmixHooks hooks;
@@ -1662,9 +1686,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
   if (w < 4) {
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
+    if constexpr (ROWS) ck_rows_head(p, sLG, w, lane, row_base);
+    else if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
     else ck_actor_head(p, sLG, w, lane, row_base, rows);
   }
+  (void)w_explore;
+  (void)w_action;
   CM3_STAMP(12, true);
 }
 
@@ -1714,101 +1741,24 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
     }
 }
 
-// split float16: the LDS planes of k_ck_actor_x3, its layers (ck_x3_h2_bias, ck_x3_others, ck_x3_self_chain)
-template <bool WIDE_T, bool WIDE_G>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_qmix_rows_x3(const CkRowsParams p) {
-  using namespace ck_actor;
-  __shared__ __attribute__((aligned(16))) _Float16 sH[kCkX3HBytes / 2];
-  __shared__ __attribute__((aligned(16))) _Float16 sX0[kCkX3X0Bytes / 2];
-  __shared__ __attribute__((aligned(16))) _Float16 sX2[kCkX3X2Bytes / 2];
-  __shared__ __attribute__((aligned(16))) _Float16 sXO[kCkX3XOBytes / 2];
-  __shared__ float sLG[64][8];
-  CkX3Planes L;
-  L.Hh = sH; L.Hl = sH + 64 * kLdHb;
-  L.X0 = sX0; L.C1h = sH; L.C1l = sH + 64 * kLhC1;
-  L.X2h = sX2; L.X2l = sX2 + 64 * kLhX2; L.XOh = sXO; L.XOl = sXO + 64 * kLhXO;
-  L.LG = sLG;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t row_base = (size_t)blockIdx.x * 64;
-  const float *pk = p.packed;
-  CkConvB b_conv;
-  ck_x3_load_conv(pk, w, lane, b_conv);
-  if (w < 4) {
-    CkRowsSinkX3 S;
-    S.X0 = L.X0; S.X2h = L.X2h; S.X2l = L.X2l; S.XOh = L.XOh; S.XOl = L.XOl;
-    ck_rows_stage<WIDE_T, WIDE_G>(p, S, tid, row_base);
-  }
-  __syncthreads();
-  f32x4 acc2[4][kCkBCT];
-  ck_x3_h2_bias(pk, w, lane, acc2);
-  ck_x3_others(L, pk, w, lane, acc2);
-  ck_x3_self_chain(L, pk, w, lane, b_conv, acc2);
-  if (w < 4) {
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    ck_rows_head(p, sLG, w, lane, row_base);
-  }
-}
-
-template <bool WIDE_T, bool WIDE_G> static int ck_rows_launch(const CkRowsParams &p, int precision, hipStream_t s) {
+// The launch of both transition-rows entries.  P = CkRowsParams: the QMIX agent network (k_ck_qmix_rows / k_ck_qmix_rows_x3, precision
+// 0 or 2); P = CkActorRowsParams: the actor (k_ck_actor_rows / k_ck_actor_rows_x3), which alone has a bf16 build.
+// (g: 1 = float64 windows, 2 = one-hot goals, 3 = both)
+template <bool WIDE_T, bool WIDE_G, typename P> static int ck_rows_launch_form(const P &p, int precision, hipStream_t s) {
+  constexpr bool ACTOR = std::is_same_v<P, CkActorRowsParams>;
   const dim3 grid((unsigned)((p.n_rows + 63) / 64));
-  // (g: 1 = float64 windows, 2 = one-hot goals, 3 = both)
-  note_variant(precision == 2 ? "k_ck_qmix_rows_x3" : "k_ck_qmix_rows", 4, p.N, precision == 2 ? 8 : 4, 0, 0, 0, 0, 0,
-               (WIDE_T ? 1 : 0) + (WIDE_G ? 2 : 0), precision);
-  if (precision == 2) hipLaunchKernelGGL((k_ck_qmix_rows_x3<WIDE_T, WIDE_G>), grid, dim3(512), 0, s, p);
-  else hipLaunchKernelGGL((k_ck_actor<false, false, true, WIDE_T, WIDE_G, CkRowsParams>), grid, dim3(256), 0, s, p);
+  const bool x3 = precision == 2;
+  note_variant(ACTOR ? (x3 ? "k_ck_actor_rows_x3" : "k_ck_actor_rows") : (x3 ? "k_ck_qmix_rows_x3" : "k_ck_qmix_rows"), 4, p.N, x3 ? 8 : 4,
+               0, 0, 0, 0, 0, (WIDE_T ? 1 : 0) + (WIDE_G ? 2 : 0), precision);
+  if (x3) hipLaunchKernelGGL((k_ck_actor_x3<false, true, WIDE_T, WIDE_G, P>), grid, dim3(512), 0, s, p);
+  else if (!ACTOR || precision == 0) hipLaunchKernelGGL((k_ck_actor<false, false, true, WIDE_T, WIDE_G, P>), grid, dim3(256), 0, s, p);
+  else if constexpr (ACTOR) hipLaunchKernelGGL((k_ck_actor<true, false, true, WIDE_T, WIDE_G, P>), grid, dim3(256), 0, s, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
-
-// the actor over transition rows in split float16: k_ck_actor_x3's layers behind the rows staging, the others branch by p.stage
-template <bool WIDE_T, bool WIDE_G>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k_ck_actor_rows_x3(const CkActorRowsParams p) {
-  using namespace ck_actor;
-  __shared__ __attribute__((aligned(16))) _Float16 sH[kCkX3HBytes / 2];
-  __shared__ __attribute__((aligned(16))) _Float16 sX0[kCkX3X0Bytes / 2];
-  __shared__ __attribute__((aligned(16))) _Float16 sX2[kCkX3X2Bytes / 2];
-  __shared__ __attribute__((aligned(16))) _Float16 sXO[kCkX3XOBytes / 2];
-  __shared__ float sLG[64][8];
-  CkX3Planes L;
-  L.Hh = sH; L.Hl = sH + 64 * kLdHb;
-  L.X0 = sX0; L.C1h = sH; L.C1l = sH + 64 * kLhC1;
-  L.X2h = sX2; L.X2l = sX2 + 64 * kLhX2; L.XOh = sXO; L.XOl = sXO + 64 * kLhXO;
-  L.LG = sLG;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const size_t row_base = (size_t)blockIdx.x * 64;
-  const float *pk = p.packed;
-  CkConvB b_conv;
-  ck_x3_load_conv(pk, w, lane, b_conv);
-  if (w < 4) {
-    CkRowsSinkX3 S;
-    S.X0 = L.X0; S.X2h = L.X2h; S.X2l = L.X2l; S.XOh = L.XOh; S.XOl = L.XOl;
-    ck_rows_stage<WIDE_T, WIDE_G>(p, S, tid, row_base);
-  }
-  __syncthreads();
-  f32x4 acc2[4][kCkBCT];
-  ck_x3_h2_bias(pk, w, lane, acc2);
-  if (p.stage > 1) ck_x3_others(L, pk, w, lane, acc2);
-  ck_x3_self_chain(L, pk, w, lane, b_conv, acc2);
-  if (w < 4) {
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    ck_rows_head(p, sLG, w, lane, row_base);
-  }
-}
-
-template <bool WIDE_T, bool WIDE_G> static int ck_actor_rows_launch(const CkActorRowsParams &p, int precision, hipStream_t s) {
-  const dim3 grid((unsigned)((p.n_rows + 63) / 64));
-  // (g: 1 = float64 windows, 2 = one-hot goals, 3 = both)
-  note_variant(precision == 2 ? "k_ck_actor_rows_x3" : "k_ck_actor_rows", 4, p.N, precision == 2 ? 8 : 4, 0, 0, 0, 0, 0,
-               (WIDE_T ? 1 : 0) + (WIDE_G ? 2 : 0), precision);
-  if (precision == 2) hipLaunchKernelGGL((k_ck_actor_rows_x3<WIDE_T, WIDE_G>), grid, dim3(512), 0, s, p);
-  else if (precision == 1) hipLaunchKernelGGL((k_ck_actor<true, false, true, WIDE_T, WIDE_G, CkActorRowsParams>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((k_ck_actor<false, false, true, WIDE_T, WIDE_G, CkActorRowsParams>), grid, dim3(256), 0, s, p);
-  CM3_HIP_CHECK(hipGetLastError());
-  return CM3_OK;
+template <typename P> static int ck_rows_launch(const P &p, bool wide_t, bool wide_g, int precision, hipStream_t s) {
+  if (wide_t) return wide_g ? ck_rows_launch_form<true, true>(p, precision, s) : ck_rows_launch_form<true, false>(p, precision, s);
+  return wide_g ? ck_rows_launch_form<false, true>(p, precision, s) : ck_rows_launch_form<false, false>(p, precision, s);
 }
 
 #endif  // CM3_NO_ENTRY_POINTS
@@ -1837,6 +1787,16 @@ static int ck_qmix_check(const cm3_actor_checkers_desc *d) {
   return CM3_OK;
 }
 
+// ... and the precision of its forward entries (cm3_qmix_checkers_f32, cm3_qmix_checkers_rows_f32), checked right behind it
+static int ck_qmix_check_forward(const cm3_actor_checkers_desc *d) {
+  int rc = ck_qmix_check(d);
+  if (rc != CM3_OK) return rc;
+  CM3_REQUIRE(d->precision == 0 || d->precision == 2,
+              "the Checkers QMIX agent runs at precision 0 (float32) or 2 (split float16); got %d (bf16 is not a parity path: argmax "
+              "would flip)", d->precision);
+  return CM3_OK;
+}
+
 static void ck_actor_weights(CkActorParams &p, const cm3_actor_checkers_weights *wt) {
   p.conv_w = wt->conv_w; p.conv_b = wt->conv_b; p.lin_w = wt->lin_w; p.lin_b = wt->lin_b;
   p.self_w = wt->self_w; p.self_b = wt->self_b; p.w_self_h2 = wt->w_self_h2;
@@ -1847,26 +1807,24 @@ static void ck_actor_weights(CkActorParams &p, const cm3_actor_checkers_weights 
 }  // namespace cm3
 
 #ifndef CM3_NO_ENTRY_POINTS
-extern "C" size_t cm3_actor_checkers_packed_bytes(void) { return (size_t)cm3::ck_actor::kPAll * sizeof(float); }
-
-extern "C" int cm3_actor_checkers_pack(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
-                                       void *packed, void *stream) {
-  using namespace cm3;
-  int rc = ck_actor_check(d);
-  if (rc != CM3_OK) return rc;
+namespace cm3 {
+// What both pack entries do behind their descriptor check: the weights' checks, the pack at `stage` (the others branch, required
+// with the entry's text, from stage 2 on) and, where `table`, the others branch as a table from the weights just packed.
+static int ck_pack_call(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, void *packed, void *stream, int stage,
+                        const char *others_missing, bool table) {
   CM3_REQUIRE(wt && packed, "null weights / packed buffer");
   CM3_REQUIRE(wt->conv_w && wt->conv_b && wt->lin_w && wt->lin_b && wt->self_w && wt->self_b && wt->w_self_h2 &&
                   wt->b_h2 && wt->out_w && wt->out_b, "missing weights");
-  if (d->stage > 1) CM3_REQUIRE(wt->others_w && wt->others_b && wt->w_others_h2, "stage 2 needs the others branch");
+  if (stage > 1) CM3_REQUIRE(wt->others_w && wt->others_b && wt->w_others_h2, "%s", others_missing);
   CkActorParams p;
   memset(&p, 0, sizeof(p));
   p.N = d->n_agents;
-  p.stage = d->stage;
+  p.stage = stage;
   p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
   ck_actor_weights(p, wt);
   hipLaunchKernelGGL(k_ck_actor_pack, dim3(128), dim3(256), 0, (hipStream_t)stream, p, (float *)packed);
   CM3_HIP_CHECK(hipGetLastError());
-  if (d->stage > 1 && d->n_agents == 2) {   // the others branch as a table (see k_ck_actor_others_table), from the weights just packed
+  if (table) {
     hipLaunchKernelGGL(k_ck_actor_others_table, dim3(2), dim3(512), 0, (hipStream_t)stream, (const float *)packed,
                        (float *)packed + ck_actor::kPOthTab);
     CM3_HIP_CHECK(hipGetLastError());
@@ -1874,7 +1832,6 @@ extern "C" int cm3_actor_checkers_pack(const cm3_actor_checkers_desc *d, const c
   return CM3_OK;
 }
 
-namespace cm3 {
 // the checks and the parameters a forward launch shares (cm3_actor_checkers_f32, cm3_qmix_checkers_f32): every argument is checked
 // before anything touches the GPU
 static int ck_actor_call_params(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, const cm3_actor_checkers_bufs *b,
@@ -1911,7 +1868,50 @@ static int ck_actor_call_params(const cm3_actor_checkers_desc *d, const cm3_acto
   p.packed = (const float *)wt->packed;
   return CM3_OK;
 }
+
+// What the two transition-rows entries (cm3_qmix_checkers_rows_f32, cm3_actor_checkers_rows_f32) ask of their rows struct, in the
+// order the checks fire: R = cm3_qmix_checkers_rows or cm3_actor_checkers_rows (the same inputs and form flags); the outputs
+// differ, so "one is set" and its text come from the entry, and the outputs' alignment stays there.
+template <typename R> static int ck_rows_check(const R *r, bool any_output, const char *no_output) {
+  CM3_REQUIRE(r->obs_self_t && r->obs_self_v && r->obs_others && r->actions_prev && r->goals,
+              "missing inputs: obs_self_t, obs_self_v, obs_others, actions_prev and goals are all required");
+  CM3_REQUIRE(any_output, "%s", no_output);
+  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
+  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
+  CM3_REQUIRE((r->obs_self_t_f64 == 0 || r->obs_self_t_f64 == 1) && (r->goals_onehot == 0 || r->goals_onehot == 1),
+              "form flags must be 0 or 1; got obs_self_t_f64 = %d, goals_onehot = %d", r->obs_self_t_f64, r->goals_onehot);
+  CM3_REQUIRE((uintptr_t)r->obs_self_t % 16 == 0 && (uintptr_t)r->obs_self_v % 16 == 0 && (uintptr_t)r->obs_others % 16 == 0 &&
+                  (uintptr_t)r->actions_prev % 4 == 0 && (r->goals_onehot == 0 || (uintptr_t)r->goals % 16 == 0),
+              "misaligned inputs: obs_self_t, obs_self_v, obs_others (and one-hot goals) must be 16-byte aligned, actions_prev 4-byte");
+  return CM3_OK;
+}
+
+// ... and the fields both parameter structs (P = CkRowsParams, CkActorRowsParams) take from them: everything else is left zero
+template <typename P, typename R>
+static void ck_rows_inputs(P &p, const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, const R *r) {
+  memset(&p, 0, sizeof(p));
+  p.n_rows = (size_t)r->n_rows;
+  p.N = d->n_agents;
+  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
+  p.obs_self_t = r->obs_self_t;
+  p.obs_self_v = r->obs_self_v;
+  p.obs_others = r->obs_others;
+  p.actions_prev = r->actions_prev;
+  p.goals = r->goals;
+  p.packed = (const float *)wt->packed;
+}
 }  // namespace cm3
+
+extern "C" size_t cm3_actor_checkers_packed_bytes(void) { return (size_t)cm3::ck_actor::kPAll * sizeof(float); }
+
+extern "C" int cm3_actor_checkers_pack(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                       void *packed, void *stream) {
+  using namespace cm3;
+  int rc = ck_actor_check(d);
+  if (rc != CM3_OK) return rc;
+  // the others branch as a table for the whole-episode kernel (see k_ck_actor_others_table): two agents at stage 2
+  return ck_pack_call(d, wt, packed, stream, d->stage, "stage 2 needs the others branch", d->stage > 1 && d->n_agents == 2);
+}
 
 extern "C" int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
                                       const cm3_actor_checkers_bufs *b, void *stream) {
@@ -1937,39 +1937,19 @@ extern "C" int cm3_qmix_checkers_pack(const cm3_actor_checkers_desc *d, const cm
   using namespace cm3;
   int rc = ck_qmix_check(d);
   if (rc != CM3_OK) return rc;
-  CM3_REQUIRE(wt && packed, "null weights / packed buffer");
-  CM3_REQUIRE(wt->conv_w && wt->conv_b && wt->lin_w && wt->lin_b && wt->self_w && wt->self_b && wt->w_self_h2 &&
-                  wt->b_h2 && wt->out_w && wt->out_b, "missing weights");
-  CM3_REQUIRE(wt->others_w && wt->others_b && wt->w_others_h2,
-              "the QMIX agent network has the others branch at every agent count (networks.Qmix_single_checkers): "
-              "branch_others/kernel, branch_others/bias and W_others_h2 are required");
-  CkActorParams p;
-  memset(&p, 0, sizeof(p));
-  p.N = d->n_agents;
-  p.stage = 2;                                      // (desc->stage is not read)
-  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
-  ck_actor_weights(p, wt);
-  hipLaunchKernelGGL(k_ck_actor_pack, dim3(128), dim3(256), 0, (hipStream_t)stream, p, (float *)packed);
-  CM3_HIP_CHECK(hipGetLastError());
-  if (d->n_agents <= 2) {
-    // the others branch as a table for cm3_policy_rollout_checkers_qmix, from the weights just packed: with one or two agents a row's
-    // v_obs_others is ONE normalised cell (N = 1: the agent's own, checkers.py:128-154), 91 possible inputs (k_ck_actor_others_table).
-    // The stand-alone kernels do not read that region.
-    hipLaunchKernelGGL(k_ck_actor_others_table, dim3(2), dim3(512), 0, (hipStream_t)stream, (const float *)packed,
-                       (float *)packed + ck_actor::kPOthTab);
-    CM3_HIP_CHECK(hipGetLastError());
-  }
-  return CM3_OK;
+  // stage 2 whatever desc->stage says; the others branch as a table for cm3_policy_rollout_checkers_qmix: with one or two agents a
+  // row's v_obs_others is ONE normalised cell (N = 1: the agent's own, checkers.py:128-154), 91 possible inputs
+  // (k_ck_actor_others_table).  The stand-alone kernels do not read that region.
+  return ck_pack_call(d, wt, packed, stream, 2,
+                      "the QMIX agent network has the others branch at every agent count (networks.Qmix_single_checkers): "
+                      "branch_others/kernel, branch_others/bias and W_others_h2 are required", d->n_agents <= 2);
 }
 
 extern "C" int cm3_qmix_checkers_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
                                      const cm3_actor_checkers_bufs *b, void *stream) {
   using namespace cm3;
-  int rc = ck_qmix_check(d);
+  int rc = ck_qmix_check_forward(d);
   if (rc != CM3_OK) return rc;
-  CM3_REQUIRE(d->precision == 0 || d->precision == 2,
-              "the Checkers QMIX agent runs at precision 0 (float32) or 2 (split float16); got %d (bf16 is not a parity path: argmax "
-              "would flip)", d->precision);
   CkActorParams p;
   rc = ck_actor_call_params(d, wt, b, p);
   if (rc != CM3_OK) return rc;
@@ -1986,44 +1966,22 @@ extern "C" int cm3_qmix_checkers_f32(const cm3_actor_checkers_desc *d, const cm3
 extern "C" int cm3_qmix_checkers_rows_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
                                           const cm3_qmix_checkers_rows *r, void *stream) {
   using namespace cm3;
-  int rc = ck_qmix_check(d);
+  int rc = ck_qmix_check_forward(d);
   if (rc != CM3_OK) return rc;
-  CM3_REQUIRE(d->precision == 0 || d->precision == 2,
-              "the Checkers QMIX agent runs at precision 0 (float32) or 2 (split float16); got %d (bf16 is not a parity path: argmax "
-              "would flip)", d->precision);
   CM3_REQUIRE(wt, "null weights");
   CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_qmix_checkers_pack once per weight update");
   CM3_REQUIRE(r, "null rows");
-  CM3_REQUIRE(r->obs_self_t && r->obs_self_v && r->obs_others && r->actions_prev && r->goals,
-              "missing inputs: obs_self_t, obs_self_v, obs_others, actions_prev and goals are all required");
-  CM3_REQUIRE(r->q || r->argmax || r->onehot || r->q_max, "no output requested: set at least one of q, argmax, onehot, q_max");
-  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
-  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
-  CM3_REQUIRE((r->obs_self_t_f64 == 0 || r->obs_self_t_f64 == 1) && (r->goals_onehot == 0 || r->goals_onehot == 1),
-              "form flags must be 0 or 1; got obs_self_t_f64 = %d, goals_onehot = %d", r->obs_self_t_f64, r->goals_onehot);
-  CM3_REQUIRE((uintptr_t)r->obs_self_t % 16 == 0 && (uintptr_t)r->obs_self_v % 16 == 0 && (uintptr_t)r->obs_others % 16 == 0 &&
-                  (uintptr_t)r->actions_prev % 4 == 0 && (r->goals_onehot == 0 || (uintptr_t)r->goals % 16 == 0),
-              "misaligned inputs: obs_self_t, obs_self_v, obs_others (and one-hot goals) must be 16-byte aligned, actions_prev 4-byte");
+  rc = ck_rows_check(r, r->q || r->argmax || r->onehot || r->q_max, "no output requested: set at least one of q, argmax, onehot, q_max");
+  if (rc != CM3_OK) return rc;
   CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0 && (uintptr_t)r->q % 4 == 0 && (uintptr_t)r->argmax % 4 == 0 && (uintptr_t)r->q_max % 4 == 0,
               "misaligned outputs: onehot must be 16-byte aligned, q, argmax and q_max 4-byte");
   CkRowsParams p;
-  memset(&p, 0, sizeof(p));
-  p.n_rows = (size_t)r->n_rows;
-  p.N = d->n_agents;
-  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
-  p.obs_self_t = r->obs_self_t;
-  p.obs_self_v = r->obs_self_v;
-  p.obs_others = r->obs_others;
-  p.actions_prev = r->actions_prev;
-  p.goals = r->goals;
+  ck_rows_inputs(p, d, wt, r);
   p.q = r->q;
   p.argmax = r->argmax;
   p.onehot = r->onehot;
   p.q_max = r->q_max;
-  p.packed = (const float *)wt->packed;
-  hipStream_t s = (hipStream_t)stream;
-  if (r->obs_self_t_f64) return r->goals_onehot ? ck_rows_launch<true, true>(p, d->precision, s) : ck_rows_launch<true, false>(p, d->precision, s);
-  return r->goals_onehot ? ck_rows_launch<false, true>(p, d->precision, s) : ck_rows_launch<false, false>(p, d->precision, s);
+  return ck_rows_launch(p, r->obs_self_t_f64 != 0, r->goals_onehot != 0, d->precision, (hipStream_t)stream);
 }
 
 // ---- the CM3 actor over transition rows (ABI 9, additive): every argument is checked before anything touches the GPU ------------------
@@ -2039,41 +1997,21 @@ extern "C" int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *d, con
   CM3_REQUIRE(d->stage == 1 || d->stage == 2, "stage must be 1 (self branch only) or 2 (+ others branch); got %d", d->stage);
   CM3_REQUIRE(d->epsilon >= 0.0f && d->epsilon <= 1.0f, "epsilon must be in [0,1]");
   CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_checkers_pack once per weight update");
-  CM3_REQUIRE(r->obs_self_t && r->obs_self_v && r->obs_others && r->actions_prev && r->goals,
-              "missing inputs: obs_self_t, obs_self_v, obs_others, actions_prev and goals are all required");
-  CM3_REQUIRE(r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
-  CM3_REQUIRE(r->n_rows > 0, "n_rows must be positive");
-  CM3_REQUIRE(r->n_rows <= (int64_t)64 * 0x7fffffff, "n_rows %lld is more than a grid of 64-row workgroups takes", (long long)r->n_rows);
-  CM3_REQUIRE((r->obs_self_t_f64 == 0 || r->obs_self_t_f64 == 1) && (r->goals_onehot == 0 || r->goals_onehot == 1),
-              "form flags must be 0 or 1; got obs_self_t_f64 = %d, goals_onehot = %d", r->obs_self_t_f64, r->goals_onehot);
-  CM3_REQUIRE((uintptr_t)r->obs_self_t % 16 == 0 && (uintptr_t)r->obs_self_v % 16 == 0 && (uintptr_t)r->obs_others % 16 == 0 &&
-                  (uintptr_t)r->actions_prev % 4 == 0 && (r->goals_onehot == 0 || (uintptr_t)r->goals % 16 == 0),
-              "misaligned inputs: obs_self_t, obs_self_v, obs_others (and one-hot goals) must be 16-byte aligned, actions_prev 4-byte");
+  rc = ck_rows_check(r, r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
+  if (rc != CM3_OK) return rc;
   CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0 && (uintptr_t)r->probs % 4 == 0 && (uintptr_t)r->actions % 4 == 0,
               "misaligned outputs: onehot must be 16-byte aligned, probs and actions 4-byte");
   CkActorRowsParams p;
-  memset(&p, 0, sizeof(p));
-  p.n_rows = (size_t)r->n_rows;
-  p.N = d->n_agents;
-  p.Lo = 2 * (d->n_agents > 1 ? d->n_agents - 1 : 1);
+  ck_rows_inputs(p, d, wt, r);
   p.stage = d->stage;
   p.eps = d->epsilon;
   p.eps_dev = r->epsilon_dev;
   p.draw = r->draw;
   p.row_id_base = r->row_id_base;
   p.seed = d->seed;
-  p.obs_self_t = r->obs_self_t;
-  p.obs_self_v = r->obs_self_v;
-  p.obs_others = r->obs_others;
-  p.actions_prev = r->actions_prev;
-  p.goals = r->goals;
   p.probs = r->probs;
   p.actions = r->actions;
   p.onehot = r->onehot;
-  p.packed = (const float *)wt->packed;
-  hipStream_t s = (hipStream_t)stream;
-  if (r->obs_self_t_f64)
-    return r->goals_onehot ? ck_actor_rows_launch<true, true>(p, d->precision, s) : ck_actor_rows_launch<true, false>(p, d->precision, s);
-  return r->goals_onehot ? ck_actor_rows_launch<false, true>(p, d->precision, s) : ck_actor_rows_launch<false, false>(p, d->precision, s);
+  return ck_rows_launch(p, r->obs_self_t_f64 != 0, r->goals_onehot != 0, d->precision, (hipStream_t)stream);
 }
 #endif  // CM3_NO_ENTRY_POINTS

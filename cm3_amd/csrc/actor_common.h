@@ -1,5 +1,6 @@
 // Pieces shared by the particle actor (actor.hip, policy.hip) and the Checkers actor (actor_checkers.hip).
 #pragma once
+#include "agent_dispatch.h"
 #include "common.h"
 #include "philox.h"
 
@@ -7,6 +8,17 @@ namespace cm3 {
 
 constexpr int kA = 5;  // l_action
 constexpr uint32_t kPurposePolicy = 0x40000000u;
+
+// An entry point's launch by agent count: f(std::integral_constant<int, N>) for the N of the list that equals n_agents
+// (agent_dispatch.h), the entry points' one refusal otherwise -- fail() runs only on a miss.
+template <int... Ns, typename F> static int agent_launch(int n_agents, F &&f) {
+  bool hit;
+  const int rc = agent_dispatch<Ns...>(n_agents, hit, f);
+  return hit ? rc : fail(CM3_ERR_INVALID, "n_agents %d unsupported", n_agents);
+}
+template <typename F> static int agent_launch_1_to_10(int n_agents, F &&f) {
+  return agent_launch<1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(n_agents, f);
+}
 
 // The matrix kernels are built for TWO waves per SIMD.  With that as the declared minimum occupancy the register budget is 256 and
 // the compiler's default selection keeps the matrix accumulators in architectural VGPRs (no v_accvgpr_read per value in the

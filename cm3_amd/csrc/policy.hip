@@ -660,15 +660,9 @@ template <int N> static int policy_launch(const PolicyParams &q, int prec, hipSt
 int policy_partial_launch(int n_agents, const PolicyParams &q, int prec, hipStream_t s);
 #ifdef CM3_POLICY_PARTIAL_TILES
 int policy_partial_launch(int n_agents, const PolicyParams &q, int prec, hipStream_t s) {
-  switch (n_agents) {
-    case 3: return policy_launch<3>(q, prec, s);
-    case 5: return policy_launch<5>(q, prec, s);
-    case 6: return policy_launch<6>(q, prec, s);
-    case 7: return policy_launch<7>(q, prec, s);
-    case 9: return policy_launch<9>(q, prec, s);
-    case 10: return policy_launch<10>(q, prec, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d has no padded-tile build", n_agents);
+  bool hit;
+  const int rc = agent_dispatch<3, 5, 6, 7, 9, 10>(n_agents, hit, [&](auto n) { return policy_launch<n()>(q, prec, s); });
+  return hit ? rc : fail(CM3_ERR_INVALID, "n_agents %d has no padded-tile build", n_agents);
 }
 #endif
 
@@ -784,12 +778,9 @@ static int policy_rollout_call(const cm3_particle_desc *d, const cm3_particle_tr
   hipStream_t s = (hipStream_t)stream;
   CM3_REQUIRE(ad->precision >= 0 && ad->precision <= 2, "precision must be 0, 1 or 2");
   const int bf16 = ad->precision;
-  switch (d->n_agents) {
-    case 1: return policy_launch<1>(q, bf16, s);
-    case 2: return policy_launch<2>(q, bf16, s);
-    case 4: return policy_launch<4>(q, bf16, s);
-    case 8: return policy_launch<8>(q, bf16, s);
-  }
+  bool hit;
+  rc = agent_dispatch<1, 2, 4, 8>(d->n_agents, hit, [&](auto n) { return policy_launch<n()>(q, bf16, s); });
+  if (hit) return rc;
   if constexpr (kPadded) return policy_partial_launch(d->n_agents, q, bf16, s);   // 3, 5, 6, 7, 9, 10: their own translation unit
   return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
 }
@@ -827,13 +818,7 @@ extern "C" int cm3_policy_rollout_qmix_f32(const cm3_particle_desc *d, const cm3
   q.eps = ad->epsilon;
   q.eps_dev = epsilon_dev;
   hipStream_t s = (hipStream_t)stream;
-  switch (d->n_agents) {
-    case 1: return policy_qmix_launch<1>(q, s);
-    case 2: return policy_qmix_launch<2>(q, s);
-    case 4: return policy_qmix_launch<4>(q, s);
-    case 8: return policy_qmix_launch<8>(q, s);
-  }
-  return fail(CM3_ERR_INVALID, "n_agents %d unsupported", d->n_agents);
+  return agent_launch<1, 2, 4, 8>(d->n_agents, [&](auto n) { return policy_qmix_launch<n()>(q, s); });
 }
 #endif
 #ifdef CM3_PARTICLE_F64

@@ -160,6 +160,26 @@ def test_index_goals_need_no_alignment(built):
     _refused(built, b"misaligned outputs", rows=_rows(built, goals=FAKE + 1, onehot=FAKE + 8))
 
 
+@pytest.mark.parametrize("desc_kw,weights,rows_kw,needle", [
+    ({"n_agents": 0}, None, {}, b"n_agents"),
+    ({}, None, None, b"null weights"),
+    ({"precision": 3}, "default", None, b"null rows"),
+    ({"precision": 3, "stage": 0}, "default", {}, b"precision must be"),
+    ({"stage": 0, "epsilon": 1.5}, "default", {}, b"stage must be"),
+    ({"epsilon": 1.5}, "unpacked", {}, b"epsilon must be"),
+    ({}, "unpacked", {"goals": None}, b"weights->packed is NULL"),
+    ({}, "default", {"goals": None, "actions": None}, b"missing inputs"),
+    ({}, "default", {"actions": None, "n_rows": 0}, b"no output requested"),
+    ({}, "default", {"n_rows": 0, "goals_onehot": 2}, b"n_rows must be positive"),
+    ({}, "default", {"n_rows": 64 * (2 ** 31 - 1) + 1, "goals_onehot": 2}, b"more than a grid"),
+    ({}, "default", {"goals_onehot": 2, "obs_self_v": FAKE + 8}, b"form flags"),
+    ({}, "default", {"obs_self_v": FAKE + 8, "actions": FAKE + 2}, b"misaligned inputs")])
+def test_rows_checks_fire_in_their_order(built, desc_kw, weights, rows_kw, needle):
+    """Two consecutive checks violated at once: the earlier one's message is the one reported."""
+    w = {None: None, "default": _weights(built), "unpacked": _weights(built, packed=None)}[weights]
+    _refused(built, needle, desc=_desc(built, **desc_kw), weights=w, rows=None if rows_kw is None else _rows(built, **rows_kw))
+
+
 def test_the_actor_has_the_rows_methods():
     from cm3_amd.actor import CheckersActor
     for name in ("enqueue_rows", "probs_rows", "sample_rows", "soft_update_from"):

@@ -134,6 +134,24 @@ def test_rows_misaligned_pointer_is_refused(built, name, value, needle):
     _refused(built, needle, rows=_rows(built, **{name: value}))
 
 
+@pytest.mark.parametrize("desc_kw,weights,rows_kw,needle", [
+    ({"n_h2": 32}, None, {}, b"64/128/64/5"),
+    ({}, None, None, b"null weights"),
+    ({"epsilon": 1.5}, "default", None, b"null rows"),
+    ({"epsilon": 1.5, "precision": 3}, "default", {}, b"epsilon must be"),
+    ({"precision": 3}, "unpacked", {}, b"precision must be"),
+    ({}, "unpacked", {"goals": None}, b"weights->packed is NULL"),
+    ({}, "default", {"goals": None, "actions": None}, b"missing inputs"),
+    ({}, "default", {"actions": None, "n_rows": 0}, b"no output requested"),
+    ({}, "default", {"n_rows": 0, "v_obs": FAKE + 4}, b"n_rows must be positive"),
+    ({}, "default", {"n_rows": 64 * (2 ** 31 - 1) + 1, "v_obs": FAKE + 4}, b"more than a grid"),
+    ({}, "default", {"v_obs": FAKE + 4, "onehot": FAKE + 8}, b"misaligned inputs")])
+def test_rows_checks_fire_in_their_order(built, desc_kw, weights, rows_kw, needle):
+    """Two consecutive checks violated at once: the earlier one's message is the one reported."""
+    w = {None: None, "default": _weights(built), "unpacked": _weights(built, packed=None)}[weights]
+    _refused(built, needle, desc=_desc(built, **desc_kw), weights=w, rows=None if rows_kw is None else _rows(built, **rows_kw))
+
+
 def test_the_actor_has_the_rows_methods():
     from cm3_amd.actor import ParticleActor
     for name in ("enqueue_rows", "probs_rows", "sample_rows", "soft_update_from"):

@@ -127,6 +127,18 @@ def test_pack_validates_before_launching(built):
     assert b"null desc" in handle.cm3_last_error()
 
 
+@pytest.mark.parametrize("entry", ["cm3_qmix_checkers_pack", "cm3_actor_checkers_pack"])
+@pytest.mark.parametrize("desc_kw,weights_kw,packed,needle", [
+    ({"n_obs": 1}, {}, None, b"n_obs"),
+    ({}, {"out_w": None}, None, b"null weights / packed buffer"),
+    ({}, {"out_w": None, "others_w": None}, FAKE, b"missing weights")])
+def test_pack_checks_fire_in_their_order(built, entry, desc_kw, weights_kw, packed, needle):
+    """Two consecutive checks violated at once, in both Checkers pack entries: the earlier one's message is the one reported."""
+    handle = built.lib()
+    assert getattr(handle, entry)(ctypes.byref(_desc(built, **desc_kw)), ctypes.byref(_weights(built, **weights_kw)), packed, None) == -1
+    assert needle in handle.cm3_last_error(), handle.cm3_last_error()
+
+
 def test_agent_refuses_a_cpu_device_and_bf16():
     from cm3_amd import Cm3Error
     from cm3_amd.qmix import CheckersQmixAgent

@@ -146,6 +146,24 @@ def test_index_goals_need_no_alignment(built):
     _refused(built, b"n_rows", rows=_rows(built, goals=FAKE + 1, n_rows=0))
 
 
+@pytest.mark.parametrize("desc_kw,weights,rows_kw,needle", [
+    ({"n_obs": 1, "precision": 1}, "default", {}, b"n_obs"),
+    ({"precision": 1}, None, {}, b"precision 0 (float32) or 2"),
+    ({}, None, None, b"null weights"),
+    ({}, "unpacked", None, b"weights->packed is NULL"),
+    ({}, "default", None, b"null rows"),
+    ({}, "default", {"goals": None, "argmax": None}, b"missing inputs"),
+    ({}, "default", {"argmax": None, "n_rows": 0}, b"no output requested"),
+    ({}, "default", {"n_rows": 0, "goals_onehot": 2}, b"n_rows must be positive"),
+    ({}, "default", {"n_rows": 64 * (2 ** 31 - 1) + 1, "goals_onehot": 2}, b"more than a grid"),
+    ({}, "default", {"goals_onehot": 2, "obs_self_v": FAKE + 8}, b"form flags"),
+    ({}, "default", {"obs_self_v": FAKE + 8, "argmax": FAKE + 2}, b"misaligned inputs")])
+def test_checks_fire_in_their_order(built, desc_kw, weights, rows_kw, needle):
+    """Two consecutive checks violated at once: the earlier one's message is the one reported."""
+    w = {None: None, "default": _weights(built), "unpacked": _weights(built, packed=None)}[weights]
+    _refused(built, needle, desc=_desc(built, **desc_kw), weights=w, rows=None if rows_kw is None else _rows(built, **rows_kw))
+
+
 def test_soft_update_and_greedy_rows_exist_on_the_agent():
     from cm3_amd.qmix import CheckersQmixAgent
     assert callable(CheckersQmixAgent.greedy_rows) and callable(CheckersQmixAgent.enqueue_rows)

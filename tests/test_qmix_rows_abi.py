@@ -120,6 +120,20 @@ def test_rows_misaligned_pointer_is_refused(built, name, value, needle):
     _refused(built, needle, rows=_rows(built, **{name: value}))
 
 
+@pytest.mark.parametrize("desc_kw,packed,rows_kw,needle", [
+    ({"n_h2": 32, "precision": 2}, FAKE, {}, b"64/64/5"),
+    ({"precision": 2}, None, {}, b"precision must be 0"),
+    ({}, None, None, b"packed weights are NULL"),
+    ({}, FAKE, {"goals": None, "argmax": None}, b"missing inputs"),
+    ({}, FAKE, {"argmax": None, "n_rows": 0}, b"no output requested"),
+    ({}, FAKE, {"n_rows": 0, "v_obs": FAKE + 4}, b"n_rows must be positive"),
+    ({}, FAKE, {"n_rows": 64 * (2 ** 31 - 1) + 1, "v_obs": FAKE + 4}, b"more than a grid"),
+    ({}, FAKE, {"v_obs": FAKE + 4, "onehot": FAKE + 8}, b"misaligned inputs")])
+def test_rows_checks_fire_in_their_order(built, desc_kw, packed, rows_kw, needle):
+    """Two consecutive checks violated at once: the earlier one's message is the one reported."""
+    _refused(built, needle, desc=_desc(built, **desc_kw), packed=packed, rows=None if rows_kw is None else _rows(built, **rows_kw))
+
+
 def test_td_target_validates_before_launching(built):
     handle = built.lib()
     fn = handle.cm3_qmix_td_target_f64

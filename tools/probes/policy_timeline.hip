@@ -51,7 +51,7 @@ int main(int argc, char **argv) {
   cm3_actor_particle_weights wt; float *q = w;
   wt.w_self = q; q += 6 * 64; wt.b_self = q; q += 64; wt.w_self_h2 = q; q += 64 * 64; wt.w_others = q; q += L * 128; wt.b_others = q; q += 128;
   wt.w_others_h2 = q; q += 128 * 64; wt.b_h2 = q; q += 64; wt.w_out = q; q += 64 * 5; wt.b_out = q;
-  void *packed; hipMalloc(&packed, cm3::packed_floats<4>() * sizeof(float)); wt.packed = packed;
+  void *packed; hipMalloc(&packed, cm3::PackLayout<4>::kTotal * sizeof(float)); wt.packed = packed;
   {  // (policy.hip compiles actor.hip without its entry points: the body of cm3_actor_particle_pack)
     cm3::ActorParams ap; memset(&ap, 0, sizeof(ap));
     ap.stage = ad.stage;
