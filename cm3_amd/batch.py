@@ -11,6 +11,8 @@ numpy=False)) with gathers / views, so a learner living on the GPU never pulls t
 Pure data movement: outputs are bit-identical to the reference's (tests/test_batch.py pins them to arrays produced
 by the REAL reference functions, tests/golden/batch_particle.npz).
 """
+import collections
+
 import torch
 
 
@@ -108,12 +110,120 @@ def particle_static_feeds_device(cols, l_action=5, out=None):
     return S
 
 
-def phase_static_feeds(cols_all, n_minibatches, l_action=5):
+TileSpec = collections.namedtuple("TileSpec", "name src rows epr dtype kind terms others shape")
+TileSpec.__doc__ = """One output of cm3_rows_tile: `name` [shape, default (rows, epr)] of `dtype`, destination row r <- row f(r) of column `src`
+(None: no source), f from the two (divisor, modulus, multiplier) `terms` or, when given, the `others` triple (N, divq, divn) of the
+reference's `np.arange(N) != n` selections (include/cm3_amd.h, cm3_tile_col); `kind` one of _lib.TILE_*."""
+
+
+def checkers_static_feed_specs(shapes, goals_dtype=torch.int64, l_action=5):
+    """The outputs of checkers_static_feeds_device as a list of TileSpec, from the shapes alone (no device, no library): shapes maps
+    grid, vec, obs_self_t, obs_self_v and goals to the shapes of those columns of CheckersRollout.as_reference_batch -- [B, R, C + 1, 2],
+    [B, N, 4], [B, N, K, K, 3], [B, N, 4], [B, N, 2]; the next_* columns have the shapes of their twins.  Source names are column names;
+    "actions" / "actions_prev" stand for the flat int32 actions, "done" for its bytes.  Three groups, in the order of train_step
+    (alg_credit_checkers.py:536-780): per agent row (B N rows), the credit repeats (B N N), the counterfactual tiling (B N N l_action)."""
+    from . import _lib
+    COPY, ONE_I, ONE_F, EYE, NOT = _lib.TILE_COPY, _lib.TILE_ONEHOT_I64, _lib.TILE_ONEHOT_F64, _lib.TILE_EYE_F64, _lib.TILE_NOT_I64
+    B, N, lv = (int(v) for v in shapes["vec"])
+    g_sh, t_sh, v_sh = tuple(shapes["grid"][1:]), tuple(shapes["obs_self_t"][2:]), tuple(shapes["obs_self_v"][2:])
+    count = lambda sh: int(torch.Size(sh).numel())                          # noqa: E731
+    ne, nt, nv, lg = count(g_sh), count(t_sh), count(v_sh), int(shapes["goals"][2])
+    A, R = int(l_action), B * N
+    f64, i64 = torch.float64, torch.int64
+    ident = ((1, 0, 1), (1, 0, 0))
+    by_n = lambda outer=1: ((outer * N * N, 0, N), (outer, N, 1))          # noqa: E731  rows (b, m, n[, a]) <- row b N + n
+    by_m = lambda outer=1: ((outer * N, 0, 1), (1, 0, 0))                   # noqa: E731  rows (r, m[, a])    <- row r
+    by_b = lambda per: ((per, 0, 1), (1, 0, 0))                             # noqa: E731  `per` rows per time step <- row b
+    oth = lambda per, inner: (N, per * (N - 1), inner * (N - 1))            # noqa: E731  `per` rows per time step, n varies every `inner`
+    T = TileSpec
+    specs = [
+        # ---- per agent row: process_batch (:414-482), process_global_state (:510-535), not_done (:560) ----
+        T("state_env", "grid", R, ne, f64, COPY, by_b(N), None, (R,) + g_sh),
+        T("state_env_next", "next_grid", R, ne, f64, COPY, by_b(N), None, (R,) + g_sh),
+        T("a1", "actions", R, A, i64, ONE_I, ident, None, None),
+        T("ao", "actions", R * (N - 1), A, f64, ONE_F, None, oth(N, 1), (R, N - 1, A)),
+        T("prev1", "actions_prev", R, A, i64, ONE_I, ident, None, None),
+        T("done_rep", "done", R, 1, torch.bool, COPY, by_b(N), None, (R,)),
+        T("not_done", "done", R, 1, i64, NOT, by_b(N), None, (R,)),
+        T("others", "vec", R * (N - 1), lv, f64, COPY, None, oth(N, 1), (R, (N - 1) * lv)),
+        T("others_next", "next_vec", R * (N - 1), lv, f64, COPY, None, oth(N, 1), (R, (N - 1) * lv)),
+        # ---- the n x n credit repeats (:590-660): things indexed by n repeat per block, things indexed by m row by row ----
+        T("goals_self_rep", "goals", R * N, lg, goals_dtype, COPY, by_n(), None, None),
+        T("one_next_rep_n", "next_vec", R * N, lv, f64, COPY, by_n(), None, None),
+        T("one_next_rep_m", "next_vec", R * N, lv, f64, COPY, by_m(), None, None),
+        T("others_next_rep_n", "next_vec", R * N * (N - 1), lv, f64, COPY, None, oth(N * N, 1), (R * N, (N - 1) * lv)),
+        T("r_rep", "local_rewards", R * N, 1, f64, COPY, by_n(), None, (R * N,)),
+        T("nd_rep", "done", R * N, 1, i64, NOT, by_b(N * N), None, (R * N,)),
+        T("s_n_rep", "vec", R * N, lv, f64, COPY, by_n(), None, None),
+        T("s_m_rep", "vec", R * N, lv, f64, COPY, by_m(), None, None),
+        T("s_others_rep", "vec", R * N * (N - 1), lv, f64, COPY, None, oth(N * N, 1), (R * N, (N - 1) * lv)),
+        T("a1_rep_m", "actions", R * N, A, i64, ONE_I, by_m(), None, None),
+        T("env_next_rep", "next_grid", R * N, ne, f64, COPY, by_b(N * N), None, (R * N,) + g_sh),
+        T("ot_next_rep", "next_obs_self_t", R * N, nt, f64, COPY, by_m(), None, (R * N,) + t_sh),
+        T("ov_next_rep", "next_obs_self_v", R * N, nv, f64, COPY, by_m(), None, (R * N,) + v_sh),
+        T("env_rep", "grid", R * N, ne, f64, COPY, by_b(N * N), None, (R * N,) + g_sh),
+        T("ot_rep", "obs_self_t", R * N, nt, f64, COPY, by_m(), None, (R * N,) + t_sh),
+        T("ov_rep", "obs_self_v", R * N, nv, f64, COPY, by_m(), None, (R * N,) + v_sh),
+        # ---- the n x n x l_action counterfactual tiling (:700-760): each of the above repeated l_action times ----
+        T("cf_s_n", "vec", R * N * A, lv, f64, COPY, by_n(A), None, None),
+        T("cf_goals", "goals", R * N * A, lg, goals_dtype, COPY, by_n(A), None, None),
+        T("cf_eye", None, R * N * A, A, f64, EYE, ident, None, None),
+        T("cf_s_m", "vec", R * N * A, lv, f64, COPY, by_m(A), None, None),
+        T("cf_s_others", "vec", R * N * A * (N - 1), lv, f64, COPY, None, oth(N * N * A, A), (R * N * A, (N - 1) * lv)),
+        T("cf_env", "grid", R * N * A, ne, f64, COPY, by_b(N * N * A), None, (R * N * A,) + g_sh),
+        T("cf_ot", "obs_self_t", R * N * A, nt, f64, COPY, by_m(A), None, (R * N * A,) + t_sh),
+        T("cf_ov", "obs_self_v", R * N * A, nv, f64, COPY, by_m(A), None, (R * N * A,) + v_sh),
+    ]
+    return specs
+
+
+_CHECKERS_WIDE = ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "reward", "local_rewards", "next_grid", "next_vec",
+                  "next_obs_others", "next_obs_self_t", "next_obs_self_v")
+
+
+def checkers_static_feeds_apply(cols):
+    """Whether checkers_static_feeds_device takes these columns: all on the GPU and contiguous, the wide ones float64, more than one
+    agent, goals of a width the copy kernel moves (1, 4 or 8 bytes per element)."""
+    vec = cols["vec"]
+    return (vec.is_cuda and vec.dim() == 3 and vec.shape[1] > 1 and all(v.is_cuda and v.is_contiguous() for v in cols.values())
+            and all(cols[n].dtype == torch.float64 for n in _CHECKERS_WIDE) and cols["goals"].element_size() in (1, 4, 8)
+            and cols["done"].dtype in (torch.bool, torch.uint8) and not cols["actions"].dtype.is_floating_point
+            and not cols["actions_prev"].dtype.is_floating_point)
+
+
+def checkers_static_feeds_device(cols, l_action=5, out=None):
+    """The Checkers twin of particle_static_feeds_device: every feed of alg_credit_checkers.train_step (:536-780; N > 1, Q-credit
+    variant) that does not depend on a network output, from the 16 device columns of CheckersRollout.as_reference_batch(numpy=False)
+    (wide columns float64, actions any integer type, goals as they come, done bool) -- the 33 outputs of checkers_static_feed_specs
+    in THREE launches of cm3_rows_tile; the 432-byte grid rows and the 600-byte window rows take its row-granular path.  Values,
+    shapes and dtypes are those of the torch composition in train_step_feeds (tests/test_gpu_checkers_static_feeds.py compares the
+    two and both with the arrays the REAL train_step fed).  out: the dict an earlier call returned for the same batch size."""
+    if not checkers_static_feeds_apply(cols):
+        raise ValueError("checkers_static_feeds_device takes contiguous device columns, float64 wide ones, more than one agent "
+                         "(checkers_static_feeds_apply); the torch composition of train_step_feeds covers the rest")
+    src = dict(cols)
+    for name in ("actions", "actions_prev"):
+        src[name] = cols[name].reshape(-1).to(torch.int32).contiguous()
+    done = cols["done"]
+    src["done"] = done.view(torch.uint8) if done.dtype == torch.bool else done
+    t = _Tiler(cols["vec"].device)
+    S, O = {}, (out or {})
+    for s in checkers_static_feed_specs({n: tuple(v.shape) for n, v in cols.items()}, cols["goals"].dtype, l_action):
+        S[s.name] = t.add(None if s.src is None else src[s.src], s.rows, s.epr, s.dtype, s.kind, terms=s.terms, others=s.others,
+                          shape=s.shape, out=O.get(s.name))
+    t.run()
+    return S
+
+
+def phase_static_feeds(cols_all, n_minibatches, l_action=5, env="particle"):
     """The static feeds of EVERY minibatch of an on-policy phase (train_onpolicy.py:359-377: 24 minibatches of 128) from the phase's
     one export (ParticleRollout.on_policy_phase: columns [n_minibatches * batch_size, ...]) -- ONE pair of cm3_rows_tile launches;
     returns a list of per-minibatch dicts of VIEWS (every feed is transition-major, so a minibatch is a contiguous block of rows).
-    Round 5 built them per minibatch: 24 x 0.09 ms of launch latency for 0.13 ms of work."""
-    S = particle_static_feeds_device(cols_all, l_action)
+    Round 5 built them per minibatch: 24 x 0.09 ms of launch latency for 0.13 ms of work.  env="checkers": the same over the export
+    of CheckersRollout.on_policy_phase, from checkers_static_feeds_device (three launches)."""
+    if env not in ("particle", "checkers"):
+        raise ValueError("phase_static_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
+    S = checkers_static_feeds_device(cols_all, l_action) if env == "checkers" else particle_static_feeds_device(cols_all, l_action)
     M = int(n_minibatches)
     out = []
     for k in range(M):
@@ -139,7 +249,11 @@ class OnPolicyPhasePlan(object):
     into tensors of its own that it keeps) -- and returns the same list of (ops, feed) with this phase's values in the same tensors.
     `run` is CALLED only while a graph is captured (the first step(k) of each k): it must not synchronise or allocate per call what
     it does not keep.  Without graphs (use_graph=False) step(k) simply calls train_step_feeds: the specification the replay is
-    tested against (tests/test_batch.py::test_phase_plan_replays_equal_eager_feeds)."""
+    tested against (tests/test_batch.py::test_phase_plan_replays_equal_eager_feeds).
+
+    rollout: a ParticleRollout (float32) or a CheckersRollout -- refresh() then tiles with checkers_static_feeds_device (three
+    launches) and step(k) captures train_step_feeds(..., env="checkers", static=...); self.env names which.  Device actors are not
+    taken: the rows sampling stream gets a per-launch counter from the host, which a replay would freeze."""
 
     def __init__(self, rollout, run, gamma, epsilon, epochs=24, batch_size=128, l_action=5, use_graph=True):
         self.ro, self.run, self.gamma, self.epsilon = rollout, run, float(gamma), float(epsilon)
@@ -151,10 +265,16 @@ class OnPolicyPhasePlan(object):
     def refresh(self, generator=None):
         first = self.cols is None
         self.cols, self.k = self.ro._phase_export(self.epochs, self.batch_size, generator, out=self.cols)
-        vg = self.cols["v_global"]
-        if not (vg.is_cuda and vg.dtype == torch.float32 and vg.shape[1] > 1):
-            raise ValueError("OnPolicyPhasePlan covers float32 device rollouts with more than one agent (the tiling kernels' case)")
-        self.static = particle_static_feeds_device(self.cols, self.l_action, out=self.static)
+        self.env = "checkers" if "vec" in self.cols else "particle"         # (a CheckersRollout exports the 16 Checkers columns)
+        if self.env == "checkers":
+            if not checkers_static_feeds_apply(self.cols):
+                raise ValueError("OnPolicyPhasePlan covers Checkers device rollouts with more than one agent (the tiling kernels' case)")
+            self.static = checkers_static_feeds_device(self.cols, self.l_action, out=self.static)
+        else:
+            vg = self.cols["v_global"]
+            if not (vg.is_cuda and vg.dtype == torch.float32 and vg.shape[1] > 1):
+                raise ValueError("OnPolicyPhasePlan covers float32 device rollouts with more than one agent (the tiling kernels' case)")
+            self.static = particle_static_feeds_device(self.cols, self.l_action, out=self.static)
         if first:
             M, k = self.epochs, self.k
             self._mb = [({n: v[m * k:(m + 1) * k] for n, v in self.cols.items()},
@@ -169,18 +289,18 @@ class OnPolicyPhasePlan(object):
         from . import _lib
         cols, static = self._mb[k]
         if not self.use_graph:
-            return train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static)
-        dev = cols["v_global"].device
+            return train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env)
+        dev = next(iter(cols.values())).device
         if k not in self._graphs:
             # once eagerly (the allocator then holds blocks of every size the capture will ask for), then captured; the tensors the
             # captured pass created are KEPT (self._calls): a replay writes to their addresses
-            train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static)
+            train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env)
             torch.cuda.synchronize(dev)
             box = {}
 
             def enqueue(stream):
                 with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                    box["calls"] = train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static)
+                    box["calls"] = train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env)
             self._graphs[k] = _lib.capture_graph(dev, enqueue)
             self._calls[k] = box["calls"]
         _lib.check(_lib.lib().cm3_graph_launch(self._graphs[k], torch.cuda.current_stream(dev).cuda_stream))
@@ -330,7 +450,9 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     for optimiser ops).  Returns the list of (ops, feed) in call order.  Pure gathers / repeats plus the float64 TD
     arithmetic: bit-identical to the arrays the REAL train_step feeds (tests/golden/trainstep_*.npz, recorded by
     oracle/gen_golden_trainstep.py from the reference code itself under a recording session).
-    static: this minibatch's entry of phase_static_feeds() -- the static feeds then cost no launch here.
+    static: this minibatch's entry of phase_static_feeds() -- the static feeds then cost no launch here.  Both envs: float32 particle
+    columns (particle_static_feeds_device, two launches) and float64 Checkers columns (checkers_static_feeds_device, three) on the GPU
+    take the tiling kernel by default; device_tiling=False, host tensors, N = 1 and the variants without Q-credit the composition.
 
     target_actor / actor (CUDA columns): device actors holding the Policy_target / Policy_main weights -- ParticleActors for the
     particle env, CheckersActors for env="checkers" (an actor of the other env's class is refused).  With target_actor, `run` is NOT
@@ -359,9 +481,23 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         return run(ops, feed) if launch else None
 
     if checkers:
-        (n_steps, state_env, state_agents, obs_others, obs_self_t, obs_self_v, actions_prev_1hot, actions_1hot,
-         actions_others_1hot, reward, reward_local, state_env_next, state_agents_next, obs_others_next, obs_self_t_next,
-         obs_self_v_next, done, goals) = process_batch_checkers(cols, l_action)
+        # float64 columns on the GPU: the static feeds come from three launches of cm3_rows_tile (checkers_static_feeds_device); host
+        # tensors, N = 1 and the variants without Q-credit go through the torch composition -- the specification, as for particle
+        S = static if static is not None else (
+            checkers_static_feeds_device(cols, l_action) if (use_Q_credit and device_tiling and checkers_static_feeds_apply(cols)) else None)
+        if S is not None:
+            B_, N_ = cols["vec"].shape[0], cols["vec"].shape[1]
+            rows = lambda x: x.reshape(B_ * N_, *x.shape[2:])            # noqa: E731
+            (n_steps, state_env, state_agents, obs_others, obs_self_t, obs_self_v, actions_prev_1hot, actions_1hot,
+             actions_others_1hot, reward, reward_local, state_env_next, state_agents_next, obs_others_next, obs_self_t_next,
+             obs_self_v_next, done, goals) = (
+                B_, S["state_env"], cols["vec"], rows(cols["obs_others"]), rows(cols["obs_self_t"]), rows(cols["obs_self_v"]), S["prev1"],
+                S["a1"], S["ao"], cols["reward"], cols["local_rewards"].reshape(B_ * N_), S["state_env_next"], cols["next_vec"],
+                rows(cols["next_obs_others"]), rows(cols["next_obs_self_t"]), rows(cols["next_obs_self_v"]), S["done_rep"], cols["goals"])
+        else:
+            (n_steps, state_env, state_agents, obs_others, obs_self_t, obs_self_v, actions_prev_1hot, actions_1hot,
+             actions_others_1hot, reward, reward_local, state_env_next, state_agents_next, obs_others_next, obs_self_t_next,
+             obs_self_v_next, done, goals) = process_batch_checkers(cols, l_action)
         v_global, v_global_next = state_agents, state_agents_next
     else:
         vg0 = cols["v_global"]
@@ -381,8 +517,6 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         else:
             (n_steps, v_global, obs_others, v_local, actions_1hot, actions_others_1hot, reward, reward_local, v_global_next,
              obs_others_next, v_local_next, done, goals) = process_batch(cols, l_action)
-    if checkers:
-        S = None
     N = v_global.shape[1]
     goals_self, _ = process_goals(goals) if S is None else (goals.reshape(-1, goals.shape[2]), None)
     if S is None:
@@ -447,7 +581,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                 "v_state_m": rep_m(one_next) if S is None else S["one_next_rep_m"],
                 "v_state_other_agents": _rep_n(others_next, N) if S is None else S["others_next_rep_n"]}
         if checkers:
-            feed = with_env(feed, rep_m(state_env_next), rep_m(obs_self_t_next), rep_m(obs_self_v_next))
+            feed = (with_env(feed, rep_m(state_env_next), rep_m(obs_self_t_next), rep_m(obs_self_v_next)) if S is None
+                    else with_env(feed, S["env_next_rep"], S["ot_next_rep"], S["ov_next_rep"]))
         qc_t = call(["Q_credit_target"], feed)[0]
         if S is None:
             r_rep = _rep_n(reward_local.reshape(-1, 1), N).reshape(-1)
@@ -461,7 +596,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                 "action_one": rep_m(actions_1hot) if S is None else S["a1_rep_m"], "v_state_m": s_m_rep,
                 "v_state_other_agents": s_others_rep}
         if checkers:
-            s_env_rep, ot_rep, ov_rep = rep_m(state_env), rep_m(obs_self_t), rep_m(obs_self_v)
+            s_env_rep, ot_rep, ov_rep = ((rep_m(state_env), rep_m(obs_self_t), rep_m(obs_self_v)) if S is None
+                                         else (S["env_rep"], S["ot_rep"], S["ov_rep"]))
             feed = with_env(feed, s_env_rep, ot_rep, ov_rep)
         call(["Q_credit_op"], feed)
     v_res_rep = None
@@ -504,7 +640,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
             feed = {"v_state_one_agent": S["cf_s_n"], "v_goal": S["cf_goals"], "action_one": S["cf_eye"], "v_state_m": S["cf_s_m"],
                     "v_state_other_agents": S["cf_s_others"]}
         if checkers:
-            feed = with_env(feed, rep_a(s_env_rep), rep_a(ot_rep), rep_a(ov_rep))
+            feed = (with_env(feed, rep_a(s_env_rep), rep_a(ot_rep), rep_a(ov_rep)) if S is None
+                    else with_env(feed, S["cf_env"], S["cf_ot"], S["cf_ov"]))
         q_cf = call(["Q_credit"], feed)[0].reshape(n_steps * N * N, l_action)
     else:
         probs = torch.zeros(1, l_action, dtype=f64, device=one.device)

@@ -697,7 +697,8 @@ template <typename I> __global__ void __launch_bounds__(256) k_ck_transitions_pa
 // (alg_credit.py:614-658 `np.repeat(np.reshape(x, [n_steps, n, d]), n, axis=0)` / `np.repeat(x, n, axis=0)`; :730-751 the same
 // repeated l_action times against np.tile(np.eye(l_action)); process_actions / process_global_state :406-443, :528-557 with their
 // `np.arange(N) != n` selections.)  Every output is "destination row r <- source row f(r)", f built from divisions and remainders of
-// r; up to 16 outputs per launch.
+// r; up to 16 outputs per launch.  The Checkers twin (alg_credit_checkers.py:536-780) repeats the same way rows of 432 and 600 bytes
+// (state_env, obs_self_t): those take the row-granular path below (tile_rows), narrow rows and the computed kinds the element loop.
 struct TileCol {
   void *dst;
   const void *src;
@@ -713,8 +714,75 @@ struct TileCols {
   TileCol c[kMaxRowCols];
 };
 
-template <typename I> __global__ void __launch_bounds__(256) k_rows_tile(const TileCols a) {
+// source row f(r) of destination row r, as the element loop of k_rows_tile forms it
+template <typename I> __device__ __forceinline__ I tile_src_row(const TileCol &c, I r) {
+  if (c.oth_n) {
+    const uint32_t k = (uint32_t)(r % (I)(c.oth_n - 1)), n = (uint32_t)((r / (I)c.oth_divn) % (I)c.oth_n);
+    return (r / (I)c.oth_divq) * (I)c.oth_n + k + (k >= n ? 1u : 0u);
+  }
+  I q0 = r / (I)c.div0, q1 = r / (I)c.div1;
+  if (c.mod0) q0 %= c.mod0;
+  if (c.mod1) q1 %= c.mod1;
+  return q0 * c.mul0 + q1 * c.mul1;
+}
+
+// The row-granular path of CM3_TILE_COPY columns with wide rows (Checkers: state_env 432 B, obs_self_t 600 B, repeated N, N^2 and
+// N^2 l_action times): a power-of-two group of lanes serves one destination row, f(r) is formed once per row instead of once per
+// 8-byte element, and every lane moves 16-byte units (8-byte ones where the row size is an odd number of 8-byte units: rows then
+// alternate between the two alignments).  Taken from kTileRowMinBytes per row, for rows of whole 8-byte units between 16-byte
+// aligned views; everything else -- narrower rows, an 8-byte aligned source view, other kinds -- stays on the element path below.
+// Block-uniform (blockIdx.y selects the column), plain stores (the networks read the feeds next).  The path lives in a build of the
+// kernel of its own, k_rows_tile<I, true>, which the launcher takes when a column of the launch qualifies: a launch without one (every
+// particle feed: rows of 16 .. 48 bytes) runs k_rows_tile<I, false>, the element loop alone -- with the row path compiled in, that
+// loop's launches were 0.3 us slower (profiles/r21_checkers_phase.txt, 4.).
+constexpr uint32_t kTileRowMinBytes = 64;   // row path from this many bytes per row (profiles/r21_checkers_phase.txt, 4.)
+// bytes per unit of the row path (16 / 8), 0: the element path
+__host__ __device__ __forceinline__ uint32_t tile_row_unit(const TileCol &c) {
+  const size_t rb = (size_t)c.epr * c.es;
+  if (c.kind != CM3_TILE_COPY || rb < kTileRowMinBytes || rb > 0x7fffffffu || (rb & 7u)) return 0;
+  if ((reinterpret_cast<uintptr_t>(c.dst) | reinterpret_cast<uintptr_t>(c.src)) & 15u) return 0;
+  return (rb & 15u) ? 8u : 16u;
+}
+// log2 of the lanes that serve one row of `units` units: about four units per lane (f(r) is then formed once per four units and a
+// wave holds several rows), at least one 128-byte line per group and pass, at most one wave
+__device__ __forceinline__ uint32_t tile_row_lanes_log2(uint32_t units, uint32_t unit_bytes) {
+  const uint32_t line = 128u / unit_bytes, least = units < line ? units : line, want = (units + 3u) / 4u;
+  const uint32_t v = want > least ? want : least;
+  const uint32_t lg = v <= 1u ? 0u : 32u - (uint32_t)__builtin_clz(v - 1u);
+  return lg > 6u ? 6u : lg;
+}
+template <typename I, typename V> __device__ __forceinline__ void tile_rows(const TileCol &c) {
+  const uint32_t rb = c.epr * c.es, units = rb / (uint32_t)sizeof(V), lg = tile_row_lanes_log2(units, (uint32_t)sizeof(V));
+  const uint32_t G = 1u << lg, lane = threadIdx.x & (G - 1u);
+  const I n_rows = (I)c.n_rows, stride = (I)(((size_t)gridDim.x * 256) >> lg);     // (n_rows <= elements: within the launcher's rule)
+  for (I r = (I)(((size_t)blockIdx.x * 256 + threadIdx.x) >> lg); r < n_rows; r += stride) {
+    const I s = tile_src_row<I>(c, r);
+    const V *sp = reinterpret_cast<const V *>(static_cast<const char *>(c.src) + (size_t)s * rb);
+    V *dp = reinterpret_cast<V *>(static_cast<char *>(c.dst) + (size_t)r * rb);
+    for (uint32_t u = lane; u < units; u += 4u * G) {       // four loads in flight per lane, then their stores
+      const uint32_t u1 = u + G, u2 = u + 2u * G, u3 = u + 3u * G;
+      V v0 = sp[u], v1 = v0, v2 = v0, v3 = v0;
+      if (u1 < units) v1 = sp[u1];
+      if (u2 < units) v2 = sp[u2];
+      if (u3 < units) v3 = sp[u3];
+      dp[u] = v0;
+      if (u1 < units) dp[u1] = v1;
+      if (u2 < units) dp[u2] = v2;
+      if (u3 < units) dp[u3] = v3;
+    }
+  }
+}
+
+template <typename I, bool ROWS> __global__ void __launch_bounds__(256) k_rows_tile(const TileCols a) {
   const TileCol &c = a.c[blockIdx.y];
+  if constexpr (ROWS) {
+    const uint32_t row_unit = tile_row_unit(c);
+    if (row_unit) {
+      if (row_unit == 16u) tile_rows<I, uint4>(c);
+      else tile_rows<I, uint2>(c);
+      return;
+    }
+  }
   const I total = (I)((size_t)c.n_rows * c.epr), stride = (I)((size_t)gridDim.x * blockDim.x);
   for (I g = (I)((size_t)blockIdx.x * blockDim.x + threadIdx.x); g < total; g += stride) {
     const I r = g / (I)c.epr;
@@ -1077,6 +1145,7 @@ int cm3_rows_tile(const cm3_tile_col *cols, int32_t n_cols, void *stream) {
   memset(&a, 0, sizeof(a));
   a.n = n_cols;
   size_t most = 0;
+  bool rows = false;      // a column of the launch takes the row-granular path
   for (int k = 0; k < n_cols; ++k) {
     const cm3_tile_col &q = cols[k];
     // (an EMPTY column may come with null pointers: torch.empty(0).data_ptr() is 0 -- ADVICE r5)
@@ -1099,13 +1168,16 @@ int cm3_rows_tile(const cm3_tile_col *cols, int32_t n_cols, void *stream) {
     c.oth_n = q.others_n; c.oth_divq = q.others_divq; c.oth_divn = q.others_divn;
     const size_t total = (size_t)q.n_rows * q.elems_per_row;
     most = total > most ? total : most;
+    rows = rows || (total != 0 && tile_row_unit(c) != 0);
   }
   if (most == 0) return CM3_OK;
   const size_t blocks = rows_tile_blocks(most);
-  if (rows_take_narrow(rows_stride_index_narrow(most, blocks)))
-    hipLaunchKernelGGL(k_rows_tile<uint32_t>, dim3((unsigned)blocks, (unsigned)n_cols), dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(k_rows_tile<size_t>, dim3((unsigned)blocks, (unsigned)n_cols), dim3(256), 0, (hipStream_t)stream, a);
+  const dim3 grid((unsigned)blocks, (unsigned)n_cols), block(256);
+  const bool narrow = rows_take_narrow(rows_stride_index_narrow(most, blocks));
+  if (narrow && rows) hipLaunchKernelGGL((k_rows_tile<uint32_t, true>), grid, block, 0, (hipStream_t)stream, a);
+  else if (narrow) hipLaunchKernelGGL((k_rows_tile<uint32_t, false>), grid, block, 0, (hipStream_t)stream, a);
+  else if (rows) hipLaunchKernelGGL((k_rows_tile<size_t, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_rows_tile<size_t, false>), grid, block, 0, (hipStream_t)stream, a);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }

@@ -5,7 +5,9 @@
 // a lane forms in the index type I stays below 2^32, else a build with I = size_t.  "Every value" is the last unit index PLUS what a
 // lane of the last workgroup adds to it before it finds out that it is past the end: the slack each rule leaves below 2^32.
 //   k_rows_copy<I>, k_rows_tile<I>        grid-stride loops of `blocks` workgroups of 256 lanes: a lane forms g + stride once past the
-//                                         end, stride = blocks * 256
+//                                         end, stride = blocks * 256 (the row-granular path of k_rows_tile strides over ROWS, at
+//                                         most as many as elements and with a smaller stride: inside the same rule; byte offsets
+//                                         there are formed in size_t, once per row)
 //   k_ck_transitions_gather<I>            kCkUnitsPerLane units per lane, 256 lanes apart: the last workgroup reaches up to
 //                                         kCkUnitsPerLane * 256 units past the end
 //   k_ck_transitions_pack<I>              byte offsets into a ring column, 16-byte pieces, kPkPiecesPerLane per lane; ring rows are

@@ -1397,6 +1397,20 @@ class CheckersRollout(_Transitions):
             goals=goals)
         return _to_numpy(cols) if numpy else cols
 
+    def on_policy_phase(self, epochs=24, batch_size=128, generator=None, l_action=5):
+        """The minibatches of on_policy_minibatches() TOGETHER WITH the static feeds of alg_credit_checkers.train_step for each of them
+        (cm3_amd.batch.phase_static_feeds(env="checkers"): process_batch / process_global_state, the n x n credit repeats, the
+        n x n x l_action counterfactual tiling of alg_credit_checkers.py:414-535, :590-760) -- for the whole phase one export launch and
+        three tiling launches; a list of (columns, static) pairs of views, static None where the tiling kernel does not apply (N = 1).
+        Feed them to cm3_amd.batch.train_step_feeds(columns, run, gamma, epsilon, env="checkers", static=static)."""
+        from . import batch as B
+        cols, k = self._phase_export(epochs, batch_size, generator)
+        if B.checkers_static_feeds_apply(cols):
+            statics = B.phase_static_feeds(cols, int(epochs), l_action, env="checkers")
+        else:
+            statics = [None] * int(epochs)
+        return [({name: v[m * k:(m + 1) * k] for name, v in cols.items()}, statics[m]) for m in range(int(epochs))]
+
     def episode_returns(self):
         v = self.valid.to(torch.float64)
         return (self.reward * v).sum(0), (self.local_rewards * v.unsqueeze(2)).sum(0)

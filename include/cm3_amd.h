@@ -1016,7 +1016,10 @@ int cm3_transitions_route_f32(const cm3_particle_desc *desc, const cm3_particle_
  *   others_n == 0:  f(r) = ((r / div[0]) % mod[0]) * mul[0] + ((r / div[1]) % mod[1]) * mul[1]      (mod 0 = no remainder taken)
  *   others_n == N:  f(r) = (r / others_divq) * N + j,  j = k + (k >= n),  k = r % (N - 1),  n = (r / others_divn) % N
  *                   (the reference's `x[:, np.arange(N) != n]` selections, whatever repeats sit around them)
- * and what is written per element depends on `kind`.  Up to 16 columns in ONE launch. */
+ * and what is written per element depends on `kind`.  Up to 16 columns in ONE launch.  CM3_TILE_COPY columns with rows of at least
+ * 64 bytes in whole 8-byte units, between 16-byte aligned dst and src, are moved row by row (a group of lanes per row, f(r) once per
+ * row, 16-byte units; 8-byte units where the row size is no multiple of 16: the Checkers feeds, 432 and 600 bytes per row); every
+ * other column element by element.  Same results either way. */
 #define CM3_TILE_COPY 0         /* elements of elem_bytes (1, 4, 8) copied */
 #define CM3_TILE_F32_TO_F64 1   /* float -> double (the reference's float64 np.zeros targets) */
 #define CM3_TILE_ONEHOT_I64 2   /* source rows are ONE int32 each; destination rows elems_per_row int64: 1 at the value's index */
