@@ -245,6 +245,8 @@ SYMBOLS = {
     "cm3_actor_particle_f32": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorParticleBufs),
                                               c_void_p]),
     "cm3_actor_particle_rows_f32": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorRows), c_void_p]),
+    "cm3_actor_particle_rows_counted_f32": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorRows), c_void_p,
+                                                           c_void_p]),
     "cm3_policy_rollout_f32": (ctypes.c_int, [P(ParticleDesc), P(ParticleTraj), P(ActorParticleDesc),
                                               P(ActorParticleWeights), c_void_p, c_size_t, c_int32, c_void_p]),
     "cm3_actor_particle_f64": (ctypes.c_int, [P(ActorParticleDesc), P(ActorParticleWeights), P(ActorParticleBufs),
@@ -291,6 +293,8 @@ SYMBOLS = {
     "cm3_actor_checkers_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersBufs),
                                               c_void_p]),
     "cm3_actor_checkers_rows_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersRows), c_void_p]),
+    "cm3_actor_checkers_rows_counted_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersRows),
+                                                           c_void_p, c_void_p]),
     "cm3_qmix_checkers_pack": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), c_void_p, c_void_p]),
     "cm3_qmix_checkers_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(ActorCheckersBufs), c_void_p]),
     "cm3_qmix_checkers_rows_f32": (ctypes.c_int, [P(ActorCheckersDesc), P(ActorCheckersWeights), P(QmixCheckersRows), c_void_p]),

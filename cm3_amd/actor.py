@@ -35,6 +35,50 @@ def _epsilon_args(epsilon):
         return 0.0, epsilon.data_ptr()
     return float(epsilon), 0
 
+
+class RowsDrawCounter(object):
+    """The draw counter of the rows sampling stream IN DEVICE MEMORY: two uint32 words {draw, arrivals} that a counted launch
+    (cm3_actor_particle_rows_counted_f32 / cm3_actor_checkers_rows_counted_f32) reads and advances itself -- what
+    ``sample_rows(..., draw=counter)`` takes, so that the launch can be captured into a hipGraph and still draw afresh on every
+    replay.  One counter may serve any number of actors; the launches that share it must be ordered on the device (one stream, or
+    the dependencies of one graph)."""
+
+    def __init__(self, device, start=0):
+        self.device = _lib.require_gpu(device)
+        # (int32 storage: the launch reads the same 32 bits)
+        self.state = torch.zeros(2, dtype=torch.int32, device=self.device)
+        if self.state.data_ptr() % 8:
+            raise Cm3Error("RowsDrawCounter: the allocator returned a tensor that is not 8-byte aligned")
+        self.set(start)
+
+    @staticmethod
+    def _signed(v):
+        v = int(v) & 0xFFFFFFFF
+        return v - (1 << 32) if v >= (1 << 31) else v
+
+    def set(self, v):
+        """draw <- v (mod 2^32), arrivals <- 0, in stream order."""
+        self.state.copy_(torch.tensor([self._signed(v), 0], dtype=torch.int32), non_blocking=False)
+        return self
+
+    def value(self):
+        """The draw the NEXT counted launch will use (a synchronising read)."""
+        return int(self.state[0].item()) & 0xFFFFFFFF
+
+    def arrivals(self):
+        """The ticket word (a synchronising read): 0 between launches."""
+        return int(self.state[1].item()) & 0xFFFFFFFF
+
+    def data_ptr(self):
+        return self.state.data_ptr()
+
+
+def _keep(keep, *tensors):
+    """Appends the tensors a launch touches to the caller's keep list (None: nobody captures, nothing to do)."""
+    if keep is not None:
+        keep.extend(t for t in tensors if t is not None)
+
+
 def _actor_entry(lib, dtype):
     """cm3_actor_particle_f32 / _f64 by the real of the env buffers the launch reads."""
     if dtype == torch.float32:
@@ -149,15 +193,22 @@ class ParticleActor(object):
                      stream=None):
         """Raw launch of cm3_actor_particle_rows_f32 on contiguous float32 device tensors; every output is optional, one is
         required.  epsilon: a float, or a one-element float32 device tensor the launch reads itself.  (seed, row_id_base + row,
-        draw) key the row's uniform; nothing is drawn when actions and onehot are both None."""
+        draw) key the row's uniform; nothing is drawn when actions and onehot are both None.  draw: an integer, or a
+        RowsDrawCounter -- then the launch is cm3_actor_particle_rows_counted_f32, which reads the counter's device word and
+        advances it itself."""
         r = _lib.ActorRows()
         r.obs_others, r.v_obs, r.goals = _lib.ptr(obs_others), _lib.ptr(v_obs), _lib.ptr(goals)
         r.probs, r.actions, r.onehot = _lib.ptr(probs), _lib.ptr(actions), _lib.ptr(onehot)
         epsilon, r.epsilon_dev = _epsilon_args(epsilon)
-        r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base), int(draw) & 0xFFFFFFFF
+        counter = draw if isinstance(draw, RowsDrawCounter) else None
+        r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base), 0 if counter is not None else int(draw) & 0xFFFFFFFF
         d = self._desc(1, epsilon, 0)
         s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_actor_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+        if counter is not None:
+            _lib.check(self._lib.cm3_actor_particle_rows_counted_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r),
+                                                                     counter.data_ptr(), s))
+        else:
+            _lib.check(self._lib.cm3_actor_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
 
     def _stage_rows(self, what, obs_others, v_obs, goals):
         """(rows, obs_others, v_obs, goals) contiguous float32 on the actor's device from [..., L], [..., 4], [..., 2] with equal
@@ -173,22 +224,26 @@ class ParticleActor(object):
         stage = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
         return rows, stage(obs_others), stage(v_obs), stage(goals)
 
-    def probs_rows(self, obs_others, v_obs, goals, epsilon):
+    def probs_rows(self, obs_others, v_obs, goals, epsilon, keep=None):
         """The mixed probabilities float32 [R, 5] over the R = prod(leading shape) rows, ONE launch: the reference's
         sess.run(self.probs, ...) of train_step (alg_credit.py:121, fetched at :708 / :729) on the columns obs_others / v_local /
-        goals of a sampled batch.  Nothing is drawn.  A row's probabilities are the bits act() computes for the same inputs."""
+        goals of a sampled batch.  Nothing is drawn.  A row's probabilities are the bits act() computes for the same inputs.
+        keep: an optional list that receives every tensor this call allocated and the launch touches (the output, the staged
+        inputs) -- whoever captures the launch into a hipGraph holds them for as long as the graph is replayed."""
         rows, oo, vo, vg = self._stage_rows("probs_rows", obs_others, v_obs, goals)
         probs = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        _keep(keep, oo, vo, vg, probs)
         self.enqueue_rows(rows, oo, vo, vg, epsilon, probs=probs)
         return probs
 
-    def sample_rows(self, obs_others, v_obs, goals, epsilon, probs=False, onehot=False, draw=None):
+    def sample_rows(self, obs_others, v_obs, goals, epsilon, probs=False, onehot=False, draw=None, keep=None):
         """Actions sampled from the mixed probabilities over transition rows, ONE launch: with the Policy_target weights this is
         action_samples_target of train_step (alg_credit.py:128, run_actor_target :272-287) on obs_others_next / v_local_next /
         goals.  Returns a dict of device tensors: "actions" int32 [R] always; "probs" float32 [R, 5] and "onehot" int64 [R, 5] when
         asked for.  The uniforms are the build's own rows stream keyed (seed, row, draw): draw=None takes the actor's counter
         self.rows_draw and advances it, so successive calls draw afresh; an explicit draw reproduces a call (and leaves the
-        counter alone)."""
+        counter alone); a RowsDrawCounter makes the launch read and advance that counter on the device (capturable: every
+        replay draws afresh; self.rows_draw is left alone).  keep: as probs_rows."""
         rows, oo, vo, vg = self._stage_rows("sample_rows", obs_others, v_obs, goals)
         out = {"actions": torch.empty(rows, dtype=torch.int32, device=self.device)}
         if probs:
@@ -197,6 +252,7 @@ class ParticleActor(object):
             out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
         if draw is None:
             draw, self.rows_draw = self.rows_draw, (self.rows_draw + 1) & 0xFFFFFFFF
+        _keep(keep, oo, vo, vg, *out.values())
         self.enqueue_rows(rows, oo, vo, vg, epsilon, draw=draw, **out)
         return out
 
@@ -379,7 +435,8 @@ class CheckersActor(object):
         """Raw launch of cm3_actor_checkers_rows_f32 on contiguous device tensors: obs_self_t int8 or float64 [R, 75], obs_self_v /
         obs_others float64, actions_prev int32 [R], goals uint8 [R] or int64 [R, 2]; every output is optional, one is required.
         epsilon: a float, or a one-element float32 device tensor the launch reads itself.  (seed, row_id_base + row, draw) key the
-        row's uniform; nothing is drawn when actions and onehot are both None."""
+        row's uniform; nothing is drawn when actions and onehot are both None.  draw: an integer, or a RowsDrawCounter -- then the
+        launch is cm3_actor_checkers_rows_counted_f32, which reads the counter's device word and advances it itself."""
         if obs_self_t.dtype not in (torch.int8, torch.float64) or goals.dtype not in (torch.uint8, torch.int64):
             raise Cm3Error("enqueue_rows reads int8 or float64 windows and uint8 index or int64 one-hot goals, not %s / %s"
                            % (obs_self_t.dtype, goals.dtype))
@@ -390,31 +447,41 @@ class CheckersActor(object):
         r.goals_onehot = 1 if goals.dtype == torch.int64 else 0
         r.probs, r.actions, r.onehot = _lib.ptr(probs), _lib.ptr(actions), _lib.ptr(onehot)
         epsilon, r.epsilon_dev = _epsilon_args(epsilon)
-        r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF
+        counter = draw if isinstance(draw, RowsDrawCounter) else None
+        r.n_rows, r.row_id_base = int(n_rows), int(row_id_base) & 0xFFFFFFFFFFFFFFFF
+        r.draw = 0 if counter is not None else int(draw) & 0xFFFFFFFF
         d = self._desc(1, epsilon, 0, 75 * self.n)
         s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_actor_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+        if counter is not None:
+            _lib.check(self._lib.cm3_actor_checkers_rows_counted_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r),
+                                                                     counter.data_ptr(), s))
+        else:
+            _lib.check(self._lib.cm3_actor_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
 
-    def probs_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon):
+    def probs_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon, keep=None):
         """The mixed probabilities float32 [R, 5] over the R = prod(leading shape) rows, ONE launch: the reference's
         sess.run(self.probs, ...) of train_step (alg_credit_checkers.py:107-113) on the columns obs_self_t / obs_self_v / obs_others /
         actions_prev / goals of a sampled batch (input forms: stage_checkers_rows).  Nothing is drawn.  At precision "f16x3" float64
         windows must hold float16-exact values (the env's are -1 / 0 / 1).  A row's probabilities are the bits act() computes for
-        the same inputs at the same precision."""
+        the same inputs at the same precision.  keep: an optional list that receives every tensor this call allocated and the launch
+        touches (the output, the staged inputs) -- whoever captures the launch into a hipGraph holds them while it is replayed."""
         rows, ot, ov, oo, ap, vg = stage_checkers_rows("probs_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
                                                        actions_prev, goals)
         probs = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
+        _keep(keep, ot, ov, oo, ap, vg, probs)
         self.enqueue_rows(rows, ot, ov, oo, ap, vg, epsilon, probs=probs)
         return probs
 
-    def sample_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon, probs=False, onehot=False, draw=None):
+    def sample_rows(self, obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon, probs=False, onehot=False, draw=None,
+                    keep=None):
         """Actions sampled from the mixed probabilities over transition rows, ONE launch: with the Policy_target weights this is
         action_samples_target of train_step (alg_credit_checkers.py:117, run_actor_target :255-260, called at :551) on
         next_obs_self_t / next_obs_self_v / next_obs_others / actions / goals (the reference feeds the action just taken as
         actions_prev there).  Returns a dict of device tensors: "actions" int32 [R] always; "probs" float32 [R, 5] and "onehot" int64
         [R, 5] when asked for.  The uniforms are the build's own rows stream keyed (seed, row, draw): draw=None takes the actor's
         counter self.rows_draw and advances it, so successive calls draw afresh; an explicit draw reproduces a call (and leaves the
-        counter alone)."""
+        counter alone); a RowsDrawCounter makes the launch read and advance that counter on the device (capturable: every replay
+        draws afresh; self.rows_draw is left alone).  keep: as probs_rows."""
         rows, ot, ov, oo, ap, vg = stage_checkers_rows("sample_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
                                                        actions_prev, goals)
         out = {"actions": torch.empty(rows, dtype=torch.int32, device=self.device)}
@@ -424,6 +491,7 @@ class CheckersActor(object):
             out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
         if draw is None:
             draw, self.rows_draw = self.rows_draw, (self.rows_draw + 1) & 0xFFFFFFFF
+        _keep(keep, ot, ov, oo, ap, vg, *out.values())
         self.enqueue_rows(rows, ot, ov, oo, ap, vg, epsilon, draw=draw, **out)
         return out
 

@@ -252,15 +252,31 @@ class OnPolicyPhasePlan(object):
     tested against (tests/test_batch.py::test_phase_plan_replays_equal_eager_feeds).
 
     rollout: a ParticleRollout (float32) or a CheckersRollout -- refresh() then tiles with checkers_static_feeds_device (three
-    launches) and step(k) captures train_step_feeds(..., env="checkers", static=...); self.env names which.  Device actors are not
-    taken: the rows sampling stream gets a per-launch counter from the host, which a replay would freeze."""
+    launches) and step(k) captures train_step_feeds(..., env="checkers", static=...); self.env names which.
 
-    def __init__(self, rollout, run, gamma, epsilon, epochs=24, batch_size=128, l_action=5, use_graph=True):
+    target_actor / actor: the device actors of train_step_feeds (ParticleActors or CheckersActors holding the Policy_target /
+    Policy_main weights); their two rows launches are then part of the replayed graph and `run` is not called for
+    ["action_samples_target"] / ["probs"].  A host-side draw counter would be frozen into the capture, so the plan samples through a
+    cm3_amd.actor.RowsDrawCounter (draw_counter, or one of its own starting at 0; self.draw_counter): the captured launch reads the
+    counter word from device memory and advances it itself, one draw per step(k) -- replayed or not.  The eager pass that precedes a
+    capture consumes no draw (the counter is put back after it), so a graph plan and a use_graph=False plan that start from equal
+    counters produce equal feeds and hold equal counters after any sequence of step(k).  The launches read the actors' persistent
+    packed weights: ``target_actor.soft_update_from(actor, tau)`` between steps is seen by the next replay, as in eager mode.
+    Every tensor the actors' calls allocate for a captured launch is held next to the step's calls (self._keep[k]) for as long as
+    the graph lives.  Without actors nothing changes and no counter is made."""
+
+    def __init__(self, rollout, run, gamma, epsilon, epochs=24, batch_size=128, l_action=5, use_graph=True, target_actor=None,
+                 actor=None, draw_counter=None):
         self.ro, self.run, self.gamma, self.epsilon = rollout, run, float(gamma), float(epsilon)
         self.epochs, self.batch_size, self.l_action, self.use_graph = int(epochs), int(batch_size), int(l_action), bool(use_graph)
         self.cols = self.static = None
         self.k = 0
-        self._graphs, self._calls = {}, {}
+        self._graphs, self._calls, self._keep = {}, {}, {}
+        self.target_actor, self.actor = target_actor, actor
+        self.draw_counter = draw_counter
+        if self.draw_counter is None and target_actor is not None:
+            from .actor import RowsDrawCounter
+            self.draw_counter = RowsDrawCounter(target_actor.device)
 
     def refresh(self, generator=None):
         first = self.cols is None
@@ -285,24 +301,35 @@ class OnPolicyPhasePlan(object):
         """(columns, static feeds) of minibatch k: views of the persistent phase tensors"""
         return self._mb[k]
 
+    def _feeds(self, k, keep):
+        cols, static = self._mb[k]
+        return train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env,
+                                target_actor=self.target_actor, actor=self.actor,
+                                draw=self.draw_counter if self.target_actor is not None else None, keep=keep)
+
     def step(self, k):
         from . import _lib
         cols, static = self._mb[k]
         if not self.use_graph:
-            return train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env)
+            self._keep[k] = []
+            return self._feeds(k, self._keep[k])
         dev = next(iter(cols.values())).device
         if k not in self._graphs:
             # once eagerly (the allocator then holds blocks of every size the capture will ask for), then captured; the tensors the
-            # captured pass created are KEPT (self._calls): a replay writes to their addresses
-            train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env)
+            # captured pass created are KEPT (self._calls, and self._keep for what the actors' launches touch): a replay writes to
+            # their addresses.  The eager pass must not consume a draw: the counter goes back to what it was.
+            draw0 = self.draw_counter.value() if self.target_actor is not None else None
+            self._feeds(k, [])
+            if draw0 is not None:
+                self.draw_counter.set(draw0)
             torch.cuda.synchronize(dev)
-            box = {}
+            box = {"keep": []}
 
             def enqueue(stream):
                 with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                    box["calls"] = train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env)
+                    box["calls"] = self._feeds(k, box["keep"])
             self._graphs[k] = _lib.capture_graph(dev, enqueue)
-            self._calls[k] = box["calls"]
+            self._calls[k], self._keep[k] = box["calls"], box["keep"]
         _lib.check(_lib.lib().cm3_graph_launch(self._graphs[k], torch.cuda.current_stream(dev).cuda_stream))
         return self._calls[k]
 
@@ -312,7 +339,7 @@ class OnPolicyPhasePlan(object):
             torch.cuda.synchronize()
             for g in self._graphs.values():
                 _lib.lib().cm3_graph_destroy(g)
-        self._graphs, self._calls = {}, {}
+        self._graphs, self._calls, self._keep = {}, {}, {}
 
 
 def td_target(reward, q, multiplier, gamma):
@@ -439,7 +466,7 @@ def _rep_n(x, n):
 
 
 def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=True, use_V=True, l_action=5, device_tiling=True,
-                     static=None, target_actor=None, actor=None):
+                     static=None, target_actor=None, actor=None, draw=None, keep=None):
     """The data movement of the reference's train_step on the device: builds, in the reference's order, the feed_dict of
     every sess.run -- TD targets, the n x n credit repeats (alg_credit.py:614-658) and the n x n x l_action counterfactual
     tiling (:730-751; Checkers twin alg_credit_checkers.py:590-760) -- from the columns of
@@ -464,7 +491,10 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     ["probs"], from actor.probs_rows(obs_others, v_local, goals, epsilon), on Checkers from
     actor.probs_rows(obs_self_t, obs_self_v, obs_others, cols["actions_prev"], goals, epsilon).  epsilon: a float, or the one-element
     float32 device tensor the actors accept.  The soft update of the target actor -- the actor half of list_update_target_ops -- is
-    left to the caller: ``target_actor.soft_update_from(actor, tau)`` after this function returns.  With both None nothing changes."""
+    left to the caller: ``target_actor.soft_update_from(actor, tau)`` after this function returns.  With both None nothing changes.
+    draw / keep go to the actors' calls as they are: draw is sample_rows' (None: the target actor's host counter; an integer; or a
+    cm3_amd.actor.RowsDrawCounter, the device counter a captured launch advances itself), keep the list that receives every tensor
+    sample_rows / probs_rows allocate for their launches (OnPolicyPhasePlan holds them while it replays the capture)."""
     checkers = env == "checkers"
     calls = []
     if target_actor is not None or actor is not None:
@@ -475,6 +505,10 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                                  % (env, "CheckersActors" if checkers else "ParticleActors", type(a).__name__))
         if not cols["obs_others"].is_cuda:
             raise ValueError("train_step_feeds: target_actor / actor evaluate device columns; call without them for host tensors")
+
+    # (draw / keep reach the actors only when given: a call without them is the call of before)
+    probs_kw = {} if keep is None else {"keep": keep}
+    sample_kw = dict(probs_kw) if draw is None else dict(probs_kw, draw=draw)
 
     def call(ops, feed, launch=True):
         calls.append((ops, feed))
@@ -549,10 +583,10 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         else:
             call(["action_samples_target"], feed, launch=False)
             acts = target_actor.sample_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(-1), goals_self,
-                                            epsilon)["actions"]
+                                            epsilon, **sample_kw)["actions"]
     elif target_actor is not None:
         call(["action_samples_target"], actor_feed(obs_others_next, v_local_next), launch=False)
-        acts = target_actor.sample_rows(obs_others_next, v_local_next, goals_self, epsilon)["actions"]
+        acts = target_actor.sample_rows(obs_others_next, v_local_next, goals_self, epsilon, **sample_kw)["actions"]
     else:
         acts = call(["action_samples_target"], actor_feed(obs_others_next, v_local_next))[0]
     a_next_rep = None
@@ -618,8 +652,9 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
             return call(["probs"], feed)[0]
         call(["probs"], feed, launch=False)
         if checkers:
-            return actor.probs_rows(obs_self_t, obs_self_v, obs_others, cols["actions_prev"].reshape(-1), goals_self, epsilon)
-        return actor.probs_rows(obs_others, v_local, goals_self, epsilon)
+            return actor.probs_rows(obs_self_t, obs_self_v, obs_others, cols["actions_prev"].reshape(-1), goals_self, epsilon,
+                                    **probs_kw)
+        return actor.probs_rows(obs_others, v_local, goals_self, epsilon, **probs_kw)
 
     rep_a = lambda x: rep_rows(x, l_action)                                         # noqa: E731
     eye = torch.eye(l_action, dtype=f64, device=one.device)                         # self.actions = np.eye(l_action)

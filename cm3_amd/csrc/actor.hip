@@ -629,6 +629,7 @@ struct ActorRowsParams {
   int64_t *onehot;                           // [n_rows][5]: the sampled action, the form of cm3_qmix_rows.onehot
   const float *eps_dev;
   const float *packed;
+  uint32_t *draw_state;                      // optional {draw, arrivals}: the launch reads and advances its own counter (rows_draw_*)
 };
 template <int N> __device__ __forceinline__ size_t actor_row_count(const ActorParams &p) { return (size_t)p.E * N; }
 template <int N> __device__ __forceinline__ size_t actor_row_count(const ActorRowsParams &p) { return p.n_rows; }
@@ -726,7 +727,8 @@ template <int N, int PREC, typename RIN, bool ROWS = false, typename P = ActorPa
   if constexpr (ROWS) {
     const bool draws = p.actions != nullptr || p.onehot != nullptr;   // (the probs fetch draws nothing: uniform over the launch)
     float u = 0.0f;
-    if (draws) u = rows_uniform(p.seed, p.row_id_base + (uint64_t)hr, p.draw);
+    const bool counted = draws && p.draw_state != nullptr;
+    if (draws) u = rows_uniform(p.seed, p.row_id_base + (uint64_t)hr, counted ? rows_draw_read(p.draw_state) : p.draw);
     actor_head_probs(lds.h2s, hb, w, lane, p.eps_dev ? *p.eps_dev : p.eps, pr);
     const int act = actor_pick(pr, u);
     if (head_ok) {
@@ -737,6 +739,7 @@ template <int N, int PREC, typename RIN, bool ROWS = false, typename P = ActorPa
       if (p.actions) p.actions[hr] = act;
       if (p.onehot) onehot_row_store(p.onehot, hr, act);
     }
+    if (counted) rows_draw_arrive(p.draw_state, tid);   // (uniform over the launch: every wave of every workgroup comes here)
   } else {
     const float u = actor_uniform(p.seed, (uint64_t)(p.env_id_base + (int64_t)he), head_episode, head_steps, hi_agent);
     actor_head_probs(lds.h2s, hb, w, lane, p.eps_dev ? *p.eps_dev : p.eps, pr);
@@ -769,6 +772,7 @@ template <int N, typename RIN> static int actor_launch(const ActorParams &p, hip
 template <int N> static int actor_rows_launch(const ActorRowsParams &p, hipStream_t s) {
   const unsigned blocks = (unsigned)((p.n_rows + 63) / 64);
   note_variant("k_actor_particle_rows", (int)sizeof(float), N, 4, 0, 0, 0, 0, 0, 0, p.bf16);
+  note_counted(p.draw_state != nullptr);
   if (p.bf16 == kPrecF16x3)
     hipLaunchKernelGGL((k_actor_particle<N, kPrecF16x3, float, true, ActorRowsParams>), dim3(blocks), dim3(256), 0, s, p);
   else if (p.bf16 == kPrecBf16)
@@ -1176,10 +1180,12 @@ extern "C" int cm3_actor_particle_f64(const cm3_actor_particle_desc *d, const cm
   return cm3::actor_particle_call<double>(d, wt, b, stream);
 }
 
-// The actor over transition rows (part of ABI 9, additive): validated like cm3_actor_particle_f32, n_envs / env_id_base not read
-extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
-                                           const cm3_actor_rows *r, void *stream) {
-  using namespace cm3;
+// The actor over transition rows (part of ABI 9, additive): validated like cm3_actor_particle_f32, n_envs / env_id_base not read.
+// One body for both entries: counted = the launch takes its draw from draw_state and advances it (rows->draw is not read); its two
+// checks come after every check of the uncounted entry.
+namespace cm3 {
+static int actor_particle_rows_call(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt, const cm3_actor_rows *r,
+                                    bool counted, uint32_t *draw_state, void *stream) {
   int rc = actor_check_desc(d);
   if (rc != CM3_OK) return rc;
   CM3_REQUIRE(wt, "null weights");
@@ -1189,6 +1195,10 @@ extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, con
   CM3_REQUIRE(wt->packed, "weights->packed is NULL: run cm3_actor_particle_pack once per weight update");
   rc = particle_rows_check(r, r->probs || r->actions || r->onehot, "no output requested: set at least one of probs, actions, onehot");
   if (rc != CM3_OK) return rc;
+  if (counted) {
+    CM3_REQUIRE(draw_state, "null draw_state");
+    CM3_REQUIRE((uintptr_t)draw_state % 8 == 0, "misaligned draw_state: the two counter words must be 8-byte aligned");
+  }
   ActorRowsParams p;
   memset(&p, 0, sizeof(p));
   p.n_rows = (size_t)r->n_rows;
@@ -1206,8 +1216,20 @@ extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, con
   p.actions = r->actions;
   p.onehot = r->onehot;
   p.packed = (const float *)wt->packed;
+  p.draw_state = counted ? draw_state : nullptr;
   hipStream_t s = (hipStream_t)stream;
   return agent_launch_1_to_10(d->n_agents, [&](auto n) { return actor_rows_launch<n()>(p, s); });
+}
+}  // namespace cm3
+
+extern "C" int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
+                                           const cm3_actor_rows *r, void *stream) {
+  return cm3::actor_particle_rows_call(d, wt, r, false, nullptr, stream);
+}
+
+extern "C" int cm3_actor_particle_rows_counted_f32(const cm3_actor_particle_desc *d, const cm3_actor_particle_weights *wt,
+                                                   const cm3_actor_rows *r, uint32_t *draw_state, void *stream) {
+  return cm3::actor_particle_rows_call(d, wt, r, true, draw_state, stream);
 }
 
 // ---- QMIX agent (ABI 9) ------------------------------------------------------------------------------------------------------

@@ -717,6 +717,7 @@ struct CkActorRowsParams {
   int32_t *actions;                        // [R]
   int64_t *onehot;                         // [R][5]: the sampled action, the form of CkRowsParams::onehot
   const float *packed;
+  uint32_t *draw_state;                    // optional {draw, arrivals}: the launch reads and advances its own counter (rows_draw_*)
 };
 
 // lane l < 16 finishes row 16w + l on the same logits as ck_actor_head, through the same ck_actor_probs; every output is optional
@@ -734,13 +735,21 @@ __device__ __forceinline__ void ck_rows_head(const CkActorRowsParams &p, const f
         for (int a = 0; a < kA; ++a) p.probs[row * kA + a] = pr[a];
       }
       if (p.actions != nullptr || p.onehot != nullptr) {
-        const int act = actor_pick(pr, rows_uniform(p.seed, p.row_id_base + (uint64_t)row, p.draw));
+        const uint32_t draw = p.draw_state ? rows_draw_read(p.draw_state) : p.draw;
+        const int act = actor_pick(pr, rows_uniform(p.seed, p.row_id_base + (uint64_t)row, draw));
         if (p.actions) p.actions[row] = act;
         if (p.onehot) onehot_row_store(p.onehot, row, act);
       }
     }
   }
 }
+
+// behind the head, by EVERY thread of the workgroup (waves that finish no row included): the workgroup's ticket of a counted launch.
+// Uniform over the launch; a probs-only launch neither reads nor advances the counter.  The QMIX rows forms draw nothing.
+__device__ __forceinline__ void ck_rows_arrive(const CkActorRowsParams &p, int tid) {
+  if (p.draw_state != nullptr && (p.actions != nullptr || p.onehot != nullptr)) rows_draw_arrive(p.draw_state, tid);
+}
+__device__ __forceinline__ void ck_rows_arrive(const CkRowsParams &, int) {}
 
 __device__ __forceinline__ size_t ck_row_count(const CkActorParams &p) { return (size_t)p.E * p.N; }
 __device__ __forceinline__ size_t ck_row_count(const CkRowsParams &p) { return p.n_rows; }
@@ -964,7 +973,10 @@ __global__ void CM3_MATRIX_KERNEL k_ck_actor(const P p) {
   }
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
-  if constexpr (ROWS) ck_rows_head(p, sLG, w, lane, row_base);
+  if constexpr (ROWS) {
+    ck_rows_head(p, sLG, w, lane, row_base);
+    ck_rows_arrive(p, tid);
+  }
   else if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
   else ck_actor_head(p, sLG, w, lane, row_base, rows);
   CM3_STAMP(12, true);
@@ -1690,6 +1702,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
     else if constexpr (GREEDY) ck_qmix_head(p, sLG, w, lane, row_base, rows, w_explore, w_action);
     else ck_actor_head(p, sLG, w, lane, row_base, rows);
   }
+  if constexpr (ROWS) ck_rows_arrive(p, tid);   // (all eight waves: it holds a barrier)
   (void)w_explore;
   (void)w_action;
   CM3_STAMP(12, true);
@@ -1750,6 +1763,7 @@ template <bool WIDE_T, bool WIDE_G, typename P> static int ck_rows_launch_form(c
   const bool x3 = precision == 2;
   note_variant(ACTOR ? (x3 ? "k_ck_actor_rows_x3" : "k_ck_actor_rows") : (x3 ? "k_ck_qmix_rows_x3" : "k_ck_qmix_rows"), 4, p.N, x3 ? 8 : 4,
                0, 0, 0, 0, 0, (WIDE_T ? 1 : 0) + (WIDE_G ? 2 : 0), precision);
+  if constexpr (ACTOR) note_counted(p.draw_state != nullptr);
   if (x3) hipLaunchKernelGGL((k_ck_actor_x3<false, true, WIDE_T, WIDE_G, P>), grid, dim3(512), 0, s, p);
   else if (!ACTOR || precision == 0) hipLaunchKernelGGL((k_ck_actor<false, false, true, WIDE_T, WIDE_G, P>), grid, dim3(256), 0, s, p);
   else if constexpr (ACTOR) hipLaunchKernelGGL((k_ck_actor<true, false, true, WIDE_T, WIDE_G, P>), grid, dim3(256), 0, s, p);
@@ -1985,9 +1999,11 @@ extern "C" int cm3_qmix_checkers_rows_f32(const cm3_actor_checkers_desc *d, cons
 }
 
 // ---- the CM3 actor over transition rows (ABI 9, additive): every argument is checked before anything touches the GPU ------------------
-extern "C" int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
-                                           const cm3_actor_checkers_rows *r, void *stream) {
-  using namespace cm3;
+// One body for both entries: counted = the launch takes its draw from draw_state and advances it (rows->draw is not read); its two
+// checks come after every check of the uncounted entry.
+namespace cm3 {
+static int ck_actor_rows_call(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt, const cm3_actor_checkers_rows *r,
+                              bool counted, uint32_t *draw_state, void *stream) {
   int rc = ck_actor_check(d);
   if (rc != CM3_OK) return rc;
   CM3_REQUIRE(wt, "null weights");
@@ -2001,6 +2017,10 @@ extern "C" int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *d, con
   if (rc != CM3_OK) return rc;
   CM3_REQUIRE((uintptr_t)r->onehot % 16 == 0 && (uintptr_t)r->probs % 4 == 0 && (uintptr_t)r->actions % 4 == 0,
               "misaligned outputs: onehot must be 16-byte aligned, probs and actions 4-byte");
+  if (counted) {
+    CM3_REQUIRE(draw_state, "null draw_state");
+    CM3_REQUIRE((uintptr_t)draw_state % 8 == 0, "misaligned draw_state: the two counter words must be 8-byte aligned");
+  }
   CkActorRowsParams p;
   ck_rows_inputs(p, d, wt, r);
   p.stage = d->stage;
@@ -2012,6 +2032,18 @@ extern "C" int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *d, con
   p.probs = r->probs;
   p.actions = r->actions;
   p.onehot = r->onehot;
+  p.draw_state = counted ? draw_state : nullptr;
   return ck_rows_launch(p, r->obs_self_t_f64 != 0, r->goals_onehot != 0, d->precision, (hipStream_t)stream);
+}
+}  // namespace cm3
+
+extern "C" int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                           const cm3_actor_checkers_rows *r, void *stream) {
+  return cm3::ck_actor_rows_call(d, wt, r, false, nullptr, stream);
+}
+
+extern "C" int cm3_actor_checkers_rows_counted_f32(const cm3_actor_checkers_desc *d, const cm3_actor_checkers_weights *wt,
+                                                   const cm3_actor_checkers_rows *r, uint32_t *draw_state, void *stream) {
+  return cm3::ck_actor_rows_call(d, wt, r, true, draw_state, stream);
 }
 #endif  // CM3_NO_ENTRY_POINTS

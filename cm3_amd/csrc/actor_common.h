@@ -131,6 +131,37 @@ __device__ __forceinline__ float rows_uniform(uint64_t seed, uint64_t row_id, ui
   return (float)u01(philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32)).x);
 }
 
+// ---- a rows launch that keeps its OWN draw counter (the *_rows_counted entries): two uint32 words in device memory, 8-byte aligned,
+// {draw, arrivals}, set up once by the caller with arrivals = 0.  A host-side `draw` is baked into a captured launch, so every replay
+// of a hipGraph would draw the same uniforms; a counted launch reads word 0 for itself -- every row of the launch draws at that
+// value -- and leaves word 0 + 1 (mod 2^32) behind, in the same launch: no node more per evaluation.  The mechanism is
+// k_returns_moments' (advantage.hip): once every wave of a workgroup has its value (the barrier), the workgroup takes a ticket from
+// `arrivals`; the workgroup whose ticket is gridDim.x - 1 knows every other one has read, writes the advanced value and resets
+// `arrivals`.  Nothing waits for another workgroup, so a grid of more workgroups than the chip holds at once is no different.
+// Ordering: the two words are ONE 64-bit atomic object (why they are 8-byte aligned; word 0 is its low half), and every access --
+// the read, the ticket, the write -- is a relaxed agent-scope atomic on it (never served by an XCD's own L2 copy).  A wave's read
+// happens before its workgroup's ticket (the barrier); the ticket modifies the object, so by the coherence of a single atomic object
+// the read took its value from before that ticket in the object's modification order; the write comes after the last ticket, hence
+// after every ticket, in that order: no read can see the advanced value, on whichever XCD it ran.  No release fence is involved: an
+// agent-scope release makes the workgroup write its XCD's L2 back first (measured with the ticket as a 32-bit acq_rel add on
+// word 1: +5.1 .. +6.2 us per launch at 16 384 rows; this form +3.2 .. +3.8, profiles/r23_rows_counter.txt).  Launches that share
+// a counter must be ordered on the device (one stream, or graph dependencies): two of them in flight at once would count each
+// other's arrivals.
+__device__ __forceinline__ uint32_t rows_draw_read(const uint32_t *state) {
+  return (uint32_t)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// called by EVERY thread of the workgroup (it holds a barrier), after the thread's last rows_draw_read
+__device__ __forceinline__ void rows_draw_arrive(uint32_t *state, int tid) {
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long *both = reinterpret_cast<unsigned long long *>(state);
+    const unsigned long long old = __hip_atomic_fetch_add(both, 1ull << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (low half: the draw every row of this launch used; high half: how many workgroups took a ticket before this one)
+    if ((uint32_t)(old >> 32) == gridDim.x - 1)
+      __hip_atomic_store(both, (unsigned long long)((uint32_t)old + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // {draw + 1, 0}
+  }
+}
+
 // One row of an int64 [rows][5] one-hot array (the reference's np.zeros(dtype=int) forms: actions_target_1hot, action_one):
 // 40 bytes per row from a 16-byte aligned base -- an even row is 16 | 16 | 8 bytes, an odd one 8 | 16 | 16
 __device__ __forceinline__ void onehot_row_store(int64_t *onehot, size_t hr, int act) {

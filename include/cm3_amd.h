@@ -65,6 +65,9 @@ extern "C" {
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
                                   alg_credit_checkers.train_step); additive.
+                                  cm3_actor_particle_rows_counted_f32 / cm3_actor_checkers_rows_counted_f32 (the two actor rows launches
+                                  with a draw counter in device memory that the launch reads and advances itself, so a captured launch
+                                  draws afresh on every replay); additive.
                                   cm3_rows_force_index_width / cm3_rows_last_index_width (the 64-bit index builds of the row, export
                                   and tiling kernels at any size: tests); additive.
                                8: ADDED cm3_actor_particle_f64, cm3_policy_rollout_f64 (policy-driven collection on float64 envs; additive).
@@ -458,6 +461,19 @@ typedef struct {
  * cm3_last_kernel_variant() names the launch k_actor_particle_rows<f32,N=..,...>. */
 int cm3_actor_particle_rows_f32(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
                                 const cm3_actor_rows *rows, void *stream);
+/* The same launch with a draw counter it keeps ITSELF (part of ABI 9, additive), for launches captured into a hipGraph: a captured
+ * cm3_actor_particle_rows_f32 bakes rows->draw in, so every replay would draw the same uniforms.  draw_state: two uint32 words in
+ * device memory, 8-byte aligned, {draw, arrivals}; the caller initialises them once, with arrivals = 0.  The launch draws every row
+ * at draw = word 0 -- the actions are those of cm3_actor_particle_rows_f32 at rows->draw = word 0, the probabilities the same bits
+ * -- and leaves word 0 + 1 (mod 2^32) in word 0 and arrivals = 0, within the same launch (no node more in a captured graph; each
+ * workgroup takes a ticket from `arrivals` once it has read word 0, the last one writes; nothing waits).  rows->draw is ignored.  A
+ * launch that draws nothing (actions and onehot both NULL) neither reads nor advances the counter.  Launches that share a counter
+ * MUST be ordered on the device -- one stream, or graph dependencies: two in flight at once would count each other's arrivals.
+ * Validation: every check of cm3_actor_particle_rows_f32 first, in its order and with its messages; then CM3_ERR_INVALID for
+ * draw_state == NULL, then for a draw_state that is not 8-byte aligned; all before any launch.  cm3_last_kernel_variant() names the
+ * kernel of the uncounted launch with a ",counted" suffix: k_actor_particle_rows<f32,N=..,...,counted>. */
+int cm3_actor_particle_rows_counted_f32(const cm3_actor_particle_desc *desc, const cm3_actor_particle_weights *weights,
+                                        const cm3_actor_rows *rows, uint32_t *draw_state, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * On-device QMIX agent (ABI 9): networks.Qmix_single_particle (networks.py:581-594) + the epsilon-greedy choice of
@@ -713,6 +729,13 @@ typedef struct {
  * F = obs_self_t_f64 + 2 * goals_onehot. */
 int cm3_actor_checkers_rows_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
                                 const cm3_actor_checkers_rows *rows, void *stream);
+/* The same launch with a draw counter it keeps itself (part of ABI 9, additive): draw_state, its two words, what the launch leaves
+ * in them, the ordering rule for launches that share a counter and the validation order (every check of
+ * cm3_actor_checkers_rows_f32 first, then NULL, then 8-byte alignment of draw_state) are those of
+ * cm3_actor_particle_rows_counted_f32.  rows->draw is ignored; a probs-only launch neither reads nor advances the counter.
+ * cm3_last_kernel_variant(): k_ck_actor_rows<..,counted> / k_ck_actor_rows_x3<..,counted>. */
+int cm3_actor_checkers_rows_counted_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
+                                        const cm3_actor_checkers_rows *rows, uint32_t *draw_state, void *stream);
 
 /* A whole POLICY-DRIVEN Checkers rollout in ONE launch (ABI 7; csrc/policy_checkers.hip): per tick the actor above (precision 2),
  * epsilon-mixed sampling and Checkers.step with the actions just drawn -- train_onpolicy.py:309-347 / train_offpolicy.py:309-368 without
