@@ -29,6 +29,9 @@ def __getattr__(name):
     if name == "ParticleActor":
         from .actor import ParticleActor
         return ParticleActor
+    if name == "ParticleCritic":
+        from .critic import ParticleCritic
+        return ParticleCritic
     if name == "ParticleQmixAgent":
         from .qmix import ParticleQmixAgent
         return ParticleQmixAgent

@@ -196,6 +196,25 @@ class ActorParticleWeights(ctypes.Structure):
                                         "b_h2", "w_out", "b_out", "packed")]
 
 
+class CriticParticleDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "stage", "kind", "n_h1_1", "n_h1_2", "n_h2")]
+
+
+class CriticParticleWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w_b1", "b_b1", "w_b1_h2", "w_b2", "b_b2", "w_b2_h2", "w_out", "packed")]
+
+
+class CriticRows(ctypes.Structure):
+    # (cm3_critic_rows: the base columns cm3_critic_particle_rows_f32 decodes its rows from, and its optional outputs)
+    _fields_ = [("form", c_int32), ("reward_f64", c_int32), ("state", c_void_p), ("goals", c_void_p), ("actions", c_void_p),
+                ("reward", c_void_p), ("done", c_void_p), ("gamma", c_double), ("q", c_void_p), ("q64", c_void_p), ("td", c_void_p),
+                ("n_steps", c_int64)]
+
+
+CRITIC_GLOBAL, CRITIC_CREDIT = 0, 1
+CRITIC_ROWS, CRITIC_PAIRS, CRITIC_CF = 0, 1, 2
+
+
 class ActorParticleBufs(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("obs_others", "state", "goals", "meta", "episode", "actions", "probs",
                                         "epsilon_dev")]
@@ -261,6 +280,9 @@ SYMBOLS = {
     "cm3_qmix_particle_f32": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(ActorParticleBufs), c_void_p]),
     "cm3_qmix_particle_f64": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(ActorParticleBufs), c_void_p]),
     "cm3_qmix_particle_rows_f32": (ctypes.c_int, [P(ActorParticleDesc), c_void_p, P(QmixRows), c_void_p]),
+    "cm3_critic_particle_packed_bytes": (c_size_t, [c_int32, c_int32]),
+    "cm3_critic_particle_pack": (ctypes.c_int, [P(CriticParticleDesc), P(CriticParticleWeights), c_void_p, c_void_p]),
+    "cm3_critic_particle_rows_f32": (ctypes.c_int, [P(CriticParticleDesc), P(CriticParticleWeights), P(CriticRows), c_void_p]),
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
     "cm3_qmix_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64,
                                               c_void_p]),

@@ -263,16 +263,22 @@ class OnPolicyPhasePlan(object):
     counters produce equal feeds and hold equal counters after any sequence of step(k).  The launches read the actors' persistent
     packed weights: ``target_actor.soft_update_from(actor, tau)`` between steps is seen by the next replay, as in eager mode.
     Every tensor the actors' calls allocate for a captured launch is held next to the step's calls (self._keep[k]) for as long as
-    the graph lives.  Without actors nothing changes and no counter is made."""
+    the graph lives.  Without actors nothing changes and no counter is made.
+
+    q_global_target / q_credit_target / q_credit: the ParticleCritics of train_step_feeds (particle rollouts only); their launches
+    -- the three evaluations and the pack launch behind Q_credit_op -- become part of the replayed graph, and their tensors are held
+    in self._keep[k] like the actors'.  `run` must write the Q_credit_main variables into q_credit.w[...] in place."""
 
     def __init__(self, rollout, run, gamma, epsilon, epochs=24, batch_size=128, l_action=5, use_graph=True, target_actor=None,
-                 actor=None, draw_counter=None):
+                 actor=None, draw_counter=None, q_global_target=None, q_credit_target=None, q_credit=None):
         self.ro, self.run, self.gamma, self.epsilon = rollout, run, float(gamma), float(epsilon)
         self.epochs, self.batch_size, self.l_action, self.use_graph = int(epochs), int(batch_size), int(l_action), bool(use_graph)
         self.cols = self.static = None
         self.k = 0
         self._graphs, self._calls, self._keep = {}, {}, {}
         self.target_actor, self.actor = target_actor, actor
+        self.critics = {k: v for k, v in (("q_global_target", q_global_target), ("q_credit_target", q_credit_target),
+                                          ("q_credit", q_credit)) if v is not None}
         self.draw_counter = draw_counter
         if self.draw_counter is None and target_actor is not None:
             from .actor import RowsDrawCounter
@@ -305,7 +311,7 @@ class OnPolicyPhasePlan(object):
         cols, static = self._mb[k]
         return train_step_feeds(cols, self.run, self.gamma, self.epsilon, l_action=self.l_action, static=static, env=self.env,
                                 target_actor=self.target_actor, actor=self.actor,
-                                draw=self.draw_counter if self.target_actor is not None else None, keep=keep)
+                                draw=self.draw_counter if self.target_actor is not None else None, keep=keep, **self.critics)
 
     def step(self, k):
         from . import _lib
@@ -466,7 +472,8 @@ def _rep_n(x, n):
 
 
 def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=True, use_V=True, l_action=5, device_tiling=True,
-                     static=None, target_actor=None, actor=None, draw=None, keep=None):
+                     static=None, target_actor=None, actor=None, draw=None, keep=None, q_global_target=None, q_credit_target=None,
+                     q_credit=None):
     """The data movement of the reference's train_step on the device: builds, in the reference's order, the feed_dict of
     every sess.run -- TD targets, the n x n credit repeats (alg_credit.py:614-658) and the n x n x l_action counterfactual
     tiling (:730-751; Checkers twin alg_credit_checkers.py:590-760) -- from the columns of
@@ -494,9 +501,43 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     left to the caller: ``target_actor.soft_update_from(actor, tau)`` after this function returns.  With both None nothing changes.
     draw / keep go to the actors' calls as they are: draw is sample_rows' (None: the target actor's host counter; an integer; or a
     cm3_amd.actor.RowsDrawCounter, the device counter a captured launch advances itself), keep the list that receives every tensor
-    sample_rows / probs_rows allocate for their launches (OnPolicyPhasePlan holds them while it replays the capture)."""
+    sample_rows / probs_rows allocate for their launches (OnPolicyPhasePlan holds them while it replays the capture).
+
+    q_global_target / q_credit_target / q_credit (particle env, CUDA columns): cm3_amd.critic.ParticleCritics holding the
+    Q_global_target / Q_credit_target / Q_credit_main weights, for the batch's agent count.  With one given, `run` is NOT called for
+    its op (the (ops, feed) entry still appears in the list) and the evaluation is one launch on the batch's base columns:
+      ["Q_global_target"]  q_global_target.q_rows(v_global_next, goals, a', reward_local, done, gamma); its "td" is the
+                           Q_global_td_target feed (kind "global")
+      ["Q_credit_target"]  q_credit_target.q_pairs(...), likewise; its "td" is the Q_credit_td_target feed (kind "credit")
+      ["Q_credit"]         the counterfactual Q_cf = q_credit.q_counterfactual(v_global, goals) (kind "credit").  With ONE agent
+                           (stage 1) the counterfactual op is ["Q_global"] on the Q_global_main weights: q_credit then takes a
+                           kind "global" critic -- the same argument, no fourth one.
+    The reference evaluates the counterfactual AFTER the optimiser step on the main critic (alg_credit.py:660, then :750; with one
+    agent :601, then :726), so q_credit.repack() is launched right after call(["Q_credit_op"], ...) (one agent: after
+    call(["Q_global_op", "Q_global"], ...)).  CONTRACT: `run` writes the updated variables INTO q_credit.w[...] in place (the
+    tensors are persistent, the pack launch capturable).  The soft updates of the two target critics -- their part of
+    list_update_target_ops -- are the caller's: ``q_global_target.soft_update_from(main, tau)`` after this function returns.  keep
+    receives the tensors of these launches too.  With all three None nothing changes: not a launch, not a bit."""
     checkers = env == "checkers"
     calls = []
+    critics = (("q_global_target", q_global_target), ("q_credit_target", q_credit_target), ("q_credit", q_credit))
+    if any(c is not None for _, c in critics):
+        from .critic import ParticleCritic
+        if checkers:
+            raise ValueError("train_step_feeds: q_global_target / q_credit_target / q_credit are ParticleCritics; env='checkers' has no "
+                             "device critics")
+        n_batch = cols["v_global"].shape[1]
+        for name, c in critics:
+            if c is None:
+                continue
+            want = "global" if (name == "q_global_target" or n_batch == 1) else "credit"
+            if not isinstance(c, ParticleCritic) or c.kind != want or c.n != n_batch:
+                raise ValueError("train_step_feeds: %s takes a ParticleCritic of kind %r for %d agents, got %s"
+                                 % (name, want, n_batch, "a %s" % type(c).__name__ if not isinstance(c, ParticleCritic)
+                                    else "kind %r for %d agents" % (c.kind, c.n)))
+        if not cols["v_global"].is_cuda:
+            raise ValueError("train_step_feeds: q_global_target / q_credit_target / q_credit evaluate device columns; call without "
+                             "them for host tensors")
     if target_actor is not None or actor is not None:
         from .actor import CheckersActor
         for a in (target_actor, actor):
@@ -594,16 +635,22 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         a_next, a_others_next, a_next_rep = process_actions_device(acts, n_steps, N, l_action, rep_m=N > 1 and use_Q_credit)
     else:
         a_next, a_others_next = process_actions(acts.reshape(n_steps, N), l_action)
-    q_t = call(["Q_global_target"], with_env({"v_state_one_agent": one_next, "v_goal": goals_self, "action_one": a_next,
-                                              "v_state_other_agents": others_next, "action_others": a_others_next},
-                                             state_env_next if checkers else None,
-                                             obs_self_t_next if checkers else None, obs_self_v_next if checkers else None))[0]
-    td = td_target(reward_local, q_t, not_done, gamma) if S is not None else reward_local.to(f64) + gamma * q_t.reshape(-1) * not_done
+    feed = with_env({"v_state_one_agent": one_next, "v_goal": goals_self, "action_one": a_next,
+                     "v_state_other_agents": others_next, "action_others": a_others_next},
+                    state_env_next if checkers else None, obs_self_t_next if checkers else None, obs_self_v_next if checkers else None)
+    if q_global_target is not None:     # one launch on the base columns: Q and the TD target
+        call(["Q_global_target"], feed, launch=False)
+        td = q_global_target.q_rows(v_global_next, goals, acts, reward_local, cols["done"], gamma, **probs_kw)["td"]
+    else:
+        q_t = call(["Q_global_target"], feed)[0]
+        td = td_target(reward_local, q_t, not_done, gamma) if S is not None else reward_local.to(f64) + gamma * q_t.reshape(-1) * not_done
     q_res = call(["Q_global_op", "Q_global"],
                  with_env({"Q_global_td_target": td, "v_state_one_agent": one, "v_goal": goals_self, "action_one": actions_1hot,
                            "v_state_other_agents": others, "action_others": actions_others_1hot},
                           state_env if checkers else None, obs_self_t if checkers else None,
                           obs_self_v if checkers else None))[1]
+    if N == 1 and q_credit is not None:
+        q_credit.repack()           # (one agent: the counterfactual below reads the Q_global_main weights this step updated)
     q_res_rep = rep_rows(q_res.reshape(n_steps, N), N)                              # :612
 
     rep_m = lambda x: rep_rows(x, N)                                                # noqa: E731  things indexed by m
@@ -617,7 +664,11 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         if checkers:
             feed = (with_env(feed, rep_m(state_env_next), rep_m(obs_self_t_next), rep_m(obs_self_v_next)) if S is None
                     else with_env(feed, S["env_next_rep"], S["ot_next_rep"], S["ov_next_rep"]))
-        qc_t = call(["Q_credit_target"], feed)[0]
+        if q_credit_target is not None:
+            call(["Q_credit_target"], feed, launch=False)
+            td_c = q_credit_target.q_pairs(v_global_next, goals, acts, reward_local, cols["done"], gamma, **probs_kw)["td"]
+        else:
+            qc_t = call(["Q_credit_target"], feed)[0]
         if S is None:
             r_rep = _rep_n(reward_local.reshape(-1, 1), N).reshape(-1)
             nd_rep = -(_rep_n(done.reshape(-1, 1).to(torch.int64), N).reshape(-1) - 1)
@@ -625,7 +676,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         else:
             r_rep, nd_rep = S["r_rep"], S["nd_rep"]
             s_n_rep, s_others_rep, s_m_rep = S["s_n_rep"], S["s_others_rep"], S["s_m_rep"]
-        td_c = td_target(r_rep, qc_t, nd_rep, gamma) if S is not None else r_rep.to(f64) + gamma * qc_t.reshape(-1) * nd_rep
+        if q_credit_target is None:
+            td_c = td_target(r_rep, qc_t, nd_rep, gamma) if S is not None else r_rep.to(f64) + gamma * qc_t.reshape(-1) * nd_rep
         feed = {"Q_credit_td_target": td_c, "v_state_one_agent": s_n_rep, "v_goal": goals_self_rep,
                 "action_one": rep_m(actions_1hot) if S is None else S["a1_rep_m"], "v_state_m": s_m_rep,
                 "v_state_other_agents": s_others_rep}
@@ -634,6 +686,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                                          else (S["env_rep"], S["ot_rep"], S["ov_rep"]))
             feed = with_env(feed, s_env_rep, ot_rep, ov_rep)
         call(["Q_credit_op"], feed)
+        if q_credit is not None:
+            q_credit.repack()       # (the counterfactual below reads the Q_credit_main weights this step updated)
     v_res_rep = None
     if N > 1 and use_V:             # ---- V_n(s) (:676-699) ----
         v_t = call(["V_target"], with_env({"v_state_one_agent": one_next, "v_goal": goals_self,
@@ -664,7 +718,11 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                 "v_state_other_agents": others, "action_others": actions_others_1hot}
         if checkers:
             feed = with_env(feed, rep_a(state_env), rep_a(obs_self_t), rep_a(obs_self_v))
-        q_cf = call(["Q_global"], feed)[0].reshape(n_steps, l_action)
+        if q_credit is not None:
+            call(["Q_global"], feed, launch=False)
+            q_cf = q_credit.q_counterfactual(v_global, goals, **probs_kw)
+        else:
+            q_cf = call(["Q_global"], feed)[0].reshape(n_steps, l_action)
     elif use_Q_credit:
         probs = rep_rows(fetch_probs(), N)
         if S is None:
@@ -677,7 +735,11 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
         if checkers:
             feed = (with_env(feed, rep_a(s_env_rep), rep_a(ot_rep), rep_a(ov_rep)) if S is None
                     else with_env(feed, S["cf_env"], S["cf_ot"], S["cf_ov"]))
-        q_cf = call(["Q_credit"], feed)[0].reshape(n_steps * N * N, l_action)
+        if q_credit is not None:
+            call(["Q_credit"], feed, launch=False)
+            q_cf = q_credit.q_counterfactual(v_global, goals, **probs_kw)
+        else:
+            q_cf = call(["Q_credit"], feed)[0].reshape(n_steps * N * N, l_action)
     else:
         probs = torch.zeros(1, l_action, dtype=f64, device=one.device)
         q_cf = torch.zeros(1, l_action, dtype=f64, device=one.device)

@@ -1,0 +1,207 @@
+"""ParticleCritic -- the reference's particle critics evaluated on the device over the rows of a sampled batch.
+
+    reference                                                    here
+    ---------------------------------------------------------   -----------------------------------------------
+    networks.Q_global_1output(s_n, g_n, a_n, s_others, a_others)  ParticleCritic(weights, n_agents, kind="global")
+      (networks.py:97-122; scopes Q_global_main / _target)
+    networks.Q_credit(s_n, g_n, a_m, s_m, s_others)               ParticleCritic(weights, n_agents, kind="credit")
+      (networks.py:186-211; scopes Q_credit_main / _target)
+    sess.run(Q_global_target, feed) + the TD target               critic.q_rows(v_global_next, goals, a', reward, done, gamma)
+      (alg_credit.py:585-594)
+    sess.run(Q_credit_target, feed) + the TD target               critic.q_pairs(v_global_next, goals, a', reward, done, gamma)
+      (alg_credit.py:616-640)
+    sess.run(Q_credit, n x n x l_action counterfactual feed)      critic.q_counterfactual(v_global, goals)
+      (alg_credit.py:730-751; stage 1: sess.run(Q_global, ...) :716-727)
+
+Every method is ONE launch of cm3_critic_particle_rows_f32, which takes no tiled feed: the n x n x 5 tilings the reference builds
+on the host are index functions of the batch's base columns (state [B, N, 4], goals [B, N, 2], actions [B, N]) and the kernel
+decodes them from the row number.  The network is float32 throughout, every contraction an exact-f32 k-ordered chain.
+
+Weights stay float32 [in][out] as TensorFlow shapes them, in ``self.w`` under short names (NAMES below), so a session that trains
+the main critics can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors,
+capturable) then makes the next launch follow them.  Scope prefixes "Q_global_main/", "Q_global_target/", "Q_credit_main/",
+"Q_credit_target/" and a ":0" suffix of the keys are ignored.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import Cm3Error
+from .actor import _keep
+
+H1_1, H1_2, H2, N_ACTIONS = 64, 128, 64, 5
+KINDS = {"global": _lib.CRITIC_GLOBAL, "credit": _lib.CRITIC_CREDIT}
+NAMES = {"w_b1": "Q_branch1/kernel", "b_b1": "Q_branch1/bias", "w_b1_h2": "W_branch1_h2",
+         "w_b2": "stage-2/Q_branch2/kernel", "b_b2": "stage-2/Q_branch2/bias", "w_b2_h2": "stage-2/W_branch2_h2",
+         "w_out": "Q_out/kernel"}
+_PREFIXES = ("Q_global_main/", "Q_global_target/", "Q_credit_main/", "Q_credit_target/")
+
+
+def _canon(name):
+    name = name.split(":")[0]
+    for prefix in _PREFIXES:
+        if name.startswith(prefix):
+            name = name[len(prefix):]
+    return name
+
+
+def weight_shapes(n_agents, kind, stage):
+    """short name -> shape of the TF variable, for the tensors a critic of this kind / stage has"""
+    shapes = {"w_b1": (11, H1_1), "b_b1": (H1_1,), "w_b1_h2": (H1_1, H2), "w_out": (H2, 1)}
+    if stage > 1:
+        k2 = 9 * (n_agents - 1) if kind == "global" else 4 * n_agents
+        shapes.update({"w_b2": (k2, H1_2), "b_b2": (H1_2,), "w_b2_h2": (H1_2, H2)})
+    return shapes
+
+
+class ParticleCritic(object):
+    def __init__(self, weights, n_agents, kind="global", stage=2, device="cuda:0"):
+        """kind "global": networks.Q_global_1output -- stage 1 with one agent, stage 2 with more; kind "credit": networks.Q_credit,
+        stage 2 with more than one agent.  float32 only."""
+        self.device = _lib.require_gpu(device)
+        if kind not in KINDS:
+            raise Cm3Error("kind must be one of %s" % sorted(KINDS))
+        self.kind, self.n, self.stage = kind, int(n_agents), int(stage)
+        if not 1 <= self.n <= _lib.MAX_AGENTS:
+            raise Cm3Error("n_agents must be in 1..%d" % _lib.MAX_AGENTS)
+        if kind == "credit" and (self.n == 1 or self.stage != 2):
+            raise Cm3Error("Q_credit exists at stage 2 with more than one agent only (n_agents %d, stage %d)" % (self.n, self.stage))
+        if self.stage not in (1, 2) or (self.stage == 1) != (self.n == 1):
+            raise Cm3Error("Q_global_1output runs at stage 1 with one agent and at stage 2 with more (n_agents %d, stage %d)"
+                           % (self.n, self.stage))
+        src = {_canon(k): v for k, v in weights.items()}
+        self.w = {}
+        for short, shape in weight_shapes(self.n, kind, self.stage).items():
+            name = NAMES[short]
+            if name not in src:
+                raise Cm3Error("missing critic weight %r" % name)
+            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise Cm3Error("critic weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            self.w[short] = t.to(self.device)
+        self._wt = _lib.CriticParticleWeights()
+        for short in NAMES:
+            setattr(self._wt, short, _lib.ptr(self.w.get(short)))
+        self._lib = _lib.lib()
+        nbytes = self._lib.cm3_critic_particle_packed_bytes(self.n, KINDS[kind])
+        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        self._wt.packed = self._packed.data_ptr()
+        self.repack()
+
+    def _desc(self):
+        d = _lib.CriticParticleDesc()
+        d.n_agents, d.stage, d.kind = self.n, self.stage, KINDS[self.kind]
+        d.n_h1_1, d.n_h1_2, d.n_h2 = H1_1, H1_2, H2
+        return d
+
+    def repack(self):
+        """Re-arrange the (possibly updated in place) TF-shaped weights into the rows kernel's layout: one launch."""
+        d = self._desc()
+        _lib.check(self._lib.cm3_critic_particle_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
+                                                      _lib.current_stream_handle(self.device)))
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the critic's part of
+        list_update_target_ops (alg_credit.py:186-194), for a critic holding target weights."""
+        if not isinstance(main, ParticleCritic) or (main.n, main.kind, main.stage) != (self.n, self.kind, self.stage):
+            raise Cm3Error("soft_update_from: the main critic must be a %s ParticleCritic for %d agents at stage %d"
+                           % (self.kind, self.n, self.stage))
+        tau = float(tau)
+        for name in self.w:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
+        self.repack()
+
+    # ---- launches -------------------------------------------------------------------------------------------------------------------
+    def enqueue(self, form, n_steps, state, goals, actions=None, reward=None, done=None, gamma=0.0, q=None, q64=None, td=None,
+                stream=None):
+        """Raw launch of cm3_critic_particle_rows_f32 on contiguous device tensors: state / goals float32, actions int32, reward
+        float32 or float64, done uint8; every output is optional, one is required."""
+        r = _lib.CriticRows()
+        r.form, r.n_steps = int(form), int(n_steps)
+        r.state, r.goals, r.actions = _lib.ptr(state), _lib.ptr(goals), _lib.ptr(actions)
+        r.reward, r.done = _lib.ptr(reward), _lib.ptr(done)
+        r.reward_f64 = 1 if (reward is not None and reward.dtype == torch.float64) else 0
+        r.gamma = float(gamma)
+        r.q, r.q64, r.td = _lib.ptr(q), _lib.ptr(q64), _lib.ptr(td)
+        d = self._desc()
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_critic_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def _stage_cols(self, what, state, goals, actions=None, reward=None, done=None):
+        """(B, state, goals, actions, reward, done) contiguous on the critic's device from [B, N, 4], [B, N, 2], [B, N], [B, N] and
+        [B] (leading dimensions may be merged: [B * N, 4] ...).  Float columns of any dtype are rounded to float32, as the
+        reference's tf.float32 placeholders do; reward stays float32 or float64 (another dtype is widened to float64)."""
+        N = self.n
+        if state.shape[-1] != 4 or goals.shape[-1] != 2 or state.numel() // 4 != goals.numel() // 2 or (state.numel() // 4) % N:
+            raise Cm3Error("%s takes state [B, %d, 4] and goals [B, %d, 2], got %s and %s"
+                           % (what, N, N, tuple(state.shape), tuple(goals.shape)))
+        B = state.numel() // (4 * N)
+        if B <= 0:
+            raise Cm3Error("%s needs at least one time step" % what)
+        f32 = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
+        state, goals = f32(state).reshape(B, N, 4), f32(goals).reshape(B, N, 2)
+        if actions is not None:
+            if actions.numel() != B * N:
+                raise Cm3Error("%s takes actions [B, %d] for %d time steps, got %s" % (what, N, B, tuple(actions.shape)))
+            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if reward is not None:
+            if reward.numel() != B * N:
+                raise Cm3Error("%s takes reward [B, %d] for %d time steps, got %s" % (what, N, B, tuple(reward.shape)))
+            reward = reward.to(device=self.device, dtype=reward.dtype if reward.dtype == torch.float32 else torch.float64).contiguous()
+        if done is not None:
+            if done.numel() != B:
+                raise Cm3Error("%s takes done [B] for %d time steps, got %s" % (what, B, tuple(done.shape)))
+            done = done.reshape(-1).to(self.device)
+            done = (done.contiguous().view(torch.uint8) if done.dtype == torch.bool else (done != 0).view(torch.uint8))
+        return B, state, goals, actions, reward, done
+
+    def _q(self, what, form, per_step, state, goals, actions, reward, done, gamma, keep):
+        given = [x is not None for x in (reward, done, gamma)]
+        if any(given) and not all(given):
+            raise Cm3Error("%s: reward, done and gamma come together (the TD target) or not at all" % what)
+        if actions is None:
+            raise Cm3Error("%s needs actions" % what)
+        B, st, go, ac, rw, dn = self._stage_cols(what, state, goals, actions, reward, done)
+        R = B * per_step
+        out = {"q": torch.empty(R, 1, dtype=torch.float32, device=self.device),
+               "q64": torch.empty(R, 1, dtype=torch.float64, device=self.device)}
+        if all(given):
+            out["td"] = torch.empty(R, dtype=torch.float64, device=self.device)
+        _keep(keep, st, go, ac, rw, dn, *out.values())
+        self.enqueue(form, B, st, go, ac, rw, dn, 0.0 if gamma is None else gamma, **out)
+        return out
+
+    def q_rows(self, state, goals, actions, reward=None, done=None, gamma=None, keep=None):
+        """Q_global_1output over the B * N agent rows r = b N + n of a batch, ONE launch: s_n, g_n and a = onehot(actions[b, n]) of
+        the row's agent, s_others / a_others over the other agents in ascending order -- the feed of sess.run(Q_global_target)
+        (alg_credit.py:585-591) with state = v_global_next and actions = the target actor's samples.  Returns a dict of device
+        tensors: "q" float32 [R, 1], "q64" the same values float64 [R, 1], and with reward [B, N] (float32 / float64), done [B] and
+        gamma also "td" float64 [R] = reward + gamma * q * (1 - done), the bits of batch.td_target on q64.  keep: an optional list
+        that receives every tensor the launch touches (the staged inputs, the outputs), for whoever captures the launch."""
+        if self.kind != "global":
+            raise Cm3Error("q_rows is the Q_global form; a credit critic takes q_pairs / q_counterfactual")
+        return self._q("q_rows", _lib.CRITIC_ROWS, self.n, state, goals, actions, reward, done, gamma, keep)
+
+    def q_pairs(self, state, goals, actions, reward=None, done=None, gamma=None, keep=None):
+        """Q_credit over the B * N * N rows r = (b N + m) N + n, ONE launch: s_n, g_n, s_others of agent n, a = onehot(actions[b, m])
+        and s_m = state[b, m] -- the feed of sess.run(Q_credit_target) (alg_credit.py:616-633).  Returns as q_rows; "td" takes
+        reward[b, n] and done[b]."""
+        if self.kind != "credit":
+            raise Cm3Error("q_pairs is the Q_credit form; a global critic takes q_rows")
+        return self._q("q_pairs", _lib.CRITIC_PAIRS, self.n * self.n, state, goals, actions, reward, done, gamma, keep)
+
+    def q_counterfactual(self, state, goals, keep=None):
+        """The critic at every action, float32 [R', 5], ONE launch and no action array: a credit critic over the R' = B * N * N pairs
+        of q_pairs (alg_credit.py:730-751), a global critic with one agent over the R' = B time steps (stage 1, :716-727).  Column
+        a of a credit row holds the bits q_pairs gives that row when actions[b, m] = a."""
+        if self.kind == "global" and self.n != 1:
+            raise Cm3Error("q_counterfactual of a global critic is the one-agent (stage 1) form")
+        B, st, go, _, _, _ = self._stage_cols("q_counterfactual", state, goals)
+        per_step = 1 if self.kind == "global" else self.n * self.n
+        q = torch.empty(B * per_step, N_ACTIONS, dtype=torch.float32, device=self.device)
+        _keep(keep, st, go, q)
+        self.enqueue(_lib.CRITIC_CF, B, st, go, q=q)
+        return q

@@ -127,6 +127,7 @@ struct KernelVariant {
   int prec;            // actor kernels: 0 float32, 1 bf16, 2 split float16 (-1: not a template parameter)
   int rec;             // pair step kernel: 1 = the packed-live-record variant
   int counted;         // actor rows kernels: 1 = the launch read and advanced its own draw counter
+  const char *tail;    // critic kernels: ",kind=..,form=.." (a string literal; NULL: nothing)
 };
 KernelVariant &last_variant();  // thread-local (util.hip)
 static inline void note_variant(const char *kernel, int real_bytes, int n, int waves, int fused, int sp, int live, int tu,
@@ -145,8 +146,10 @@ static inline void note_variant(const char *kernel, int real_bytes, int n, int w
   v.prec = prec;
   v.rec = rec;
   v.counted = 0;
+  v.tail = nullptr;
 }
 static inline void note_counted(bool counted) { last_variant().counted = counted ? 1 : 0; }
+static inline void note_tail(const char *tail) { last_variant().tail = tail; }
 
 #define CM3_HIP_CHECK(expr)                                                                  \
   do {                                                                                       \

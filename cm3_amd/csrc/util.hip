@@ -11,7 +11,7 @@ char *last_error_buf() {
 }
 
 KernelVariant &last_variant() {
-  static thread_local KernelVariant v = {"none", 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0};
+  static thread_local KernelVariant v = {"none", 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0, 0, nullptr};
   return v;
 }
 
@@ -167,10 +167,10 @@ const char *cm3_last_kernel_variant(void) {
   const cm3::KernelVariant &v = cm3::last_variant();
   static const char *const sp[] = {"plain", "nt", "wt"};
   static const char *const prec[] = {"", ",prec=f32", ",prec=bf16", ",prec=f16x3"};  // (the actor kernels only)
-  snprintf(buf, sizeof(buf), "%s<%s,N=%d,waves=%d,fused=%d,sp=%s,live=%d,early=%d,g=%d,tu=%s%s%s%s>", v.kernel,
+  snprintf(buf, sizeof(buf), "%s<%s,N=%d,waves=%d,fused=%d,sp=%s,live=%d,early=%d,g=%d,tu=%s%s%s%s%s>", v.kernel,
            v.real_bytes == 4 ? "f32" : (v.real_bytes == 8 ? "f64" : "-"), v.n, v.waves, v.fused, sp[v.sp >= 0 && v.sp <= 2 ? v.sp : 0],
            v.live, v.early, v.g, v.tu ? "ilp" : "default", prec[v.prec >= 0 && v.prec <= 2 ? v.prec + 1 : 0], v.rec ? ",rec=1" : "",
-           v.counted ? ",counted" : "");
+           v.counted ? ",counted" : "", v.tail ? v.tail : "");
   return buf;
 }
 

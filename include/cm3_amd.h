@@ -61,6 +61,9 @@ extern "C" {
                                   cm3_qmix_td_target_f64 (the QMIX TD target): the data side of alg_qmix.train_step; additive.
                                   cm3_qmix_checkers_rows_f32 (the Checkers QMIX agent network over transition rows, argmax head): the
                                   data side of alg_qmix_checkers.train_step; additive.
+                                  cm3_critic_particle_packed_bytes / _pack / _rows_f32 (the CM3 particle critics Q_global_1output and
+                                  Q_credit over transition rows decoded from a batch's base columns, with the TD target): the critic
+                                  evaluations of alg_credit.train_step that carry no gradient; additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
@@ -521,6 +524,79 @@ typedef struct {
  * requested, n_rows <= 0 or more than 64 * (2^31 - 1), a misaligned input or onehot pointer.  cm3_last_kernel_variant() names the
  * launch k_qmix_particle_rows<f32,N=..>. */
 int cm3_qmix_particle_rows_f32(const cm3_actor_particle_desc *desc, const void *packed, const cm3_qmix_rows *rows, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CM3 particle critics over TRANSITION rows (part of ABI 9, additive): networks.Q_global_1output (networks.py:97-122) and
+ * networks.Q_credit (:186-211) -- the evaluations of alg_credit.train_step that carry no gradient (Q_global_target :597,
+ * Q_credit_target :620-640, the counterfactual Q_credit over every action :730-751, at one agent the counterfactual Q_global).
+ * Float32 weights, row-major [in][out] as the TF variables of a scope "Q_global_main/..." / "Q_credit_target/..." are shaped:
+ *   w_b1    Q_branch1/kernel [11][64]           b_b1  Q_branch1/bias [64]          (input = concat(s_n[4], g_n[2], a[5]))
+ *   w_b1_h2 W_branch1_h2 [64][64]
+ *   w_b2    stage-2/Q_branch2/kernel [K2][128]  b_b2  stage-2/Q_branch2/bias [128]  w_b2_h2 stage-2/W_branch2_h2 [128][64]
+ *             global: K2 = 9 (N-1), input concat(s_others[4(N-1)], a_others[5(N-1)]); credit: K2 = 4 N, concat(s_m[4], s_others)
+ *   w_out   Q_out/kernel [64][1]                (h2 and out have no bias)
+ * The three stage-2 tensors are read at stage 2 only.  kind global: stage 1 with one agent, stage 2 with more; kind credit: stage 2
+ * with more than one agent.
+ * ---------------------------------------------------------------------------------------- */
+#define CM3_CRITIC_GLOBAL 0
+#define CM3_CRITIC_CREDIT 1
+typedef struct {
+  int32_t n_agents;              /* 1..CM3_MAX_AGENTS */
+  int32_t stage;                 /* 1 / 2 */
+  int32_t kind;                  /* CM3_CRITIC_GLOBAL / CM3_CRITIC_CREDIT */
+  int32_t n_h1_1, n_h1_2, n_h2;  /* 64 / 128 / 64 */
+} cm3_critic_particle_desc;
+
+typedef struct {
+  const float *w_b1, *b_b1, *w_b1_h2, *w_b2, *b_b2, *w_b2_h2, *w_out;
+  const void *packed; /* kernel-layout copy written by cm3_critic_particle_pack (cm3_critic_particle_packed_bytes() bytes, 16-byte
+                         aligned); the rows launch reads ONLY this buffer, re-pack after every weight update */
+} cm3_critic_particle_weights;
+
+/* The launch takes NO tiled feed: its inputs are the base columns of a batch of n_steps transitions, and a row's inputs are decoded
+ * from the row number by `form` (s_others / a_others run over the agents j != n in ascending order):
+ *   CM3_CRITIC_ROWS  (global)  r = b N + n             s_n, g_n of (b, n); a = onehot(actions[b][n])
+ *   CM3_CRITIC_PAIRS (credit)  r = (b N + m) N + n     s_n, g_n, s_others of n; a = onehot(actions[b][m]), s_m = state[b][m]
+ *   CM3_CRITIC_CF              r = r' 5 + a            a = row a of eye(5), no action array read; credit: r' = the PAIRS index;
+ *                                                      global with one agent: r' = b
+ * Every output is optional, at least one is required; rows at or past the row count n_steps * N (* N) (* 5) are not written:
+ *   q    float32 [R]     q64  float64 [R], the same value widened
+ *   td   float64 [R] = reward[b][n] + gamma * q * (1 - done[b]), in the order and bits of cm3_td_target_f64 applied to q64 (ROWS and
+ *        PAIRS only)
+ * Every contraction is k-ordered: a row's bits depend on neither its place in a workgroup nor the row count, and a PAIRS row equals
+ * the CF row of the same (b, m, n) at a = actions[b][m].  (Anonymous struct tags, like cm3_qmix_rows.) */
+#define CM3_CRITIC_ROWS 0
+#define CM3_CRITIC_PAIRS 1
+#define CM3_CRITIC_CF 2
+typedef struct {
+  int32_t form;             /* CM3_CRITIC_ROWS / _PAIRS / _CF */
+  int32_t reward_f64;       /* reward holds float64 (else float32) */
+  const float *state;       /* [n_steps][N][4], 16-byte aligned */
+  const float *goals;       /* [n_steps][N][2],  8-byte aligned */
+  const int32_t *actions;   /* [n_steps][N], values 0..4 (ROWS, PAIRS) */
+  const void *reward;       /* [n_steps][N] (td) */
+  const uint8_t *done;      /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *q;
+  double *q64;
+  double *td;
+  int64_t n_steps;
+} cm3_critic_rows;
+
+/* 0 for an agent count outside 1..10, an unknown kind, and kind credit with one agent */
+size_t cm3_critic_particle_packed_bytes(int32_t n_agents, int32_t kind);
+/* Re-arranges the TensorFlow-shaped weights into the rows kernel's per-lane operand order: one small launch per weight update, on
+ * persistent tensors (capturable).  CM3_ERR_INVALID: the descriptor checks below, null weights / packed, a missing tensor. */
+int cm3_critic_particle_pack(const cm3_critic_particle_desc *desc, const cm3_critic_particle_weights *weights, void *packed,
+                             void *stream);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device: null desc / weights / rows,
+ * weights->packed NULL, n_agents outside 1..10, an unknown kind or stage, kind credit with one agent or stage 1, kind global with a
+ * stage that does not go with the agent count, other widths than 64/128/64, a form the kind does not have, n_steps <= 0 or a row
+ * count above 2^31 - 1, a missing input the form needs (state, goals; actions for ROWS / PAIRS; reward and done with td), no
+ * output requested, td with CF, a misaligned pointer.  cm3_last_kernel_variant() names the launch
+ * k_critic_particle_rows<f32,N=..,...,kind=..,form=..>. */
+int cm3_critic_particle_rows_f32(const cm3_critic_particle_desc *desc, const cm3_critic_particle_weights *weights,
+                                 const cm3_critic_rows *rows, void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
