@@ -32,6 +32,9 @@ def __getattr__(name):
     if name == "ParticleCritic":
         from .critic import ParticleCritic
         return ParticleCritic
+    if name == "CheckersCritic":
+        from .critic import CheckersCritic
+        return CheckersCritic
     if name == "ParticleQmixAgent":
         from .qmix import ParticleQmixAgent
         return ParticleQmixAgent

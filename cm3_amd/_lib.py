@@ -211,6 +211,23 @@ class CriticRows(ctypes.Structure):
                 ("n_steps", c_int64)]
 
 
+class CriticCheckersDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "stage", "kind", "grid_h", "grid_w", "grid_c", "win_h", "win_w", "win_c", "n_h1_1",
+                                       "n_h1_2", "n_h2")]
+
+
+class CriticCheckersWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("conv_w", "conv_b", "conv_o_w", "conv_o_b", "w_b1", "b_b1", "w_b1_h2", "w_b2", "b_b2", "w_b2_h2",
+                                        "w_out", "b_out", "packed")]
+
+
+class CriticCheckersRows(ctypes.Structure):
+    # (cm3_critic_checkers_rows: the base columns cm3_critic_checkers_rows_f32 decodes its rows from, and its optional outputs)
+    _fields_ = ([(n, c_int32) for n in ("form", "reward_f64", "grid_f64", "windows_f64", "goals_onehot", "reserved")]
+                + [(n, c_void_p) for n in ("grid", "vec", "goals", "actions", "windows", "obs_self_v", "reward", "done")]
+                + [("gamma", c_double), ("q", c_void_p), ("q64", c_void_p), ("td", c_void_p), ("n_steps", c_int64)])
+
+
 CRITIC_GLOBAL, CRITIC_CREDIT = 0, 1
 CRITIC_ROWS, CRITIC_PAIRS, CRITIC_CF = 0, 1, 2
 
@@ -283,6 +300,9 @@ SYMBOLS = {
     "cm3_critic_particle_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "cm3_critic_particle_pack": (ctypes.c_int, [P(CriticParticleDesc), P(CriticParticleWeights), c_void_p, c_void_p]),
     "cm3_critic_particle_rows_f32": (ctypes.c_int, [P(CriticParticleDesc), P(CriticParticleWeights), P(CriticRows), c_void_p]),
+    "cm3_critic_checkers_packed_bytes": (c_size_t, [c_int32, c_int32]),
+    "cm3_critic_checkers_pack": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), c_void_p, c_void_p]),
+    "cm3_critic_checkers_rows_f32": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), P(CriticCheckersRows), c_void_p]),
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
     "cm3_qmix_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64,
                                               c_void_p]),

@@ -265,7 +265,7 @@ class OnPolicyPhasePlan(object):
     Every tensor the actors' calls allocate for a captured launch is held next to the step's calls (self._keep[k]) for as long as
     the graph lives.  Without actors nothing changes and no counter is made.
 
-    q_global_target / q_credit_target / q_credit: the ParticleCritics of train_step_feeds (particle rollouts only); their launches
+    q_global_target / q_credit_target / q_credit: the ParticleCritics (over a CheckersRollout: CheckersCritics) of train_step_feeds; their launches
     -- the three evaluations and the pack launch behind Q_credit_op -- become part of the replayed graph, and their tensors are held
     in self._keep[k] like the actors'.  `run` must write the Q_credit_main variables into q_credit.w[...] in place."""
 
@@ -503,8 +503,11 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     cm3_amd.actor.RowsDrawCounter, the device counter a captured launch advances itself), keep the list that receives every tensor
     sample_rows / probs_rows allocate for their launches (OnPolicyPhasePlan holds them while it replays the capture).
 
-    q_global_target / q_credit_target / q_credit (particle env, CUDA columns): cm3_amd.critic.ParticleCritics holding the
-    Q_global_target / Q_credit_target / Q_credit_main weights, for the batch's agent count.  With one given, `run` is NOT called for
+    q_global_target / q_credit_target / q_credit (CUDA columns): cm3_amd.critic.ParticleCritics -- for env="checkers" CheckersCritics;
+    a critic of the other env's class is refused -- holding the Q_global_target / Q_credit_target / Q_credit_main weights, for the
+    batch's agent count.  On Checkers the launches read next_grid / next_vec / next_obs_self_t / next_obs_self_v (the two targets,
+    with local_rewards and done) and grid / vec / obs_self_t / obs_self_v (the counterfactual) next to goals and the actions; the
+    window and obs_self_v of a pair row are agent m's, as the reference repeats them.  With one given, `run` is NOT called for
     its op (the (ops, feed) entry still appears in the list) and the evaluation is one launch on the batch's base columns:
       ["Q_global_target"]  q_global_target.q_rows(v_global_next, goals, a', reward_local, done, gamma); its "td" is the
                            Q_global_td_target feed (kind "global")
@@ -522,20 +525,24 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     calls = []
     critics = (("q_global_target", q_global_target), ("q_credit_target", q_credit_target), ("q_credit", q_credit))
     if any(c is not None for _, c in critics):
-        from .critic import ParticleCritic
-        if checkers:
-            raise ValueError("train_step_feeds: q_global_target / q_credit_target / q_credit are ParticleCritics; env='checkers' has no "
-                             "device critics")
-        n_batch = cols["v_global"].shape[1]
+        from .critic import CheckersCritic, ParticleCritic
+        cls = CheckersCritic if checkers else ParticleCritic
+        if checkers:        # (before the columns are read)
+            for name, c in critics:
+                if isinstance(c, ParticleCritic):
+                    raise ValueError("train_step_feeds: %s is a ParticleCritic; env='checkers' has no device critics of that class, "
+                                     "pass CheckersCritics" % name)
+        base = cols["vec" if checkers else "v_global"]
+        n_batch = base.shape[1]
         for name, c in critics:
             if c is None:
                 continue
             want = "global" if (name == "q_global_target" or n_batch == 1) else "credit"
-            if not isinstance(c, ParticleCritic) or c.kind != want or c.n != n_batch:
-                raise ValueError("train_step_feeds: %s takes a ParticleCritic of kind %r for %d agents, got %s"
-                                 % (name, want, n_batch, "a %s" % type(c).__name__ if not isinstance(c, ParticleCritic)
+            if not isinstance(c, cls) or c.kind != want or c.n != n_batch:
+                raise ValueError("train_step_feeds: %s takes a %s of kind %r for %d agents, got %s"
+                                 % (name, cls.__name__, want, n_batch, "a %s" % type(c).__name__ if not isinstance(c, cls)
                                     else "kind %r for %d agents" % (c.kind, c.n)))
-        if not cols["v_global"].is_cuda:
+        if not base.is_cuda:
             raise ValueError("train_step_feeds: q_global_target / q_credit_target / q_credit evaluate device columns; call without "
                              "them for host tensors")
     if target_actor is not None or actor is not None:
@@ -554,6 +561,13 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     def call(ops, feed, launch=True):
         calls.append((ops, feed))
         return run(ops, feed) if launch else None
+
+    def critic_cols(nxt):
+        """the base columns a device critic decodes its rows from, as (those before the actions, those after them)"""
+        if checkers:
+            pre = "next_" if nxt else ""
+            return (cols[pre + "grid"], cols[pre + "vec"], goals), (cols[pre + "obs_self_t"], cols[pre + "obs_self_v"])
+        return (v_global_next if nxt else v_global, goals), ()
 
     if checkers:
         # float64 columns on the GPU: the static feeds come from three launches of cm3_rows_tile (checkers_static_feeds_device); host
@@ -640,7 +654,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                     state_env_next if checkers else None, obs_self_t_next if checkers else None, obs_self_v_next if checkers else None)
     if q_global_target is not None:     # one launch on the base columns: Q and the TD target
         call(["Q_global_target"], feed, launch=False)
-        td = q_global_target.q_rows(v_global_next, goals, acts, reward_local, cols["done"], gamma, **probs_kw)["td"]
+        head, tail = critic_cols(True)
+        td = q_global_target.q_rows(*head, acts, *tail, reward_local, cols["done"], gamma, **probs_kw)["td"]
     else:
         q_t = call(["Q_global_target"], feed)[0]
         td = td_target(reward_local, q_t, not_done, gamma) if S is not None else reward_local.to(f64) + gamma * q_t.reshape(-1) * not_done
@@ -666,7 +681,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                     else with_env(feed, S["env_next_rep"], S["ot_next_rep"], S["ov_next_rep"]))
         if q_credit_target is not None:
             call(["Q_credit_target"], feed, launch=False)
-            td_c = q_credit_target.q_pairs(v_global_next, goals, acts, reward_local, cols["done"], gamma, **probs_kw)["td"]
+            head, tail = critic_cols(True)
+            td_c = q_credit_target.q_pairs(*head, acts, *tail, reward_local, cols["done"], gamma, **probs_kw)["td"]
         else:
             qc_t = call(["Q_credit_target"], feed)[0]
         if S is None:
@@ -720,7 +736,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
             feed = with_env(feed, rep_a(state_env), rep_a(obs_self_t), rep_a(obs_self_v))
         if q_credit is not None:
             call(["Q_global"], feed, launch=False)
-            q_cf = q_credit.q_counterfactual(v_global, goals, **probs_kw)
+            head, tail = critic_cols(False)
+            q_cf = q_credit.q_counterfactual(*head, *tail, **probs_kw)
         else:
             q_cf = call(["Q_global"], feed)[0].reshape(n_steps, l_action)
     elif use_Q_credit:
@@ -737,7 +754,8 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                     else with_env(feed, S["cf_env"], S["cf_ot"], S["cf_ov"]))
         if q_credit is not None:
             call(["Q_credit"], feed, launch=False)
-            q_cf = q_credit.q_counterfactual(v_global, goals, **probs_kw)
+            head, tail = critic_cols(False)
+            q_cf = q_credit.q_counterfactual(*head, *tail, **probs_kw)
         else:
             q_cf = call(["Q_credit"], feed)[0].reshape(n_steps * N * N, l_action)
     else:

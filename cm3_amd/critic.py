@@ -1,4 +1,4 @@
-"""ParticleCritic -- the reference's particle critics evaluated on the device over the rows of a sampled batch.
+"""ParticleCritic and CheckersCritic -- the reference's CM3 critics evaluated on the device over the rows of a sampled batch.
 
     reference                                                    here
     ---------------------------------------------------------   -----------------------------------------------
@@ -21,6 +21,10 @@ Weights stay float32 [in][out] as TensorFlow shapes them, in ``self.w`` under sh
 the main critics can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors,
 capturable) then makes the next launch follow them.  Scope prefixes "Q_global_main/", "Q_global_target/", "Q_credit_main/",
 "Q_credit_target/" and a ":0" suffix of the keys are ignored.
+
+CheckersCritic (below) is the Checkers twin: networks.Q_global_checkers / Q_credit_checkers at the widths of
+config_checkers_stage{1,2}.json, one launch of cm3_critic_checkers_rows_f32 per method on the base columns grid, vec, goals, actions,
+obs_self_t, obs_self_v.
 """
 import ctypes
 
@@ -204,4 +208,207 @@ class ParticleCritic(object):
         q = torch.empty(B * per_step, N_ACTIONS, dtype=torch.float32, device=self.device)
         _keep(keep, st, go, q)
         self.enqueue(_lib.CRITIC_CF, B, st, go, q=q)
+        return q
+
+
+# ---- Checkers -------------------------------------------------------------------------------------------------------------------------
+CK_H1_1, CK_H1_2, CK_H2 = 256, 32, 256              # Q_n_h1_1, Q_n_h1_2, Q_n_h2 of config_checkers_stage{1,2}.json
+CK_MAX_AGENTS = 8                                   # the Checkers actor's range
+CK_GRID, CK_WINDOW = (3, 9, 2), (5, 5, 3)
+CK_NAMES = {"conv_w": "conv/Conv/weights", "conv_b": "conv/Conv/biases", "conv_o_w": "conv_o/Conv/weights",
+            "conv_o_b": "conv_o/Conv/biases", "w_b1": "Q_branch1/kernel", "b_b1": "Q_branch1/bias", "w_b1_h2": "W_branch1_h2",
+            "w_b2": "stage-2/Q_branch2/kernel", "b_b2": "stage-2/Q_branch2/bias", "w_b2_h2": "stage-2/W_branch2_h2",
+            "w_out": "Q_out/kernel", "b_out": "Q_out/bias"}
+
+
+def checkers_weight_shapes(n_agents, kind, stage):
+    """short name -> shape of the TF variable, for the tensors a Checkers critic of this kind / stage has"""
+    shapes = {"conv_w": (3, 5, 2, 4), "conv_b": (4,), "conv_o_w": (3, 3, 3, 6), "conv_o_b": (6,), "w_b1": (273, CK_H1_1),
+              "b_b1": (CK_H1_1,), "w_b1_h2": (CK_H1_1, CK_H2), "w_out": (CK_H2, 1), "b_out": (1,)}
+    if stage > 1:
+        k2 = 9 * (n_agents - 1) if kind == "global" else 4 * n_agents
+        shapes.update({"w_b2": (k2, CK_H1_2), "b_b2": (CK_H1_2,), "w_b2_h2": (CK_H1_2, CK_H2)})
+    return shapes
+
+
+class CheckersCritic(object):
+    """The reference's Checkers critics on the device over the rows of a sampled batch, the twin of ParticleCritic.
+
+        reference                                                        here
+        -------------------------------------------------------------   ------------------------------------------------
+        networks.Q_global_checkers (networks.py:155-183)                 CheckersCritic(weights, n_agents, kind="global")
+        networks.Q_credit_checkers (:244-272)                            CheckersCritic(weights, n_agents, kind="credit")
+        sess.run(Q_global_target) + TD target                            critic.q_rows(next_grid, next_vec, goals, a', next_obs_self_t,
+          (alg_credit_checkers.py:558-572)                                 next_obs_self_v, reward, done, gamma)
+        sess.run(Q_credit_target) + TD target (:611-632)                 critic.q_pairs(...the same arguments...)
+        sess.run(Q_credit, n x n x l_action feed) (:738-747;             critic.q_counterfactual(grid, vec, goals, obs_self_t, obs_self_v)
+          stage 1: sess.run(Q_global) :704-713)
+
+    Columns: grid [B, 3, 9, 2]; vec [B, N, 4]; goals one-hot [B, N, 2] or indices [B, N]; actions [B, N]; obs_self_t [B, N, 5, 5, 3]
+    (or [B, N, 75]); obs_self_v [B, N, 4] (leading dimensions may be merged).  int8 grids and windows and uint8 index goals go in as
+    they are; everything else is staged to float64 / int64 as cm3_amd.actor.stage_checkers_rows does, and rounded to float32 in the
+    kernel as the reference's tf.float32 placeholders do.  In the pair forms the window and obs_self_v of a row are agent M's (the
+    reference repeats them "indexed by m").  Weights: ``self.w`` under the short names of CK_NAMES, see ParticleCritic."""
+
+    def __init__(self, weights, n_agents, kind="global", stage=2, device="cuda:0"):
+        self.device = _lib.require_gpu(device)
+        if kind not in KINDS:
+            raise Cm3Error("kind must be one of %s" % sorted(KINDS))
+        self.kind, self.n, self.stage = kind, int(n_agents), int(stage)
+        if not 1 <= self.n <= CK_MAX_AGENTS:
+            raise Cm3Error("n_agents must be in 1..%d" % CK_MAX_AGENTS)
+        if kind == "credit" and (self.n == 1 or self.stage != 2):
+            raise Cm3Error("Q_credit_checkers exists at stage 2 with more than one agent only (n_agents %d, stage %d)"
+                           % (self.n, self.stage))
+        if self.stage not in (1, 2) or (self.stage == 1) != (self.n == 1):
+            raise Cm3Error("Q_global_checkers runs at stage 1 with one agent and at stage 2 with more (n_agents %d, stage %d)"
+                           % (self.n, self.stage))
+        src = {_canon(k): v for k, v in weights.items()}
+        self.w = {}
+        for short, shape in checkers_weight_shapes(self.n, kind, self.stage).items():
+            name = CK_NAMES[short]
+            if name not in src:
+                raise Cm3Error("missing critic weight %r" % name)
+            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise Cm3Error("critic weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            self.w[short] = t.to(self.device)
+        self._wt = _lib.CriticCheckersWeights()
+        for short in CK_NAMES:
+            setattr(self._wt, short, _lib.ptr(self.w.get(short)))
+        self._lib = _lib.lib()
+        nbytes = self._lib.cm3_critic_checkers_packed_bytes(self.n, KINDS[kind])
+        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        self._wt.packed = self._packed.data_ptr()
+        self.repack()
+
+    def _desc(self):
+        d = _lib.CriticCheckersDesc()
+        d.n_agents, d.stage, d.kind = self.n, self.stage, KINDS[self.kind]
+        (d.grid_h, d.grid_w, d.grid_c), (d.win_h, d.win_w, d.win_c) = CK_GRID, CK_WINDOW
+        d.n_h1_1, d.n_h1_2, d.n_h2 = CK_H1_1, CK_H1_2, CK_H2
+        return d
+
+    def repack(self):
+        """Re-arrange the (possibly updated in place) TF-shaped weights into the rows kernel's layout, the two convolutions as
+        Toeplitz matrices: one launch."""
+        d = self._desc()
+        _lib.check(self._lib.cm3_critic_checkers_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
+                                                      _lib.current_stream_handle(self.device)))
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the critic's part of
+        list_update_target_ops, for a critic holding target weights."""
+        if not isinstance(main, CheckersCritic) or (main.n, main.kind, main.stage) != (self.n, self.kind, self.stage):
+            raise Cm3Error("soft_update_from: the main critic must be a %s CheckersCritic for %d agents at stage %d"
+                           % (self.kind, self.n, self.stage))
+        tau = float(tau)
+        for name in self.w:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
+        self.repack()
+
+    # ---- launches -------------------------------------------------------------------------------------------------------------------
+    def enqueue(self, form, n_steps, grid, vec, goals, windows, obs_self_v, actions=None, reward=None, done=None, gamma=0.0, q=None,
+                q64=None, td=None, stream=None):
+        """Raw launch of cm3_critic_checkers_rows_f32 on contiguous device tensors: grid / windows int8 or float64, vec / obs_self_v
+        float64, goals uint8 indices or int64 one-hot, actions int32, reward float32 or float64, done uint8; every output is
+        optional, one is required."""
+        r = _lib.CriticCheckersRows()
+        r.form, r.n_steps = int(form), int(n_steps)
+        r.grid_f64 = 0 if grid.dtype == torch.int8 else 1
+        r.windows_f64 = 0 if windows.dtype == torch.int8 else 1
+        r.goals_onehot = 0 if goals.dtype == torch.uint8 else 1
+        r.grid, r.vec, r.goals, r.actions = _lib.ptr(grid), _lib.ptr(vec), _lib.ptr(goals), _lib.ptr(actions)
+        r.windows, r.obs_self_v = _lib.ptr(windows), _lib.ptr(obs_self_v)
+        r.reward, r.done = _lib.ptr(reward), _lib.ptr(done)
+        r.reward_f64 = 1 if (reward is not None and reward.dtype == torch.float64) else 0
+        r.gamma = float(gamma)
+        r.q, r.q64, r.td = _lib.ptr(q), _lib.ptr(q64), _lib.ptr(td)
+        d = self._desc()
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_critic_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def _stage_cols(self, what, grid, vec, goals, obs_self_t, obs_self_v, actions=None, reward=None, done=None):
+        """(B, grid, vec, goals, windows, obs_self_v, actions, reward, done) contiguous on the critic's device in the forms the kernel
+        reads: int8 grids / windows and uint8 index goals as they are, everything else float64 / int64 one-hot."""
+        N = self.n
+        if vec.shape[-1] != 4 or (vec.numel() // 4) % N or vec.numel() == 0:
+            raise Cm3Error("%s takes vec [B, %d, 4], got %s" % (what, N, tuple(vec.shape)))
+        B = vec.numel() // (4 * N)
+        if (grid.numel() != B * 54 or obs_self_t.numel() != B * N * 75 or obs_self_v.numel() != B * N * 4
+                or goals.numel() not in (B * N, B * N * 2)):
+            raise Cm3Error("%s takes grid [B, 3, 9, 2], goals [B, %d, 2] (or [B, %d]), obs_self_t [B, %d, 5, 5, 3] and obs_self_v "
+                           "[B, %d, 4] for %d time steps, got %s, %s, %s, %s"
+                           % (what, N, N, N, N, B, tuple(grid.shape), tuple(goals.shape), tuple(obs_self_t.shape),
+                              tuple(obs_self_v.shape)))
+        stage = lambda t, dt: t.to(device=self.device, dtype=dt).contiguous()      # noqa: E731
+        narrow = lambda t: stage(t, torch.int8 if t.dtype == torch.int8 else torch.float64)      # noqa: E731
+        if goals.numel() == B * N:      # indices (a one-hot column has twice as many elements)
+            go = (stage(goals, torch.uint8) if goals.dtype == torch.uint8
+                  else torch.nn.functional.one_hot(goals.to(self.device).long(), 2).contiguous())
+        else:
+            go = stage(goals, torch.int64)
+        if actions is not None:
+            if actions.numel() != B * N:
+                raise Cm3Error("%s takes actions [B, %d] for %d time steps, got %s" % (what, N, B, tuple(actions.shape)))
+            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if reward is not None:
+            if reward.numel() != B * N:
+                raise Cm3Error("%s takes reward [B, %d] for %d time steps, got %s" % (what, N, B, tuple(reward.shape)))
+            reward = reward.to(device=self.device, dtype=reward.dtype if reward.dtype == torch.float32 else torch.float64).contiguous()
+        if done is not None:
+            if done.numel() != B:
+                raise Cm3Error("%s takes done [B] for %d time steps, got %s" % (what, B, tuple(done.shape)))
+            done = done.reshape(-1).to(self.device)
+            done = (done.contiguous().view(torch.uint8) if done.dtype == torch.bool else (done != 0).view(torch.uint8))
+        return B, narrow(grid), stage(vec, torch.float64), go, narrow(obs_self_t), stage(obs_self_v, torch.float64), actions, reward, done
+
+    def _q(self, what, form, per_step, grid, vec, goals, actions, obs_self_t, obs_self_v, reward, done, gamma, keep):
+        given = [x is not None for x in (reward, done, gamma)]
+        if any(given) and not all(given):
+            raise Cm3Error("%s: reward, done and gamma come together (the TD target) or not at all" % what)
+        if actions is None:
+            raise Cm3Error("%s needs actions" % what)
+        B, gr, ve, go, wi, ov, ac, rw, dn = self._stage_cols(what, grid, vec, goals, obs_self_t, obs_self_v, actions, reward, done)
+        R = B * per_step
+        out = {"q": torch.empty(R, 1, dtype=torch.float32, device=self.device),
+               "q64": torch.empty(R, 1, dtype=torch.float64, device=self.device)}
+        if all(given):
+            out["td"] = torch.empty(R, dtype=torch.float64, device=self.device)
+        _keep(keep, gr, ve, go, wi, ov, ac, rw, dn, *out.values())
+        self.enqueue(form, B, gr, ve, go, wi, ov, ac, rw, dn, 0.0 if gamma is None else gamma, **out)
+        return out
+
+    def q_rows(self, grid, vec, goals, actions, obs_self_t, obs_self_v, reward=None, done=None, gamma=None, keep=None):
+        """Q_global_checkers over the B * N agent rows r = b N + n of a batch, ONE launch: the grid of step b; s_n, g_n, window, v_obs
+        and a = onehot(actions[b, n]) of the row's agent; s_others / a_others over the other agents in ascending order -- the feed of
+        sess.run(Q_global_target) (alg_credit_checkers.py:558-569) with the next-step columns and the target actor's samples.
+        Returns a dict of device tensors: "q" float32 [R, 1], "q64" the same values float64 [R, 1], and with reward [B, N] (float32 /
+        float64), done [B] and gamma also "td" float64 [R] = reward + gamma * q * (1 - done), the bits of batch.td_target on q64.
+        keep: an optional list that receives every tensor the launch touches, for whoever captures the launch."""
+        if self.kind != "global":
+            raise Cm3Error("q_rows is the Q_global form; a credit critic takes q_pairs / q_counterfactual")
+        return self._q("q_rows", _lib.CRITIC_ROWS, self.n, grid, vec, goals, actions, obs_self_t, obs_self_v, reward, done, gamma, keep)
+
+    def q_pairs(self, grid, vec, goals, actions, obs_self_t, obs_self_v, reward=None, done=None, gamma=None, keep=None):
+        """Q_credit_checkers over the B * N * N rows r = (b N + m) N + n, ONE launch: s_n, g_n, s_others of agent n; a =
+        onehot(actions[b, m]), s_m = vec[b, m], and the window and v_obs of agent m -- the feed of sess.run(Q_credit_target)
+        (alg_credit_checkers.py:596-629).  Returns as q_rows; "td" takes reward[b, n] and done[b]."""
+        if self.kind != "credit":
+            raise Cm3Error("q_pairs is the Q_credit form; a global critic takes q_rows")
+        return self._q("q_pairs", _lib.CRITIC_PAIRS, self.n * self.n, grid, vec, goals, actions, obs_self_t, obs_self_v, reward, done,
+                       gamma, keep)
+
+    def q_counterfactual(self, grid, vec, goals, obs_self_t, obs_self_v, keep=None):
+        """The critic at every action, float32 [R', 5], ONE launch and no action array: a credit critic over the R' = B * N * N pairs
+        of q_pairs (alg_credit_checkers.py:738-747), a global critic with one agent over the R' = B time steps (stage 1, :704-713).
+        Column a of a credit row holds the bits q_pairs gives that row when actions[b, m] = a."""
+        if self.kind == "global" and self.n != 1:
+            raise Cm3Error("q_counterfactual of a global critic is the one-agent (stage 1) form")
+        B, gr, ve, go, wi, ov, _, _, _ = self._stage_cols("q_counterfactual", grid, vec, goals, obs_self_t, obs_self_v)
+        per_step = 1 if self.kind == "global" else self.n * self.n
+        q = torch.empty(B * per_step, N_ACTIONS, dtype=torch.float32, device=self.device)
+        _keep(keep, gr, ve, go, wi, ov, q)
+        self.enqueue(_lib.CRITIC_CF, B, gr, ve, go, wi, ov, q=q)
         return q

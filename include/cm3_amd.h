@@ -64,6 +64,9 @@ extern "C" {
                                   cm3_critic_particle_packed_bytes / _pack / _rows_f32 (the CM3 particle critics Q_global_1output and
                                   Q_credit over transition rows decoded from a batch's base columns, with the TD target): the critic
                                   evaluations of alg_credit.train_step that carry no gradient; additive.
+                                  cm3_critic_checkers_packed_bytes / _pack / _rows_f32 (the CM3 Checkers critics Q_global_checkers and
+                                  Q_credit_checkers over transition rows decoded from a batch's base columns, with the TD target): the
+                                  critic evaluations of alg_credit_checkers.train_step that carry no gradient; additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
@@ -597,6 +600,91 @@ int cm3_critic_particle_pack(const cm3_critic_particle_desc *desc, const cm3_cri
  * k_critic_particle_rows<f32,N=..,...,kind=..,form=..>. */
 int cm3_critic_particle_rows_f32(const cm3_critic_particle_desc *desc, const cm3_critic_particle_weights *weights,
                                  const cm3_critic_rows *rows, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CM3 Checkers critics over TRANSITION rows (part of ABI 9, additive): networks.Q_global_checkers (networks.py:155-183) and
+ * networks.Q_credit_checkers (:244-272) at the widths of config_checkers_stage{1,2}.json -- the evaluations of
+ * alg_credit_checkers.train_step that carry no gradient (Q_global_target :558-569, Q_credit_target :611-629, the counterfactual
+ * Q_credit over every action :738-747, at one agent the counterfactual Q_global :704-713).
+ * Float32 weights as the TF variables of a scope "Q_global_main/..." / "Q_credit_target/..." are shaped:
+ *   conv_w   conv/Conv/weights [3][5][2][4]      conv_b   conv/Conv/biases [4]      (SAME, over the grid [3][9][2])
+ *   conv_o_w conv_o/Conv/weights [3][3][3][6]    conv_o_b conv_o/Conv/biases [6]    (SAME, over the window [5][5][3])
+ *   w_b1     Q_branch1/kernel [273][256]         b_b1     Q_branch1/bias [256]
+ *              (input = concat(conv[108], s_n[4], g_n[2], a[5], conv_o[150], v_obs[4]), convolution outputs flattened NHWC)
+ *   w_b1_h2  W_branch1_h2 [256][256]
+ *   w_b2     stage-2/Q_branch2/kernel [K2][32]   b_b2     stage-2/Q_branch2/bias [32]   w_b2_h2 stage-2/W_branch2_h2 [32][256]
+ *              global: K2 = 9 (N-1), input concat(s_others[4(N-1)], a_others[5(N-1)]); credit: K2 = 4 N, concat(s_m[4], s_others)
+ *   w_out    Q_out/kernel [256][1]               b_out    Q_out/bias [1]            (h2 has no bias)
+ * The three stage-2 tensors are read at stage 2 only.  kind global: stage 1 with one agent, stage 2 with more; kind credit: stage 2
+ * with more than one agent.  Agent counts 1..8 (the Checkers actor's range).  CM3_CRITIC_GLOBAL / _CREDIT and CM3_CRITIC_ROWS /
+ * _PAIRS / _CF are those of the particle critics above.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_agents;                 /* 1..8 */
+  int32_t stage;                    /* 1 / 2 */
+  int32_t kind;                     /* CM3_CRITIC_GLOBAL / CM3_CRITIC_CREDIT */
+  int32_t grid_h, grid_w, grid_c;   /* 3 / 9 / 2 */
+  int32_t win_h, win_w, win_c;      /* 5 / 5 / 3 */
+  int32_t n_h1_1, n_h1_2, n_h2;     /* 256 / 32 / 256 */
+} cm3_critic_checkers_desc;
+
+typedef struct {
+  const float *conv_w, *conv_b, *conv_o_w, *conv_o_b;
+  const float *w_b1, *b_b1, *w_b1_h2, *w_b2, *b_b2, *w_b2_h2, *w_out, *b_out;
+  const void *packed; /* kernel-layout copy written by cm3_critic_checkers_pack (cm3_critic_checkers_packed_bytes() bytes, 16-byte
+                         aligned); the rows launch reads ONLY this buffer, re-pack after every weight update */
+} cm3_critic_checkers_weights;
+
+/* The launch takes NO tiled feed: its inputs are the base columns of a batch of n_steps transitions, and a row's inputs are decoded
+ * from the row number by `form` (s_others / a_others run over the agents j != n in ascending order; the grid is that of step b):
+ *   CM3_CRITIC_ROWS  (global)  r = b N + n             s_n, g_n, window, v_obs of (b, n); a = onehot(actions[b][n])
+ *   CM3_CRITIC_PAIRS (credit)  r = (b N + m) N + n     s_n, g_n, s_others of n; a = onehot(actions[b][m]), s_m = vec[b][m]; the
+ *                                                      window and v_obs are those of agent M (the reference repeats obs_self_t /
+ *                                                      obs_self_v "indexed by m")
+ *   CM3_CRITIC_CF              r = r' 5 + a            a = row a of eye(5), no action array read; credit: r' = the PAIRS index;
+ *                                                      global with one agent: r' = b
+ * float64 inputs are rounded to float32 in the kernel, as the reference's tf.float32 placeholders do.  Outputs as in
+ * cm3_critic_rows: q float32 [R], q64 the same value widened, td float64 [R] = reward[b][n] + gamma * q * (1 - done[b]) in the bits
+ * of cm3_td_target_f64 applied to q64 (ROWS and PAIRS only); at least one is required; rows past the row count are not written.
+ * Every contraction is k-ordered: a row's bits depend on neither its place in a workgroup nor the row count, and a PAIRS row equals
+ * the CF row of the same (b, m, n) at a = actions[b][m]. */
+typedef struct {
+  int32_t form;             /* CM3_CRITIC_ROWS / _PAIRS / _CF */
+  int32_t reward_f64;       /* reward holds float64 (else float32) */
+  int32_t grid_f64;         /* grid holds float64 (else int8) */
+  int32_t windows_f64;      /* windows holds float64 (else int8) */
+  int32_t goals_onehot;     /* goals holds int64 one-hot [n_steps][N][2] (else uint8 indices [n_steps][N]) */
+  int32_t reserved;         /* 0 */
+  const void *grid;         /* [n_steps][3][9][2] */
+  const double *vec;        /* [n_steps][N][4] agent state */
+  const void *goals;
+  const int32_t *actions;   /* [n_steps][N], values 0..4 (ROWS, PAIRS) */
+  const void *windows;      /* [n_steps][N][75] (obs_self_t) */
+  const double *obs_self_v; /* [n_steps][N][4] */
+  const void *reward;       /* [n_steps][N] (td) */
+  const uint8_t *done;      /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *q;
+  double *q64;
+  double *td;
+  int64_t n_steps;
+} cm3_critic_checkers_rows;
+
+/* 0 for an agent count outside 1..8, an unknown kind, and kind credit with one agent */
+size_t cm3_critic_checkers_packed_bytes(int32_t n_agents, int32_t kind);
+/* Re-arranges the TensorFlow-shaped weights into the rows kernel's per-lane operand order, the two convolutions as Toeplitz
+ * matrices: one launch per weight update, on persistent tensors (capturable).  CM3_ERR_INVALID: the descriptor checks below, null
+ * weights / packed, a missing tensor. */
+int cm3_critic_checkers_pack(const cm3_critic_checkers_desc *desc, const cm3_critic_checkers_weights *weights, void *packed,
+                             void *stream);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device: null desc / weights / rows,
+ * weights->packed NULL, n_agents outside 1..8, an unknown kind or stage, kind credit with one agent or stage 1, kind global with a
+ * stage that does not go with the agent count, another geometry than 3x9x2 / 5x5x3, other widths than 256/32/256, a form the kind
+ * does not have, n_steps <= 0 or a row count above 2^31 - 1, a missing input the form needs (grid, vec, goals, windows, obs_self_v;
+ * actions for ROWS / PAIRS; reward and done with td), no output requested, td with CF, a misaligned pointer.
+ * cm3_last_kernel_variant() names the launch k_critic_checkers_rows<f32,N=..,...,kind=..,form=..>. */
+int cm3_critic_checkers_rows_f32(const cm3_critic_checkers_desc *desc, const cm3_critic_checkers_weights *weights,
+                                 const cm3_critic_checkers_rows *rows, void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
