@@ -41,4 +41,7 @@ def __getattr__(name):
     if name == "CheckersQmixAgent":
         from .qmix import CheckersQmixAgent
         return CheckersQmixAgent
+    if name == "ParticleQmixMixer":
+        from .qmix import ParticleQmixMixer
+        return ParticleQmixMixer
     raise AttributeError(name)

@@ -232,6 +232,21 @@ CRITIC_GLOBAL, CRITIC_CREDIT = 0, 1
 CRITIC_ROWS, CRITIC_PAIRS, CRITIC_CF = 0, 1, 2
 
 
+class QmixMixerParticleDesc(ctypes.Structure):
+    _fields_ = [("n_agents", c_int32), ("embed_dim", c_int32)]
+
+
+class QmixMixerParticleWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("hyper_w_1", "hyper_w_final", "hyper_b_1", "hyper_b_final_l1", "hyper_b_final", "packed")]
+
+
+class QmixMixerRows(ctypes.Structure):
+    # (cm3_qmix_mixer_rows: the base columns of cm3_qmix_mixer_particle_rows_f32 and its optional outputs)
+    _fields_ = [("reward_f64", c_int32), ("reserved", c_int32), ("state", c_void_p), ("goals", c_void_p), ("agent_qs", c_void_p),
+                ("reward", c_void_p), ("done", c_void_p), ("gamma", c_double), ("q_tot", c_void_p), ("q_tot64", c_void_p),
+                ("td", c_void_p), ("n_steps", c_int64)]
+
+
 class ActorParticleBufs(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("obs_others", "state", "goals", "meta", "episode", "actions", "probs",
                                         "epsilon_dev")]
@@ -303,6 +318,9 @@ SYMBOLS = {
     "cm3_critic_checkers_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "cm3_critic_checkers_pack": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), c_void_p, c_void_p]),
     "cm3_critic_checkers_rows_f32": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), P(CriticCheckersRows), c_void_p]),
+    "cm3_qmix_mixer_particle_packed_bytes": (c_size_t, [c_int32]),
+    "cm3_qmix_mixer_particle_pack": (ctypes.c_int, [P(QmixMixerParticleDesc), P(QmixMixerParticleWeights), c_void_p, c_void_p]),
+    "cm3_qmix_mixer_particle_rows_f32": (ctypes.c_int, [P(QmixMixerParticleDesc), P(QmixMixerParticleWeights), P(QmixMixerRows), c_void_p]),
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
     "cm3_qmix_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64,
                                               c_void_p]),

@@ -896,13 +896,13 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action):
     return calls
 
 
-def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle"):
+def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle", target_mixer=None):
     """The data side of the QMIX train_step (alg_qmix.py:338-380) from the columns of a sampled particle batch: builds, in the
     reference's order, the feed_dict of its four sess.run calls -- ["argmax_Q_target"], ["mixer_target"], ["mixer_op"],
     ["list_update_target_ops"] -- and returns the list of (ops, feed).  ``run(ops, feed)`` plays sess.run as in train_step_feeds: ops
     and placeholders are the reference's attribute names (v_state, v_goal_all, actions_1hot, obs_others, v_obs, v_goal, td_target);
-    it returns one tensor per op (None for mixer_op and list_update_target_ops).  The mixer, its target copy and the optimiser step
-    are `run`'s: nothing here evaluates or trains them.
+    it returns one tensor per op (None for mixer_op and list_update_target_ops).  The main mixer's loss, gradient and optimiser step
+    are `run`'s, and without target_mixer the target mixer's forward pass as well.
 
     Without target_agent everything is the torch composition -- the specification, pinned bit for bit to the arrays the REAL
     train_step fed (tests/golden/trainstep_qmix_particle_n*.npz); it runs on CPU tensors and calls `run` for the argmax.
@@ -911,6 +911,14 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     target_agent.greedy_rows in one launch, actions_1hot from one tiling launch, the TD target from cm3_qmix_td_target_f64.
     The soft update of the agent's target weights -- the agent half of list_update_target_ops -- is left to the caller:
     ``target_agent.soft_update_from(main_agent, tau)`` after this function returns.
+    With target_mixer as well (a ParticleQmixMixer holding the Mixer_target weights; particle only), `run` is NOT called for
+    mixer_target either (its (ops, feed) entry still appears, in the same place with the same keys): greedy_rows runs once with
+    q_max, and ONE launch of target_mixer.q_tot on v_global_next, goals and those Q values gives mixer_op's td_target, so `run` is
+    left with what needs a gradient or an optimiser.  The caller's contract: `run` trains the main mixer (mixer_op) and writes the
+    trained variables into its ParticleQmixMixer in place; after this function returns the caller does
+    ``target_mixer.soft_update_from(main_mixer, tau)`` next to ``target_agent.soft_update_from(main_agent, tau)`` -- the two halves of
+    list_update_target_ops.  Refused with a ValueError that names the remedy: target_mixer without target_agent, host columns, a
+    mixer for another agent count, an object that is no ParticleQmixMixer, env="checkers".  Without target_mixer nothing changes.
 
     env="checkers": the same four calls of alg_qmix_checkers.train_step (alg_qmix_checkers.py:342-393) from the columns of a sampled
     Checkers batch; placeholders state_env, v_state, v_goal_all, actions_1hot, actions_prev, obs_others, obs_self_t, obs_self_v,
@@ -918,9 +926,24 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     in mixer_op the one-hot actions_prev column.  target_agent: a CheckersQmixAgent holding the Agent_target weights; both one-hot
     action feeds come from one tiling launch.  Pinned to tests/golden/trainstep_qmix_checkers_n*.npz."""
     if env == "checkers":
+        if target_mixer is not None:
+            raise ValueError("qmix_train_step_feeds: env='checkers' has no device mixer (the Checkers mixer is not built); call "
+                             "without target_mixer, `run` answers mixer_target")
         return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action)
     if env != "particle":
         raise ValueError("qmix_train_step_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
+    if target_mixer is not None:
+        from .qmix import ParticleQmixMixer
+        n_batch = cols["v_global"].shape[1]
+        if not isinstance(target_mixer, ParticleQmixMixer) or target_mixer.n != n_batch:
+            raise ValueError("qmix_train_step_feeds: target_mixer takes a ParticleQmixMixer for %d agents (the batch's count), got %s"
+                             % (n_batch, "one for %d agents" % target_mixer.n if isinstance(target_mixer, ParticleQmixMixer)
+                                else type(target_mixer).__name__))
+        if target_agent is None:
+            raise ValueError("qmix_train_step_feeds: target_mixer reads the target agents' Q values on the device; pass target_agent "
+                             "(a ParticleQmixAgent holding the Agent_target weights) as well")
+        if not cols["v_global"].is_cuda:
+            raise ValueError("qmix_train_step_feeds: target_mixer evaluates device columns; call without it for host tensors")
     calls = []
 
     def call(ops, feed, launch=True):
@@ -950,14 +973,22 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     feed = {"obs_others": obs_others_next, "v_obs": v_local_next, "v_goal": goals_self}
     if device:
         call(["argmax_Q_target"], feed, launch=False)
-        target_1hot = target_agent.greedy_rows(obs_others_next, v_local_next, goals_self, onehot=True)["onehot"]
+        greedy = target_agent.greedy_rows(obs_others_next, v_local_next, goals_self, onehot=True, q_max=target_mixer is not None)
+        target_1hot = greedy["onehot"]
     else:
         argmax = call(["argmax_Q_target"], feed)[0]
         target_1hot = torch.nn.functional.one_hot(argmax.reshape(-1).long(), int(l_action))
     # ---- Q_tot of the target mixer, TD target (:358-369) ----
-    q_tot = call(["mixer_target"], {"v_state": state_next, "v_goal_all": goals_all, "actions_1hot": target_1hot,
-                                    "obs_others": obs_others_next, "v_obs": v_local_next, "v_goal": goals_self})[0]
-    target = qmix_td_target(cols["reward_local"].reshape(B, N), q_tot, cols["done"], gamma)
+    feed = {"v_state": state_next, "v_goal_all": goals_all, "actions_1hot": target_1hot, "obs_others": obs_others_next,
+            "v_obs": v_local_next, "v_goal": goals_self}
+    if target_mixer is not None:
+        # agent_qs of the target evaluation is reduce_sum(Q_target * actions_1hot) (alg_qmix.py:101-103): the Q at the argmax
+        call(["mixer_target"], feed, launch=False)
+        target = target_mixer.q_tot(cols["v_global_next"], goals, greedy["q_max"].reshape(B, N), cols["reward_local"].reshape(B, N),
+                                    cols["done"], gamma)["td"]
+    else:
+        q_tot = call(["mixer_target"], feed)[0]
+        target = qmix_td_target(cols["reward_local"].reshape(B, N), q_tot, cols["done"], gamma)
     # ---- optimiser step of the main mixer, soft update (:371-380) ----
     call(["mixer_op"], {"v_state": state, "v_goal_all": goals_all, "actions_1hot": actions_1hot, "obs_others": obs_others,
                         "v_obs": v_local, "v_goal": goals_self, "td_target": target})

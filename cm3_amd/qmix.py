@@ -16,8 +16,9 @@ ignored, so ``{v.name: sess.run(v)}`` of either scope loads unchanged.  The netw
 (a float64 env's observation is rounded to float32 as the inputs are staged, as the reference's tf.float32 placeholders do).
 
 Exploration draws come from the build's own Philox stream (csrc/actor.hip, kPurposeExplore): the same law as the reference's
-np.random calls, not the same numbers.  The mixer and the learner stay on the reference's side; both agents
-serve a learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from.
+np.random calls, not the same numbers.  The learner stays on the reference's side; both agents serve a
+learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from, and ParticleQmixMixer
+(below) evaluates the particle target mixer -- mixer_target and the TD target -- on the same rows.
 """
 import ctypes
 
@@ -26,7 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import Cm3Error
-from .actor import _epsilon_args, stage_checkers_rows
+from .actor import _epsilon_args, _keep, stage_checkers_rows
 
 H, N_ACTIONS = 64, 5
 # the six tensors of cm3_qmix_particle_pack, in its order
@@ -404,3 +405,151 @@ class CheckersQmixAgent(object):
             # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
             self.w[short].copy_(tau * main.w[short].to(self.device) + (1.0 - tau) * self.w[short])
         self.repack()
+
+
+# ---- the particle mixer ---------------------------------------------------------------------------------------------------------------
+EMBED = 64                                          # embed_dim of networks.Qmix_mixer
+# the five variables of networks.Qmix_mixer (networks.py:657-665) by the fields of cm3_qmix_mixer_particle_weights
+MIXER_NAMES = {"w1": "hyper_w_1", "w_final": "hyper_w_final", "b1": "hyper_b_1", "b_final_l1": "hyper_b_final_l1/kernel",
+               "b_final": "hyper_b_final/kernel"}
+_MIXER_FIELDS = {"w1": "hyper_w_1", "w_final": "hyper_w_final", "b1": "hyper_b_1", "b_final_l1": "hyper_b_final_l1",
+                 "b_final": "hyper_b_final"}
+
+
+def _mixer_canon(name):
+    name = name.split(":")[0]
+    for prefix in ("Mixer_main/", "Mixer_target/"):
+        if name.startswith(prefix):
+            name = name[len(prefix):]
+    return name
+
+
+def mixer_weight_shapes(n_agents):
+    """short name -> shape of the TF variable of networks.Qmix_mixer for this agent count"""
+    k = 6 * n_agents
+    return {"w1": (k, EMBED * n_agents), "w_final": (k, EMBED), "b1": (k, EMBED), "b_final_l1": (k, EMBED), "b_final": (EMBED, 1)}
+
+
+class ParticleQmixMixer(object):
+    """The reference's particle QMIX mixer evaluated on the device over the transitions of a sampled batch.
+
+        reference                                                    here
+        ---------------------------------------------------------   -----------------------------------------------
+        networks.Qmix_mixer(agent_qs, state, goals_all, ...)         ParticleQmixMixer(weights, n_agents)
+          (networks.py:640-685; scopes Mixer_main / Mixer_target)
+        sess.run(mixer_target, feed) + the TD target                 mixer.q_tot(v_global_next, goals, q_max, reward_local, done, gamma)
+          (alg_qmix.py:358-369)                                        (ONE launch of cm3_qmix_mixer_particle_rows_f32)
+        the mixer half of list_update_target_ops (:139-156)          mixer.soft_update_from(main_mixer, tau)
+
+    The forward pass only: the main mixer's loss, gradient and optimiser step stay the session's.  Weights stay
+    float32 [in][out] as TensorFlow shapes them, in ``self.w`` under the short names of MIXER_NAMES, so a session that trains the
+    main mixer can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors, capturable)
+    then makes the next launch follow them.  The prefixes "Mixer_main/", "Mixer_target/" and a ":0" suffix of the keys are ignored."""
+
+    def __init__(self, weights, n_agents, device="cuda:0"):
+        self.device = _lib.require_gpu(device)
+        self.n = int(n_agents)
+        if not 1 <= self.n <= _lib.MAX_AGENTS:
+            raise Cm3Error("n_agents must be in 1..%d" % _lib.MAX_AGENTS)
+        src = {_mixer_canon(k): v for k, v in weights.items()}
+        self.w = {}
+        for short, shape in mixer_weight_shapes(self.n).items():
+            name = MIXER_NAMES[short]
+            if name not in src:
+                raise Cm3Error("missing mixer weight %r" % name)
+            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise Cm3Error("mixer weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            self.w[short] = t.to(self.device)
+        self._wt = _lib.QmixMixerParticleWeights()
+        for short, field in _MIXER_FIELDS.items():
+            setattr(self._wt, field, _lib.ptr(self.w[short]))
+        self._lib = _lib.lib()
+        nbytes = self._lib.cm3_qmix_mixer_particle_packed_bytes(self.n)
+        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
+        self._wt.packed = self._packed.data_ptr()
+        self.repack()
+
+    def _desc(self):
+        d = _lib.QmixMixerParticleDesc()
+        d.n_agents, d.embed_dim = self.n, EMBED
+        return d
+
+    def repack(self):
+        """Re-arrange the (possibly updated in place) TF-shaped weights into the rows kernel's layout: one launch."""
+        d = self._desc()
+        _lib.check(self._lib.cm3_qmix_mixer_particle_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
+                                                          _lib.current_stream_handle(self.device)))
+
+    def soft_update_from(self, main, tau):
+        """w <- tau * main.w + (1 - tau) * w on the five TF-shaped float32 tensors in place, then repack(): the mixer half of
+        list_update_target_ops (alg_qmix.py:139-156), for a mixer holding the Mixer_target weights."""
+        if not isinstance(main, ParticleQmixMixer) or main.n != self.n:
+            raise Cm3Error("soft_update_from: the main mixer must be a ParticleQmixMixer for %d agents" % self.n)
+        tau = float(tau)
+        for name in self.w:
+            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
+            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
+        self.repack()
+
+    # ---- launches -------------------------------------------------------------------------------------------------------------------
+    def enqueue(self, n_steps, state, goals, agent_qs, reward=None, done=None, gamma=0.0, q_tot=None, q_tot64=None, td=None,
+                stream=None):
+        """Raw launch of cm3_qmix_mixer_particle_rows_f32 on contiguous device tensors: state / goals / agent_qs float32, reward
+        float32 or float64, done uint8; every output is optional, one is required."""
+        r = _lib.QmixMixerRows()
+        r.n_steps = int(n_steps)
+        r.state, r.goals, r.agent_qs = _lib.ptr(state), _lib.ptr(goals), _lib.ptr(agent_qs)
+        r.reward, r.done = _lib.ptr(reward), _lib.ptr(done)
+        r.reward_f64 = 1 if (reward is not None and reward.dtype == torch.float64) else 0
+        r.gamma = float(gamma)
+        r.q_tot, r.q_tot64, r.td = _lib.ptr(q_tot), _lib.ptr(q_tot64), _lib.ptr(td)
+        d = self._desc()
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_qmix_mixer_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def _stage_cols(self, what, state, goals, agent_qs, reward=None, done=None):
+        """(B, state, goals, agent_qs, reward, done) contiguous on the mixer's device from [B, N, 4], [B, N, 2], [B, N], [B, N] and
+        [B] (leading dimensions may be merged or flattened: [B, 4 N], [B * N] ...), staged as ParticleCritic._stage_cols stages them:
+        float columns of any dtype are rounded to float32, as the reference's tf.float32 placeholders do; reward stays float32 or
+        float64 (another dtype is widened to float64); bool or integer done becomes uint8."""
+        N = self.n
+        if state.numel() == 0 or state.numel() % (4 * N) or goals.numel() * 2 != state.numel():
+            raise Cm3Error("%s takes state [B, %d, 4] and goals [B, %d, 2], got %s and %s"
+                           % (what, N, N, tuple(state.shape), tuple(goals.shape)))
+        B = state.numel() // (4 * N)
+        f32 = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
+        state, goals = f32(state).reshape(B, N, 4), f32(goals).reshape(B, N, 2)
+        if agent_qs.numel() != B * N:
+            raise Cm3Error("%s takes agent_qs [B, %d] for %d time steps, got %s" % (what, N, B, tuple(agent_qs.shape)))
+        agent_qs = f32(agent_qs).reshape(B, N)
+        if reward is not None:
+            if reward.numel() != B * N:
+                raise Cm3Error("%s takes reward_local [B, %d] for %d time steps, got %s" % (what, N, B, tuple(reward.shape)))
+            reward = reward.to(device=self.device, dtype=reward.dtype if reward.dtype == torch.float32 else torch.float64).contiguous()
+        if done is not None:
+            if done.numel() != B:
+                raise Cm3Error("%s takes done [B] for %d time steps, got %s" % (what, B, tuple(done.shape)))
+            done = done.reshape(-1).to(self.device)
+            done = (done.contiguous().view(torch.uint8) if done.dtype == torch.bool else (done != 0).view(torch.uint8))
+        return B, state, goals, agent_qs, reward, done
+
+    def q_tot(self, state, goals, agent_qs, reward_local=None, done=None, gamma=None, keep=None):
+        """Qmix_mixer over the B transitions of a batch, ONE launch: state = v_global_next [B, N, 4], goals [B, N, 2] and agent_qs
+        [B, N] = each target agent's Q at its argmax (greedy_rows(..., q_max=True)) give sess.run(mixer_target) of
+        alg_qmix.train_step (alg_qmix.py:358-365).  Returns a dict of device tensors: "q_tot" float32 [B, 1] (the shape the session
+        returns), "q_tot64" the same values float64 [B, 1], and with reward_local [B, N] (float32 / float64), done [B] and gamma also
+        "td" float64 [B] = sum(reward_local[b]) + gamma * q_tot * (1 - done), the bits of batch.qmix_td_target on "q_tot".  The three
+        come together or not at all.  keep: an optional list that receives every tensor the launch touches (the staged inputs, the
+        outputs), for whoever captures the launch."""
+        given = [x is not None for x in (reward_local, done, gamma)]
+        if any(given) and not all(given):
+            raise Cm3Error("q_tot: reward_local, done and gamma come together (the TD target) or not at all")
+        B, st, go, aq, rw, dn = self._stage_cols("q_tot", state, goals, agent_qs, reward_local, done)
+        out = {"q_tot": torch.empty(B, 1, dtype=torch.float32, device=self.device),
+               "q_tot64": torch.empty(B, 1, dtype=torch.float64, device=self.device)}
+        if all(given):
+            out["td"] = torch.empty(B, dtype=torch.float64, device=self.device)
+        _keep(keep, st, go, aq, rw, dn, *out.values())
+        self.enqueue(B, st, go, aq, rw, dn, 0.0 if gamma is None else gamma, **out)
+        return out

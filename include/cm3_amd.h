@@ -67,6 +67,9 @@ extern "C" {
                                   cm3_critic_checkers_packed_bytes / _pack / _rows_f32 (the CM3 Checkers critics Q_global_checkers and
                                   Q_credit_checkers over transition rows decoded from a batch's base columns, with the TD target): the
                                   critic evaluations of alg_credit_checkers.train_step that carry no gradient; additive.
+                                  cm3_qmix_mixer_particle_packed_bytes / _pack / _rows_f32 (the particle QMIX mixer over transition rows
+                                  with the TD target: mixer_target of alg_qmix.train_step, the last evaluation without a gradient);
+                                  additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
@@ -685,6 +688,66 @@ int cm3_critic_checkers_pack(const cm3_critic_checkers_desc *desc, const cm3_cri
  * cm3_last_kernel_variant() names the launch k_critic_checkers_rows<f32,N=..,...,kind=..,form=..>. */
 int cm3_critic_checkers_rows_f32(const cm3_critic_checkers_desc *desc, const cm3_critic_checkers_weights *weights,
                                  const cm3_critic_checkers_rows *rows, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The particle QMIX mixer over TRANSITION rows (part of ABI 9, additive): networks.Qmix_mixer (networks.py:640-685) -- mixer_target
+ * of alg_qmix.train_step (alg_qmix.py:358-365), the one evaluation of the mixer that carries no gradient -- and the TD target that
+ * follows it (:367-369).  Per transition b, x = concat(state[b] [4N], goals[b] [2N]), K = 6N.  Float32 weights, row-major [in][out]
+ * as the TF variables of a scope "Mixer_main/..." / "Mixer_target/..." are shaped:
+ *   hyper_w_1        hyper_w_1 [K][64 N]                 w1 = |x . hyper_w_1| viewed [N][64]
+ *   hyper_w_final    hyper_w_final [K][64]               w_final = |x . hyper_w_final|
+ *   hyper_b_1        hyper_b_1 [K][64]                   b1 = x . hyper_b_1
+ *   hyper_b_final_l1 hyper_b_final_l1/kernel [K][64]     l1 = relu(x . kernel)                    (no bias)
+ *   hyper_b_final    hyper_b_final/kernel [64][1]        b_final = l1 . kernel                    (no bias)
+ *   hidden = elu(agent_qs[b][0..N) . w1 + b1),  q_tot = hidden . w_final + b_final
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_agents;   /* 1..CM3_MAX_AGENTS */
+  int32_t embed_dim;  /* 64 */
+} cm3_qmix_mixer_particle_desc;
+
+typedef struct {
+  const float *hyper_w_1, *hyper_w_final, *hyper_b_1, *hyper_b_final_l1, *hyper_b_final;
+  const void *packed; /* kernel-layout copy written by cm3_qmix_mixer_particle_pack (cm3_qmix_mixer_particle_packed_bytes() bytes,
+                         16-byte aligned); the rows launch reads ONLY this buffer, re-pack after every weight update */
+} cm3_qmix_mixer_particle_weights;
+
+/* The base columns of a batch of n_steps transitions and the optional outputs, at least one required; nothing is written at or past
+ * n_steps:
+ *   q_tot    float32 [n_steps]    q_tot64  float64 [n_steps], the same value widened
+ *   td       float64 [n_steps] = sum(reward[b][0..N)) + gamma * q_tot * (1 - done[b]), the bits cm3_qmix_td_target_f64 produces from
+ *            this launch's float32 q_tot (np.sum's order in float64, gamma * q_tot in float32)
+ * The sum over agents is a chain in ascending n started by the product for n = 0, b1 added last; the sum over the 64 embedding
+ * units is a fixed tree (csrc/mixer.hip): a row's bits depend on neither its place in a workgroup nor n_steps.  (Anonymous struct
+ * tags, like cm3_qmix_rows.) */
+typedef struct {
+  int32_t reward_f64;       /* reward holds float64 (else float32) */
+  int32_t reserved;         /* 0 */
+  const float *state;       /* [n_steps][N][4], 16-byte aligned */
+  const float *goals;       /* [n_steps][N][2],  8-byte aligned */
+  const float *agent_qs;    /* [n_steps][N]: the target agents' Q at their argmax (cm3_qmix_rows.q_max) */
+  const void *reward;       /* [n_steps][N] reward_local (td) */
+  const uint8_t *done;      /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *q_tot;
+  double *q_tot64;
+  double *td;
+  int64_t n_steps;
+} cm3_qmix_mixer_rows;
+
+/* 0 for an agent count outside 1..10 */
+size_t cm3_qmix_mixer_particle_packed_bytes(int32_t n_agents);
+/* Re-arranges the TensorFlow-shaped weights into the rows kernel's per-lane operand order, K zero-padded to whole k-steps: one small
+ * launch per weight update, on persistent tensors (capturable).  CM3_ERR_INVALID: the descriptor checks below, null weights /
+ * packed, a missing tensor, a misaligned packed. */
+int cm3_qmix_mixer_particle_pack(const cm3_qmix_mixer_particle_desc *desc, const cm3_qmix_mixer_particle_weights *weights, void *packed,
+                                 void *stream);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device: null desc / weights / rows,
+ * weights->packed NULL, n_agents outside 1..10, another embedding width than 64, n_steps <= 0 or above 2^31 - 1, a missing input
+ * (state, goals, agent_qs; reward and done with td), no output requested, a misaligned pointer.  cm3_last_kernel_variant() names the
+ * launch k_qmix_mixer_rows<f32,N=..>. */
+int cm3_qmix_mixer_particle_rows_f32(const cm3_qmix_mixer_particle_desc *desc, const cm3_qmix_mixer_particle_weights *weights,
+                                     const cm3_qmix_mixer_rows *rows, void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
