@@ -16,6 +16,10 @@ Weights stay float32 [in][out] as TensorFlow shapes them, so a checkpoint export
 The actor reads float32 and float64 env buffers (VecParticleEnv(dtype=...)).  On a float64 env -- the reference-precision mode --
 it rounds the observation to float32 as it stages its inputs, which is what the reference's tf.float32 placeholders do with its
 float64 observations (alg_credit.py:96-111): the network itself is float32 either way.
+
+Both actors derive from cm3_amd._net._DeviceNet, which loads the weights and has ``soft_update_from(main, tau)``: w <- tau * main.w +
+(1 - tau) * w in float32, then repack() -- the actor half of list_update_target_ops (alg_credit.py:186-194, run at :775;
+alg_credit_checkers.py:72, run at :773), for an actor holding the Policy_target weights.
 """
 import ctypes
 
@@ -24,6 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import Cm3Error
+from ._net import _DeviceNet, _keep, canon, sample_outputs, stage_particle_rows      # noqa: F401  (_keep: re-exported)
 
 
 def _epsilon_args(epsilon):
@@ -73,12 +78,6 @@ class RowsDrawCounter(object):
         return self.state.data_ptr()
 
 
-def _keep(keep, *tensors):
-    """Appends the tensors a launch touches to the caller's keep list (None: nobody captures, nothing to do)."""
-    if keep is not None:
-        keep.extend(t for t in tensors if t is not None)
-
-
 def _actor_entry(lib, dtype):
     """cm3_actor_particle_f32 / _f64 by the real of the env buffers the launch reads."""
     if dtype == torch.float32:
@@ -94,17 +93,17 @@ _NAMES = {
     "w_self": "actor_branch_self/kernel", "b_self": "actor_branch_self/bias", "w_self_h2": "W_branch_self_h2",
     "w_others": "stage-2/actor_others/kernel", "b_others": "stage-2/actor_others/bias",
     "w_others_h2": "stage-2/W_others_h2", "b_h2": "b", "w_out": "actor_out/kernel", "b_out": "actor_out/bias"}
+_PREFIXES = ("Policy_main/", "Policy_target/")
 
 
 def _canon(name):
-    name = name.split(":")[0]
-    for prefix in ("Policy_main/", "Policy_target/"):
-        if name.startswith(prefix):
-            name = name[len(prefix):]
-    return name
+    return canon(name, _PREFIXES)
 
 
-class ParticleActor(object):
+class ParticleActor(_DeviceNet):
+    _match = ("n", "stage")
+    _refusal = "the main actor must be a ParticleActor for %(n)d agents at stage %(stage)d"
+
     def __init__(self, weights, n_agents, stage=2, device="cuda:0", seed=12341, env_id_base=0, precision="f32"):
         """precision of the 192 -> 64 second layer (87 % of the network's FLOPs):
         "f32"     exact float32 MFMA -- a k-ordered fmaf chain, the numerics of a plain float32 loop;
@@ -124,34 +123,18 @@ class ParticleActor(object):
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
         self.rows_draw = 0          # launch counter of the rows stream (sample_rows)
-        src = {_canon(k): v for k, v in weights.items()}
         shapes = {"w_self": (6, H1_SELF), "b_self": (H1_SELF,), "w_self_h2": (H1_SELF, H2), "b_h2": (H2,),
                   "w_out": (H2, N_ACTIONS), "b_out": (N_ACTIONS,)}
         if self.stage > 1:
             shapes.update({"w_others": (self.L, H1_OTHERS), "b_others": (H1_OTHERS,), "w_others_h2": (H1_OTHERS, H2)})
-        self.w = {}
-        for short, shape in shapes.items():
-            name = _NAMES[short]
-            if name not in src:
-                raise Cm3Error("missing actor weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise Cm3Error("actor weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            self.w[short] = t.to(self.device)
-        self._wt = _lib.ActorParticleWeights()
-        for short in _NAMES:
-            setattr(self._wt, short, _lib.ptr(self.w.get(short)))
-        self._lib = _lib.lib()
-        nbytes = self._lib.cm3_actor_particle_packed_bytes(self.n)
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self._wt.packed = self._packed.data_ptr()
-        self.repack()
+        self._load(weights, _PREFIXES, _NAMES, shapes, "actor", lambda lib: lib.cm3_actor_particle_packed_bytes(self.n),
+                   _lib.ActorParticleWeights())
 
     def repack(self):
         """Re-arrange the (possibly updated in place) TF-shaped weights into the forward kernel's layout."""
         d = self._desc(1, 0.0, 0)
         _lib.check(self._lib.cm3_actor_particle_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
-                                                     _lib.current_stream_handle(self.device)))
+                                                     self._stream(None)))
 
     def _desc(self, n_envs, epsilon, env_id_base):
         d = _lib.ActorParticleDesc()
@@ -173,7 +156,7 @@ class ParticleActor(object):
         b.meta, b.episode, b.actions, b.probs = _lib.ptr(meta), _lib.ptr(episode), _lib.ptr(actions), _lib.ptr(probs)
         epsilon, b.epsilon_dev = _epsilon_args(epsilon)
         d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(fn(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
 
     def act(self, env, epsilon, return_probs=False):
@@ -203,26 +186,12 @@ class ParticleActor(object):
         counter = draw if isinstance(draw, RowsDrawCounter) else None
         r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base), 0 if counter is not None else int(draw) & 0xFFFFFFFF
         d = self._desc(1, epsilon, 0)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         if counter is not None:
             _lib.check(self._lib.cm3_actor_particle_rows_counted_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r),
                                                                      counter.data_ptr(), s))
         else:
             _lib.check(self._lib.cm3_actor_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
-
-    def _stage_rows(self, what, obs_others, v_obs, goals):
-        """(rows, obs_others, v_obs, goals) contiguous float32 on the actor's device from [..., L], [..., 4], [..., 2] with equal
-        leading shape (a float64 column is rounded, as the reference's tf.float32 placeholders do)."""
-        lead = tuple(v_obs.shape[:-1])
-        if (tuple(obs_others.shape) != lead + (self.L,) or tuple(v_obs.shape) != lead + (4,)
-                or tuple(goals.shape) != lead + (2,)):
-            raise Cm3Error("%s takes [..., %d], [..., 4] and [..., 2] with equal leading shape, got %s, %s, %s"
-                           % (what, self.L, tuple(obs_others.shape), tuple(v_obs.shape), tuple(goals.shape)))
-        rows = int(np.prod(lead, dtype=np.int64))
-        if rows <= 0:
-            raise Cm3Error("%s needs at least one row" % what)
-        stage = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
-        return rows, stage(obs_others), stage(v_obs), stage(goals)
 
     def probs_rows(self, obs_others, v_obs, goals, epsilon, keep=None):
         """The mixed probabilities float32 [R, 5] over the R = prod(leading shape) rows, ONE launch: the reference's
@@ -230,7 +199,7 @@ class ParticleActor(object):
         goals of a sampled batch.  Nothing is drawn.  A row's probabilities are the bits act() computes for the same inputs.
         keep: an optional list that receives every tensor this call allocated and the launch touches (the output, the staged
         inputs) -- whoever captures the launch into a hipGraph holds them for as long as the graph is replayed."""
-        rows, oo, vo, vg = self._stage_rows("probs_rows", obs_others, v_obs, goals)
+        rows, oo, vo, vg = stage_particle_rows("probs_rows", self.device, self.L, obs_others, v_obs, goals)
         probs = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
         _keep(keep, oo, vo, vg, probs)
         self.enqueue_rows(rows, oo, vo, vg, epsilon, probs=probs)
@@ -244,28 +213,14 @@ class ParticleActor(object):
         self.rows_draw and advances it, so successive calls draw afresh; an explicit draw reproduces a call (and leaves the
         counter alone); a RowsDrawCounter makes the launch read and advance that counter on the device (capturable: every
         replay draws afresh; self.rows_draw is left alone).  keep: as probs_rows."""
-        rows, oo, vo, vg = self._stage_rows("sample_rows", obs_others, v_obs, goals)
-        out = {"actions": torch.empty(rows, dtype=torch.int32, device=self.device)}
-        if probs:
-            out["probs"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
-        if onehot:
-            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
+        rows, oo, vo, vg = stage_particle_rows("sample_rows", self.device, self.L, obs_others, v_obs, goals)
+        out = sample_outputs(self.device, rows, probs, onehot)
         if draw is None:
             draw, self.rows_draw = self.rows_draw, (self.rows_draw + 1) & 0xFFFFFFFF
         _keep(keep, oo, vo, vg, *out.values())
         self.enqueue_rows(rows, oo, vo, vg, epsilon, draw=draw, **out)
         return out
 
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the actor half of
-        list_update_target_ops (alg_credit.py:186-194, run at :775), for an actor holding the Policy_target weights."""
-        if not isinstance(main, ParticleActor) or main.n != self.n or main.stage != self.stage:
-            raise Cm3Error("soft_update_from: the main actor must be a ParticleActor for %d agents at stage %d" % (self.n, self.stage))
-        tau = float(tau)
-        for name in self.w:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
-        self.repack()
 
 
 _CK_NAMES = {
@@ -274,6 +229,14 @@ _CK_NAMES = {
     "others_w": "stage-2/branch_others/kernel", "others_b": "stage-2/branch_others/bias",
     "w_others_h2": "stage-2/W_others_h2", "b_h2": "b", "out_w": "actor_out/kernel", "out_b": "actor_out/bias"}
 CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2 = 6, 32, 256, 256
+
+
+def checkers_policy_shapes(Lo):
+    """short name -> shape of the thirteen TF variables of networks.actor_checkers / Qmix_single_checkers with Lo others inputs"""
+    return {"conv_w": (3, 3, 3, CK_CONV_F), "conv_b": (CK_CONV_F,), "lin_w": (25 * CK_CONV_F, CK_CONV_LIN),
+            "lin_b": (CK_CONV_LIN,), "self_w": (CK_CONV_LIN + 4 + N_ACTIONS + 2, CK_H1), "self_b": (CK_H1,),
+            "w_self_h2": (CK_H1, CK_H2), "others_w": (Lo, CK_H1), "others_b": (CK_H1,), "w_others_h2": (CK_H1, CK_H2),
+            "b_h2": (CK_H2,), "out_w": (CK_H2, N_ACTIONS), "out_b": (N_ACTIONS,)}
 
 
 def stage_checkers_rows(what, device, Lo, obs_self_t, obs_self_v, obs_others, actions_prev, goals):
@@ -304,7 +267,44 @@ def stage_checkers_rows(what, device, Lo, obs_self_t, obs_self_v, obs_others, ac
     return rows, ot, stage(obs_self_v, torch.float64), stage(obs_others, torch.float64), stage(actions_prev, torch.int32), vg
 
 
-class CheckersActor(object):
+class _CheckersPolicyNet(_DeviceNet):
+    """What CheckersActor and CheckersQmixAgent share: one network (cm3_actor_checkers_weights / _desc), two heads.  The launches are
+    private here and take the library's entry point; each class publishes them under the hook names cm3_amd.rollout looks for."""
+    _net_stage = 2          # cm3_actor_checkers_desc.stage (the QMIX network has the others branch at every agent count)
+
+    def _desc(self, n_envs, epsilon, env_id_base, obst_stride):
+        d = _lib.ActorCheckersDesc()
+        d.n_envs, d.n_agents, d.stage, d.n_obs = int(n_envs), self.n, self._net_stage, 2
+        d.conv_f, d.n_conv_linear, d.n_h1, d.n_h2, d.n_actions = CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2, N_ACTIONS
+        d.epsilon = float(epsilon)
+        d.precision = PRECISIONS[self.precision]
+        d.obs_self_t_stride = int(obst_stride)
+        d.env_id_base = int(env_id_base)
+        d.seed = self.seed & 0xFFFFFFFFFFFFFFFF
+        return d
+
+    def _enqueue_tick(self, fn, n_envs, obs_self_t_raw, obst_stride, obs_self_v, obs_others, goals, actions_prev, steps, episode,
+                      actions, epsilon, probs, stream, env_id_base, prev_done):
+        b = _lib.ActorCheckersBufs()
+        b.obs_self_t, b.obs_self_v, b.obs_others = _lib.ptr(obs_self_t_raw), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
+        b.goals, b.actions_prev, b.steps, b.episode = (_lib.ptr(goals), _lib.ptr(actions_prev), _lib.ptr(steps),
+                                                       _lib.ptr(episode))
+        b.actions, b.probs = _lib.ptr(actions), _lib.ptr(probs)
+        b.prev_done = _lib.ptr(prev_done)
+        epsilon, b.epsilon_dev = _epsilon_args(epsilon)
+        d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base, obst_stride)
+        _lib.check(fn(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), self._stream(stream)))
+
+    def _enqueue_whole(self, fn, env_desc, traj, n_envs, obst_stride, n_ticks, epsilon, prev0, probs, stream, final_obs, prev0_next):
+        epsilon, eps_dev = _epsilon_args(epsilon)
+        d = self._desc(n_envs, epsilon, env_desc.env_id_base, obst_stride)
+        _lib.check(fn(
+            ctypes.byref(env_desc), ctypes.byref(traj), ctypes.byref(d), ctypes.byref(self._wt), _lib.ptr(prev0), _lib.ptr(prev0_next),
+            _lib.ptr(probs), 0 if probs is None else probs[0].numel() * probs.element_size(), eps_dev,
+            None if final_obs is None else ctypes.byref(final_obs), int(n_ticks), self._stream(stream)))
+
+
+class CheckersActor(_CheckersPolicyNet):
     """The reference's Checkers policy evaluated on the device.
 
         reference                                                        here
@@ -318,6 +318,8 @@ class CheckersActor(object):
             goals, eps, sess)  (alg_credit_checkers.py:229-253)            epsilon=..): actor and step launches alternate
                                                                            inside ONE hipGraph
     """
+    _match = ("n", "stage")
+    _refusal = "the main actor must be a CheckersActor for %(n)d agents at stage %(stage)d"
 
     def __init__(self, weights, n_agents, stage=2, device="cuda:0", seed=12341, env_id_base=0, precision="f32"):
         """precision: "f32" (default: every layer on the exact-f32 MFMA), "f16x3" (every layer in split float16: activations and
@@ -329,79 +331,37 @@ class CheckersActor(object):
             raise Cm3Error("precision must be one of %s" % sorted(PRECISIONS))
         self.precision = precision
         self.n = int(n_agents)
-        self.stage = int(stage)
+        self.stage = self._net_stage = int(stage)
         self.Lo = 2 * max(self.n - 1, 1)
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
         self.rows_draw = 0          # launch counter of the rows stream (sample_rows)
-        src = {_canon(k): v for k, v in weights.items()}
-        cat = CK_CONV_LIN + 4 + N_ACTIONS + 2
-        shapes = {"conv_w": (3, 3, 3, CK_CONV_F), "conv_b": (CK_CONV_F,), "lin_w": (25 * CK_CONV_F, CK_CONV_LIN),
-                  "lin_b": (CK_CONV_LIN,), "self_w": (cat, CK_H1), "self_b": (CK_H1,), "w_self_h2": (CK_H1, CK_H2),
-                  "b_h2": (CK_H2,), "out_w": (CK_H2, N_ACTIONS), "out_b": (N_ACTIONS,)}
-        if self.stage > 1:
-            shapes.update({"others_w": (self.Lo, CK_H1), "others_b": (CK_H1,), "w_others_h2": (CK_H1, CK_H2)})
-        self.w = {}
-        for short, shape in shapes.items():
-            name = _CK_NAMES[short]
-            if name not in src:
-                raise Cm3Error("missing actor weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise Cm3Error("actor weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            self.w[short] = t.to(self.device)
-        self._wt = _lib.ActorCheckersWeights()
-        for short in _CK_NAMES:
-            setattr(self._wt, short, _lib.ptr(self.w.get(short)))
-        self._lib = _lib.lib()
-        nbytes = self._lib.cm3_actor_checkers_packed_bytes()
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self._wt.packed = self._packed.data_ptr()
-        self.repack()
-
-    def _desc(self, n_envs, epsilon, env_id_base, obst_stride):
-        d = _lib.ActorCheckersDesc()
-        d.n_envs, d.n_agents, d.stage, d.n_obs = int(n_envs), self.n, self.stage, 2
-        d.conv_f, d.n_conv_linear, d.n_h1, d.n_h2, d.n_actions = CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2, N_ACTIONS
-        d.epsilon = float(epsilon)
-        d.precision = PRECISIONS[self.precision]
-        d.obs_self_t_stride = int(obst_stride)
-        d.env_id_base = int(env_id_base)
-        d.seed = self.seed & 0xFFFFFFFFFFFFFFFF
-        return d
+        shapes = checkers_policy_shapes(self.Lo)
+        if self.stage == 1:
+            for short in ("others_w", "others_b", "w_others_h2"):
+                del shapes[short]
+        self._load(weights, _PREFIXES, _CK_NAMES, shapes, "actor", lambda lib: lib.cm3_actor_checkers_packed_bytes(),
+                   _lib.ActorCheckersWeights())
 
     def repack(self):
         d = self._desc(1, 0.0, 0, 75 * self.n)
         _lib.check(self._lib.cm3_actor_checkers_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
-                                                     _lib.current_stream_handle(self.device)))
+                                                     self._stream(None)))
 
     def enqueue(self, n_envs, obs_self_t_raw, obst_stride, obs_self_v, obs_others, goals, actions_prev, steps, episode,
                 actions, epsilon, probs=None, stream=None, env_id_base=None, prev_done=None):
         """Raw launch on the env's device buffers (obs_self_t_raw: the int8 storage with obst_stride bytes per env).
         prev_done (uint8 [E], optional): envs that finished an episode on the previous tick see actions_prev = 0."""
-        b = _lib.ActorCheckersBufs()
-        b.obs_self_t, b.obs_self_v, b.obs_others = _lib.ptr(obs_self_t_raw), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
-        b.goals, b.actions_prev, b.steps, b.episode = (_lib.ptr(goals), _lib.ptr(actions_prev), _lib.ptr(steps),
-                                                       _lib.ptr(episode))
-        b.actions, b.probs = _lib.ptr(actions), _lib.ptr(probs)
-        b.prev_done = _lib.ptr(prev_done)
-        epsilon, b.epsilon_dev = _epsilon_args(epsilon)
-        d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base, obst_stride)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_actor_checkers_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
+        self._enqueue_tick(self._lib.cm3_actor_checkers_f32, n_envs, obs_self_t_raw, obst_stride, obs_self_v, obs_others, goals,
+                           actions_prev, steps, episode, actions, epsilon, probs, stream, env_id_base, prev_done)
 
     def enqueue_rollout(self, env_desc, traj, n_envs, obst_stride, n_ticks, epsilon, prev0=None, probs=None, stream=None,
                         final_obs=None, prev0_next=None):
         """The whole policy-driven rollout in ONE launch (cm3_policy_rollout_checkers): env_desc / traj are the env's descriptor and
         the rollout's trajectory struct; probs: optional float32 [T, E, N, 5]; final_obs: optional _lib.CheckersBufs naming the env's
         current-observation buffers, which then receive the state the rollout leaves."""
-        epsilon, eps_dev = _epsilon_args(epsilon)
-        d = self._desc(n_envs, epsilon, env_desc.env_id_base, obst_stride)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_policy_rollout_checkers(
-            ctypes.byref(env_desc), ctypes.byref(traj), ctypes.byref(d), ctypes.byref(self._wt), _lib.ptr(prev0), _lib.ptr(prev0_next), _lib.ptr(probs),
-            0 if probs is None else probs[0].numel() * probs.element_size(), eps_dev,
-            None if final_obs is None else ctypes.byref(final_obs), int(n_ticks), s))
+        self._enqueue_whole(self._lib.cm3_policy_rollout_checkers, env_desc, traj, n_envs, obst_stride, n_ticks, epsilon, prev0,
+                            probs, stream, final_obs, prev0_next)
 
     def fused_rollout_ok(self, env):
         """cm3_policy_rollout_checkers covers the reference's configurations: split-float16 actor, one agent at stage 1 or two at
@@ -451,7 +411,7 @@ class CheckersActor(object):
         r.n_rows, r.row_id_base = int(n_rows), int(row_id_base) & 0xFFFFFFFFFFFFFFFF
         r.draw = 0 if counter is not None else int(draw) & 0xFFFFFFFF
         d = self._desc(1, epsilon, 0, 75 * self.n)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         if counter is not None:
             _lib.check(self._lib.cm3_actor_checkers_rows_counted_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r),
                                                                      counter.data_ptr(), s))
@@ -484,24 +444,10 @@ class CheckersActor(object):
         draws afresh; self.rows_draw is left alone).  keep: as probs_rows."""
         rows, ot, ov, oo, ap, vg = stage_checkers_rows("sample_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
                                                        actions_prev, goals)
-        out = {"actions": torch.empty(rows, dtype=torch.int32, device=self.device)}
-        if probs:
-            out["probs"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
-        if onehot:
-            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
+        out = sample_outputs(self.device, rows, probs, onehot)
         if draw is None:
             draw, self.rows_draw = self.rows_draw, (self.rows_draw + 1) & 0xFFFFFFFF
         _keep(keep, ot, ov, oo, ap, vg, *out.values())
         self.enqueue_rows(rows, ot, ov, oo, ap, vg, epsilon, draw=draw, **out)
         return out
 
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the actor half of
-        list_update_target_ops (alg_credit_checkers.py:72, run at :773), for an actor holding the Policy_target weights."""
-        if not isinstance(main, CheckersActor) or main.n != self.n or main.stage != self.stage:
-            raise Cm3Error("soft_update_from: the main actor must be a CheckersActor for %d agents at stage %d" % (self.n, self.stage))
-        tau = float(tau)
-        for name in self.w:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
-        self.repack()

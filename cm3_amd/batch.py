@@ -10,10 +10,18 @@ Here the same arrays are produced from the device trajectory columns (ParticleRo
 numpy=False)) with gathers / views, so a learner living on the GPU never pulls the batch through the host.
 Pure data movement: outputs are bit-identical to the reference's (tests/test_batch.py pins them to arrays produced
 by the REAL reference functions, tests/golden/batch_particle.npz).
+
+Layout: _Tiler and the two TileSpec tables (particle_static_feed_specs / checkers_static_feed_specs) -- every feed of train_step
+that does not depend on a network output, as "destination row r <- source row f(r)" outputs of cm3_rows_tile; the torch composition
+of the same dict (_static_feeds_composed: the specification, and the path of the inputs the kernels do not take); train_step_feeds,
+which reads either dict on one path, the envs differing in data only (_Particle / _Checkers); OnPolicyPhasePlan, which captures one
+train_step_feeds per minibatch into a hipGraph and holds every tensor the captured launches touch; the QMIX feed builders.
 """
 import collections
 
 import torch
+
+from ._net import _keep
 
 
 def rep_rows(x, n):
@@ -57,63 +65,64 @@ class _Tiler(object):
         self.specs, self.keep = [], []
 
 
-def particle_static_feeds_device(cols, l_action=5, out=None):
-    """Every feed of the reference's train_step that does not depend on a network output (particle env, N > 1, Q-credit variant), from
-    the float32 columns of ParticleRollout.as_reference_batch(numpy=False), in TWO launches of cm3_rows_tile: process_actions /
-    process_global_state (alg_credit.py:406-443, :528-557), the n x n credit repeats (:614-658), the n x n x l_action counterfactual
-    tiling (:730-751).  Values and dtypes are those of the torch composition in train_step_feeds (tests/test_batch.py compares the two
-    and both with the arrays the REAL train_step fed).  out: the dict an earlier call returned for the same batch size -- the feeds are
-    written into those tensors again (persistent addresses for a captured consumer)."""
-    from . import _lib
-    vg, vgn = cols["v_global"].contiguous(), cols["v_global_next"].contiguous()
-    B, N, l = vg.shape
-    A, R, dev = int(l_action), B * N, vg.device
-    actions = cols["actions"].to(torch.int32).contiguous()
-    done = cols["done"].contiguous()
-    done_u8 = done.view(torch.uint8) if done.dtype == torch.bool else done.to(torch.uint8)
-    goals = cols["goals"].contiguous()
-    lg = goals.shape[2]
-    reward, reward_local = cols["reward"].contiguous(), cols["reward_local"].contiguous()
-    f64, i64 = torch.float64, torch.int64
-    by_n = lambda outer=1: ((outer * N * N, 0, N), (outer, N, 1))          # noqa: E731  rows (b, m, n[, a]) <- row b N + n
-    by_m = lambda outer=1: ((outer * N, 0, 1), (1, 0, 0))                   # noqa: E731  rows (r, m[, a])    <- row r
-    t = _Tiler(dev)
-    S, O = {}, (out or {})
-    S["a1"] = t.add(actions, R, A, i64, _lib.TILE_ONEHOT_I64, out=O.get("a1"))
-    S["ao"] = t.add(actions, R * (N - 1), A, f64, _lib.TILE_ONEHOT_F64, others=(N, N * (N - 1), N - 1), shape=(R, N - 1, A), out=O.get("ao"))
-    S["reward_rep"] = t.add(reward, R, 1, reward.dtype, _lib.TILE_COPY, terms=by_m(), shape=(R,), out=O.get("reward_rep"))
-    S["done_rep"] = t.add(done_u8, R, 1, torch.bool, _lib.TILE_COPY, terms=by_m(), shape=(R,), out=O.get("done_rep"))
-    S["not_done"] = t.add(done_u8, R, 1, i64, _lib.TILE_NOT_I64, terms=by_m(), shape=(R,), out=O.get("not_done"))
-    S["others"] = t.add(vg, R * (N - 1), l, f64, _lib.TILE_F32_TO_F64, others=(N, N * (N - 1), N - 1), shape=(R, (N - 1) * l), out=O.get("others"))
-    S["others_next"] = t.add(vgn, R * (N - 1), l, f64, _lib.TILE_F32_TO_F64, others=(N, N * (N - 1), N - 1), shape=(R, (N - 1) * l), out=O.get("others_next"))
-    S["goals_self_rep"] = t.add(goals, R * N, lg, goals.dtype, _lib.TILE_COPY, terms=by_n(), out=O.get("goals_self_rep"))
-    S["one_next_rep_n"] = t.add(vgn, R * N, l, vgn.dtype, _lib.TILE_COPY, terms=by_n(), out=O.get("one_next_rep_n"))
-    S["one_next_rep_m"] = t.add(vgn, R * N, l, vgn.dtype, _lib.TILE_COPY, terms=by_m(), out=O.get("one_next_rep_m"))
-    S["others_next_rep_n"] = t.add(vgn, R * N * (N - 1), l, f64, _lib.TILE_F32_TO_F64, others=(N, N * N * (N - 1), N - 1),
-                                   shape=(R * N, (N - 1) * l), out=O.get("others_next_rep_n"))
-    S["r_rep"] = t.add(reward_local, R * N, 1, reward_local.dtype, _lib.TILE_COPY, terms=by_n(), shape=(R * N,), out=O.get("r_rep"))
-    # (done per time step -> per agent row -> repeated by n: row (b, m, n) <- done[b])
-    S["nd_rep"] = t.add(done_u8, R * N, 1, i64, _lib.TILE_NOT_I64, terms=((N * N, 0, 1), (1, 0, 0)), shape=(R * N,), out=O.get("nd_rep"))
-    S["s_n_rep"] = t.add(vg, R * N, l, vg.dtype, _lib.TILE_COPY, terms=by_n(), out=O.get("s_n_rep"))
-    S["s_m_rep"] = t.add(vg, R * N, l, vg.dtype, _lib.TILE_COPY, terms=by_m(), out=O.get("s_m_rep"))
-    S["s_others_rep"] = t.add(vg, R * N * (N - 1), l, f64, _lib.TILE_F32_TO_F64, others=(N, N * N * (N - 1), N - 1),
-                              shape=(R * N, (N - 1) * l), out=O.get("s_others_rep"))
-    t.run()
-    S["a1_rep_m"] = t.add(actions, R * N, A, i64, _lib.TILE_ONEHOT_I64, terms=by_m(), out=O.get("a1_rep_m"))
-    S["cf_s_n"] = t.add(vg, R * N * A, l, vg.dtype, _lib.TILE_COPY, terms=by_n(A), out=O.get("cf_s_n"))
-    S["cf_goals"] = t.add(goals, R * N * A, lg, goals.dtype, _lib.TILE_COPY, terms=by_n(A), out=O.get("cf_goals"))
-    S["cf_eye"] = t.add(None, R * N * A, A, f64, _lib.TILE_EYE_F64, out=O.get("cf_eye"))
-    S["cf_s_m"] = t.add(vg, R * N * A, l, vg.dtype, _lib.TILE_COPY, terms=by_m(A), out=O.get("cf_s_m"))
-    S["cf_s_others"] = t.add(vg, R * N * A * (N - 1), l, f64, _lib.TILE_F32_TO_F64, others=(N, N * N * A * (N - 1), A * (N - 1)),
-                             shape=(R * N * A, (N - 1) * l), out=O.get("cf_s_others"))
-    t.run()
-    return S
-
-
 TileSpec = collections.namedtuple("TileSpec", "name src rows epr dtype kind terms others shape")
 TileSpec.__doc__ = """One output of cm3_rows_tile: `name` [shape, default (rows, epr)] of `dtype`, destination row r <- row f(r) of column `src`
 (None: no source), f from the two (divisor, modulus, multiplier) `terms` or, when given, the `others` triple (N, divq, divn) of the
 reference's `np.arange(N) != n` selections (include/cm3_amd.h, cm3_tile_col); `kind` one of _lib.TILE_*."""
+_IDENT = ((1, 0, 1), (1, 0, 0))
+
+
+def _row_maps(N):
+    """The row functions both spec tables use, for N agents: by_n / by_m (things the reference repeats "indexed by n" / "by m"), by_b
+    (per time step) and the `others` triple."""
+    by_n = lambda outer=1: ((outer * N * N, 0, N), (outer, N, 1))          # noqa: E731  rows (b, m, n[, a]) <- row b N + n
+    by_m = lambda outer=1: ((outer * N, 0, 1), (1, 0, 0))                   # noqa: E731  rows (r, m[, a])    <- row r
+    by_b = lambda per: ((per, 0, 1), (1, 0, 0))                             # noqa: E731  `per` rows per time step <- row b
+    oth = lambda per, inner: (N, per * (N - 1), inner * (N - 1))            # noqa: E731  `per` rows per time step, n varies every `inner`
+    return by_n, by_m, by_b, oth
+
+
+def particle_static_feed_specs(shapes, dtypes, l_action=5):
+    """The outputs of particle_static_feeds_device as a list of TileSpec, from shapes and dtypes alone (no device, no library): shapes
+    maps v_global and goals to the shapes of those columns of ParticleRollout.as_reference_batch -- [B, N, l], [B, N, l_goal] -- and
+    dtypes maps v_global, goals, reward and reward_local to theirs (the copies keep them; v_global_next is v_global's twin).  Source
+    names are column names; "actions" stands for the flat int32 actions, "done" for its bytes.  The sixteen outputs of the first
+    launch, then the six of the second: per agent row (B N rows; alg_credit.py:406-443, :528-557), the credit repeats (B N N;
+    :614-658), the counterfactual tiling (B N N l_action; :730-751)."""
+    from . import _lib
+    COPY, WIDEN, ONE_I, ONE_F, EYE, NOT = (_lib.TILE_COPY, _lib.TILE_F32_TO_F64, _lib.TILE_ONEHOT_I64, _lib.TILE_ONEHOT_F64,
+                                           _lib.TILE_EYE_F64, _lib.TILE_NOT_I64)
+    B, N, l = (int(v) for v in shapes["v_global"])
+    lg = int(shapes["goals"][2])
+    A, R = int(l_action), B * N
+    f64, i64, vt, gt = torch.float64, torch.int64, dtypes["v_global"], dtypes["goals"]
+    by_n, by_m, by_b, oth = _row_maps(N)
+    T = TileSpec
+    return [
+        T("a1", "actions", R, A, i64, ONE_I, _IDENT, None, None),
+        T("ao", "actions", R * (N - 1), A, f64, ONE_F, None, oth(N, 1), (R, N - 1, A)),
+        T("reward_rep", "reward", R, 1, dtypes["reward"], COPY, by_b(N), None, (R,)),
+        T("done_rep", "done", R, 1, torch.bool, COPY, by_b(N), None, (R,)),
+        T("not_done", "done", R, 1, i64, NOT, by_b(N), None, (R,)),
+        T("others", "v_global", R * (N - 1), l, f64, WIDEN, None, oth(N, 1), (R, (N - 1) * l)),
+        T("others_next", "v_global_next", R * (N - 1), l, f64, WIDEN, None, oth(N, 1), (R, (N - 1) * l)),
+        T("goals_self_rep", "goals", R * N, lg, gt, COPY, by_n(), None, None),
+        T("one_next_rep_n", "v_global_next", R * N, l, vt, COPY, by_n(), None, None),
+        T("one_next_rep_m", "v_global_next", R * N, l, vt, COPY, by_m(), None, None),
+        T("others_next_rep_n", "v_global_next", R * N * (N - 1), l, f64, WIDEN, None, oth(N * N, 1), (R * N, (N - 1) * l)),
+        T("r_rep", "reward_local", R * N, 1, dtypes["reward_local"], COPY, by_n(), None, (R * N,)),
+        T("nd_rep", "done", R * N, 1, i64, NOT, by_b(N * N), None, (R * N,)),
+        T("s_n_rep", "v_global", R * N, l, vt, COPY, by_n(), None, None),
+        T("s_m_rep", "v_global", R * N, l, vt, COPY, by_m(), None, None),
+        T("s_others_rep", "v_global", R * N * (N - 1), l, f64, WIDEN, None, oth(N * N, 1), (R * N, (N - 1) * l)),
+        # ---- second launch ----
+        T("a1_rep_m", "actions", R * N, A, i64, ONE_I, by_m(), None, None),
+        T("cf_s_n", "v_global", R * N * A, l, vt, COPY, by_n(A), None, None),
+        T("cf_goals", "goals", R * N * A, lg, gt, COPY, by_n(A), None, None),
+        T("cf_eye", None, R * N * A, A, f64, EYE, _IDENT, None, None),
+        T("cf_s_m", "v_global", R * N * A, l, vt, COPY, by_m(A), None, None),
+        T("cf_s_others", "v_global", R * N * A * (N - 1), l, f64, WIDEN, None, oth(N * N * A, A), (R * N * A, (N - 1) * l)),
+    ]
 
 
 def checkers_static_feed_specs(shapes, goals_dtype=torch.int64, l_action=5):
@@ -130,19 +139,15 @@ def checkers_static_feed_specs(shapes, goals_dtype=torch.int64, l_action=5):
     ne, nt, nv, lg = count(g_sh), count(t_sh), count(v_sh), int(shapes["goals"][2])
     A, R = int(l_action), B * N
     f64, i64 = torch.float64, torch.int64
-    ident = ((1, 0, 1), (1, 0, 0))
-    by_n = lambda outer=1: ((outer * N * N, 0, N), (outer, N, 1))          # noqa: E731  rows (b, m, n[, a]) <- row b N + n
-    by_m = lambda outer=1: ((outer * N, 0, 1), (1, 0, 0))                   # noqa: E731  rows (r, m[, a])    <- row r
-    by_b = lambda per: ((per, 0, 1), (1, 0, 0))                             # noqa: E731  `per` rows per time step <- row b
-    oth = lambda per, inner: (N, per * (N - 1), inner * (N - 1))            # noqa: E731  `per` rows per time step, n varies every `inner`
+    by_n, by_m, by_b, oth = _row_maps(N)
     T = TileSpec
-    specs = [
+    return [
         # ---- per agent row: process_batch (:414-482), process_global_state (:510-535), not_done (:560) ----
         T("state_env", "grid", R, ne, f64, COPY, by_b(N), None, (R,) + g_sh),
         T("state_env_next", "next_grid", R, ne, f64, COPY, by_b(N), None, (R,) + g_sh),
-        T("a1", "actions", R, A, i64, ONE_I, ident, None, None),
+        T("a1", "actions", R, A, i64, ONE_I, _IDENT, None, None),
         T("ao", "actions", R * (N - 1), A, f64, ONE_F, None, oth(N, 1), (R, N - 1, A)),
-        T("prev1", "actions_prev", R, A, i64, ONE_I, ident, None, None),
+        T("prev1", "actions_prev", R, A, i64, ONE_I, _IDENT, None, None),
         T("done_rep", "done", R, 1, torch.bool, COPY, by_b(N), None, (R,)),
         T("not_done", "done", R, 1, i64, NOT, by_b(N), None, (R,)),
         T("others", "vec", R * (N - 1), lv, f64, COPY, None, oth(N, 1), (R, (N - 1) * lv)),
@@ -167,14 +172,13 @@ def checkers_static_feed_specs(shapes, goals_dtype=torch.int64, l_action=5):
         # ---- the n x n x l_action counterfactual tiling (:700-760): each of the above repeated l_action times ----
         T("cf_s_n", "vec", R * N * A, lv, f64, COPY, by_n(A), None, None),
         T("cf_goals", "goals", R * N * A, lg, goals_dtype, COPY, by_n(A), None, None),
-        T("cf_eye", None, R * N * A, A, f64, EYE, ident, None, None),
+        T("cf_eye", None, R * N * A, A, f64, EYE, _IDENT, None, None),
         T("cf_s_m", "vec", R * N * A, lv, f64, COPY, by_m(A), None, None),
         T("cf_s_others", "vec", R * N * A * (N - 1), lv, f64, COPY, None, oth(N * N * A, A), (R * N * A, (N - 1) * lv)),
         T("cf_env", "grid", R * N * A, ne, f64, COPY, by_b(N * N * A), None, (R * N * A,) + g_sh),
         T("cf_ot", "obs_self_t", R * N * A, nt, f64, COPY, by_m(A), None, (R * N * A,) + t_sh),
         T("cf_ov", "obs_self_v", R * N * A, nv, f64, COPY, by_m(A), None, (R * N * A,) + v_sh),
     ]
-    return specs
 
 
 _CHECKERS_WIDE = ("grid", "vec", "obs_others", "obs_self_t", "obs_self_v", "reward", "local_rewards", "next_grid", "next_vec",
@@ -191,6 +195,47 @@ def checkers_static_feeds_apply(cols):
             and not cols["actions_prev"].dtype.is_floating_point)
 
 
+def _particle_static_feeds_apply(cols):
+    """Whether particle_static_feeds_device takes these columns: float32 on the GPU, more than one agent."""
+    vg = cols["v_global"]
+    return vg.is_cuda and vg.dtype == torch.float32 and vg.shape[1] > 1
+
+
+def _static_feeds_device(cols, specs, out):
+    """name -> device tensor for every TileSpec, 16 per launch of cm3_rows_tile, from the columns the specs name: action columns as
+    flat int32, done as its bytes, the rest made contiguous.  out: the dict of an earlier call -- written into again."""
+    src = {None: None}
+    for name in (s.src for s in specs):
+        if name in src:
+            continue
+        c = cols[name]
+        if name in ("actions", "actions_prev"):
+            src[name] = c.reshape(-1).to(torch.int32).contiguous()
+        elif name == "done":
+            c = c.contiguous()
+            src[name] = c.view(torch.uint8) if c.dtype == torch.bool else c.to(torch.uint8)
+        else:
+            src[name] = c.contiguous()
+    t = _Tiler(cols["goals"].device)
+    S, O = {}, (out or {})
+    for s in specs:
+        S[s.name] = t.add(src[s.src], s.rows, s.epr, s.dtype, s.kind, terms=s.terms, others=s.others,
+                          shape=s.shape, out=O.get(s.name))
+    t.run()
+    return S
+
+
+def particle_static_feeds_device(cols, l_action=5, out=None):
+    """Every feed of the reference's train_step that does not depend on a network output (particle env, N > 1, Q-credit variant), from
+    the float32 columns of ParticleRollout.as_reference_batch(numpy=False) -- the 22 outputs of particle_static_feed_specs in TWO
+    launches of cm3_rows_tile.  Values and dtypes are those of the torch composition (_static_feeds_composed; tests/test_batch.py
+    compares the two and both with the arrays the REAL train_step fed).  out: the dict an earlier call returned for the same batch
+    size -- the feeds are written into those tensors again (persistent addresses for a captured consumer)."""
+    names = ("v_global", "goals", "reward", "reward_local")
+    return _static_feeds_device(cols, particle_static_feed_specs({n: tuple(cols[n].shape) for n in names},
+                                                                 {n: cols[n].dtype for n in names}, l_action), out)
+
+
 def checkers_static_feeds_device(cols, l_action=5, out=None):
     """The Checkers twin of particle_static_feeds_device: every feed of alg_credit_checkers.train_step (:536-780; N > 1, Q-credit
     variant) that does not depend on a network output, from the 16 device columns of CheckersRollout.as_reference_batch(numpy=False)
@@ -201,18 +246,8 @@ def checkers_static_feeds_device(cols, l_action=5, out=None):
     if not checkers_static_feeds_apply(cols):
         raise ValueError("checkers_static_feeds_device takes contiguous device columns, float64 wide ones, more than one agent "
                          "(checkers_static_feeds_apply); the torch composition of train_step_feeds covers the rest")
-    src = dict(cols)
-    for name in ("actions", "actions_prev"):
-        src[name] = cols[name].reshape(-1).to(torch.int32).contiguous()
-    done = cols["done"]
-    src["done"] = done.view(torch.uint8) if done.dtype == torch.bool else done
-    t = _Tiler(cols["vec"].device)
-    S, O = {}, (out or {})
-    for s in checkers_static_feed_specs({n: tuple(v.shape) for n, v in cols.items()}, cols["goals"].dtype, l_action):
-        S[s.name] = t.add(None if s.src is None else src[s.src], s.rows, s.epr, s.dtype, s.kind, terms=s.terms, others=s.others,
-                          shape=s.shape, out=O.get(s.name))
-    t.run()
-    return S
+    return _static_feeds_device(cols, checkers_static_feed_specs({n: tuple(v.shape) for n, v in cols.items()}, cols["goals"].dtype,
+                                                                 l_action), out)
 
 
 def phase_static_feeds(cols_all, n_minibatches, l_action=5, env="particle"):
@@ -223,7 +258,7 @@ def phase_static_feeds(cols_all, n_minibatches, l_action=5, env="particle"):
     of CheckersRollout.on_policy_phase, from checkers_static_feeds_device (three launches)."""
     if env not in ("particle", "checkers"):
         raise ValueError("phase_static_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
-    S = checkers_static_feeds_device(cols_all, l_action) if env == "checkers" else particle_static_feeds_device(cols_all, l_action)
+    S = _ENVS[env].static_device(cols_all, l_action)
     M = int(n_minibatches)
     out = []
     for k in range(M):
@@ -288,15 +323,10 @@ class OnPolicyPhasePlan(object):
         first = self.cols is None
         self.cols, self.k = self.ro._phase_export(self.epochs, self.batch_size, generator, out=self.cols)
         self.env = "checkers" if "vec" in self.cols else "particle"         # (a CheckersRollout exports the 16 Checkers columns)
-        if self.env == "checkers":
-            if not checkers_static_feeds_apply(self.cols):
-                raise ValueError("OnPolicyPhasePlan covers Checkers device rollouts with more than one agent (the tiling kernels' case)")
-            self.static = checkers_static_feeds_device(self.cols, self.l_action, out=self.static)
-        else:
-            vg = self.cols["v_global"]
-            if not (vg.is_cuda and vg.dtype == torch.float32 and vg.shape[1] > 1):
-                raise ValueError("OnPolicyPhasePlan covers float32 device rollouts with more than one agent (the tiling kernels' case)")
-            self.static = particle_static_feeds_device(self.cols, self.l_action, out=self.static)
+        E = _ENVS[self.env]
+        if not E.static_apply(self.cols):
+            raise ValueError("OnPolicyPhasePlan covers %s with more than one agent (the tiling kernels' case)" % E.plan_covers)
+        self.static = E.static_device(self.cols, self.l_action, out=self.static)
         if first:
             M, k = self.epochs, self.k
             self._mb = [({n: v[m * k:(m + 1) * k] for n, v in self.cols.items()},
@@ -363,12 +393,14 @@ def td_target(reward, q, multiplier, gamma):
     return reward.to(torch.float64) + gamma * q * multiplier
 
 
-def process_actions_device(acts, n_steps, n_agents, l_action=5, rep_m=False):
+def process_actions_device(acts, n_steps, n_agents, l_action=5, rep_m=False, keep=None):
     """process_actions(acts.reshape(n_steps, N)) -- and optionally the one-hot rows repeated N times (`rep_m`, alg_credit.py:628) -- in
-    ONE cm3_rows_tile launch for a device tensor of sampled actions (any integer dtype)."""
+    ONE cm3_rows_tile launch for a device tensor of sampled actions (any integer dtype).  keep: an optional list that receives the
+    int32 form of the actions the launch reads (a temporary unless acts is flat int32) -- whoever captures the launch holds it."""
     from . import _lib
     N, A, R = n_agents, int(l_action), n_steps * n_agents
     a32 = acts.reshape(-1).to(torch.int32).contiguous()
+    _keep(keep, a32)
     t = _Tiler(acts.device)
     one = t.add(a32, R, A, torch.int64, _lib.TILE_ONEHOT_I64)
     others = t.add(a32, R * (N - 1), A, torch.float64, _lib.TILE_ONEHOT_F64, others=(N, N * (N - 1), N - 1), shape=(R, N - 1, A))
@@ -466,9 +498,87 @@ CHECKERS_BATCH_NAMES = ("n_steps", "state_env", "state_agents", "obs_others", "o
 
 # ---- every feed_dict of train_step (alg_credit.py:558-800, alg_credit_checkers.py:536-780) -------------------------------
 
-def _rep_n(x, n):
-    """things indexed by n: each time step's block of N rows repeated N times (alg_credit.py:621-623)"""
-    return repeat_indexed_by_n(x, n)
+PARTICLE_BATCH_NAMES = ("n_steps", "v_global", "obs_others", "v_local", "actions_1hot", "actions_others_1hot", "reward", "reward_local",
+                        "v_global_next", "obs_others_next", "v_local_next", "done", "goals")
+
+
+class _Particle(object):
+    """What train_step_feeds needs to know about the env -- column names, the feeds' keys, the static-feed builders -- as data."""
+    next_fmt, state, reward_local = "%s_next", "v_global", "reward_local"
+    actor_cols = ("obs_others", "v_local")                      # the actors' observation columns, in their rows methods' order
+    feed_keys = ("obs_others", "v_obs")                         # ... and the placeholders they feed
+    actions_prev = False                                        # the actors take no previous action
+    critic_head, critic_tail = ("v_global",), ()                # the critics' columns before (goals, actions) and after them
+    env_keys = ()                                               # placeholders of the env's own state: none
+    static_apply, static_device = staticmethod(_particle_static_feeds_apply), staticmethod(particle_static_feeds_device)
+    plan_covers = "float32 device rollouts"
+    process_batch, batch_names = staticmethod(process_batch), PARTICLE_BATCH_NAMES
+    # the composed static dict: entries taken from process_batch, entries repeated by m, entries repeated l_action times
+    from_batch = (("a1", "actions_1hot"), ("ao", "actions_others_1hot"), ("reward_rep", "reward"), ("done_rep", "done"))
+    env_rep_m, env_rep_a = (), ()
+
+
+class _Checkers(object):
+    next_fmt, state, reward_local = "next_%s", "vec", "local_rewards"
+    actor_cols = feed_keys = ("obs_self_t", "obs_self_v", "obs_others")
+    actions_prev = True                                         # ... and the previous action (one-hot in the feed, an index to an actor)
+    critic_head, critic_tail = ("grid", "vec"), ("obs_self_t", "obs_self_v")
+    env_keys = ("state_env", "obs_self_t", "obs_self_v")
+    static_apply, static_device = staticmethod(checkers_static_feeds_apply), staticmethod(checkers_static_feeds_device)
+    plan_covers = "Checkers device rollouts"
+    process_batch, batch_names = staticmethod(process_batch_checkers), CHECKERS_BATCH_NAMES
+    from_batch = (("state_env", "state_env"), ("state_env_next", "state_env_next"), ("a1", "actions_1hot"),
+                  ("ao", "actions_others_1hot"), ("prev1", "actions_prev_1hot"), ("done_rep", "done"))
+    env_rep_m = (("env_next_rep", "state_env_next"), ("ot_next_rep", "obs_self_t_next"), ("ov_next_rep", "obs_self_v_next"),
+                 ("env_rep", "state_env"), ("ot_rep", "obs_self_t"), ("ov_rep", "obs_self_v"))
+    env_rep_a = (("cf_env", "env_rep"), ("cf_ot", "ot_rep"), ("cf_ov", "ov_rep"))
+
+
+_ENVS = {"particle": _Particle, "checkers": _Checkers}
+
+
+class _Recorder(object):
+    """Plays sess.run for the feed builders: call(ops, feed) records (ops, feed) in self.calls and returns run(ops, feed) -- or, with
+    launch=False (a device network answers instead), None."""
+
+    def __init__(self, run):
+        self.run, self.calls = run, []
+
+    def __call__(self, ops, feed, launch=True):
+        self.calls.append((ops, feed))
+        return self.run(ops, feed) if launch else None
+
+
+def _static_feeds_composed(cols, E, l_action, credit):
+    """The dict of particle_static_feeds_device / checkers_static_feeds_device -- the same names, shapes, dtypes and bits
+    (tests/test_static_feeds_composed.py) -- from torch's own gathers and repeats, as the reference composes them: the specification
+    the tiling kernels are tested against, and the path of the inputs they do not take (host tensors, float64 particle columns, one
+    agent, device_tiling=False, the variants without Q-credit).  Per agent row always; the n x n credit repeats and the n x n x
+    l_action counterfactual tiling only with `credit`."""
+    T = dict(zip(E.batch_names, E.process_batch(cols, l_action)))
+    S = {name: T[src] for name, src in E.from_batch}
+    v_global, v_global_next, goals = cols[E.state], cols[E.next_fmt % E.state], cols["goals"]
+    B, N = v_global.shape[0], v_global.shape[1]
+    one, S["others"], _ = process_global_state(v_global)
+    one_next, S["others_next"], _ = process_global_state(v_global_next)
+    S["not_done"] = -(S["done_rep"].to(torch.int64) - 1)                            # if true, then 0, else 1 (:590)
+    if not credit:
+        return S
+    rep_n = lambda x: repeat_indexed_by_n(x, N)                                     # noqa: E731  things indexed by n (:621-623)
+    rep_m = lambda x: repeat_indexed_by_m(x, N)                                     # noqa: E731  things indexed by m (:628-629)
+    rep_a = lambda x: rep_rows(x, l_action)                                         # noqa: E731
+    S["goals_self_rep"] = rep_n(goals.reshape(-1, goals.shape[2]))
+    S["one_next_rep_n"], S["one_next_rep_m"], S["others_next_rep_n"] = rep_n(one_next), rep_m(one_next), rep_n(S["others_next"])
+    S["r_rep"] = rep_n(T["reward_local"].reshape(-1, 1)).reshape(-1)
+    S["nd_rep"] = -(rep_n(S["done_rep"].reshape(-1, 1).to(torch.int64)).reshape(-1) - 1)
+    S["s_n_rep"], S["s_others_rep"], S["s_m_rep"] = rep_n(one), rep_n(S["others"]), rep_m(one)
+    S["a1_rep_m"] = rep_m(S["a1"])
+    S.update((name, rep_m(T[src])) for name, src in E.env_rep_m)
+    eye = torch.eye(l_action, dtype=torch.float64, device=one.device)               # self.actions = np.eye(l_action)
+    S["cf_s_n"], S["cf_goals"], S["cf_eye"] = rep_a(S["s_n_rep"]), rep_a(S["goals_self_rep"]), eye.repeat(N * N * B, 1)
+    S["cf_s_m"], S["cf_s_others"] = rep_a(S["s_m_rep"]), rep_a(S["s_others_rep"])
+    S.update((name, rep_a(S[src])) for name, src in E.env_rep_a)
+    return S
 
 
 def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=True, use_V=True, l_action=5, device_tiling=True,
@@ -522,7 +632,7 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     list_update_target_ops -- are the caller's: ``q_global_target.soft_update_from(main, tau)`` after this function returns.  keep
     receives the tensors of these launches too.  With all three None nothing changes: not a launch, not a bit."""
     checkers = env == "checkers"
-    calls = []
+    E = _ENVS["checkers" if checkers else "particle"]
     critics = (("q_global_target", q_global_target), ("q_credit_target", q_credit_target), ("q_credit", q_credit))
     if any(c is not None for _, c in critics):
         from .critic import CheckersCritic, ParticleCritic
@@ -532,7 +642,7 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
                 if isinstance(c, ParticleCritic):
                     raise ValueError("train_step_feeds: %s is a ParticleCritic; env='checkers' has no device critics of that class, "
                                      "pass CheckersCritics" % name)
-        base = cols["vec" if checkers else "v_global"]
+        base = cols[E.state]
         n_batch = base.shape[1]
         for name, c in critics:
             if c is None:
@@ -557,217 +667,140 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     # (draw / keep reach the actors only when given: a call without them is the call of before)
     probs_kw = {} if keep is None else {"keep": keep}
     sample_kw = dict(probs_kw) if draw is None else dict(probs_kw, draw=draw)
+    call = _Recorder(run)
+    f64 = torch.float64
+    v_global, goals = cols[E.state], cols["goals"]
+    n_steps, N = v_global.shape[0], v_global.shape[1]
+    credit = N > 1 and use_Q_credit
+    # S: every feed that does not depend on a network output, under the names of the spec tables.  Columns the tiling kernels take
+    # (float32 particle / float64 Checkers on the GPU, N > 1, Q-credit) come from cm3_rows_tile -- or from `static`, at no launch
+    # here; everything else from the torch composition, the specification both are tested against
+    tiled = static is not None or bool(use_Q_credit and device_tiling and E.static_apply(cols))
+    S = static if static is not None else (E.static_device(cols, l_action) if tiled
+                                           else _static_feeds_composed(cols, E, l_action, credit))
+    rows = lambda x: x.reshape(n_steps * N, *x.shape[2:])                           # noqa: E731
+    col = lambda name, nxt=False: cols[E.next_fmt % name if nxt else name]          # noqa: E731
+    v_global_next, reward_local = col(E.state, True), cols[E.reward_local].reshape(n_steps * N)
+    obs = {nxt: tuple(rows(col(name, nxt)) for name in E.actor_cols) for nxt in (False, True)}
+    goals_self = goals.reshape(-1, goals.shape[2])
+    one, one_next = v_global.reshape(-1, v_global.shape[2]), v_global_next.reshape(-1, v_global_next.shape[2])
+    X = dict(S)                     # ... and the per-agent observation rows, for with_env
+    X.update(zip(E.actor_cols, obs[False]))
+    X.update(zip((name + "_next" for name in E.actor_cols), obs[True]))
 
-    def call(ops, feed, launch=True):
-        calls.append((ops, feed))
-        return run(ops, feed) if launch else None
+    def actor_feed(nxt):
+        """the feed of an actor op on this step's (the next step's) observation"""
+        feed = dict(zip(E.feed_keys, obs[nxt]), v_goal=goals_self, epsilon=epsilon)
+        if E.actions_prev:          # run_actor_target(actions_1hot, obs_others_next, ...) (alg_credit_checkers.py:551)
+            feed["actions_prev"] = S["a1"] if nxt else S["prev1"]
+        return feed
+
+    def actor_args(nxt):
+        """the same as the arguments of a device actor's rows methods"""
+        prev = (cols["actions" if nxt else "actions_prev"].reshape(-1),) if E.actions_prev else ()
+        return obs[nxt] + prev + (goals_self, epsilon)
+
+    def with_env(feed, *names, f=lambda x: x):
+        """Checkers: the env's state and the windows under state_env / obs_self_t / obs_self_v; particle: nothing"""
+        feed.update((key, f(X[name])) for key, name in zip(E.env_keys, names))
+        return feed
 
     def critic_cols(nxt):
         """the base columns a device critic decodes its rows from, as (those before the actions, those after them)"""
-        if checkers:
-            pre = "next_" if nxt else ""
-            return (cols[pre + "grid"], cols[pre + "vec"], goals), (cols[pre + "obs_self_t"], cols[pre + "obs_self_v"])
-        return (v_global_next if nxt else v_global, goals), ()
+        return tuple(col(name, nxt) for name in E.critic_head) + (goals,), tuple(col(name, nxt) for name in E.critic_tail)
 
-    if checkers:
-        # float64 columns on the GPU: the static feeds come from three launches of cm3_rows_tile (checkers_static_feeds_device); host
-        # tensors, N = 1 and the variants without Q-credit go through the torch composition -- the specification, as for particle
-        S = static if static is not None else (
-            checkers_static_feeds_device(cols, l_action) if (use_Q_credit and device_tiling and checkers_static_feeds_apply(cols)) else None)
-        if S is not None:
-            B_, N_ = cols["vec"].shape[0], cols["vec"].shape[1]
-            rows = lambda x: x.reshape(B_ * N_, *x.shape[2:])            # noqa: E731
-            (n_steps, state_env, state_agents, obs_others, obs_self_t, obs_self_v, actions_prev_1hot, actions_1hot,
-             actions_others_1hot, reward, reward_local, state_env_next, state_agents_next, obs_others_next, obs_self_t_next,
-             obs_self_v_next, done, goals) = (
-                B_, S["state_env"], cols["vec"], rows(cols["obs_others"]), rows(cols["obs_self_t"]), rows(cols["obs_self_v"]), S["prev1"],
-                S["a1"], S["ao"], cols["reward"], cols["local_rewards"].reshape(B_ * N_), S["state_env_next"], cols["next_vec"],
-                rows(cols["next_obs_others"]), rows(cols["next_obs_self_t"]), rows(cols["next_obs_self_v"]), S["done_rep"], cols["goals"])
-        else:
-            (n_steps, state_env, state_agents, obs_others, obs_self_t, obs_self_v, actions_prev_1hot, actions_1hot,
-             actions_others_1hot, reward, reward_local, state_env_next, state_agents_next, obs_others_next, obs_self_t_next,
-             obs_self_v_next, done, goals) = process_batch_checkers(cols, l_action)
-        v_global, v_global_next = state_agents, state_agents_next
-    else:
-        vg0 = cols["v_global"]
-        # float32 columns on the GPU: everything that does not depend on a network output comes from two launches of
-        # cm3_rows_tile (particle_static_feeds_device); other inputs (the float64 parity path, host tensors of the CPU tests, N = 1,
-        # the variants without Q-credit) go through the torch composition below -- the specification both are tested against
-        S = static if static is not None else (
-            particle_static_feeds_device(cols, l_action)
-            if (vg0.is_cuda and vg0.dtype == torch.float32 and vg0.shape[1] > 1 and use_Q_credit and device_tiling) else None)
-        if S is not None:
-            B_, N_ = vg0.shape[0], vg0.shape[1]
-            (n_steps, v_global, obs_others, v_local, actions_1hot, actions_others_1hot, reward, reward_local, v_global_next,
-             obs_others_next, v_local_next, done, goals) = (
-                B_, vg0, cols["obs_others"].reshape(B_ * N_, -1), cols["v_local"].reshape(B_ * N_, -1), S["a1"], S["ao"], S["reward_rep"],
-                cols["reward_local"].reshape(B_ * N_), cols["v_global_next"], cols["obs_others_next"].reshape(B_ * N_, -1),
-                cols["v_local_next"].reshape(B_ * N_, -1), S["done_rep"], cols["goals"])
-        else:
-            (n_steps, v_global, obs_others, v_local, actions_1hot, actions_others_1hot, reward, reward_local, v_global_next,
-             obs_others_next, v_local_next, done, goals) = process_batch(cols, l_action)
-    N = v_global.shape[1]
-    goals_self, _ = process_goals(goals) if S is None else (goals.reshape(-1, goals.shape[2]), None)
-    if S is None:
-        one, others, _ = process_global_state(v_global)
-        one_next, others_next, _ = process_global_state(v_global_next)
-    else:
-        one, others = v_global.reshape(-1, v_global.shape[2]), S["others"]
-        one_next, others_next = v_global_next.reshape(-1, v_global_next.shape[2]), S["others_next"]
-    f64 = torch.float64
-    not_done = (-(done.to(torch.int64) - 1)) if S is None else S["not_done"]      # if true, then 0, else 1 (:590)
-
-    def actor_feed(oo, *obs):
-        if checkers:
-            return {"obs_others": oo, "obs_self_t": obs[0], "obs_self_v": obs[1], "actions_prev": obs[2],
-                    "v_goal": goals_self, "epsilon": epsilon}
-        return {"obs_others": oo, "v_obs": obs[0], "v_goal": goals_self, "epsilon": epsilon}
-
-    def with_env(feed, s_env=None, ot=None, ov=None):
-        if checkers:
-            feed["state_env"] = s_env
-            if ot is not None:
-                feed["obs_self_t"], feed["obs_self_v"] = ot, ov
-        return feed
+    def td(reward, q, multiplier):
+        """reward + gamma * q * multiplier, float64 (:594, :640, :684): one launch next to the tiled feeds, torch's own otherwise"""
+        return td_target(reward, q, multiplier, gamma) if tiled else reward.to(f64) + gamma * q.reshape(-1) * multiplier
 
     # ---- Q_n(s, a): target actions a', TD target, optimiser step (alg_credit.py:574-612) ----
-    if checkers:      # run_actor_target(actions_1hot, obs_others_next, ...) (alg_credit_checkers.py:551)
-        feed = actor_feed(obs_others_next, obs_self_t_next, obs_self_v_next, actions_1hot)
-        if target_actor is None:
-            acts = call(["action_samples_target"], feed)[0]
-        else:
-            call(["action_samples_target"], feed, launch=False)
-            acts = target_actor.sample_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(-1), goals_self,
-                                            epsilon, **sample_kw)["actions"]
-    elif target_actor is not None:
-        call(["action_samples_target"], actor_feed(obs_others_next, v_local_next), launch=False)
-        acts = target_actor.sample_rows(obs_others_next, v_local_next, goals_self, epsilon, **sample_kw)["actions"]
+    if target_actor is None:
+        acts = call(["action_samples_target"], actor_feed(True))[0]
     else:
-        acts = call(["action_samples_target"], actor_feed(obs_others_next, v_local_next))[0]
-    a_next_rep = None
-    if S is not None and acts.is_cuda:    # one launch: both one-hot forms and the rows repeated by m (Q-credit target, :628)
-        a_next, a_others_next, a_next_rep = process_actions_device(acts, n_steps, N, l_action, rep_m=N > 1 and use_Q_credit)
+        call(["action_samples_target"], actor_feed(True), launch=False)
+        acts = target_actor.sample_rows(*actor_args(True), **sample_kw)["actions"]
+    if tiled and acts.is_cuda:      # one launch: both one-hot forms and the rows repeated by m (Q-credit target, :628)
+        a_next, a_others_next, a_next_rep = process_actions_device(acts, n_steps, N, l_action, rep_m=credit, keep=keep)
     else:
-        a_next, a_others_next = process_actions(acts.reshape(n_steps, N), l_action)
+        a_next, a_others_next, a_next_rep = process_actions(acts.reshape(n_steps, N), l_action) + (None,)
     feed = with_env({"v_state_one_agent": one_next, "v_goal": goals_self, "action_one": a_next,
-                     "v_state_other_agents": others_next, "action_others": a_others_next},
-                    state_env_next if checkers else None, obs_self_t_next if checkers else None, obs_self_v_next if checkers else None)
+                     "v_state_other_agents": S["others_next"], "action_others": a_others_next},
+                    "state_env_next", "obs_self_t_next", "obs_self_v_next")
     if q_global_target is not None:     # one launch on the base columns: Q and the TD target
         call(["Q_global_target"], feed, launch=False)
         head, tail = critic_cols(True)
-        td = q_global_target.q_rows(*head, acts, *tail, reward_local, cols["done"], gamma, **probs_kw)["td"]
+        td_g = q_global_target.q_rows(*head, acts, *tail, reward_local, cols["done"], gamma, **probs_kw)["td"]
     else:
-        q_t = call(["Q_global_target"], feed)[0]
-        td = td_target(reward_local, q_t, not_done, gamma) if S is not None else reward_local.to(f64) + gamma * q_t.reshape(-1) * not_done
+        td_g = td(reward_local, call(["Q_global_target"], feed)[0], S["not_done"])
     q_res = call(["Q_global_op", "Q_global"],
-                 with_env({"Q_global_td_target": td, "v_state_one_agent": one, "v_goal": goals_self, "action_one": actions_1hot,
-                           "v_state_other_agents": others, "action_others": actions_others_1hot},
-                          state_env if checkers else None, obs_self_t if checkers else None,
-                          obs_self_v if checkers else None))[1]
+                 with_env({"Q_global_td_target": td_g, "v_state_one_agent": one, "v_goal": goals_self, "action_one": S["a1"],
+                           "v_state_other_agents": S["others"], "action_others": S["ao"]},
+                          "state_env", "obs_self_t", "obs_self_v"))[1]
     if N == 1 and q_credit is not None:
         q_credit.repack()           # (one agent: the counterfactual below reads the Q_global_main weights this step updated)
     q_res_rep = rep_rows(q_res.reshape(n_steps, N), N)                              # :612
 
-    rep_m = lambda x: rep_rows(x, N)                                                # noqa: E731  things indexed by m
-    s_n_rep = s_m_rep = s_others_rep = goals_self_rep = s_env_rep = ot_rep = ov_rep = None
-    if N > 1 and use_Q_credit:      # ---- Q_n(s, a^m) (:616-674) ----
-        goals_self_rep = _rep_n(goals_self, N) if S is None else S["goals_self_rep"]
-        feed = {"v_state_one_agent": _rep_n(one_next, N) if S is None else S["one_next_rep_n"], "v_goal": goals_self_rep,
-                "action_one": rep_m(a_next) if a_next_rep is None else a_next_rep,
-                "v_state_m": rep_m(one_next) if S is None else S["one_next_rep_m"],
-                "v_state_other_agents": _rep_n(others_next, N) if S is None else S["others_next_rep_n"]}
-        if checkers:
-            feed = (with_env(feed, rep_m(state_env_next), rep_m(obs_self_t_next), rep_m(obs_self_v_next)) if S is None
-                    else with_env(feed, S["env_next_rep"], S["ot_next_rep"], S["ov_next_rep"]))
+    if credit:                      # ---- Q_n(s, a^m) (:616-674): things indexed by n repeat per block, things indexed by m row by row ----
+        feed = with_env({"v_state_one_agent": S["one_next_rep_n"], "v_goal": S["goals_self_rep"],
+                         "action_one": rep_rows(a_next, N) if a_next_rep is None else a_next_rep,
+                         "v_state_m": S["one_next_rep_m"], "v_state_other_agents": S["others_next_rep_n"]},
+                        "env_next_rep", "ot_next_rep", "ov_next_rep")
         if q_credit_target is not None:
             call(["Q_credit_target"], feed, launch=False)
             head, tail = critic_cols(True)
             td_c = q_credit_target.q_pairs(*head, acts, *tail, reward_local, cols["done"], gamma, **probs_kw)["td"]
         else:
-            qc_t = call(["Q_credit_target"], feed)[0]
-        if S is None:
-            r_rep = _rep_n(reward_local.reshape(-1, 1), N).reshape(-1)
-            nd_rep = -(_rep_n(done.reshape(-1, 1).to(torch.int64), N).reshape(-1) - 1)
-            s_n_rep, s_others_rep, s_m_rep = _rep_n(one, N), _rep_n(others, N), rep_m(one)
-        else:
-            r_rep, nd_rep = S["r_rep"], S["nd_rep"]
-            s_n_rep, s_others_rep, s_m_rep = S["s_n_rep"], S["s_others_rep"], S["s_m_rep"]
-        if q_credit_target is None:
-            td_c = td_target(r_rep, qc_t, nd_rep, gamma) if S is not None else r_rep.to(f64) + gamma * qc_t.reshape(-1) * nd_rep
-        feed = {"Q_credit_td_target": td_c, "v_state_one_agent": s_n_rep, "v_goal": goals_self_rep,
-                "action_one": rep_m(actions_1hot) if S is None else S["a1_rep_m"], "v_state_m": s_m_rep,
-                "v_state_other_agents": s_others_rep}
-        if checkers:
-            s_env_rep, ot_rep, ov_rep = ((rep_m(state_env), rep_m(obs_self_t), rep_m(obs_self_v)) if S is None
-                                         else (S["env_rep"], S["ot_rep"], S["ov_rep"]))
-            feed = with_env(feed, s_env_rep, ot_rep, ov_rep)
-        call(["Q_credit_op"], feed)
+            td_c = td(S["r_rep"], call(["Q_credit_target"], feed)[0], S["nd_rep"])
+        call(["Q_credit_op"], with_env({"Q_credit_td_target": td_c, "v_state_one_agent": S["s_n_rep"], "v_goal": S["goals_self_rep"],
+                                        "action_one": S["a1_rep_m"], "v_state_m": S["s_m_rep"],
+                                        "v_state_other_agents": S["s_others_rep"]}, "env_rep", "ot_rep", "ov_rep"))
         if q_credit is not None:
             q_credit.repack()       # (the counterfactual below reads the Q_credit_main weights this step updated)
     v_res_rep = None
     if N > 1 and use_V:             # ---- V_n(s) (:676-699) ----
         v_t = call(["V_target"], with_env({"v_state_one_agent": one_next, "v_goal": goals_self,
-                                           "v_state_other_agents": others_next}, state_env_next if checkers else None))[0]
-        td_v = td_target(reward_local, v_t, not_done, gamma) if S is not None else reward_local.to(f64) + gamma * v_t.reshape(-1) * not_done
-        v_res = call(["V_op", "V"], with_env({"V_td_target": td_v, "v_state_one_agent": one, "v_goal": goals_self,
-                                              "v_state_other_agents": others}, state_env if checkers else None))[1]
+                                           "v_state_other_agents": S["others_next"]}, "state_env_next"))[0]
+        v_res = call(["V_op", "V"], with_env({"V_td_target": td(reward_local, v_t, S["not_done"]), "v_state_one_agent": one,
+                                              "v_goal": goals_self, "v_state_other_agents": S["others"]}, "state_env"))[1]
         v_res_rep = rep_rows(v_res.reshape(n_steps, N), N)
 
     # ---- policy: probabilities + counterfactual Q for every action (:704-757) ----
-    pol_obs = (obs_self_t, obs_self_v, actions_prev_1hot) if checkers else (v_local,)
-
     def fetch_probs():
-        feed = actor_feed(obs_others, *pol_obs)
         if actor is None:
-            return call(["probs"], feed)[0]
-        call(["probs"], feed, launch=False)
-        if checkers:
-            return actor.probs_rows(obs_self_t, obs_self_v, obs_others, cols["actions_prev"].reshape(-1), goals_self, epsilon,
-                                    **probs_kw)
-        return actor.probs_rows(obs_others, v_local, goals_self, epsilon, **probs_kw)
+            return call(["probs"], actor_feed(False))[0]
+        call(["probs"], actor_feed(False), launch=False)
+        return actor.probs_rows(*actor_args(False), **probs_kw)
 
-    rep_a = lambda x: rep_rows(x, l_action)                                         # noqa: E731
-    eye = torch.eye(l_action, dtype=f64, device=one.device)                         # self.actions = np.eye(l_action)
+    def counterfactual(op, feed, n_rows):
+        if q_credit is None:
+            return call([op], feed)[0].reshape(n_rows, l_action)
+        call([op], feed, launch=False)
+        head, tail = critic_cols(False)
+        return q_credit.q_counterfactual(*head, *tail, **probs_kw)
+
     if N == 1:                      # stage 1: Q(s, a = every action, g)
         probs = fetch_probs()
-        feed = {"v_state_one_agent": rep_a(one), "v_goal": rep_a(goals_self), "action_one": eye.repeat(n_steps, 1),
-                "v_state_other_agents": others, "action_others": actions_others_1hot}
-        if checkers:
-            feed = with_env(feed, rep_a(state_env), rep_a(obs_self_t), rep_a(obs_self_v))
-        if q_credit is not None:
-            call(["Q_global"], feed, launch=False)
-            head, tail = critic_cols(False)
-            q_cf = q_credit.q_counterfactual(*head, *tail, **probs_kw)
-        else:
-            q_cf = call(["Q_global"], feed)[0].reshape(n_steps, l_action)
+        rep_a = lambda x: rep_rows(x, l_action)                                     # noqa: E731
+        eye = torch.eye(l_action, dtype=f64, device=one.device)                     # self.actions = np.eye(l_action)
+        q_cf = counterfactual("Q_global", with_env({"v_state_one_agent": rep_a(one), "v_goal": rep_a(goals_self),
+                                                    "action_one": eye.repeat(n_steps, 1), "v_state_other_agents": S["others"],
+                                                    "action_others": S["ao"]}, "state_env", "obs_self_t", "obs_self_v", f=rep_a),
+                              n_steps)
     elif use_Q_credit:
         probs = rep_rows(fetch_probs(), N)
-        if S is None:
-            feed = {"v_state_one_agent": rep_a(s_n_rep), "v_goal": rep_a(goals_self_rep),
-                    "action_one": eye.repeat(N * N * n_steps, 1), "v_state_m": rep_a(s_m_rep),
-                    "v_state_other_agents": rep_a(s_others_rep)}
-        else:
-            feed = {"v_state_one_agent": S["cf_s_n"], "v_goal": S["cf_goals"], "action_one": S["cf_eye"], "v_state_m": S["cf_s_m"],
-                    "v_state_other_agents": S["cf_s_others"]}
-        if checkers:
-            feed = (with_env(feed, rep_a(s_env_rep), rep_a(ot_rep), rep_a(ov_rep)) if S is None
-                    else with_env(feed, S["cf_env"], S["cf_ot"], S["cf_ov"]))
-        if q_credit is not None:
-            call(["Q_credit"], feed, launch=False)
-            head, tail = critic_cols(False)
-            q_cf = q_credit.q_counterfactual(*head, *tail, **probs_kw)
-        else:
-            q_cf = call(["Q_credit"], feed)[0].reshape(n_steps * N * N, l_action)
+        q_cf = counterfactual("Q_credit", with_env({"v_state_one_agent": S["cf_s_n"], "v_goal": S["cf_goals"], "action_one": S["cf_eye"],
+                                                    "v_state_m": S["cf_s_m"], "v_state_other_agents": S["cf_s_others"]},
+                                                   "cf_env", "cf_ot", "cf_ov"), n_steps * N * N)
     else:
         probs = torch.zeros(1, l_action, dtype=f64, device=one.device)
         q_cf = torch.zeros(1, l_action, dtype=f64, device=one.device)
-    feed = actor_feed(obs_others, *pol_obs)
-    feed.update({"action_taken": actions_1hot, "Q_actual": q_res_rep, "probs_evaluated": probs, "Q_cf": q_cf})
+    feed = actor_feed(False)
+    feed.update({"action_taken": S["a1"], "Q_actual": q_res_rep, "probs_evaluated": probs, "Q_cf": q_cf})
     if N > 1 and use_V:
         feed["V_evaluated"] = v_res_rep
     call(["policy_op"], feed)
     call(["list_update_target_ops"], {})
-    return calls
+    return call.calls
 
 
 # ---- QMIX (alg_qmix.py:236-380): everything of train_step that is not the mixer ----------------------------------------------
@@ -841,14 +874,24 @@ def process_batch_qmix_checkers(cols, l_action=5):
             rows(cols["next_obs_self_v"]), cols["done"], cols["goals"])
 
 
-def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action):
+def _onehot_rows(columns, l_action, device, keep=None):
+    """The int64 one-hot rows [B * N, l_action] of each action column [B, N]: on the device all of them in ONE tiling launch (keep, if
+    given, receives the flat int32 forms the launch reads), otherwise torch's one_hot."""
+    A = int(l_action)
+    if not device:
+        return [torch.nn.functional.one_hot(c.long(), A).reshape(-1, A) for c in columns]
+    from . import _lib
+    t = _Tiler(columns[0].device)
+    a32 = [c.reshape(-1).to(torch.int32).contiguous() for c in columns]
+    _keep(keep, *a32)
+    out = [t.add(a, a.numel(), A, torch.int64, _lib.TILE_ONEHOT_I64) for a in a32]
+    t.run()
+    return out
+
+
+def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep):
     """The Checkers form of qmix_train_step_feeds (alg_qmix_checkers.py:342-393)."""
-    calls = []
-
-    def call(ops, feed, launch=True):
-        calls.append((ops, feed))
-        return run(ops, feed) if launch else None
-
+    call = _Recorder(run)
     vec = cols["vec"]
     B, N = vec.shape[0], vec.shape[1]
     device = target_agent is not None
@@ -861,16 +904,7 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action):
     goals = cols["goals"]
     goals_all, goals_self = goals.reshape(B, -1), rows(goals)                       # :348-349
     state_agents_next, state_agents = cols["next_vec"].reshape(B, -1), vec.reshape(B, -1)   # :350-351
-    if device:
-        from . import _lib
-        t = _Tiler(vec.device)
-        actions_1hot = t.add(cols["actions"].reshape(-1).to(torch.int32).contiguous(), B * N, int(l_action), torch.int64, _lib.TILE_ONEHOT_I64)
-        actions_prev_1hot = t.add(cols["actions_prev"].reshape(-1).to(torch.int32).contiguous(), B * N, int(l_action), torch.int64,
-                                  _lib.TILE_ONEHOT_I64)
-        t.run()
-    else:
-        actions_1hot = process_actions(cols["actions"], l_action)[0]
-        actions_prev_1hot = torch.nn.functional.one_hot(cols["actions_prev"].long(), int(l_action)).reshape(B * N, int(l_action))
+    actions_1hot, actions_prev_1hot = _onehot_rows((cols["actions"], cols["actions_prev"]), l_action, device, keep)
 
     # ---- argmax actions of the target agents, one-hot (:353-362).  The reference feeds actions_prev : actions_1hot here and in the
     # mixer_target feed -- the action JUST TAKEN, next to the next_* observations -- not the actions_prev column ----
@@ -893,10 +927,10 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action):
                         "actions_prev": actions_prev_1hot, "obs_others": obs_others, "obs_self_t": obs_self_t,
                         "obs_self_v": obs_self_v, "v_goal": goals_self, "td_target": target})
     call(["list_update_target_ops"], {})
-    return calls
+    return call.calls
 
 
-def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle", target_mixer=None):
+def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle", target_mixer=None, keep=None):
     """The data side of the QMIX train_step (alg_qmix.py:338-380) from the columns of a sampled particle batch: builds, in the
     reference's order, the feed_dict of its four sess.run calls -- ["argmax_Q_target"], ["mixer_target"], ["mixer_op"],
     ["list_update_target_ops"] -- and returns the list of (ops, feed).  ``run(ops, feed)`` plays sess.run as in train_step_feeds: ops
@@ -924,12 +958,15 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     Checkers batch; placeholders state_env, v_state, v_goal_all, actions_1hot, actions_prev, obs_others, obs_self_t, obs_self_v,
     v_goal, td_target.  In the two TARGET feeds actions_prev is fed actions_1hot (the action just taken, as the reference does),
     in mixer_op the one-hot actions_prev column.  target_agent: a CheckersQmixAgent holding the Agent_target weights; both one-hot
-    action feeds come from one tiling launch.  Pinned to tests/golden/trainstep_qmix_checkers_n*.npz."""
+    action feeds come from one tiling launch.  Pinned to tests/golden/trainstep_qmix_checkers_n*.npz.
+
+    keep: an optional list that receives the int32 action temporaries the one-hot tiling launch reads -- whoever captures this
+    function's launches into a hipGraph holds them for as long as the graph is replayed."""
     if env == "checkers":
         if target_mixer is not None:
             raise ValueError("qmix_train_step_feeds: env='checkers' has no device mixer (the Checkers mixer is not built); call "
                              "without target_mixer, `run` answers mixer_target")
-        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action)
+        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep)
     if env != "particle":
         raise ValueError("qmix_train_step_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
     if target_mixer is not None:
@@ -944,12 +981,7 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
                              "(a ParticleQmixAgent holding the Agent_target weights) as well")
         if not cols["v_global"].is_cuda:
             raise ValueError("qmix_train_step_feeds: target_mixer evaluates device columns; call without it for host tensors")
-    calls = []
-
-    def call(ops, feed, launch=True):
-        calls.append((ops, feed))
-        return run(ops, feed) if launch else None
-
+    call = _Recorder(run)
     vg = cols["v_global"]
     B, N = vg.shape[0], vg.shape[1]
     device = target_agent is not None
@@ -961,13 +993,7 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     goals = cols["goals"]
     goals_all, goals_self = goals.reshape(B, -1), rows(goals)                       # :344-345
     state_next, state = cols["v_global_next"].reshape(B, -1), vg.reshape(B, -1)     # :346-347
-    if device:
-        from . import _lib
-        t = _Tiler(vg.device)
-        actions_1hot = t.add(cols["actions"].reshape(-1).to(torch.int32).contiguous(), B * N, int(l_action), torch.int64, _lib.TILE_ONEHOT_I64)
-        t.run()
-    else:
-        actions_1hot = process_actions(cols["actions"], l_action)[0]
+    actions_1hot, = _onehot_rows((cols["actions"],), l_action, device, keep)
 
     # ---- argmax actions of the target agents, one-hot (:349-356) ----
     feed = {"obs_others": obs_others_next, "v_obs": v_local_next, "v_goal": goals_self}
@@ -993,4 +1019,4 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     call(["mixer_op"], {"v_state": state, "v_goal_all": goals_all, "actions_1hot": actions_1hot, "obs_others": obs_others,
                         "v_obs": v_local, "v_goal": goals_self, "td_target": target})
     call(["list_update_target_ops"], {})
-    return calls
+    return call.calls

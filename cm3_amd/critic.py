@@ -20,7 +20,8 @@ decodes them from the row number.  The network is float32 throughout, every cont
 Weights stay float32 [in][out] as TensorFlow shapes them, in ``self.w`` under short names (NAMES below), so a session that trains
 the main critics can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors,
 capturable) then makes the next launch follow them.  Scope prefixes "Q_global_main/", "Q_global_target/", "Q_credit_main/",
-"Q_credit_target/" and a ":0" suffix of the keys are ignored.
+"Q_credit_target/" and a ":0" suffix of the keys are ignored.  Loading and ``soft_update_from(main, tau)`` -- the critic's part of
+list_update_target_ops (alg_credit.py:186-194), for a critic holding target weights -- are cm3_amd._net._DeviceNet's.
 
 CheckersCritic (below) is the Checkers twin: networks.Q_global_checkers / Q_credit_checkers at the widths of
 config_checkers_stage{1,2}.json, one launch of cm3_critic_checkers_rows_f32 per method on the base columns grid, vec, goals, actions,
@@ -28,12 +29,11 @@ obs_self_t, obs_self_v.
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import Cm3Error
-from .actor import _keep
+from ._net import _DeviceNet, _keep, canon, stage_td_cols, td_given, td_outputs
 
 H1_1, H1_2, H2, N_ACTIONS = 64, 128, 64, 5
 KINDS = {"global": _lib.CRITIC_GLOBAL, "credit": _lib.CRITIC_CREDIT}
@@ -44,11 +44,7 @@ _PREFIXES = ("Q_global_main/", "Q_global_target/", "Q_credit_main/", "Q_credit_t
 
 
 def _canon(name):
-    name = name.split(":")[0]
-    for prefix in _PREFIXES:
-        if name.startswith(prefix):
-            name = name[len(prefix):]
-    return name
+    return canon(name, _PREFIXES)
 
 
 def weight_shapes(n_agents, kind, stage):
@@ -60,7 +56,10 @@ def weight_shapes(n_agents, kind, stage):
     return shapes
 
 
-class ParticleCritic(object):
+class ParticleCritic(_DeviceNet):
+    _match = ("n", "kind", "stage")
+    _refusal = "the main critic must be a %(kind)s ParticleCritic for %(n)d agents at stage %(stage)d"
+
     def __init__(self, weights, n_agents, kind="global", stage=2, device="cuda:0"):
         """kind "global": networks.Q_global_1output -- stage 1 with one agent, stage 2 with more; kind "credit": networks.Q_credit,
         stage 2 with more than one agent.  float32 only."""
@@ -75,24 +74,8 @@ class ParticleCritic(object):
         if self.stage not in (1, 2) or (self.stage == 1) != (self.n == 1):
             raise Cm3Error("Q_global_1output runs at stage 1 with one agent and at stage 2 with more (n_agents %d, stage %d)"
                            % (self.n, self.stage))
-        src = {_canon(k): v for k, v in weights.items()}
-        self.w = {}
-        for short, shape in weight_shapes(self.n, kind, self.stage).items():
-            name = NAMES[short]
-            if name not in src:
-                raise Cm3Error("missing critic weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise Cm3Error("critic weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            self.w[short] = t.to(self.device)
-        self._wt = _lib.CriticParticleWeights()
-        for short in NAMES:
-            setattr(self._wt, short, _lib.ptr(self.w.get(short)))
-        self._lib = _lib.lib()
-        nbytes = self._lib.cm3_critic_particle_packed_bytes(self.n, KINDS[kind])
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self._wt.packed = self._packed.data_ptr()
-        self.repack()
+        self._load(weights, _PREFIXES, NAMES, weight_shapes(self.n, kind, self.stage), "critic",
+                   lambda lib: lib.cm3_critic_particle_packed_bytes(self.n, KINDS[kind]), _lib.CriticParticleWeights())
 
     def _desc(self):
         d = _lib.CriticParticleDesc()
@@ -104,19 +87,7 @@ class ParticleCritic(object):
         """Re-arrange the (possibly updated in place) TF-shaped weights into the rows kernel's layout: one launch."""
         d = self._desc()
         _lib.check(self._lib.cm3_critic_particle_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
-                                                      _lib.current_stream_handle(self.device)))
-
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the critic's part of
-        list_update_target_ops (alg_credit.py:186-194), for a critic holding target weights."""
-        if not isinstance(main, ParticleCritic) or (main.n, main.kind, main.stage) != (self.n, self.kind, self.stage):
-            raise Cm3Error("soft_update_from: the main critic must be a %s ParticleCritic for %d agents at stage %d"
-                           % (self.kind, self.n, self.stage))
-        tau = float(tau)
-        for name in self.w:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
-        self.repack()
+                                                      self._stream(None)))
 
     # ---- launches -------------------------------------------------------------------------------------------------------------------
     def enqueue(self, form, n_steps, state, goals, actions=None, reward=None, done=None, gamma=0.0, q=None, q64=None, td=None,
@@ -131,7 +102,7 @@ class ParticleCritic(object):
         r.gamma = float(gamma)
         r.q, r.q64, r.td = _lib.ptr(q), _lib.ptr(q64), _lib.ptr(td)
         d = self._desc()
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(self._lib.cm3_critic_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
 
     def _stage_cols(self, what, state, goals, actions=None, reward=None, done=None):
@@ -147,33 +118,15 @@ class ParticleCritic(object):
             raise Cm3Error("%s needs at least one time step" % what)
         f32 = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
         state, goals = f32(state).reshape(B, N, 4), f32(goals).reshape(B, N, 2)
-        if actions is not None:
-            if actions.numel() != B * N:
-                raise Cm3Error("%s takes actions [B, %d] for %d time steps, got %s" % (what, N, B, tuple(actions.shape)))
-            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        if reward is not None:
-            if reward.numel() != B * N:
-                raise Cm3Error("%s takes reward [B, %d] for %d time steps, got %s" % (what, N, B, tuple(reward.shape)))
-            reward = reward.to(device=self.device, dtype=reward.dtype if reward.dtype == torch.float32 else torch.float64).contiguous()
-        if done is not None:
-            if done.numel() != B:
-                raise Cm3Error("%s takes done [B] for %d time steps, got %s" % (what, B, tuple(done.shape)))
-            done = done.reshape(-1).to(self.device)
-            done = (done.contiguous().view(torch.uint8) if done.dtype == torch.bool else (done != 0).view(torch.uint8))
+        actions, reward, done = stage_td_cols(what, self.device, B, N, actions, reward, done)
         return B, state, goals, actions, reward, done
 
     def _q(self, what, form, per_step, state, goals, actions, reward, done, gamma, keep):
-        given = [x is not None for x in (reward, done, gamma)]
-        if any(given) and not all(given):
-            raise Cm3Error("%s: reward, done and gamma come together (the TD target) or not at all" % what)
+        td = td_given(what, "reward", reward, done, gamma)
         if actions is None:
             raise Cm3Error("%s needs actions" % what)
         B, st, go, ac, rw, dn = self._stage_cols(what, state, goals, actions, reward, done)
-        R = B * per_step
-        out = {"q": torch.empty(R, 1, dtype=torch.float32, device=self.device),
-               "q64": torch.empty(R, 1, dtype=torch.float64, device=self.device)}
-        if all(given):
-            out["td"] = torch.empty(R, dtype=torch.float64, device=self.device)
+        out = td_outputs(self.device, B * per_step, "q", td)
         _keep(keep, st, go, ac, rw, dn, *out.values())
         self.enqueue(form, B, st, go, ac, rw, dn, 0.0 if gamma is None else gamma, **out)
         return out
@@ -231,7 +184,7 @@ def checkers_weight_shapes(n_agents, kind, stage):
     return shapes
 
 
-class CheckersCritic(object):
+class CheckersCritic(_DeviceNet):
     """The reference's Checkers critics on the device over the rows of a sampled batch, the twin of ParticleCritic.
 
         reference                                                        here
@@ -249,6 +202,8 @@ class CheckersCritic(object):
     they are; everything else is staged to float64 / int64 as cm3_amd.actor.stage_checkers_rows does, and rounded to float32 in the
     kernel as the reference's tf.float32 placeholders do.  In the pair forms the window and obs_self_v of a row are agent M's (the
     reference repeats them "indexed by m").  Weights: ``self.w`` under the short names of CK_NAMES, see ParticleCritic."""
+    _match = ("n", "kind", "stage")
+    _refusal = "the main critic must be a %(kind)s CheckersCritic for %(n)d agents at stage %(stage)d"
 
     def __init__(self, weights, n_agents, kind="global", stage=2, device="cuda:0"):
         self.device = _lib.require_gpu(device)
@@ -263,24 +218,8 @@ class CheckersCritic(object):
         if self.stage not in (1, 2) or (self.stage == 1) != (self.n == 1):
             raise Cm3Error("Q_global_checkers runs at stage 1 with one agent and at stage 2 with more (n_agents %d, stage %d)"
                            % (self.n, self.stage))
-        src = {_canon(k): v for k, v in weights.items()}
-        self.w = {}
-        for short, shape in checkers_weight_shapes(self.n, kind, self.stage).items():
-            name = CK_NAMES[short]
-            if name not in src:
-                raise Cm3Error("missing critic weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise Cm3Error("critic weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            self.w[short] = t.to(self.device)
-        self._wt = _lib.CriticCheckersWeights()
-        for short in CK_NAMES:
-            setattr(self._wt, short, _lib.ptr(self.w.get(short)))
-        self._lib = _lib.lib()
-        nbytes = self._lib.cm3_critic_checkers_packed_bytes(self.n, KINDS[kind])
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self._wt.packed = self._packed.data_ptr()
-        self.repack()
+        self._load(weights, _PREFIXES, CK_NAMES, checkers_weight_shapes(self.n, kind, self.stage), "critic",
+                   lambda lib: lib.cm3_critic_checkers_packed_bytes(self.n, KINDS[kind]), _lib.CriticCheckersWeights())
 
     def _desc(self):
         d = _lib.CriticCheckersDesc()
@@ -294,19 +233,7 @@ class CheckersCritic(object):
         Toeplitz matrices: one launch."""
         d = self._desc()
         _lib.check(self._lib.cm3_critic_checkers_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
-                                                      _lib.current_stream_handle(self.device)))
-
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the TF-shaped float32 tensors in place, then repack(): the critic's part of
-        list_update_target_ops, for a critic holding target weights."""
-        if not isinstance(main, CheckersCritic) or (main.n, main.kind, main.stage) != (self.n, self.kind, self.stage):
-            raise Cm3Error("soft_update_from: the main critic must be a %s CheckersCritic for %d agents at stage %d"
-                           % (self.kind, self.n, self.stage))
-        tau = float(tau)
-        for name in self.w:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
-        self.repack()
+                                                      self._stream(None)))
 
     # ---- launches -------------------------------------------------------------------------------------------------------------------
     def enqueue(self, form, n_steps, grid, vec, goals, windows, obs_self_v, actions=None, reward=None, done=None, gamma=0.0, q=None,
@@ -326,7 +253,7 @@ class CheckersCritic(object):
         r.gamma = float(gamma)
         r.q, r.q64, r.td = _lib.ptr(q), _lib.ptr(q64), _lib.ptr(td)
         d = self._desc()
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(self._lib.cm3_critic_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
 
     def _stage_cols(self, what, grid, vec, goals, obs_self_t, obs_self_v, actions=None, reward=None, done=None):
@@ -349,33 +276,15 @@ class CheckersCritic(object):
                   else torch.nn.functional.one_hot(goals.to(self.device).long(), 2).contiguous())
         else:
             go = stage(goals, torch.int64)
-        if actions is not None:
-            if actions.numel() != B * N:
-                raise Cm3Error("%s takes actions [B, %d] for %d time steps, got %s" % (what, N, B, tuple(actions.shape)))
-            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        if reward is not None:
-            if reward.numel() != B * N:
-                raise Cm3Error("%s takes reward [B, %d] for %d time steps, got %s" % (what, N, B, tuple(reward.shape)))
-            reward = reward.to(device=self.device, dtype=reward.dtype if reward.dtype == torch.float32 else torch.float64).contiguous()
-        if done is not None:
-            if done.numel() != B:
-                raise Cm3Error("%s takes done [B] for %d time steps, got %s" % (what, B, tuple(done.shape)))
-            done = done.reshape(-1).to(self.device)
-            done = (done.contiguous().view(torch.uint8) if done.dtype == torch.bool else (done != 0).view(torch.uint8))
+        actions, reward, done = stage_td_cols(what, self.device, B, N, actions, reward, done)
         return B, narrow(grid), stage(vec, torch.float64), go, narrow(obs_self_t), stage(obs_self_v, torch.float64), actions, reward, done
 
     def _q(self, what, form, per_step, grid, vec, goals, actions, obs_self_t, obs_self_v, reward, done, gamma, keep):
-        given = [x is not None for x in (reward, done, gamma)]
-        if any(given) and not all(given):
-            raise Cm3Error("%s: reward, done and gamma come together (the TD target) or not at all" % what)
+        td = td_given(what, "reward", reward, done, gamma)
         if actions is None:
             raise Cm3Error("%s needs actions" % what)
         B, gr, ve, go, wi, ov, ac, rw, dn = self._stage_cols(what, grid, vec, goals, obs_self_t, obs_self_v, actions, reward, done)
-        R = B * per_step
-        out = {"q": torch.empty(R, 1, dtype=torch.float32, device=self.device),
-               "q64": torch.empty(R, 1, dtype=torch.float64, device=self.device)}
-        if all(given):
-            out["td"] = torch.empty(R, dtype=torch.float64, device=self.device)
+        out = td_outputs(self.device, B * per_step, "q", td)
         _keep(keep, gr, ve, go, wi, ov, ac, rw, dn, *out.values())
         self.enqueue(form, B, gr, ve, go, wi, ov, ac, rw, dn, 0.0 if gamma is None else gamma, **out)
         return out

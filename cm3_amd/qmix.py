@@ -18,31 +18,32 @@ ignored, so ``{v.name: sess.run(v)}`` of either scope loads unchanged.  The netw
 Exploration draws come from the build's own Philox stream (csrc/actor.hip, kPurposeExplore): the same law as the reference's
 np.random calls, not the same numbers.  The learner stays on the reference's side; both agents serve a
 learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from, and ParticleQmixMixer
-(below) evaluates the particle target mixer -- mixer_target and the TD target -- on the same rows.
+(below) evaluates the particle target mixer -- mixer_target and the TD target -- on the same rows.  soft_update_from and the
+weight loading are cm3_amd._net._DeviceNet's (the agent and mixer halves of list_update_target_ops, alg_qmix.py:135-156,
+alg_qmix_checkers.py:128-130); CheckersQmixAgent shares descriptor and launch bodies with CheckersActor (actor._CheckersPolicyNet).
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib
 from ._lib import Cm3Error
-from .actor import _epsilon_args, _keep, stage_checkers_rows
+from ._net import _DeviceNet, _keep, canon, greedy_outputs, stage_particle_rows, stage_td_cols, td_given, td_outputs
+from .actor import _CheckersPolicyNet, _epsilon_args, checkers_policy_shapes, stage_checkers_rows
 
 H, N_ACTIONS = 64, 5
 # the six tensors of cm3_qmix_particle_pack, in its order
 NAMES = ("h/kernel", "h/bias", "h2/kernel", "h2/bias", "out/kernel", "out/bias")
 
 
+_PREFIXES = ("Agent_main/", "Agent_target/")
+
+
 def _canon(name):
-    name = name.split(":")[0]
-    for prefix in ("Agent_main/", "Agent_target/"):
-        if name.startswith(prefix):
-            name = name[len(prefix):]
-    return name
+    return canon(name, _PREFIXES)
 
 
-class ParticleQmixAgent(object):
+class ParticleQmixAgent(_DeviceNet):
     """episode_kernel=True opts this agent in to the one-launch rollout (cm3_policy_rollout_qmix_f32: the network, the epsilon-greedy
     choice and the env step of every tick in ONE launch, the same bits as the launch pairs): ParticleRollout then runs it under
     policy_mode "episode" and, where it is eligible and measured faster, "auto" (episode_ok / episode_refusal / enqueue_episode
@@ -51,6 +52,7 @@ class ParticleQmixAgent(object):
     # agent was built with episode_kernel=True
     fused_kernels = False
     EPISODE_AGENTS = (1, 2, 4, 8)        # whole envs per 16-row wave tile
+    _refusal = "the main agent must be a ParticleQmixAgent for %(n)d agents"
 
     def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0, episode_kernel=False):
         self.episode_kernel = bool(episode_kernel)
@@ -61,28 +63,16 @@ class ParticleQmixAgent(object):
         self.L = 4 * max(self.n - 1, 1)
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
-        src = {_canon(k): v for k, v in weights.items()}
         shapes = {"h/kernel": (self.L + 6, H), "h/bias": (H,), "h2/kernel": (H, H), "h2/bias": (H,),
                   "out/kernel": (H, N_ACTIONS), "out/bias": (N_ACTIONS,)}
-        self.w = {}
-        for name in NAMES:
-            if name not in src:
-                raise Cm3Error("missing QMIX weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shapes[name]:
-                raise Cm3Error("QMIX weight %r has shape %s, expected %s" % (name, tuple(t.shape), shapes[name]))
-            self.w[name] = t.to(self.device)
-        self._lib = _lib.lib()
-        self._tensors = (ctypes.c_void_p * 6)(*[self.w[k].data_ptr() for k in NAMES])
-        nbytes = self._lib.cm3_qmix_particle_packed_bytes(self.n)
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self.repack()
+        # (no weights struct: cm3_qmix_particle_pack takes the six pointers in the order of NAMES, the launches the packed pointer)
+        self._load(weights, _PREFIXES, {k: k for k in NAMES}, shapes, "QMIX", lambda lib: lib.cm3_qmix_particle_packed_bytes(self.n))
 
     def repack(self):
         """Re-arrange the (possibly updated in place) TF-shaped weights into the forward kernel's layout: after every update."""
         d = self._desc(1, 0.0, 0)
         _lib.check(self._lib.cm3_qmix_particle_pack(ctypes.byref(d), self._tensors, self._packed.data_ptr(),
-                                                    _lib.current_stream_handle(self.device)))
+                                                    self._stream(None)))
 
     def _desc(self, n_envs, epsilon, env_id_base):
         d = _lib.ActorParticleDesc()
@@ -109,7 +99,7 @@ class ParticleQmixAgent(object):
         b.meta, b.episode, b.actions, b.probs = _lib.ptr(meta), _lib.ptr(episode), _lib.ptr(actions), _lib.ptr(probs)
         epsilon, b.epsilon_dev = _epsilon_args(epsilon)
         d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(fn(ctypes.byref(d), self._packed.data_ptr(), ctypes.byref(b), s))
 
     def act(self, env, epsilon, return_q=False):
@@ -151,7 +141,7 @@ class ParticleQmixAgent(object):
         float32 device tensor of one element that the launch reads itself."""
         epsilon, eps_dev = _epsilon_args(epsilon)
         d = self._desc(n_envs, epsilon, env_desc.env_id_base)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(self._lib.cm3_policy_rollout_qmix_f32(
             ctypes.byref(env_desc), ctypes.byref(traj), ctypes.byref(d), self._packed.data_ptr(), _lib.ptr(q_values),
             0 if q_values is None else q_values[0].numel() * q_values.element_size(), eps_dev, int(n_ticks), s))
@@ -164,23 +154,8 @@ class ParticleQmixAgent(object):
         the R = prod(leading shape) rows: "argmax" int32 [R] always; "q" float32 [R, 5], "onehot" int64 [R, 5] (the reference's
         actions_target_1hot), "q_max" float32 [R] when asked for.  A row's Q values are the bits act() computes for the same
         inputs."""
-        lead = tuple(v_obs.shape[:-1])
-        if (tuple(obs_others.shape) != lead + (self.L,) or tuple(v_obs.shape) != lead + (4,)
-                or tuple(goals.shape) != lead + (2,)):
-            raise Cm3Error("greedy_rows takes [..., %d], [..., 4] and [..., 2] with equal leading shape, got %s, %s, %s"
-                           % (self.L, tuple(obs_others.shape), tuple(v_obs.shape), tuple(goals.shape)))
-        rows = int(np.prod(lead, dtype=np.int64))
-        if rows <= 0:
-            raise Cm3Error("greedy_rows needs at least one row")
-        stage = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
-        oo, vo, vg = stage(obs_others), stage(v_obs), stage(goals)
-        out = {"argmax": torch.empty(rows, dtype=torch.int32, device=self.device)}
-        if q:
-            out["q"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
-        if onehot:
-            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
-        if q_max:
-            out["q_max"] = torch.empty(rows, dtype=torch.float32, device=self.device)
+        rows, oo, vo, vg = stage_particle_rows("greedy_rows", self.device, self.L, obs_others, v_obs, goals)
+        out = greedy_outputs(self.device, rows, q, onehot, q_max)
         self.enqueue_rows(rows, oo, vo, vg, **out)
         return out
 
@@ -191,19 +166,8 @@ class ParticleQmixAgent(object):
         r.q, r.argmax, r.onehot, r.q_max = _lib.ptr(q), _lib.ptr(argmax), _lib.ptr(onehot), _lib.ptr(q_max)
         r.n_rows = int(n_rows)
         d = self._desc(1, 0.0, 0)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(self._lib.cm3_qmix_particle_rows_f32(ctypes.byref(d), self._packed.data_ptr(), ctypes.byref(r), s))
-
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the six TF-shaped float32 tensors in place, then repack(): the agent half of
-        list_update_target_ops (alg_qmix.py:135-137), for an agent holding the Agent_target weights."""
-        if not isinstance(main, ParticleQmixAgent) or main.n != self.n:
-            raise Cm3Error("soft_update_from: the main agent must be a ParticleQmixAgent for %d agents" % self.n)
-        tau = float(tau)
-        for name in NAMES:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
-        self.repack()
 
 
 # ---- Checkers -------------------------------------------------------------------------------------------------------------------
@@ -216,7 +180,7 @@ CK_NAMES = {
 CK_PRECISIONS = {"f32": 0, "f16x3": 2}       # cm3_actor_checkers_desc.precision (bf16 is refused: argmax would flip)
 
 
-class CheckersQmixAgent(object):
+class CheckersQmixAgent(_CheckersPolicyNet):
     """The QMIX baseline's Checkers agent network and its epsilon-greedy choice, evaluated on the device.
 
         reference                                                        here
@@ -246,9 +210,10 @@ class CheckersQmixAgent(object):
     one launch, no draws), soft_update_from moves an Agent_target copy towards the main agent; cm3_amd.batch.qmix_train_step_feeds(
     env="checkers", target_agent=...) builds every feed of train_step around them.  The mixer stays the caller's.
     """
+    _match = ("n", "precision")
+    _refusal = "the main agent must be a CheckersQmixAgent for %(n)d agents at precision %(precision)r"
 
     def __init__(self, weights, n_agents, device="cuda:0", seed=12341, env_id_base=0, precision="f32"):
-        from .actor import CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2
         if precision not in CK_PRECISIONS:
             raise Cm3Error("precision must be one of %s (bf16 is not a parity path: argmax would flip)" % sorted(CK_PRECISIONS))
         self.device = _lib.require_gpu(device)
@@ -259,74 +224,28 @@ class CheckersQmixAgent(object):
         self.Lo = 2 * max(self.n - 1, 1)
         self.seed = int(seed)
         self.env_id_base = int(env_id_base)
-        self._widths = (CK_CONV_F, CK_CONV_LIN, CK_H1, CK_H2)
-        src = {_canon(k): v for k, v in weights.items()}
-        shapes = {"conv_w": (3, 3, 3, CK_CONV_F), "conv_b": (CK_CONV_F,), "lin_w": (25 * CK_CONV_F, CK_CONV_LIN),
-                  "lin_b": (CK_CONV_LIN,), "self_w": (CK_CONV_LIN + 4 + N_ACTIONS + 2, CK_H1), "self_b": (CK_H1,),
-                  "w_self_h2": (CK_H1, CK_H2), "others_w": (self.Lo, CK_H1), "others_b": (CK_H1,),
-                  "w_others_h2": (CK_H1, CK_H2), "b_h2": (CK_H2,), "out_w": (CK_H2, N_ACTIONS), "out_b": (N_ACTIONS,)}
-        self.w = {}
-        for short, shape in shapes.items():
-            name = CK_NAMES[short]
-            if name not in src:
-                raise Cm3Error("missing QMIX weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise Cm3Error("QMIX weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            self.w[short] = t.to(self.device)
-        self._wt = _lib.ActorCheckersWeights()
-        for short in CK_NAMES:
-            setattr(self._wt, short, _lib.ptr(self.w[short]))
-        self._lib = _lib.lib()
-        nbytes = self._lib.cm3_actor_checkers_packed_bytes()
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self._wt.packed = self._packed.data_ptr()
-        self.repack()
-
-    def _desc(self, n_envs, epsilon, env_id_base, obst_stride):
-        conv_f, lin, h1, h2 = self._widths
-        d = _lib.ActorCheckersDesc()
-        d.n_envs, d.n_agents, d.stage, d.n_obs = int(n_envs), self.n, 2, 2
-        d.conv_f, d.n_conv_linear, d.n_h1, d.n_h2, d.n_actions = conv_f, lin, h1, h2, N_ACTIONS
-        d.epsilon = float(epsilon)
-        d.precision = CK_PRECISIONS[self.precision]
-        d.obs_self_t_stride = int(obst_stride)
-        d.env_id_base = int(env_id_base)
-        d.seed = self.seed & 0xFFFFFFFFFFFFFFFF
-        return d
+        self._load(weights, _PREFIXES, CK_NAMES, checkers_policy_shapes(self.Lo), "QMIX",
+                   lambda lib: lib.cm3_actor_checkers_packed_bytes(), _lib.ActorCheckersWeights())
 
     def repack(self):
         """Re-arrange the (possibly updated in place) TF-shaped weights into the forward kernel's layout: after every update."""
         d = self._desc(1, 0.0, 0, 75 * self.n)
         _lib.check(self._lib.cm3_qmix_checkers_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
-                                                    _lib.current_stream_handle(self.device)))
+                                                    self._stream(None)))
 
     def enqueue(self, n_envs, obs_self_t_raw, obst_stride, obs_self_v, obs_others, goals, actions_prev, steps, episode,
                 actions, epsilon, probs=None, stream=None, env_id_base=None, prev_done=None):
         """Raw launch on the env's device buffers, the signature of CheckersActor.enqueue.  probs (optional) receives the Q
         values float32 [E, N, 5]."""
-        b = _lib.ActorCheckersBufs()
-        b.obs_self_t, b.obs_self_v, b.obs_others = _lib.ptr(obs_self_t_raw), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
-        b.goals, b.actions_prev, b.steps, b.episode = (_lib.ptr(goals), _lib.ptr(actions_prev), _lib.ptr(steps),
-                                                       _lib.ptr(episode))
-        b.actions, b.probs = _lib.ptr(actions), _lib.ptr(probs)
-        b.prev_done = _lib.ptr(prev_done)
-        epsilon, b.epsilon_dev = _epsilon_args(epsilon)
-        d = self._desc(n_envs, epsilon, self.env_id_base if env_id_base is None else env_id_base, obst_stride)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_qmix_checkers_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(b), s))
+        self._enqueue_tick(self._lib.cm3_qmix_checkers_f32, n_envs, obs_self_t_raw, obst_stride, obs_self_v, obs_others, goals,
+                           actions_prev, steps, episode, actions, epsilon, probs, stream, env_id_base, prev_done)
 
     def enqueue_episode(self, env_desc, traj, n_envs, obst_stride, n_ticks, epsilon, prev0=None, probs=None, stream=None,
                         final_obs=None, prev0_next=None):
         """The whole agent-driven rollout in ONE launch (cm3_policy_rollout_checkers_qmix), the signature of
         CheckersActor.enqueue_rollout; probs: optional float32 [T, E, N, 5], receives the Q values."""
-        epsilon, eps_dev = _epsilon_args(epsilon)
-        d = self._desc(n_envs, epsilon, env_desc.env_id_base, obst_stride)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_policy_rollout_checkers_qmix(
-            ctypes.byref(env_desc), ctypes.byref(traj), ctypes.byref(d), ctypes.byref(self._wt), _lib.ptr(prev0), _lib.ptr(prev0_next),
-            _lib.ptr(probs), 0 if probs is None else probs[0].numel() * probs.element_size(), eps_dev,
-            None if final_obs is None else ctypes.byref(final_obs), int(n_ticks), s))
+        self._enqueue_whole(self._lib.cm3_policy_rollout_checkers_qmix, env_desc, traj, n_envs, obst_stride, n_ticks, epsilon, prev0,
+                            probs, stream, final_obs, prev0_next)
 
     def episode_ok(self, env):
         """cm3_policy_rollout_checkers_qmix applies: split float16, one or two agents (the env's count), the 3 x 8 band with
@@ -366,13 +285,7 @@ class CheckersQmixAgent(object):
         [R] when asked for.  A row's Q values are the bits act() computes for the same inputs at the same precision."""
         rows, ot, ov, oo, ap, vg = stage_checkers_rows("greedy_rows", self.device, self.Lo, obs_self_t, obs_self_v, obs_others,
                                                        actions_prev, goals)
-        out = {"argmax": torch.empty(rows, dtype=torch.int32, device=self.device)}
-        if q:
-            out["q"] = torch.empty(rows, N_ACTIONS, dtype=torch.float32, device=self.device)
-        if onehot:
-            out["onehot"] = torch.empty(rows, N_ACTIONS, dtype=torch.int64, device=self.device)
-        if q_max:
-            out["q_max"] = torch.empty(rows, dtype=torch.float32, device=self.device)
+        out = greedy_outputs(self.device, rows, q, onehot, q_max)
         self.enqueue_rows(rows, ot, ov, oo, ap, vg, **out)
         return out
 
@@ -391,20 +304,8 @@ class CheckersQmixAgent(object):
         r.q, r.argmax, r.onehot, r.q_max = _lib.ptr(q), _lib.ptr(argmax), _lib.ptr(onehot), _lib.ptr(q_max)
         r.n_rows = int(n_rows)
         d = self._desc(1, 0.0, 0, 75 * self.n)
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(self._lib.cm3_qmix_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
-
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the thirteen TF-shaped float32 tensors in place, then repack(): the agent half of
-        list_update_target_ops (alg_qmix_checkers.py:128-130), for an agent holding the Agent_target weights."""
-        if not isinstance(main, CheckersQmixAgent) or main.n != self.n or main.precision != self.precision:
-            raise Cm3Error("soft_update_from: the main agent must be a CheckersQmixAgent for %d agents at precision %r"
-                           % (self.n, self.precision))
-        tau = float(tau)
-        for short in CK_NAMES:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[short].copy_(tau * main.w[short].to(self.device) + (1.0 - tau) * self.w[short])
-        self.repack()
 
 
 # ---- the particle mixer ---------------------------------------------------------------------------------------------------------------
@@ -414,14 +315,11 @@ MIXER_NAMES = {"w1": "hyper_w_1", "w_final": "hyper_w_final", "b1": "hyper_b_1",
                "b_final": "hyper_b_final/kernel"}
 _MIXER_FIELDS = {"w1": "hyper_w_1", "w_final": "hyper_w_final", "b1": "hyper_b_1", "b_final_l1": "hyper_b_final_l1",
                  "b_final": "hyper_b_final"}
+_MIXER_PREFIXES = ("Mixer_main/", "Mixer_target/")
 
 
 def _mixer_canon(name):
-    name = name.split(":")[0]
-    for prefix in ("Mixer_main/", "Mixer_target/"):
-        if name.startswith(prefix):
-            name = name[len(prefix):]
-    return name
+    return canon(name, _MIXER_PREFIXES)
 
 
 def mixer_weight_shapes(n_agents):
@@ -430,7 +328,7 @@ def mixer_weight_shapes(n_agents):
     return {"w1": (k, EMBED * n_agents), "w_final": (k, EMBED), "b1": (k, EMBED), "b_final_l1": (k, EMBED), "b_final": (EMBED, 1)}
 
 
-class ParticleQmixMixer(object):
+class ParticleQmixMixer(_DeviceNet):
     """The reference's particle QMIX mixer evaluated on the device over the transitions of a sampled batch.
 
         reference                                                    here
@@ -445,30 +343,15 @@ class ParticleQmixMixer(object):
     float32 [in][out] as TensorFlow shapes them, in ``self.w`` under the short names of MIXER_NAMES, so a session that trains the
     main mixer can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors, capturable)
     then makes the next launch follow them.  The prefixes "Mixer_main/", "Mixer_target/" and a ":0" suffix of the keys are ignored."""
+    _refusal = "the main mixer must be a ParticleQmixMixer for %(n)d agents"
 
     def __init__(self, weights, n_agents, device="cuda:0"):
         self.device = _lib.require_gpu(device)
         self.n = int(n_agents)
         if not 1 <= self.n <= _lib.MAX_AGENTS:
             raise Cm3Error("n_agents must be in 1..%d" % _lib.MAX_AGENTS)
-        src = {_mixer_canon(k): v for k, v in weights.items()}
-        self.w = {}
-        for short, shape in mixer_weight_shapes(self.n).items():
-            name = MIXER_NAMES[short]
-            if name not in src:
-                raise Cm3Error("missing mixer weight %r" % name)
-            t = torch.as_tensor(np.asarray(src[name]), dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise Cm3Error("mixer weight %r has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            self.w[short] = t.to(self.device)
-        self._wt = _lib.QmixMixerParticleWeights()
-        for short, field in _MIXER_FIELDS.items():
-            setattr(self._wt, field, _lib.ptr(self.w[short]))
-        self._lib = _lib.lib()
-        nbytes = self._lib.cm3_qmix_mixer_particle_packed_bytes(self.n)
-        self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=self.device)
-        self._wt.packed = self._packed.data_ptr()
-        self.repack()
+        self._load(weights, _MIXER_PREFIXES, MIXER_NAMES, mixer_weight_shapes(self.n), "mixer",
+                   lambda lib: lib.cm3_qmix_mixer_particle_packed_bytes(self.n), _lib.QmixMixerParticleWeights(), _MIXER_FIELDS)
 
     def _desc(self):
         d = _lib.QmixMixerParticleDesc()
@@ -479,18 +362,7 @@ class ParticleQmixMixer(object):
         """Re-arrange the (possibly updated in place) TF-shaped weights into the rows kernel's layout: one launch."""
         d = self._desc()
         _lib.check(self._lib.cm3_qmix_mixer_particle_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
-                                                          _lib.current_stream_handle(self.device)))
-
-    def soft_update_from(self, main, tau):
-        """w <- tau * main.w + (1 - tau) * w on the five TF-shaped float32 tensors in place, then repack(): the mixer half of
-        list_update_target_ops (alg_qmix.py:139-156), for a mixer holding the Mixer_target weights."""
-        if not isinstance(main, ParticleQmixMixer) or main.n != self.n:
-            raise Cm3Error("soft_update_from: the main mixer must be a ParticleQmixMixer for %d agents" % self.n)
-        tau = float(tau)
-        for name in self.w:
-            # float32 throughout, as TF evaluates tau * var + (1 - tau) * target with float32 constants
-            self.w[name].copy_(tau * main.w[name].to(self.device) + (1.0 - tau) * self.w[name])
-        self.repack()
+                                                          self._stream(None)))
 
     # ---- launches -------------------------------------------------------------------------------------------------------------------
     def enqueue(self, n_steps, state, goals, agent_qs, reward=None, done=None, gamma=0.0, q_tot=None, q_tot64=None, td=None,
@@ -505,7 +377,7 @@ class ParticleQmixMixer(object):
         r.gamma = float(gamma)
         r.q_tot, r.q_tot64, r.td = _lib.ptr(q_tot), _lib.ptr(q_tot64), _lib.ptr(td)
         d = self._desc()
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        s = self._stream(stream)
         _lib.check(self._lib.cm3_qmix_mixer_particle_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
 
     def _stage_cols(self, what, state, goals, agent_qs, reward=None, done=None):
@@ -523,15 +395,7 @@ class ParticleQmixMixer(object):
         if agent_qs.numel() != B * N:
             raise Cm3Error("%s takes agent_qs [B, %d] for %d time steps, got %s" % (what, N, B, tuple(agent_qs.shape)))
         agent_qs = f32(agent_qs).reshape(B, N)
-        if reward is not None:
-            if reward.numel() != B * N:
-                raise Cm3Error("%s takes reward_local [B, %d] for %d time steps, got %s" % (what, N, B, tuple(reward.shape)))
-            reward = reward.to(device=self.device, dtype=reward.dtype if reward.dtype == torch.float32 else torch.float64).contiguous()
-        if done is not None:
-            if done.numel() != B:
-                raise Cm3Error("%s takes done [B] for %d time steps, got %s" % (what, B, tuple(done.shape)))
-            done = done.reshape(-1).to(self.device)
-            done = (done.contiguous().view(torch.uint8) if done.dtype == torch.bool else (done != 0).view(torch.uint8))
+        _, reward, done = stage_td_cols(what, self.device, B, N, None, reward, done, reward_name="reward_local")
         return B, state, goals, agent_qs, reward, done
 
     def q_tot(self, state, goals, agent_qs, reward_local=None, done=None, gamma=None, keep=None):
@@ -542,14 +406,9 @@ class ParticleQmixMixer(object):
         "td" float64 [B] = sum(reward_local[b]) + gamma * q_tot * (1 - done), the bits of batch.qmix_td_target on "q_tot".  The three
         come together or not at all.  keep: an optional list that receives every tensor the launch touches (the staged inputs, the
         outputs), for whoever captures the launch."""
-        given = [x is not None for x in (reward_local, done, gamma)]
-        if any(given) and not all(given):
-            raise Cm3Error("q_tot: reward_local, done and gamma come together (the TD target) or not at all")
+        td = td_given("q_tot", "reward_local", reward_local, done, gamma)
         B, st, go, aq, rw, dn = self._stage_cols("q_tot", state, goals, agent_qs, reward_local, done)
-        out = {"q_tot": torch.empty(B, 1, dtype=torch.float32, device=self.device),
-               "q_tot64": torch.empty(B, 1, dtype=torch.float64, device=self.device)}
-        if all(given):
-            out["td"] = torch.empty(B, dtype=torch.float64, device=self.device)
+        out = td_outputs(self.device, B, "q_tot", td)
         _keep(keep, st, go, aq, rw, dn, *out.values())
         self.enqueue(B, st, go, aq, rw, dn, 0.0 if gamma is None else gamma, **out)
         return out

@@ -89,7 +89,7 @@ def _static_composition(cols, l_action=5):
     goals_self, _ = BR.process_goals(goals)
     one, others, _ = BR.process_global_state(vec)
     one_next, others_next, _ = BR.process_global_state(vec_next)
-    rep_m, rep_n, rep_a = (lambda x: BR.rep_rows(x, N)), (lambda x: BR._rep_n(x, N)), (lambda x: BR.rep_rows(x, l_action))
+    rep_m, rep_n, rep_a = (lambda x: BR.rep_rows(x, N)), (lambda x: BR.repeat_indexed_by_n(x, N)), (lambda x: BR.rep_rows(x, l_action))
     S = dict(state_env=state_env, state_env_next=state_env_next, a1=a1, ao=ao, prev1=prev1, done_rep=done,
              not_done=-(done.to(torch.int64) - 1), others=others, others_next=others_next, goals_self_rep=rep_n(goals_self),
              one_next_rep_n=rep_n(one_next), one_next_rep_m=rep_m(one_next), others_next_rep_n=rep_n(others_next),
