@@ -100,6 +100,16 @@ def _canon(name):
     return canon(name, _PREFIXES)
 
 
+def rows_id_base_i64(row_id_base):
+    """row_id_base as cm3_actor_rows holds it: an int64_t (include/cm3_amd.h).  A value outside the field is refused -- a ctypes
+    field would keep its low 64 bits without a word, and ids from 2^63 on would come back negative.  (cm3_actor_checkers_rows
+    declares its base uint64_t and takes every 64-bit value.)"""
+    base = int(row_id_base)
+    if not -(1 << 63) <= base < (1 << 63):
+        raise Cm3Error("row_id_base %d does not fit cm3_actor_rows.row_id_base (int64_t): -2^63 <= row_id_base < 2^63" % base)
+    return base
+
+
 class ParticleActor(_DeviceNet):
     _match = ("n", "stage")
     _refusal = "the main actor must be a ParticleActor for %(n)d agents at stage %(stage)d"
@@ -176,15 +186,15 @@ class ParticleActor(_DeviceNet):
                      stream=None):
         """Raw launch of cm3_actor_particle_rows_f32 on contiguous float32 device tensors; every output is optional, one is
         required.  epsilon: a float, or a one-element float32 device tensor the launch reads itself.  (seed, row_id_base + row,
-        draw) key the row's uniform; nothing is drawn when actions and onehot are both None.  draw: an integer, or a
-        RowsDrawCounter -- then the launch is cm3_actor_particle_rows_counted_f32, which reads the counter's device word and
-        advances it itself."""
+        draw) key the row's uniform; nothing is drawn when actions and onehot are both None.  row_id_base: an int64 (the ABI's
+        field; Cm3Error outside it).  draw: an integer, or a RowsDrawCounter -- then the launch is
+        cm3_actor_particle_rows_counted_f32, which reads the counter's device word and advances it itself."""
         r = _lib.ActorRows()
         r.obs_others, r.v_obs, r.goals = _lib.ptr(obs_others), _lib.ptr(v_obs), _lib.ptr(goals)
         r.probs, r.actions, r.onehot = _lib.ptr(probs), _lib.ptr(actions), _lib.ptr(onehot)
         epsilon, r.epsilon_dev = _epsilon_args(epsilon)
         counter = draw if isinstance(draw, RowsDrawCounter) else None
-        r.n_rows, r.row_id_base, r.draw = int(n_rows), int(row_id_base), 0 if counter is not None else int(draw) & 0xFFFFFFFF
+        r.n_rows, r.row_id_base, r.draw = int(n_rows), rows_id_base_i64(row_id_base), 0 if counter is not None else int(draw) & 0xFFFFFFFF
         d = self._desc(1, epsilon, 0)
         s = self._stream(stream)
         if counter is not None:

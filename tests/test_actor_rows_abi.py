@@ -202,3 +202,42 @@ def test_rows_draw_is_not_the_policy_stream(N):
     for call in range((N + 3) // 4):
         for word in philox.action_block(seed, np.arange(E), call):
             assert (word == blocks).mean() < 0.01
+
+
+def test_row_id_base_field_widths_are_the_headers():
+    """cm3_actor_rows.row_id_base is int64_t, cm3_actor_checkers_rows.row_id_base uint64_t: the ctypes mirrors hold the same types,
+    draw is 32 bits in both, and a 64-bit seed fits every descriptor that carries one."""
+    from cm3_amd import _lib
+    text = open(os.path.join(ROOT, "include", "cm3_amd.h")).read()
+    for struct, ctype, cls in (("cm3_actor_rows", "int64_t", _lib.ActorRows), ("cm3_actor_checkers_rows", "uint64_t", _lib.ActorCheckersRows)):
+        body = re.search(r"typedef struct \{([^}]*)\}\s*%s;" % struct, text).group(1)
+        assert re.search(r"\b%s\s+row_id_base;" % ctype, body), struct
+        assert re.search(r"\buint32_t\s+draw;", body), struct
+        fields = dict(cls._fields_)
+        assert fields["row_id_base"] is (ctypes.c_int64 if ctype == "int64_t" else ctypes.c_uint64), struct
+        assert fields["draw"] is ctypes.c_uint32 and fields["n_rows"] is ctypes.c_int64, struct
+    for cls in (_lib.ParticleDesc, _lib.CheckersDesc, _lib.ActorParticleDesc, _lib.ActorCheckersDesc):
+        fields = dict(cls._fields_)
+        assert fields["seed"] is ctypes.c_uint64 and fields["env_id_base"] is ctypes.c_int64, cls.__name__
+        d = cls()
+        d.seed, d.env_id_base = 0x9E3779B97F4A7C15, (5 << 32) - 19
+        assert (d.seed, d.env_id_base) == (0x9E3779B97F4A7C15, (5 << 32) - 19), cls.__name__
+
+
+def test_particle_rows_wrapper_refuses_a_base_outside_int64():
+    """The wrapper hands row_id_base to an int64_t field: every value of that type passes unchanged (the kernel reads it as the
+    64-bit pattern, as tests/actor_rows_ref.py does), a value from 2^63 on is refused instead of being wrapped without a word."""
+    from cm3_amd import Cm3Error
+    from cm3_amd import _lib
+    from cm3_amd.actor import rows_id_base_i64
+    for ok in (0, 5, (5 << 32) - 19, (1 << 63) - 1, -1, -(1 << 63)):
+        r = _lib.ActorRows()
+        r.row_id_base = rows_id_base_i64(ok)
+        assert r.row_id_base == ok
+        assert np.array_equal(RR.rows_uniforms(7, 3, 0, row_id_base=ok), RR.rows_uniforms(7, 3, 0, row_id_base=ok & ((1 << 64) - 1)))
+    for bad in (1 << 63, (1 << 63) + 11, (1 << 64) - 1, -(1 << 63) - 1):
+        with pytest.raises(Cm3Error, match="row_id_base"):
+            rows_id_base_i64(bad)
+    c = _lib.ActorCheckersRows()
+    c.row_id_base = (1 << 63) + 11                                           # the Checkers twin is unsigned: nothing to refuse
+    assert c.row_id_base == (1 << 63) + 11
