@@ -39,25 +39,11 @@ done
 # keeps the accumulators in architectural VGPRs -- k_ck_actor_x3 236 registers, k_policy_rollout<8, ., 4> <= 256; round 4's
 # experimental -amdgpu-mfma-vgpr-form=1 is gone: the accumulators' form is the compiler's default selection, no flag)
 MFMA_FORM=""
-for f in actor actor_checkers policy policy_checkers; do
+for f in actor actor_checkers policy policy_checkers critic critic_checkers mixer; do
   "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/${f}.hip" -o "${OBJ}/${f}.o" 2> "${OBJ}/${f}.resource_usage.txt" \
     || { grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" >&2; exit 1; } &
   pids+=($!)
 done
-# the CM3 particle critics over transition rows (critic.hip): a matrix unit like the four above -- the same flags, CM3_MATRIX_KERNEL, no
-# inline assembly -- on a line of its own (tests/test_abi.py pins the loop's list to the units whose sources it scans)
-"${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/critic.hip" -o "${OBJ}/critic.o" 2> "${OBJ}/critic.resource_usage.txt" \
-  || { grep -v "remark:" "${OBJ}/critic.resource_usage.txt" >&2; exit 1; } &
-pids+=($!)
-# ... and their Checkers twins (critic_checkers.hip, on the Checkers actor's tile loop): the same flags, a line of its own likewise
-"${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/critic_checkers.hip" -o "${OBJ}/critic_checkers.o" 2> "${OBJ}/critic_checkers.resource_usage.txt" \
-  || { grep -v "remark:" "${OBJ}/critic_checkers.resource_usage.txt" >&2; exit 1; } &
-pids+=($!)
-# the particle QMIX target mixer over transition rows (mixer.hip): a matrix unit as well -- the same flags, CM3_MATRIX_KERNEL, no inline
-# assembly -- on a line of its own likewise
-"${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/mixer.hip" -o "${OBJ}/mixer.o" 2> "${OBJ}/mixer.resource_usage.txt" \
-  || { grep -v "remark:" "${OBJ}/mixer.resource_usage.txt" >&2; exit 1; } &
-pids+=($!)
 # the one-launch policy episode once more for float64 envs (policy.hip: PolicyReal = double), with the same flags as the float32 build
 "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_PARTICLE_F64 -Rpass-analysis=kernel-resource-usage -c "${HERE}/policy.hip" -o "${OBJ}/policy_f64.o" 2> "${OBJ}/policy_f64.resource_usage.txt" \
   || { grep -v "remark:" "${OBJ}/policy_f64.resource_usage.txt" >&2; exit 1; } &

@@ -20,12 +20,12 @@
 //   h2 (192 -> 64, ONE chain over concat(branch1, branch2): 51 % .. 83 % of the FLOPs): wave w owns columns [16w, 16w+16).
 //   out (64 -> 1): one 16 x 16 tile per wave, only output row 0 carries weights; lane l < 16 of wave w finishes row 16w + l.
 // LDS: hidden [64][194] + inputs [64][13] + [64][K2P + 1]; h2 [64][66] reuses the input tiles.  N = 10 global: 74 752 bytes.
-#include "actor_common.h"
+#include "critic_rows.h"
 
 namespace cm3 {
 
-constexpr int kCriticGlobal = CM3_CRITIC_GLOBAL, kCriticCredit = CM3_CRITIC_CREDIT;
-constexpr int kFormRows = CM3_CRITIC_ROWS, kFormPairs = CM3_CRITIC_PAIRS, kFormCf = CM3_CRITIC_CF;
+using namespace critic_rows;   // (kinds, forms, form_exists, decode, form_dispatch, the entries' checks)
+constexpr int kCriticGlobal = kGlobal, kCriticCredit = kCredit;
 constexpr int kCH1 = 64, kCH2B = 128, kCH2 = 64;     // n_h1_1, n_h1_2, n_h2 (config.json nn block)
 
 template <int N, int KIND> struct CriticLayout {
@@ -101,29 +101,9 @@ struct CriticParams {
   const float *packed;
 };
 
-// (b, m, n, a) of row r; m = n where the form has no m, a = -1 where the action comes from the action array
-template <int N, int FORM> __device__ __forceinline__ void critic_decode(uint32_t r, uint32_t &b, int &m, int &n, int &a) {
-  a = -1;
-  if constexpr (FORM == kFormCf) {
-    a = (int)(r % 5u);
-    r /= 5u;
-  }
-  if constexpr (FORM == kFormRows || N == 1) {
-    b = r / (uint32_t)N;
-    n = (int)(r - b * (uint32_t)N);
-    m = n;
-  } else {
-    const uint32_t t = r / (uint32_t)N;
-    n = (int)(r - t * (uint32_t)N);
-    b = t / (uint32_t)N;
-    m = (int)(t - b * (uint32_t)N);
-  }
-}
-
 template <int N, int KIND, int FORM> __global__ void CM3_MATRIX_KERNEL k_critic_particle_rows(const CriticParams p) {
   using CL = CriticLayout<N, KIND>;
-  static_assert(KIND == kCriticGlobal ? (FORM == kFormRows || (FORM == kFormCf && N == 1)) : (N > 1 && FORM != kFormRows),
-                "forms: global ROWS (and CF at N = 1), credit PAIRS / CF at N > 1");
+  static_assert(form_exists(KIND, FORM, N), "forms: global ROWS (and CF at N = 1), credit PAIRS / CF at N > 1");
   static_assert(CL::kLdsFloats * 4 <= 80 * 1024, "two workgroups per CU");
   __shared__ __attribute__((aligned(16))) float smem[CL::kLdsFloats];
   float(*hs)[CL::HS] = reinterpret_cast<float(*)[CL::HS]>(smem);
@@ -140,7 +120,7 @@ template <int N, int KIND, int FORM> __global__ void CM3_MATRIX_KERNEL k_critic_
     const uint32_t r = row_base + lane;
     uint32_t b;
     int m, n, a;
-    critic_decode<N, FORM>(r < rows ? r : rows - 1, b, m, n, a);
+    decode<N, FORM>(r < rows ? r : rows - 1, b, m, n, a);
     const uint32_t base = b * (uint32_t)N;
     if (w == 0) {
       const float4 s = reinterpret_cast<const float4 *>(p.state)[base + n];
@@ -272,7 +252,7 @@ template <int N, int KIND, int FORM> __global__ void CM3_MATRIX_KERNEL k_critic_
         // reward + gamma * q * not_done in the order of k_td_target (batch.hip) on the widened q
         uint32_t b;
         int m, n, a;
-        critic_decode<N, FORM>(hr, b, m, n, a);
+        decode<N, FORM>(hr, b, m, n, a);
         const size_t bn = (size_t)b * N + n;
         const double rw = p.reward_f64 ? reinterpret_cast<const double *>(p.reward)[bn] : (double)reinterpret_cast<const float *>(p.reward)[bn];
         const double gq = p.gamma * (double)q;
@@ -282,30 +262,17 @@ template <int N, int KIND, int FORM> __global__ void CM3_MATRIX_KERNEL k_critic_
   }
 }
 
-static const char *critic_variant_tail(int kind, int form) {
-  static const char *const kTail[2][3] = {{",kind=global,form=rows", ",kind=global,form=pairs", ",kind=global,form=cf"},
-                                          {",kind=credit,form=rows", ",kind=credit,form=pairs", ",kind=credit,form=cf"}};
-  return kTail[kind][form];
-}
-
 template <int N, int KIND, int FORM> static int critic_launch(const CriticParams &p, hipStream_t s) {
   const unsigned blocks = (p.n_rows + 63u) / 64u;
   note_variant("k_critic_particle_rows", (int)sizeof(float), N, 4, 0, 0, 0, 0, 0, 0, /* prec=f32 */ 0);
-  note_tail(critic_variant_tail(KIND, FORM));
+  note_tail(variant_tail(KIND, FORM));
   hipLaunchKernelGGL((k_critic_particle_rows<N, KIND, FORM>), dim3(blocks), dim3(256), 0, s, p);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }
 
-// the forms a (kind, N) has: global ROWS at every N and CF at N = 1; credit PAIRS and CF at N > 1 (checked by the entry point)
 template <int N> static int critic_launch_form(int kind, int form, const CriticParams &p, hipStream_t s) {
-  if (kind == kCriticGlobal) {
-    if (form == kFormRows) return critic_launch<N, kCriticGlobal, kFormRows>(p, s);
-    if constexpr (N == 1) return critic_launch<1, kCriticGlobal, kFormCf>(p, s);
-  } else if constexpr (N > 1) {
-    return form == kFormPairs ? critic_launch<N, kCriticCredit, kFormPairs>(p, s) : critic_launch<N, kCriticCredit, kFormCf>(p, s);
-  }
-  return fail(CM3_ERR_INVALID, "the critic of kind %d has no form %d at %d agents", kind, form, N);
+  return form_dispatch<N>(kind, form, "critic", [&](auto k, auto f) { return critic_launch<N, k(), f()>(p, s); });
 }
 
 template <int N> static int critic_pack_launch(int kind, const CriticPackParams &p, float *out, hipStream_t s) {
@@ -318,26 +285,13 @@ template <int N> static int critic_pack_launch(int kind, const CriticPackParams 
   return CM3_OK;
 }
 
-static size_t critic_floats_for(int n, int kind) {   // (0 for an agent count outside 1..10, an unknown kind, credit at N = 1)
-  bool hit;
-  return agent_dispatch_1_to_10(n, hit, [&](auto k) {
-    constexpr int N = k();
-    if (kind == kCriticGlobal) return (size_t)CriticLayout<N, kCriticGlobal>::kTotal;
-    if (kind == kCriticCredit && N > 1) return (size_t)CriticLayout<(N > 1 ? N : 2), kCriticCredit>::kTotal;
-    return (size_t)0;
-  });
-}
+static size_t critic_floats_for(int n, int kind) { return floats_for<CriticLayout, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(n, kind); }
 
 static int critic_check_desc(const cm3_critic_particle_desc *d) {
   CM3_REQUIRE(d, "null desc");
   CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= CM3_MAX_AGENTS, "n_agents must be in 1..%d", CM3_MAX_AGENTS);
-  CM3_REQUIRE(d->kind == kCriticGlobal || d->kind == kCriticCredit, "kind must be CM3_CRITIC_GLOBAL (0) or CM3_CRITIC_CREDIT (1), got %d",
-              d->kind);
-  CM3_REQUIRE(d->stage == 1 || d->stage == 2, "stage must be 1 or 2, got %d", d->stage);
-  CM3_REQUIRE(!(d->kind == kCriticCredit && (d->n_agents == 1 || d->stage == 1)),
-              "Q_credit exists at stage 2 with more than one agent only (n_agents %d, stage %d)", d->n_agents, d->stage);
-  CM3_REQUIRE((d->stage == 1) == (d->n_agents == 1),
-              "Q_global_1output runs at stage 1 with one agent and at stage 2 with more (n_agents %d, stage %d)", d->n_agents, d->stage);
+  const int rc = check_kind_stage(d->kind, d->stage, d->n_agents, "Q_global_1output", "Q_credit");
+  if (rc != CM3_OK) return rc;
   CM3_REQUIRE(d->n_h1_1 == kCH1 && d->n_h1_2 == kCH2B && d->n_h2 == kCH2,
               "supported critic widths are 64/128/64 (config.json nn block); got %d/%d/%d", d->n_h1_1, d->n_h1_2, d->n_h2);
   return CM3_OK;
@@ -374,28 +328,14 @@ extern "C" int cm3_critic_particle_rows_f32(const cm3_critic_particle_desc *d, c
   CM3_REQUIRE(r, "null rows");
   CM3_REQUIRE(wt->packed, "packed weights are NULL: run cm3_critic_particle_pack once per weight update");
   const int N = d->n_agents;
-  const bool form_ok = d->kind == kCriticGlobal ? (r->form == kFormRows || (r->form == kFormCf && N == 1))
-                                                : (r->form == kFormPairs || r->form == kFormCf);
-  CM3_REQUIRE(form_ok, "form %d does not exist for kind %d at %d agents: Q_global takes ROWS (0), and CF (2) with one agent; Q_credit "
-              "takes PAIRS (1) and CF (2)", r->form, d->kind, N);
-  CM3_REQUIRE(r->n_steps > 0, "n_steps must be positive");
-  const int64_t per_step = (int64_t)N * (r->form == kFormRows || N == 1 ? 1 : N) * (r->form == kFormCf ? kA : 1);
-  CM3_REQUIRE(r->n_steps <= (int64_t)0x7fffffff / per_step, "n_steps %lld gives more than 2^31 - 1 rows (%lld per time step)",
-              (long long)r->n_steps, (long long)per_step);
-  CM3_REQUIRE(r->state && r->goals, "missing inputs: state and goals are required");
-  CM3_REQUIRE(r->form == kFormCf || r->actions, "missing input: the forms ROWS and PAIRS read actions");
-  CM3_REQUIRE(r->q || r->q64 || r->td, "no output requested: set q, q64 or td");
-  CM3_REQUIRE(!(r->td && r->form == kFormCf), "td is not defined for the counterfactual form");
-  CM3_REQUIRE(!r->td || (r->reward && r->done), "missing inputs: td needs reward and done");
-  CM3_REQUIRE((uintptr_t)r->state % 16 == 0 && (uintptr_t)r->goals % 8 == 0 && (uintptr_t)r->actions % 4 == 0,
-              "misaligned inputs: state must be 16-byte aligned, goals 8-byte aligned, actions 4-byte aligned");
-  CM3_REQUIRE(!r->td || (uintptr_t)r->reward % (r->reward_f64 ? 8 : 4) == 0, "misaligned reward");
-  CM3_REQUIRE((uintptr_t)r->q % 4 == 0 && (uintptr_t)r->q64 % 8 == 0 && (uintptr_t)r->td % 8 == 0,
-              "misaligned outputs: q must be 4-byte aligned, q64 and td 8-byte aligned");
-  CM3_REQUIRE((uintptr_t)wt->packed % 16 == 0, "misaligned packed: must be 16-byte aligned");
+  uint32_t n_rows;
+  rc = check_rows(r, wt->packed, d->kind, N, "Q_global", "Q_credit", r->state && r->goals, "missing inputs: state and goals are required",
+                  (uintptr_t)r->state % 16 == 0 && (uintptr_t)r->goals % 8 == 0 && (uintptr_t)r->actions % 4 == 0,
+                  "misaligned inputs: state must be 16-byte aligned, goals 8-byte aligned, actions 4-byte aligned", n_rows);
+  if (rc != CM3_OK) return rc;
   CriticParams p;
   memset(&p, 0, sizeof(p));
-  p.n_rows = (uint32_t)(r->n_steps * per_step);
+  p.n_rows = n_rows;
   p.state = r->state;
   p.goals = r->goals;
   p.actions = r->actions;

@@ -16,7 +16,7 @@
 //                                                       window and v_obs of agent M (the reference repeats obs_self_t / obs_self_v
 //                                                       "indexed by m", alg_credit_checkers.py:604-605, :637-638)
 //   CF    (credit; global N=1) r = r' 5 + a             a = row a of eye(5); r' = the PAIRS index, or b
-// Mapping: the Checkers actor's (actor_checkers.hip) -- 256 threads = 4 waves own 64 rows, every layer is its tile loop gemm_tiles on
+// Mapping: the Checkers actor's (actor_checkers.hip) -- 256 threads = 4 waves own 64 rows, every layer is ck_tiles.h's gemm_tiles on
 // the exact-f32 matrix instruction (v_mfma_f32_16x16x4_f32) in a fixed k order, B operands from packed per-lane tiles; a row's bits
 // depend on neither its place in the workgroup nor the launch's row count, and the one-hot inputs are 0 / 1 INPUTS of the same chains
 // in every form.  Both convolutions are Toeplitz matrices (grid 54 -> 108 as [64 x 112], window 75 -> 150 as [80 x 160]).
@@ -24,14 +24,13 @@
 //   region B: the input tiles grid [64][68], window [64][84], x2 [64][68]; later hidden = concat(branch1[256], branch2[32]) [64][292]
 //   region A: x1 [64][292] = conv out (cols 0..111), conv_o out (112..271), s_n g_n a v_obs (272..286); later h2 [64][292]
 // branch2 runs with the convolutions (its inputs sit in region B) and waits in 8 accumulator registers until region B is free.
-#define CM3_NO_ENTRY_POINTS 1
-#include "actor_checkers.hip"
+#include "ck_tiles.h"
+#include "critic_rows.h"
 
 namespace cm3 {
 namespace ck_critic {
 
-constexpr int kGlobal = CM3_CRITIC_GLOBAL, kCredit = CM3_CRITIC_CREDIT;
-constexpr int kFormRows = CM3_CRITIC_ROWS, kFormPairs = CM3_CRITIC_PAIRS, kFormCf = CM3_CRITIC_CF;
+using namespace critic_rows;   // (kinds, forms, form_exists, decode, form_dispatch, the entries' checks)
 constexpr int kMaxAgents = 8;                                 // the Checkers actor's range
 constexpr int kH1 = 256, kH1B = 32, kH2 = 256;                // Q_n_h1_1, Q_n_h1_2, Q_n_h2 (config_checkers_stage{1,2}.json)
 constexpr int kGrid = 54, kGridF = 4, kGridOut = 108;         // 3 x 9 x 2 -> 3 x 9 x 4
@@ -51,7 +50,7 @@ template <int N, int KIND> struct Layout {
   static constexpr int K2 = !kStage2 ? 0 : (KIND == kGlobal ? 9 * (N - 1) : 4 * N);
   static constexpr int K2P = (K2 + 15) / 16 * 16;             // <= 64
   static constexpr int KH = kStage2 ? kH1 + kH1B : kH1;       // width of concat(branch1, branch2)
-  // packed weights (floats): B tiles [col tile][k group][lane][4] (actor_checkers.hip), each followed by its bias
+  // packed weights (floats): B tiles [col tile][k group][lane][4] (ck_tiles.h), each followed by its bias
   static constexpr int kPG = 0;
   static constexpr int kPGB = kPG + tiles(kKG, kNG);
   static constexpr int kPW = kPGB + kNG;
@@ -155,32 +154,12 @@ struct Params {
   const float *packed;
 };
 
-// (b, m, n, a) of row r; m = n where the form has no m, a = -1 where the action comes from the action array
-template <int N, int FORM> __device__ __forceinline__ void decode(uint32_t r, uint32_t &b, int &m, int &n, int &a) {
-  a = -1;
-  if constexpr (FORM == kFormCf) {
-    a = (int)(r % 5u);
-    r /= 5u;
-  }
-  if constexpr (FORM == kFormRows || N == 1) {
-    b = r / (uint32_t)N;
-    n = (int)(r - b * (uint32_t)N);
-    m = n;
-  } else {
-    const uint32_t t = r / (uint32_t)N;
-    n = (int)(r - t * (uint32_t)N);
-    b = t / (uint32_t)N;
-    m = (int)(t - b * (uint32_t)N);
-  }
-}
-
 // (CM3_MATRIX_KERNEL's register budget -- 256 VGPRs, accumulators in architectural registers -- with the occupancy the LDS tile allows:
 // one workgroup per CU, so the declared range is 1..2 waves per SIMD and not "at least 2")
 template <int N, int KIND, int FORM>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) k_critic_checkers_rows(const Params p) {
   using L = Layout<N, KIND>;
-  static_assert(KIND == kGlobal ? (FORM == kFormRows || (FORM == kFormCf && N == 1)) : (N > 1 && FORM != kFormRows),
-                "forms: global ROWS (and CF at N = 1), credit PAIRS / CF at N > 1");
+  static_assert(form_exists(KIND, FORM, N), "forms: global ROWS (and CF at N = 1), credit PAIRS / CF at N > 1");
   __shared__ __attribute__((aligned(16))) float smem[kLdsFloats];
   __shared__ uint32_t sB[64];
   __shared__ int sMNA[64];
@@ -356,12 +335,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   }
 }
 
-static const char *variant_tail(int kind, int form) {
-  static const char *const kTail[2][3] = {{",kind=global,form=rows", ",kind=global,form=pairs", ",kind=global,form=cf"},
-                                          {",kind=credit,form=rows", ",kind=credit,form=pairs", ",kind=credit,form=cf"}};
-  return kTail[kind][form];
-}
-
 template <int N, int KIND, int FORM> static int launch(const Params &p, hipStream_t s) {
   const unsigned blocks = (p.n_rows + 63u) / 64u;
   note_variant("k_critic_checkers_rows", (int)sizeof(float), N, 4, 0, 0, 0, 0, 0, 0, /* prec=f32 */ 0);
@@ -371,15 +344,8 @@ template <int N, int KIND, int FORM> static int launch(const Params &p, hipStrea
   return CM3_OK;
 }
 
-// the forms a (kind, N) has: global ROWS at every N and CF at N = 1; credit PAIRS and CF at N > 1 (checked by the entry point)
 template <int N> static int launch_form(int kind, int form, const Params &p, hipStream_t s) {
-  if (kind == kGlobal) {
-    if (form == kFormRows) return launch<N, kGlobal, kFormRows>(p, s);
-    if constexpr (N == 1) return launch<1, kGlobal, kFormCf>(p, s);
-  } else if constexpr (N > 1) {
-    return form == kFormPairs ? launch<N, kCredit, kFormPairs>(p, s) : launch<N, kCredit, kFormCf>(p, s);
-  }
-  return fail(CM3_ERR_INVALID, "the Checkers critic of kind %d has no form %d at %d agents", kind, form, N);
+  return form_dispatch<N>(kind, form, "Checkers critic", [&](auto k, auto f) { return launch<N, k(), f()>(p, s); });
 }
 
 template <int N> static int pack_launch(int kind, const PackParams &p, float *out, hipStream_t s) {
@@ -394,25 +360,11 @@ template <int N> static int pack_launch(int kind, const PackParams &p, float *ou
 
 template <typename F> static int agents_1_to_8(int n_agents, F &&f) { return agent_launch<1, 2, 3, 4, 5, 6, 7, 8>(n_agents, f); }
 
-static size_t floats_for(int n, int kind) {   // (0 for an agent count outside 1..8, an unknown kind, credit at N = 1)
-  bool hit;
-  return agent_dispatch<1, 2, 3, 4, 5, 6, 7, 8>(n, hit, [&](auto k) {
-    constexpr int N = k();
-    if (kind == kGlobal) return (size_t)Layout<N, kGlobal>::kTotal;
-    if (kind == kCredit && N > 1) return (size_t)Layout<(N > 1 ? N : 2), kCredit>::kTotal;
-    return (size_t)0;
-  });
-}
-
 static int check_desc(const cm3_critic_checkers_desc *d) {
   CM3_REQUIRE(d, "null desc");
   CM3_REQUIRE(d->n_agents >= 1 && d->n_agents <= kMaxAgents, "n_agents must be in 1..%d", kMaxAgents);
-  CM3_REQUIRE(d->kind == kGlobal || d->kind == kCredit, "kind must be CM3_CRITIC_GLOBAL (0) or CM3_CRITIC_CREDIT (1), got %d", d->kind);
-  CM3_REQUIRE(d->stage == 1 || d->stage == 2, "stage must be 1 or 2, got %d", d->stage);
-  CM3_REQUIRE(!(d->kind == kCredit && (d->n_agents == 1 || d->stage == 1)),
-              "Q_credit_checkers exists at stage 2 with more than one agent only (n_agents %d, stage %d)", d->n_agents, d->stage);
-  CM3_REQUIRE((d->stage == 1) == (d->n_agents == 1),
-              "Q_global_checkers runs at stage 1 with one agent and at stage 2 with more (n_agents %d, stage %d)", d->n_agents, d->stage);
+  const int rc = check_kind_stage(d->kind, d->stage, d->n_agents, "Q_global_checkers", "Q_credit_checkers");
+  if (rc != CM3_OK) return rc;
   CM3_REQUIRE(d->grid_h == 3 && d->grid_w == 9 && d->grid_c == 2 && d->win_h == 5 && d->win_w == 5 && d->win_c == 3,
               "supported geometry is a 3x9x2 grid and a 5x5x3 window; got %dx%dx%d and %dx%dx%d", d->grid_h, d->grid_w, d->grid_c,
               d->win_h, d->win_w, d->win_c);
@@ -425,7 +377,8 @@ static int check_desc(const cm3_critic_checkers_desc *d) {
 }  // namespace cm3
 
 extern "C" size_t cm3_critic_checkers_packed_bytes(int32_t n_agents, int32_t kind) {
-  return cm3::ck_critic::floats_for(n_agents, kind) * sizeof(float);
+  using namespace cm3::ck_critic;
+  return floats_for<Layout, 1, 2, 3, 4, 5, 6, 7, 8>(n_agents, kind) * sizeof(float);
 }
 
 extern "C" int cm3_critic_checkers_pack(const cm3_critic_checkers_desc *d, const cm3_critic_checkers_weights *wt, void *packed,
@@ -460,32 +413,19 @@ extern "C" int cm3_critic_checkers_rows_f32(const cm3_critic_checkers_desc *d, c
   CM3_REQUIRE(r, "null rows");
   CM3_REQUIRE(wt->packed, "packed weights are NULL: run cm3_critic_checkers_pack once per weight update");
   const int N = d->n_agents;
-  const bool form_ok = d->kind == kGlobal ? (r->form == kFormRows || (r->form == kFormCf && N == 1))
-                                          : (r->form == kFormPairs || r->form == kFormCf);
-  CM3_REQUIRE(form_ok, "form %d does not exist for kind %d at %d agents: Q_global_checkers takes ROWS (0), and CF (2) with one agent; "
-              "Q_credit_checkers takes PAIRS (1) and CF (2)", r->form, d->kind, N);
-  CM3_REQUIRE(r->n_steps > 0, "n_steps must be positive");
-  const int64_t per_step = (int64_t)N * (r->form == kFormRows || N == 1 ? 1 : N) * (r->form == kFormCf ? kA : 1);
-  CM3_REQUIRE(r->n_steps <= (int64_t)0x7fffffff / per_step, "n_steps %lld gives more than 2^31 - 1 rows (%lld per time step)",
-              (long long)r->n_steps, (long long)per_step);
-  CM3_REQUIRE(r->grid && r->vec && r->goals && r->windows && r->obs_self_v,
-              "missing inputs: grid, vec, goals, windows and obs_self_v are required");
-  CM3_REQUIRE(r->form == kFormCf || r->actions, "missing input: the forms ROWS and PAIRS read actions");
-  CM3_REQUIRE(r->q || r->q64 || r->td, "no output requested: set q, q64 or td");
-  CM3_REQUIRE(!(r->td && r->form == kFormCf), "td is not defined for the counterfactual form");
-  CM3_REQUIRE(!r->td || (r->reward && r->done), "missing inputs: td needs reward and done");
-  CM3_REQUIRE((uintptr_t)r->vec % 8 == 0 && (uintptr_t)r->obs_self_v % 8 == 0 && (uintptr_t)r->actions % 4 == 0 &&
-                  (!r->grid_f64 || (uintptr_t)r->grid % 8 == 0) && (!r->windows_f64 || (uintptr_t)r->windows % 8 == 0) &&
-                  (!r->goals_onehot || (uintptr_t)r->goals % 8 == 0),
-              "misaligned inputs: vec, obs_self_v, float64 grids / windows and one-hot goals must be 8-byte aligned, actions 4-byte "
-              "aligned");
-  CM3_REQUIRE(!r->td || (uintptr_t)r->reward % (r->reward_f64 ? 8 : 4) == 0, "misaligned reward");
-  CM3_REQUIRE((uintptr_t)r->q % 4 == 0 && (uintptr_t)r->q64 % 8 == 0 && (uintptr_t)r->td % 8 == 0,
-              "misaligned outputs: q must be 4-byte aligned, q64 and td 8-byte aligned");
-  CM3_REQUIRE((uintptr_t)wt->packed % 16 == 0, "misaligned packed: must be 16-byte aligned");
+  uint32_t n_rows;
+  rc = check_rows(r, wt->packed, d->kind, N, "Q_global_checkers", "Q_credit_checkers",
+                  r->grid && r->vec && r->goals && r->windows && r->obs_self_v,
+                  "missing inputs: grid, vec, goals, windows and obs_self_v are required",
+                  (uintptr_t)r->vec % 8 == 0 && (uintptr_t)r->obs_self_v % 8 == 0 && (uintptr_t)r->actions % 4 == 0 &&
+                      (!r->grid_f64 || (uintptr_t)r->grid % 8 == 0) && (!r->windows_f64 || (uintptr_t)r->windows % 8 == 0) &&
+                      (!r->goals_onehot || (uintptr_t)r->goals % 8 == 0),
+                  "misaligned inputs: vec, obs_self_v, float64 grids / windows and one-hot goals must be 8-byte aligned, actions 4-byte "
+                  "aligned", n_rows);
+  if (rc != CM3_OK) return rc;
   Params p;
   memset(&p, 0, sizeof(p));
-  p.n_rows = (uint32_t)(r->n_steps * per_step);
+  p.n_rows = n_rows;
   p.grid_f64 = r->grid_f64;
   p.windows_f64 = r->windows_f64;
   p.goals_onehot = r->goals_onehot;

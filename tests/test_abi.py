@@ -145,28 +145,42 @@ def test_library_carries_the_identity_of_its_sources(built):
 
 
 def test_matrix_kernel_sources_hold_no_inline_assembly():
-    """actor.hip / actor_checkers.hip / policy.hip keep the matrix accumulators in architectural VGPRs (CM3_MATRIX_KERNEL: two
-    waves per SIMD declared): there an asm statement's registers can be ones a matrix instruction in flight still reads or
-    writes, and the compiler's hazard recogniser does not look into asm statements (round 4: an inline `v_max_f32` relu read a
-    result before its passes were through; profiles/r04_policy_head.txt (4)).  The rule is enforced here, on the sources.
-    (policy.hip also includes particle.hip: its one asm statement, the write-through store, only READS registers that ordinary
-    VALU instructions produced.)"""
+    """The matrix translation units -- actor / actor_checkers / policy / policy_checkers / critic / critic_checkers / mixer -- keep
+    the matrix accumulators in architectural VGPRs (CM3_MATRIX_KERNEL: two waves per SIMD declared): there an asm statement's
+    registers can be ones a matrix instruction in flight still reads or writes, and the compiler's hazard recogniser does not look
+    into asm statements (round 4: an inline `v_max_f32` relu read a result before its passes were through;
+    profiles/r04_policy_head.txt (4)).  The rule is enforced here, on the sources: the seven units and every csrc file they
+    include, directly or through another file.
+    (policy.hip also includes particle.hip, and policy_checkers.hip checkers.hip: the two physics units are not scanned and their
+    own includes are not followed -- particle.hip's asm statements, the write-through store first of all, only READ registers that
+    ordinary VALU instructions produced.)"""
     import re
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cm3_amd", "csrc")
     build = open(os.path.join(root, "build.sh")).read()
     m = re.search(r"for f in ([a-z_ ]+); do\s*\n\s*\"\$\{HIPCC\}\" \$\{FLAGS\} \$\{PHYS\} \$\{MFMA_FORM\}", build)
     assert m, "build.sh: the loop that compiles the matrix translation units was not found"
     units = m.group(1).split()
-    assert set(units) == {"actor", "actor_checkers", "policy", "policy_checkers"}
+    assert set(units) == {"actor", "actor_checkers", "policy", "policy_checkers", "critic", "critic_checkers", "mixer"}
     assert "amdgpu-mfma-vgpr-form=1" not in re.sub(r"#[^\n]*", "", build), "the experimental flag is not part of the default build"
-    for name in units + ["actor_common"]:
-        path = os.path.join(root, name + (".h" if name == "actor_common" else ".hip"))
-        code = re.sub(r"//[^\n]*", "", open(path).read())          # (comments may talk about asm)
+    physics = {"particle.hip", "checkers.hip"}
+    todo, scanned = [u + ".hip" for u in units], []
+    while todo:
+        name = todo.pop()
+        if name in scanned or name in physics:
+            continue
+        scanned.append(name)
+        text = open(os.path.join(root, name)).read()
+        todo += [inc for inc in re.findall(r'^\s*#\s*include\s+"([^"/]+)"', text, flags=re.M)]
+        code = re.sub(r"//[^\n]*", "", text)          # (comments may talk about asm)
         # the one form that is allowed (round 6, policy_checkers.hip): an EMPTY statement whose only operand is a scalar-register
         # pointer -- `asm volatile("" : "+s"(ptr))`, a barrier for loop-invariant code motion that emits no instruction and names no
         # vector register, so it cannot touch a matrix result
         code = re.sub(r'asm\s+volatile\s*\(\s*""\s*:\s*"\+s"\s*\(\w+\)\s*\)', "", code)
+        # ... and its input-only twin in common.h, which every unit includes (cm3_fetch_one behind CM3_FETCH_EARLY, called by the env
+        # kernels only): `asm volatile("" ::"s"(v))` -- again no instruction, one scalar operand, no vector register
+        code = re.sub(r'asm\s+volatile\s*\(\s*""\s*:\s*:\s*"s"\s*\(\w+\)\s*\)', "", code)
         assert not re.search(r"\basm\s*(volatile\s*)?\(", code), "%s: inline assembly in a matrix translation unit" % name
+    assert {"common.h", "actor_common.h", "ck_tiles.h", "critic_rows.h", "policy_tiles.h", "philox.h"} <= set(scanned), scanned
     for name, kernels in (("actor", ["k_actor_particle"]), ("actor_checkers", ["k_ck_actor"]), ("policy", ["k_policy_rollout"])):
         code = open(os.path.join(root, name + ".hip")).read()
         for k in kernels:
@@ -176,6 +190,28 @@ def test_matrix_kernel_sources_hold_no_inline_assembly():
         code = open(os.path.join(root, name + ".hip")).read()
         for k in kernels:
             assert re.search(r"__launch_bounds__\(512\) __attribute__\(\(amdgpu_waves_per_eu\(2\)\)\) %s\(" % k, code), k
+
+
+def test_units_include_no_other_units_but_the_policy_pair():
+    """Units share code through headers.  Every file under cm3_amd/csrc is read: the only `.hip` includes left are the two policy
+    units' -- policy.hip takes particle.hip and actor.hip, policy_checkers.hip takes checkers.hip and actor_checkers.hip, whole and
+    under a macro that cuts the entry points out -- and this list may only shrink.  A probe under tools/probes includes csrc units
+    only in the stand-alone form: the unit(s) it drives plus util.hip, in one translation unit of its own."""
+    csrc = os.path.join(ROOT, "cm3_amd", "csrc")
+    found = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".h")):
+            incs = re.findall(r'^\s*#\s*include\s+"([^"]*\.hip)"', open(os.path.join(csrc, name)).read(), flags=re.M)
+            if incs:
+                found[name] = incs
+    allowed = {"policy.hip": ["particle.hip", "actor.hip"], "policy_checkers.hip": ["checkers.hip", "actor_checkers.hip"]}
+    assert set(found) <= set(allowed) and all(set(found[n]) <= set(allowed[n]) for n in found), found
+    probes = os.path.join(ROOT, "tools", "probes")
+    for name in sorted(os.listdir(probes)):
+        if name.endswith(".hip"):
+            incs = re.findall(r'^\s*#\s*include\s+"([^"]*\.hip)"', open(os.path.join(probes, name)).read(), flags=re.M)
+            assert all(i.startswith("../../cm3_amd/csrc/") for i in incs), (name, incs)
+            assert not incs or incs[-1].endswith("/util.hip"), "%s: csrc units come with util.hip, which closes the list" % name
 
 
 def test_device_code_holds_no_packed_float32_cross_half_select():
