@@ -44,4 +44,7 @@ def __getattr__(name):
     if name == "ParticleQmixMixer":
         from .qmix import ParticleQmixMixer
         return ParticleQmixMixer
+    if name == "CheckersQmixMixer":
+        from .qmix import CheckersQmixMixer
+        return CheckersQmixMixer
     raise AttributeError(name)

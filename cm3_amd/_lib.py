@@ -247,6 +247,22 @@ class QmixMixerRows(ctypes.Structure):
                 ("td", c_void_p), ("n_steps", c_int64)]
 
 
+class QmixMixerCheckersDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "embed_dim", "grid_h", "grid_w", "grid_c", "conv_f", "conv_kh", "conv_kw")]
+
+
+class QmixMixerCheckersWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("conv_w", "conv_b", "hyper_w_1", "hyper_w_final", "hyper_b_1", "hyper_b_final_l1", "hyper_b_final",
+                                        "packed")]
+
+
+class QmixMixerCheckersRows(ctypes.Structure):
+    # (cm3_qmix_mixer_checkers_rows: the base columns of cm3_qmix_mixer_checkers_rows_f32 and its optional outputs)
+    _fields_ = ([(n, c_int32) for n in ("grid_f64", "goals_onehot", "reward_f64", "reserved")]
+                + [(n, c_void_p) for n in ("grid", "vec", "goals", "agent_qs", "reward", "done")]
+                + [("gamma", c_double), ("q_tot", c_void_p), ("q_tot64", c_void_p), ("td", c_void_p), ("n_steps", c_int64)])
+
+
 class ActorParticleBufs(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("obs_others", "state", "goals", "meta", "episode", "actions", "probs",
                                         "epsilon_dev")]
@@ -321,6 +337,10 @@ SYMBOLS = {
     "cm3_qmix_mixer_particle_packed_bytes": (c_size_t, [c_int32]),
     "cm3_qmix_mixer_particle_pack": (ctypes.c_int, [P(QmixMixerParticleDesc), P(QmixMixerParticleWeights), c_void_p, c_void_p]),
     "cm3_qmix_mixer_particle_rows_f32": (ctypes.c_int, [P(QmixMixerParticleDesc), P(QmixMixerParticleWeights), P(QmixMixerRows), c_void_p]),
+    "cm3_qmix_mixer_checkers_packed_bytes": (c_size_t, [c_int32]),
+    "cm3_qmix_mixer_checkers_pack": (ctypes.c_int, [P(QmixMixerCheckersDesc), P(QmixMixerCheckersWeights), c_void_p, c_void_p]),
+    "cm3_qmix_mixer_checkers_rows_f32": (ctypes.c_int, [P(QmixMixerCheckersDesc), P(QmixMixerCheckersWeights), P(QmixMixerCheckersRows),
+                                                        c_void_p]),
     "cm3_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_int64, c_void_p]),
     "cm3_qmix_td_target_f64": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, ctypes.c_double, c_void_p, c_int64,
                                               c_void_p]),

@@ -889,8 +889,30 @@ def _onehot_rows(columns, l_action, device, keep=None):
     return out
 
 
-def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep):
+def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer=None, mixer_q_agent=None):
     """The Checkers form of qmix_train_step_feeds (alg_qmix_checkers.py:342-393)."""
+    if target_mixer is not None:
+        # (what needs no column comes first: the type, the target agent; then the batch's agent count and where its columns live)
+        from .qmix import CheckersQmixMixer
+        if not isinstance(target_mixer, CheckersQmixMixer):
+            raise ValueError("qmix_train_step_feeds: env='checkers' takes a CheckersQmixMixer as target_mixer, got %s: the Checkers mixer is "
+                             "not built from another network's weights; build a CheckersQmixMixer from the Mixer_target variables, or call "
+                             "without target_mixer and `run` answers mixer_target" % type(target_mixer).__name__)
+        if target_agent is None:
+            raise ValueError("qmix_train_step_feeds: target_mixer reads the target agents' Q values on the device; pass target_agent "
+                             "(a CheckersQmixAgent holding the Agent_target weights) as well")
+        if target_mixer.n != cols["vec"].shape[1]:
+            raise ValueError("qmix_train_step_feeds: target_mixer takes a CheckersQmixMixer for %d agents (the batch's count), got one for "
+                             "%d agents" % (cols["vec"].shape[1], target_mixer.n))
+        if not cols["vec"].is_cuda:
+            raise ValueError("qmix_train_step_feeds: target_mixer evaluates device columns; call without it for host tensors")
+    if mixer_q_agent is not None:
+        if target_mixer is None:
+            raise ValueError("qmix_train_step_feeds: mixer_q_agent names the agent whose Q values enter the device target mixer; pass "
+                             "target_mixer as well, or leave it out and `run` answers mixer_target")
+        if type(mixer_q_agent) is not type(target_agent) or mixer_q_agent.n != target_agent.n:
+            raise ValueError("qmix_train_step_feeds: mixer_q_agent must be a %s for %d agents like target_agent (the main agent), got %s"
+                             % (type(target_agent).__name__, target_agent.n, type(mixer_q_agent).__name__))
     call = _Recorder(run)
     vec = cols["vec"]
     B, N = vec.shape[0], vec.shape[1]
@@ -912,16 +934,30 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, ke
                   "obs_self_v": obs_self_v_next, "v_goal": goals_self}
     if device:
         call(["argmax_Q_target"], dict(agent_next), launch=False)
-        target_1hot = target_agent.greedy_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(B * N),
-                                               goals_self, onehot=True)["onehot"]
+        greedy = target_agent.greedy_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(B * N), goals_self,
+                                          onehot=True, q_max=target_mixer is not None)
+        target_1hot = greedy["onehot"]
     else:
         argmax = call(["argmax_Q_target"], dict(agent_next))[0]
         target_1hot = torch.nn.functional.one_hot(argmax.reshape(-1).long(), int(l_action))
     # ---- Q_tot of the target mixer, TD target (:364-379; the arithmetic of the particle train_step) ----
     feed = {"state_env": cols["next_grid"], "v_state": state_agents_next, "v_goal_all": goals_all, "actions_1hot": target_1hot}
     feed.update(agent_next)
-    q_tot = call(["mixer_target"], feed)[0]
-    target = qmix_td_target(cols["local_rewards"].reshape(B, N), q_tot, cols["done"], gamma)
+    if target_mixer is not None:
+        # agent_qs of the target evaluation is reduce_sum(Q_target * actions_1hot) (alg_qmix_checkers.py:93-95): the Q at the argmax
+        call(["mixer_target"], feed, launch=False)
+        agent_qs = greedy["q_max"]
+        if mixer_q_agent is not None:
+            # the reference's Checkers graph builds mixer_target on mixer_q_input (alg_qmix_checkers.py:96-97, :106): the Q values of
+            # Agent_MAIN on this feed, selected by the fed one-hot actions -- the target agents' argmax
+            q_main = mixer_q_agent.greedy_rows(obs_self_t_next, obs_self_v_next, obs_others_next, cols["actions"].reshape(B * N),
+                                               goals_self, q=True, onehot=False)["q"]
+            agent_qs = q_main.gather(1, greedy["argmax"].long().unsqueeze(1))
+        target = target_mixer.q_tot(cols["next_grid"], cols["next_vec"], goals, agent_qs.reshape(B, N),
+                                    cols["local_rewards"].reshape(B, N), cols["done"], gamma)["td"]
+    else:
+        q_tot = call(["mixer_target"], feed)[0]
+        target = qmix_td_target(cols["local_rewards"].reshape(B, N), q_tot, cols["done"], gamma)
     # ---- optimiser step of the main mixer, soft update (:381-393) ----
     call(["mixer_op"], {"state_env": cols["grid"], "v_state": state_agents, "v_goal_all": goals_all, "actions_1hot": actions_1hot,
                         "actions_prev": actions_prev_1hot, "obs_others": obs_others, "obs_self_t": obs_self_t,
@@ -930,7 +966,8 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, ke
     return call.calls
 
 
-def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle", target_mixer=None, keep=None):
+def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle", target_mixer=None, keep=None,
+                          mixer_q_agent=None):
     """The data side of the QMIX train_step (alg_qmix.py:338-380) from the columns of a sampled particle batch: builds, in the
     reference's order, the feed_dict of its four sess.run calls -- ["argmax_Q_target"], ["mixer_target"], ["mixer_op"],
     ["list_update_target_ops"] -- and returns the list of (ops, feed).  ``run(ops, feed)`` plays sess.run as in train_step_feeds: ops
@@ -945,30 +982,43 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     target_agent.greedy_rows in one launch, actions_1hot from one tiling launch, the TD target from cm3_qmix_td_target_f64.
     The soft update of the agent's target weights -- the agent half of list_update_target_ops -- is left to the caller:
     ``target_agent.soft_update_from(main_agent, tau)`` after this function returns.
-    With target_mixer as well (a ParticleQmixMixer holding the Mixer_target weights; particle only), `run` is NOT called for
+    With target_mixer as well (a ParticleQmixMixer holding the Mixer_target weights), `run` is NOT called for
     mixer_target either (its (ops, feed) entry still appears, in the same place with the same keys): greedy_rows runs once with
     q_max, and ONE launch of target_mixer.q_tot on v_global_next, goals and those Q values gives mixer_op's td_target, so `run` is
     left with what needs a gradient or an optimiser.  The caller's contract: `run` trains the main mixer (mixer_op) and writes the
     trained variables into its ParticleQmixMixer in place; after this function returns the caller does
     ``target_mixer.soft_update_from(main_mixer, tau)`` next to ``target_agent.soft_update_from(main_agent, tau)`` -- the two halves of
     list_update_target_ops.  Refused with a ValueError that names the remedy: target_mixer without target_agent, host columns, a
-    mixer for another agent count, an object that is no ParticleQmixMixer, env="checkers".  Without target_mixer nothing changes.
+    mixer for another agent count, an object that is no ParticleQmixMixer (a CheckersQmixMixer included).  Without target_mixer
+    nothing changes.
 
     env="checkers": the same four calls of alg_qmix_checkers.train_step (alg_qmix_checkers.py:342-393) from the columns of a sampled
     Checkers batch; placeholders state_env, v_state, v_goal_all, actions_1hot, actions_prev, obs_others, obs_self_t, obs_self_v,
     v_goal, td_target.  In the two TARGET feeds actions_prev is fed actions_1hot (the action just taken, as the reference does),
     in mixer_op the one-hot actions_prev column.  target_agent: a CheckersQmixAgent holding the Agent_target weights; both one-hot
     action feeds come from one tiling launch.  Pinned to tests/golden/trainstep_qmix_checkers_n*.npz.
+    target_mixer: a CheckersQmixMixer holding the Mixer_target weights, under the same contract as the particle one -- greedy_rows
+    runs once with q_max, the ["mixer_target"] entry is recorded in its place with its keys but `run` is not called for it, and ONE
+    launch of target_mixer.q_tot on next_grid, next_vec, goals, those Q values, local_rewards and done gives mixer_op's td_target;
+    the caller does ``target_mixer.soft_update_from(main_mixer, tau)`` next to the agent's afterwards.  Refused with a ValueError that
+    names the remedy, before a column is read: an object that is no CheckersQmixMixer (a ParticleQmixMixer included), target_mixer
+    without target_agent; then a mixer for another agent count than the batch's, host columns.
+    mixer_q_agent (with target_mixer only): WHOSE Q values enter the target mixer.  Default None: the target agents' Q at their argmax
+    (q_max of the one greedy_rows launch), the wiring of the particle graph (alg_qmix.py:107, :113) and of QMIX as published.  The
+    reference's CHECKERS graph is wired differently: alg_qmix_checkers.py:106 builds mixer_target on mixer_q_input (:96-97), the Q
+    values of Agent_MAIN on the fed next observations, selected by the fed one-hot actions (the target agents' argmax).  Pass the main
+    CheckersQmixAgent as mixer_q_agent to evaluate exactly that: one more greedy_rows launch on the main agent, its Q gathered at the
+    target's argmax.  A `run` that plays the reference's session computes the same inside sess.run(mixer_target).
 
     keep: an optional list that receives the int32 action temporaries the one-hot tiling launch reads -- whoever captures this
     function's launches into a hipGraph holds them for as long as the graph is replayed."""
     if env == "checkers":
-        if target_mixer is not None:
-            raise ValueError("qmix_train_step_feeds: env='checkers' has no device mixer (the Checkers mixer is not built); call "
-                             "without target_mixer, `run` answers mixer_target")
-        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep)
+        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer, mixer_q_agent)
     if env != "particle":
         raise ValueError("qmix_train_step_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
+    if mixer_q_agent is not None:
+        raise ValueError("qmix_train_step_feeds: mixer_q_agent belongs to env='checkers'; the particle graph builds mixer_target on the "
+                         "target agents' Q values (alg_qmix.py:113), leave it out")
     if target_mixer is not None:
         from .qmix import ParticleQmixMixer
         n_batch = cols["v_global"].shape[1]

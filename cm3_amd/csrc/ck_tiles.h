@@ -1,5 +1,6 @@
-// The tile loop of the Checkers networks on the exact-f32 matrix instruction: every layer of the Checkers actor (actor_checkers.hip) and of
-// the Checkers critics (critic_checkers.hip) is gemm_tiles over packed per-lane B tiles [col tile][k group][lane][4].
+// The tile loop of the Checkers networks on the exact-f32 matrix instruction: every layer of the Checkers actor (actor_checkers.hip), of
+// the Checkers critics (critic_checkers.hip) and of the Checkers QMIX mixer (mixer.hip) is gemm_tiles over packed per-lane B tiles
+// [col tile][k group][lane][4]; toeplitz (below) is the matrix form of their grid and window convolutions, for the pack kernels.
 #pragma once
 #include "actor_common.h"
 
@@ -85,6 +86,17 @@ __device__ __forceinline__ void store_relu(float *O, int ldo, int rt0, int ct0, 
       for (int reg = 0; reg < 4; ++reg)
         O[(16 * (rt0 + t) + 4 * hi + reg) * ldo + 16 * (ct0 + c) + col] = fmaxf(acc[t][c][reg] + b, 0.0f);
   }
+}
+
+// element (k, n) of a SAME convolution [H][W][C] -> [H][W][F] with a [KH][KW][C][F] kernel as a matrix over the NHWC flattenings
+template <int H, int W, int C, int F, int KH, int KW>
+__device__ __forceinline__ float toeplitz(const float *wt, int k, int n) {
+  if (k >= H * W * C || n >= H * W * F) return 0.0f;
+  const int pin = k / C, ch = k - C * pin, r = pin / W, c = pin - W * r;
+  const int pout = n / F, f = n - F * pout, ro = pout / W, co = pout - W * ro;
+  const int dr = r - ro + KH / 2, dc = c - co + KW / 2;       // out[ro][co] += x[ro + dr - KH/2][co + dc - KW/2] w[dr][dc]
+  if (dr < 0 || dr >= KH || dc < 0 || dc >= KW) return 0.0f;
+  return wt[((dr * KW + dc) * C + ch) * F + f];
 }
 
 }  // namespace cm3

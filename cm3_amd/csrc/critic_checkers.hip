@@ -70,17 +70,6 @@ struct PackParams {
   const float *conv_w, *conv_b, *conv_o_w, *conv_o_b, *w_b1, *b_b1, *w_b1_h2, *w_b2, *b_b2, *w_b2_h2, *w_out, *b_out;
 };
 
-// element (k, n) of a SAME convolution [H][W][C] -> [H][W][F] with a [KH][KW][C][F] kernel as a matrix over the NHWC flattenings
-template <int H, int W, int C, int F, int KH, int KW>
-__device__ __forceinline__ float toeplitz(const float *wt, int k, int n) {
-  if (k >= H * W * C || n >= H * W * F) return 0.0f;
-  const int pin = k / C, ch = k - C * pin, r = pin / W, c = pin - W * r;
-  const int pout = n / F, f = n - F * pout, ro = pout / W, co = pout - W * ro;
-  const int dr = r - ro + KH / 2, dc = c - co + KW / 2;       // out[ro][co] += x[ro + dr - KH/2][co + dc - KW/2] w[dr][dc]
-  if (dr < 0 || dr >= KH || dc < 0 || dc >= KW) return 0.0f;
-  return wt[((dr * KW + dc) * C + ch) * F + f];
-}
-
 // input of Q_branch1/kernel that column c of the x1 tile holds (-1: padding)
 __device__ __forceinline__ int x1_input(int c) {
   if (c < kNG) return c < kGridOut ? c : -1;                                  // conv

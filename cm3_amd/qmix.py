@@ -17,8 +17,8 @@ ignored, so ``{v.name: sess.run(v)}`` of either scope loads unchanged.  The netw
 
 Exploration draws come from the build's own Philox stream (csrc/actor.hip, kPurposeExplore): the same law as the reference's
 np.random calls, not the same numbers.  The learner stays on the reference's side; both agents serve a
-learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from, and ParticleQmixMixer
-(below) evaluates the particle target mixer -- mixer_target and the TD target -- on the same rows.  soft_update_from and the
+learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from, and ParticleQmixMixer /
+CheckersQmixMixer (below) evaluate the target mixer -- mixer_target and the TD target -- on the same rows.  soft_update_from and the
 weight loading are cm3_amd._net._DeviceNet's (the agent and mixer halves of list_update_target_ops, alg_qmix.py:135-156,
 alg_qmix_checkers.py:128-130); CheckersQmixAgent shares descriptor and launch bodies with CheckersActor (actor._CheckersPolicyNet).
 """
@@ -208,7 +208,8 @@ class CheckersQmixAgent(_CheckersPolicyNet):
 
     For a learner: greedy_rows evaluates the network on the rows of a sampled batch (argmax_Q_target of the reference's train_step,
     one launch, no draws), soft_update_from moves an Agent_target copy towards the main agent; cm3_amd.batch.qmix_train_step_feeds(
-    env="checkers", target_agent=...) builds every feed of train_step around them.  The mixer stays the caller's.
+    env="checkers", target_agent=...) builds every feed of train_step around them; with target_mixer= (a CheckersQmixMixer, below) the
+    target mixer's forward pass runs on the device too.  The main mixer's optimiser step stays the caller's.
     """
     _match = ("n", "precision")
     _refusal = "the main agent must be a CheckersQmixAgent for %(n)d agents at precision %(precision)r"
@@ -411,4 +412,119 @@ class ParticleQmixMixer(_DeviceNet):
         out = td_outputs(self.device, B, "q_tot", td)
         _keep(keep, st, go, aq, rw, dn, *out.values())
         self.enqueue(B, st, go, aq, rw, dn, 0.0 if gamma is None else gamma, **out)
+        return out
+
+
+# ---- the Checkers mixer ---------------------------------------------------------------------------------------------------------------
+CK_EMBED = 128                                      # embed_dim of networks.Qmix_mixer_checkers
+# the seven variables of networks.Qmix_mixer_checkers (networks.py:697-714) by the fields of cm3_qmix_mixer_checkers_weights
+CK_MIXER_NAMES = {"conv_w": "conv/Conv/weights", "conv_b": "conv/Conv/biases", "hyper_w_1": "hyper_w_1", "hyper_w_final": "hyper_w_final",
+                  "hyper_b_1": "hyper_b_1", "hyper_b_final_l1": "hyper_b_final_l1/kernel", "hyper_b_final": "hyper_b_final/kernel"}
+
+
+def checkers_mixer_weight_shapes(n_agents):
+    """short name -> shape of the TF variable of networks.Qmix_mixer_checkers for this agent count (Q_conv_f 4, Q_conv_k [3, 5])"""
+    k = 108 + 6 * n_agents
+    return {"conv_w": (3, 5, 2, 4), "conv_b": (4,), "hyper_w_1": (k, CK_EMBED * n_agents), "hyper_w_final": (k, CK_EMBED),
+            "hyper_b_1": (k, CK_EMBED), "hyper_b_final_l1": (k, CK_EMBED), "hyper_b_final": (CK_EMBED, 1)}
+
+
+class CheckersQmixMixer(_DeviceNet):
+    """The reference's Checkers QMIX mixer evaluated on the device over the transitions of a sampled batch.
+
+        reference                                                        here
+        -------------------------------------------------------------   -----------------------------------------------
+        networks.Qmix_mixer_checkers(agent_qs, state_env, state,         CheckersQmixMixer(weights, n_agents)
+            goals_all, ..., f1=4, k1=[3,5])
+          (networks.py:688-734; scopes Mixer_main / Mixer_target)
+        sess.run(mixer_target, feed) + the TD target                     mixer.q_tot(next_grid, next_vec, goals, q_max, local_rewards,
+          (alg_qmix_checkers.py:364-379)                                   done, gamma)  (ONE launch of cm3_qmix_mixer_checkers_rows_f32)
+        the mixer half of list_update_target_ops (:128-130)              mixer.soft_update_from(main_mixer, tau)
+
+    The forward pass only: the main mixer's loss, gradient and optimiser step stay the session's.  Weights stay
+    float32 as TensorFlow shapes them, in ``self.w`` under the short names of CK_MIXER_NAMES, so a session that trains the main mixer
+    can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors, capturable) then makes
+    the next launch follow them.  The prefixes "Mixer_main/", "Mixer_target/" and a ":0" suffix of the keys are ignored."""
+    _refusal = "the main mixer must be a CheckersQmixMixer for %(n)d agents"
+
+    def __init__(self, weights, n_agents, device="cuda:0"):
+        self.device = _lib.require_gpu(device)
+        self.n = int(n_agents)
+        if not 1 <= self.n <= 8:
+            raise Cm3Error("the Checkers QMIX mixer supports 1..8 agents")
+        self._load(weights, _MIXER_PREFIXES, CK_MIXER_NAMES, checkers_mixer_weight_shapes(self.n), "mixer",
+                   lambda lib: lib.cm3_qmix_mixer_checkers_packed_bytes(self.n), _lib.QmixMixerCheckersWeights())
+
+    def _desc(self):
+        d = _lib.QmixMixerCheckersDesc()
+        d.n_agents, d.embed_dim = self.n, CK_EMBED
+        d.grid_h, d.grid_w, d.grid_c = 3, 9, 2
+        d.conv_f, d.conv_kh, d.conv_kw = 4, 3, 5
+        return d
+
+    def repack(self):
+        """Re-arrange the (possibly updated in place) TF-shaped weights into the rows kernel's layout: one launch."""
+        d = self._desc()
+        _lib.check(self._lib.cm3_qmix_mixer_checkers_pack(ctypes.byref(d), ctypes.byref(self._wt), self._packed.data_ptr(),
+                                                          self._stream(None)))
+
+    # ---- launches -------------------------------------------------------------------------------------------------------------------
+    def enqueue(self, n_steps, grid, vec, goals, agent_qs, reward=None, done=None, gamma=0.0, q_tot=None, q_tot64=None, td=None,
+                stream=None):
+        """Raw launch of cm3_qmix_mixer_checkers_rows_f32 on contiguous device tensors: grid int8 or float64 [B, 54], vec float64
+        [B, N, 4], goals uint8 [B, N] or int64 [B, N, 2], agent_qs float32 [B, N], reward float32 or float64, done uint8; every output
+        is optional, one is required."""
+        if grid.dtype not in (torch.int8, torch.float64) or goals.dtype not in (torch.uint8, torch.int64):
+            raise Cm3Error("enqueue reads int8 or float64 grids and uint8 index or int64 one-hot goals, not %s / %s"
+                           % (grid.dtype, goals.dtype))
+        r = _lib.QmixMixerCheckersRows()
+        r.n_steps = int(n_steps)
+        r.grid, r.vec, r.goals, r.agent_qs = _lib.ptr(grid), _lib.ptr(vec), _lib.ptr(goals), _lib.ptr(agent_qs)
+        r.grid_f64 = 1 if grid.dtype == torch.float64 else 0
+        r.goals_onehot = 1 if goals.dtype == torch.int64 else 0
+        r.reward, r.done = _lib.ptr(reward), _lib.ptr(done)
+        r.reward_f64 = 1 if (reward is not None and reward.dtype == torch.float64) else 0
+        r.gamma = float(gamma)
+        r.q_tot, r.q_tot64, r.td = _lib.ptr(q_tot), _lib.ptr(q_tot64), _lib.ptr(td)
+        d = self._desc()
+        s = self._stream(stream)
+        _lib.check(self._lib.cm3_qmix_mixer_checkers_rows_f32(ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(r), s))
+
+    def _stage_cols(self, what, grid, vec, goals, agent_qs, reward=None, done=None):
+        """(B, grid, vec, goals, agent_qs, reward, done) contiguous on the mixer's device in the forms the kernel reads, staged as
+        CheckersCritic._stage_cols stages them: int8 grids and uint8 index goals as they are, everything else float64 / int64 one-hot
+        (leading dimensions may be merged or flattened: vec [B, 4 N], goals [B, 2 N] ...); agent_qs of any float dtype is rounded to
+        float32; reward stays float32 or float64 (another dtype is widened to float64); bool or integer done becomes uint8."""
+        N = self.n
+        if vec.numel() == 0 or vec.numel() % (4 * N):
+            raise Cm3Error("%s takes vec [B, %d, 4], got %s" % (what, N, tuple(vec.shape)))
+        B = vec.numel() // (4 * N)
+        if grid.numel() != B * 54 or goals.numel() not in (B * N, B * N * 2):
+            raise Cm3Error("%s takes grid [B, 3, 9, 2] and goals [B, %d, 2] (or [B, %d]) for %d time steps, got %s and %s"
+                           % (what, N, N, B, tuple(grid.shape), tuple(goals.shape)))
+        if agent_qs.numel() != B * N:
+            raise Cm3Error("%s takes agent_qs [B, %d] for %d time steps, got %s" % (what, N, B, tuple(agent_qs.shape)))
+        stage = lambda t, dt: t.to(device=self.device, dtype=dt).contiguous()      # noqa: E731
+        if goals.numel() == B * N:      # indices (a one-hot column has twice as many elements)
+            go = (stage(goals, torch.uint8) if goals.dtype == torch.uint8
+                  else torch.nn.functional.one_hot(goals.to(self.device).long().reshape(B, N), 2).contiguous())
+        else:
+            go = stage(goals, torch.int64)
+        gr = stage(grid, torch.int8 if grid.dtype == torch.int8 else torch.float64)
+        _, reward, done = stage_td_cols(what, self.device, B, N, None, reward, done, reward_name="reward_local")
+        return B, gr, stage(vec, torch.float64), go, stage(agent_qs, torch.float32).reshape(B, N), reward, done
+
+    def q_tot(self, grid, vec, goals, agent_qs, reward_local=None, done=None, gamma=None, keep=None):
+        """Qmix_mixer_checkers over the B transitions of a batch, ONE launch: grid = next_grid [B, 3, 9, 2], vec = next_vec [B, N, 4],
+        goals [B, N, 2] (or an index [B, N]) and agent_qs [B, N] = each target agent's Q at its argmax (greedy_rows(..., q_max=True))
+        give sess.run(mixer_target) of alg_qmix_checkers.train_step (alg_qmix_checkers.py:364-375).  Returns a dict of device tensors:
+        "q_tot" float32 [B, 1] (the shape the session returns), "q_tot64" the same values float64 [B, 1], and with reward_local [B, N]
+        (float32 / float64), done [B] and gamma also "td" float64 [B] = sum(reward_local[b]) + gamma * q_tot * (1 - done), the bits of
+        batch.qmix_td_target on "q_tot".  The three come together or not at all.  keep: an optional list that receives every tensor
+        the launch touches (the staged inputs, the outputs), for whoever captures the launch."""
+        td = td_given("q_tot", "reward_local", reward_local, done, gamma)
+        B, gr, ve, go, aq, rw, dn = self._stage_cols("q_tot", grid, vec, goals, agent_qs, reward_local, done)
+        out = td_outputs(self.device, B, "q_tot", td)
+        _keep(keep, gr, ve, go, aq, rw, dn, *out.values())
+        self.enqueue(B, gr, ve, go, aq, rw, dn, 0.0 if gamma is None else gamma, **out)
         return out

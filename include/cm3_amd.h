@@ -70,6 +70,8 @@ extern "C" {
                                   cm3_qmix_mixer_particle_packed_bytes / _pack / _rows_f32 (the particle QMIX mixer over transition rows
                                   with the TD target: mixer_target of alg_qmix.train_step, the last evaluation without a gradient);
                                   additive.
+                                  cm3_qmix_mixer_checkers_packed_bytes / _pack / _rows_f32 (the Checkers QMIX mixer over transition rows
+                                  with the TD target: mixer_target of alg_qmix_checkers.train_step); additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
@@ -748,6 +750,70 @@ int cm3_qmix_mixer_particle_pack(const cm3_qmix_mixer_particle_desc *desc, const
  * launch k_qmix_mixer_rows<f32,N=..>. */
 int cm3_qmix_mixer_particle_rows_f32(const cm3_qmix_mixer_particle_desc *desc, const cm3_qmix_mixer_particle_weights *weights,
                                      const cm3_qmix_mixer_rows *rows, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The Checkers QMIX mixer over TRANSITION rows (part of ABI 9, additive): networks.Qmix_mixer_checkers (networks.py:688-734) at the
+ * widths of config_checkers_stage{1,2}.json -- mixer_target of alg_qmix_checkers.train_step (alg_qmix_checkers.py:364-375) -- and the
+ * TD target that follows it (:377-379).  Per transition b, conv = relu(conv2d SAME 3x5x2 -> 4 over grid[b] [3][9][2] + biases)
+ * flattened NHWC to 108, x = concat(conv, state[b] [4N], goals[b] [2N]), K = 108 + 6N; the rest is the particle mixer above at
+ * embed_dim 128.  Float32 weights as the TF variables of a scope "Mixer_main/..." / "Mixer_target/..." are shaped:
+ *   conv_w           conv/Conv/weights [3][5][2][4]      conv_b   conv/Conv/biases [4]
+ *   hyper_w_1        hyper_w_1 [K][128 N]                w1 = |x . hyper_w_1| viewed [N][128]
+ *   hyper_w_final    hyper_w_final [K][128]              w_final = |x . hyper_w_final|
+ *   hyper_b_1        hyper_b_1 [K][128]                  b1 = x . hyper_b_1
+ *   hyper_b_final_l1 hyper_b_final_l1/kernel [K][128]    l1 = relu(x . kernel)                    (no bias)
+ *   hyper_b_final    hyper_b_final/kernel [128][1]       b_final = l1 . kernel                    (no bias)
+ *   hidden = elu(agent_qs[b][0..N) . w1 + b1),  q_tot = hidden . w_final + b_final
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_agents;                  /* 1..8 */
+  int32_t embed_dim;                 /* 128 */
+  int32_t grid_h, grid_w, grid_c;    /* 3, 9, 2 */
+  int32_t conv_f, conv_kh, conv_kw;  /* 4, 3, 5 (Q_conv_f, Q_conv_k) */
+} cm3_qmix_mixer_checkers_desc;
+
+typedef struct {
+  const float *conv_w, *conv_b, *hyper_w_1, *hyper_w_final, *hyper_b_1, *hyper_b_final_l1, *hyper_b_final;
+  const void *packed; /* kernel-layout copy written by cm3_qmix_mixer_checkers_pack (cm3_qmix_mixer_checkers_packed_bytes() bytes,
+                         16-byte aligned); the rows launch reads ONLY this buffer, re-pack after every weight update */
+} cm3_qmix_mixer_checkers_weights;
+
+/* The base columns of a batch of n_steps transitions in the forms the Checkers columns have, and the optional outputs (those of
+ * cm3_qmix_mixer_rows, at least one required; nothing is written at or past n_steps).  Float64 values are rounded to float32 as they
+ * are read, as a tf.float32 placeholder rounds its feed.  td = sum(reward[b][0..N)) + gamma * q_tot * (1 - done[b]), the bits
+ * cm3_qmix_td_target_f64 produces from this launch's float32 q_tot.  Every sum has a fixed order (csrc/mixer.hip): a row's bits depend
+ * on neither its place in a workgroup nor n_steps.  (Anonymous struct tags, like cm3_qmix_rows.) */
+typedef struct {
+  int32_t grid_f64;         /* grid holds float64 [n_steps][54] (else int8) */
+  int32_t goals_onehot;     /* goals holds int64 one-hot [n_steps][N][2] (else uint8 index [n_steps][N]) */
+  int32_t reward_f64;       /* reward holds float64 (else float32) */
+  int32_t reserved;         /* 0 */
+  const void *grid;         /* [n_steps][3][9][2]; float64: 8-byte aligned */
+  const double *vec;        /* [n_steps][N][4] the agents' states */
+  const void *goals;        /* one-hot: 8-byte aligned */
+  const float *agent_qs;    /* [n_steps][N]: the target agents' Q at their argmax (cm3_qmix_checkers_rows.q_max) */
+  const void *reward;       /* [n_steps][N] local_rewards (td) */
+  const uint8_t *done;      /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *q_tot;
+  double *q_tot64;
+  double *td;
+  int64_t n_steps;
+} cm3_qmix_mixer_checkers_rows;
+
+/* 0 for an agent count outside 1..8 */
+size_t cm3_qmix_mixer_checkers_packed_bytes(int32_t n_agents);
+/* Re-arranges the TensorFlow-shaped weights into the rows kernel's tiles -- the convolution as a Toeplitz matrix, K zero-padded to
+ * whole k groups: one small launch per weight update, on persistent tensors (capturable).  CM3_ERR_INVALID: the descriptor checks
+ * below, null weights / packed, a missing tensor, a misaligned packed. */
+int cm3_qmix_mixer_checkers_pack(const cm3_qmix_mixer_checkers_desc *desc, const cm3_qmix_mixer_checkers_weights *weights, void *packed,
+                                 void *stream);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device: null desc / weights / rows,
+ * weights->packed NULL, n_agents outside 1..8, another embedding width than 128, another grid than 3x9x2 or convolution than 4 filters
+ * of 3x5, n_steps <= 0 or above 2^31 - 1, a missing input (grid, vec, goals, agent_qs; reward and done with td), no output requested,
+ * a misaligned pointer.  cm3_last_kernel_variant() names the launch k_ck_qmix_mixer_rows<f32,N=..>. */
+int cm3_qmix_mixer_checkers_rows_f32(const cm3_qmix_mixer_checkers_desc *desc, const cm3_qmix_mixer_checkers_weights *weights,
+                                     const cm3_qmix_mixer_checkers_rows *rows, void *stream);
 
 /* A whole policy-driven episode in ONE launch: for every tick, actor forward pass + sampling (as cm3_actor_particle_f32)
  * followed by the env step (as cm3_particle_step_f32), with the network weights, the observation tile and the env
