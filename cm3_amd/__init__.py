@@ -35,6 +35,9 @@ def __getattr__(name):
     if name == "CheckersCritic":
         from .critic import CheckersCritic
         return CheckersCritic
+    if name in ("ParticleValue", "ParticleComaCritic"):
+        from . import baseline
+        return getattr(baseline, name)
     if name == "ParticleQmixAgent":
         from .qmix import ParticleQmixAgent
         return ParticleQmixAgent

@@ -232,6 +232,39 @@ CRITIC_GLOBAL, CRITIC_CREDIT = 0, 1
 CRITIC_ROWS, CRITIC_PAIRS, CRITIC_CF = 0, 1, 2
 
 
+class ValueParticleDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "stage", "kind", "n_h1", "n_others", "n_h2")]
+
+
+class ValueParticleWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w_b1", "b_b1", "w_b1_h2", "w_b2", "b_b2", "w_b2_h2", "w_out", "packed")]
+
+
+class ValueRows(ctypes.Structure):
+    # (cm3_value_rows: the base columns cm3_value_particle_rows_f32 decodes its rows from, and its optional outputs)
+    _fields_ = [("reward_f64", c_int32), ("reserved", c_int32), ("state", c_void_p), ("obs_others", c_void_p), ("goals", c_void_p),
+                ("reward", c_void_p), ("done", c_void_p), ("gamma", c_double), ("v", c_void_p), ("v64", c_void_p), ("td", c_void_p),
+                ("n_steps", c_int64)]
+
+
+class ComaParticleDesc(ctypes.Structure):
+    _fields_ = [("n_agents", c_int32), ("units", c_int32)]
+
+
+class ComaParticleWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("w_h1", "b_h1", "w_h2", "b_h2", "w_out", "b_out", "packed")]
+
+
+class ComaRows(ctypes.Structure):
+    # (cm3_coma_rows: the base columns cm3_coma_particle_rows_f32 decodes its rows from, and its optional outputs)
+    _fields_ = [("reward_f64", c_int32), ("reserved", c_int32), ("state", c_void_p), ("goals", c_void_p), ("v_obs", c_void_p),
+                ("actions", c_void_p), ("own_actions", c_void_p), ("reward", c_void_p), ("done", c_void_p), ("gamma", c_double),
+                ("q", c_void_p), ("q_taken", c_void_p), ("q_taken64", c_void_p), ("td", c_void_p), ("n_steps", c_int64)]
+
+
+VALUE_LOCAL, VALUE_GLOBAL = 0, 1
+
+
 class QmixMixerParticleDesc(ctypes.Structure):
     _fields_ = [("n_agents", c_int32), ("embed_dim", c_int32)]
 
@@ -331,6 +364,12 @@ SYMBOLS = {
     "cm3_critic_particle_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "cm3_critic_particle_pack": (ctypes.c_int, [P(CriticParticleDesc), P(CriticParticleWeights), c_void_p, c_void_p]),
     "cm3_critic_particle_rows_f32": (ctypes.c_int, [P(CriticParticleDesc), P(CriticParticleWeights), P(CriticRows), c_void_p]),
+    "cm3_value_particle_packed_bytes": (c_size_t, [c_int32, c_int32]),
+    "cm3_value_particle_pack": (ctypes.c_int, [P(ValueParticleDesc), P(ValueParticleWeights), c_void_p, c_void_p]),
+    "cm3_value_particle_rows_f32": (ctypes.c_int, [P(ValueParticleDesc), P(ValueParticleWeights), P(ValueRows), c_void_p]),
+    "cm3_coma_particle_packed_bytes": (c_size_t, [c_int32]),
+    "cm3_coma_particle_pack": (ctypes.c_int, [P(ComaParticleDesc), P(ComaParticleWeights), c_void_p, c_void_p]),
+    "cm3_coma_particle_rows_f32": (ctypes.c_int, [P(ComaParticleDesc), P(ComaParticleWeights), P(ComaRows), c_void_p]),
     "cm3_critic_checkers_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "cm3_critic_checkers_pack": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), c_void_p, c_void_p]),
     "cm3_critic_checkers_rows_f32": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), P(CriticCheckersRows), c_void_p]),

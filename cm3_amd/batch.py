@@ -803,6 +803,157 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     return call.calls
 
 
+# ---- the IAC / COMA baselines (alg_baseline.py:507-655; particle env) ------------------------------------------------------------
+
+def _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, target_actor, actor):
+    """The refusals of baseline_train_step_feeds, before any column is read beyond the agent count."""
+    given = lambda *xs: [x is not None for x in xs]                                  # noqa: E731
+    if any(given(v_target, v_main)) and not all(given(v_target, v_main)):
+        raise ValueError("baseline_train_step_feeds: v_target and v_main come together (the reference fetches V_target and V in one "
+                         "sess.run) or not at all")
+    if any(given(q_main, actor)) and not all(given(q_main, actor)):
+        raise ValueError("baseline_train_step_feeds: q_main and actor come together (the reference fetches Q and probs in one "
+                         "sess.run) or not at all")
+    nets = (("v_target", v_target), ("v_main", v_main), ("q_target", q_target), ("q_main", q_main))
+    if not any(given(v_target, v_main, q_target, q_main, target_actor, actor)):
+        return
+    n_batch = cols["v_global"].shape[1]
+    if any(c is not None for _, c in nets):
+        from .baseline import ParticleComaCritic, ParticleValue
+        kind = "local" if IAC else "global"
+        for name, c in nets:
+            if c is None:
+                continue
+            if name.startswith("v_"):
+                if not isinstance(c, ParticleValue) or c.kind != kind or c.n != n_batch:
+                    raise ValueError("baseline_train_step_feeds: %s takes a ParticleValue of kind %r for %d agents (IAC=%s), got %s"
+                                     % (name, kind, n_batch, bool(IAC), "a %s" % type(c).__name__ if not isinstance(c, ParticleValue)
+                                        else "kind %r for %d agents" % (c.kind, c.n)))
+            elif not isinstance(c, ParticleComaCritic) or c.n != n_batch:
+                raise ValueError("baseline_train_step_feeds: %s takes a ParticleComaCritic for %d agents, got %s"
+                                 % (name, n_batch, "a %s" % type(c).__name__ if not isinstance(c, ParticleComaCritic)
+                                    else "one for %d agents" % c.n))
+    if target_actor is not None or actor is not None:
+        from .actor import ParticleActor
+        for a in (target_actor, actor):
+            if a is not None and not isinstance(a, ParticleActor):
+                raise ValueError("baseline_train_step_feeds: target_actor / actor take ParticleActors, got a %s" % type(a).__name__)
+    if not cols["v_global"].is_cuda:
+        raise ValueError("baseline_train_step_feeds: the device networks evaluate device columns; call without them for host tensors")
+
+
+def baseline_train_step_feeds(cols, run, gamma, epsilon, IAC=False, use_Q=1, use_V=1, l_action=5, target_actor=None, actor=None,
+                              v_target=None, v_main=None, q_target=None, q_main=None, draw=None, keep=None):
+    """The data movement of alg_baseline.Alg.train_step (alg_baseline.py:507-655; IAC and COMA, particle env), in the reference's
+    call order, from the columns of ParticleRollout.as_reference_batch(numpy=False).  ``run(ops, feed)`` and the returned list of
+    (ops, feed) mean what they mean in train_step_feeds; IAC / use_Q / use_V are the reference's switches (IAC: IAC=True, use_V=1,
+    use_Q=0; COMA: use_Q=1, use_V=0; both critics: use_Q=1, use_V=1).
+
+    With every device network None this is the torch composition alone -- process_goals and process_global_state in their baseline
+    forms (:450-505), agent_labels, the TD targets and the three policy feeds of :618-647 -- bit-identical to the arrays the REAL
+    train_step feeds (tests/golden/trainstep_baseline_*.npz).
+
+    With a device network (CUDA columns) `run` is NOT called for its op; the (ops, feed) entry still appears in the list:
+      ["V_target", "V"]            v_target / v_main, cm3_amd.baseline.ParticleValues of kind "local" with IAC, "global" without,
+        (:534)                     both or neither: v_target.v_rows(next-step columns, reward_local, done, gamma)["td"] is the
+                                   V_td_target feed; the same launch on v_main gives V_next_res ("v64") and the policy's V_td_target
+      ["action_samples_target"]    target_actor.sample_rows(obs_others_next, v_local_next, goals, epsilon), as in train_step_feeds
+      ["Q_target"] (:576)          q_target, a ParticleComaCritic: q_target.q_rows(v_global_next, goals, a', v_local_next, reward,
+                                   done, gamma)["td"] is the Q_td_target feed (the GLOBAL reward)
+      ["Q", "probs"] (:616)        q_main and actor, both or neither: q_main.q_rows(v_global, goals, actions, v_local)["q"] and
+                                   actor.probs_rows(obs_others, v_local, goals, epsilon)
+    CONTRACT, as for q_credit in train_step_feeds: `run` writes the trained variables INTO v_main.w[...] / q_main.w[...] in place;
+    v_main.repack() is launched right after call(["V_op", "V"]) and q_main.repack() right after call(["Q_op"]) (the reference reads Q
+    after that optimiser step).  The soft updates stay the caller's.  A ParticleValue of the wrong kind for IAC, or a network of the
+    wrong agent count or class, is refused before any column is read.  draw / keep: as in train_step_feeds."""
+    _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, target_actor, actor)
+    probs_kw = {} if keep is None else {"keep": keep}
+    sample_kw = dict(probs_kw) if draw is None else dict(probs_kw, draw=draw)
+    call = _Recorder(run)
+    f64 = torch.float64
+    v_global, v_global_next, goals = cols["v_global"], cols["v_global_next"], cols["goals"]
+    n_steps, N = v_global.shape[0], v_global.shape[1]
+    coma = N > 1 and bool(use_Q)
+    if not use_V and not coma:
+        raise ValueError("baseline_train_step_feeds: nothing to train the policy on (use_V = 0 and no COMA critic: use_Q = 0 or one agent)")
+    rows = lambda x: x.reshape(n_steps * N, *x.shape[2:])                           # noqa: E731
+    obs_others, v_local = rows(cols["obs_others"]), rows(cols["v_local"])
+    obs_others_next, v_local_next = rows(cols["obs_others_next"]), rows(cols["v_local_next"])
+    reward_local, reward_rep = cols["reward_local"].reshape(n_steps * N), rep_rows(cols["reward"], N)
+    a1, ao = process_actions(cols["actions"], l_action)
+    goals_self, goals_others = process_goals(goals)
+    one, others, state = process_global_state(v_global)
+    one_next, others_next, state_next = process_global_state(v_global_next)
+    labels = torch.eye(N, dtype=f64, device=v_global.device).repeat(n_steps, 1)     # np.tile(np.eye(N), (n_steps, 1)) (:518)
+    not_done = -(rep_rows(cols["done"], N).to(torch.int64) - 1)                     # if true, then 0, else 1 (:538, :580)
+
+    def value_feed(nxt):
+        if IAC:
+            return {"obs_others": obs_others_next if nxt else obs_others, "v_obs": v_local_next if nxt else v_local, "v_goal": goals_self}
+        return {"v_state_one_agent": one_next if nxt else one, "v_goal": goals_self,
+                "v_state_other_agents": others_next if nxt else others, "v_goal_others": goals_others}
+
+    v_res = v_td_policy = None
+    if use_V:                       # ---- local critic (:522-558) ----
+        if v_target is not None:
+            call(["V_target", "V"], value_feed(True), launch=False)
+            args = (cols["obs_others_next"], cols["v_local_next"], goals) if IAC else (v_global_next, goals)
+            v_td = v_target.v_rows(*args, reward_local, cols["done"], gamma, **probs_kw)["td"]
+            v_td_policy = v_main.v_rows(*args, reward_local, cols["done"], gamma, **probs_kw)["td"]      # (on V_next_res, :604)
+        else:
+            v_t, v_next = call(["V_target", "V"], value_feed(True))
+            v_td = td_target(reward_local, v_t, not_done, gamma)
+            v_td_policy = td_target(reward_local, v_next, not_done, gamma)
+        v_res = call(["V_op", "V"], dict(value_feed(False), V_td_target=v_td))[1]
+        if v_main is not None:
+            v_main.repack()         # (the next evaluation reads the V_main weights this step updated)
+        v_res = v_res.reshape(-1)
+
+    if coma:                        # ---- global critic (:562-597) ----
+        feed = {"obs_others": obs_others_next, "v_obs": v_local_next, "v_goal": goals_self, "epsilon": epsilon}
+        if target_actor is None:
+            acts = call(["action_samples_target"], feed)[0]
+        else:
+            call(["action_samples_target"], feed, launch=False)
+            acts = target_actor.sample_rows(obs_others_next, v_local_next, goals_self, epsilon, **sample_kw)["actions"]
+        if acts.is_cuda:
+            a_next, a_others_next, _ = process_actions_device(acts, n_steps, N, l_action, keep=keep)
+        else:
+            a_next, a_others_next = process_actions(acts.reshape(n_steps, N), l_action)
+        feed = {"v_state": state_next, "action_others": a_others_next, "v_goal": goals_self, "v_goal_others": goals_others,
+                "v_labels": labels, "v_obs": v_local_next}
+        if q_target is not None:
+            call(["Q_target"], feed, launch=False)
+            q_td = q_target.q_rows(v_global_next, goals, acts, cols["v_local_next"], cols["reward"], cols["done"], gamma, **probs_kw)["td"]
+        else:
+            q_t = call(["Q_target"], feed)[0]
+            q_taken = (q_t.to(f64) * a_next).sum(dim=1)                             # np.sum(Q_target_res * actions_self_next, axis=1)
+            q_td = td_target(reward_rep, q_taken, not_done, gamma)
+        call(["Q_op"], {"Q_td_target": q_td, "actions_self_1hot": a1, "v_state": state, "action_others": ao, "v_goal": goals_self,
+                        "v_goal_others": goals_others, "v_labels": labels, "v_obs": v_local})
+        if q_main is not None:
+            q_main.repack()         # (Q below reads the Q_main weights this step updated)
+        # ---- Q(s, a, g) and pi(a | o, g) for the policy gradient (:606-616) ----
+        feed = {"v_state": state, "v_obs": v_local, "action_others": ao, "obs_others": obs_others, "v_goal": goals_self,
+                "v_goal_others": goals_others, "v_labels": labels, "epsilon": epsilon}
+        if q_main is not None:
+            call(["Q", "probs"], feed, launch=False)
+            q_res = q_main.q_rows(v_global, goals, cols["actions"], cols["v_local"], **probs_kw)["q"]
+            probs = actor.probs_rows(obs_others, v_local, goals_self, epsilon, **probs_kw)
+        else:
+            q_res, probs = call(["Q", "probs"], feed)
+
+    # ---- policy (:618-653) ----
+    feed = {"action_taken": a1, "epsilon": epsilon, "obs_others": obs_others, "v_obs": v_local, "v_goal": goals_self}
+    if use_V:
+        feed.update({"V_td_target": v_td_policy, "V_evaluated": v_res})
+    if coma:
+        feed.update({"v_goal_others": goals_others, "v_labels": labels, "Q_evaluated": q_res, "probs_evaluated": probs})
+    call(["policy_op"], feed)
+    call(["list_update_target_ops"], {})
+    return call.calls
+
+
 # ---- QMIX (alg_qmix.py:236-380): everything of train_step that is not the mixer ----------------------------------------------
 
 def process_batch_qmix(cols, l_action=5):

@@ -72,6 +72,10 @@ extern "C" {
                                   additive.
                                   cm3_qmix_mixer_checkers_packed_bytes / _pack / _rows_f32 (the Checkers QMIX mixer over transition rows
                                   with the TD target: mixer_target of alg_qmix_checkers.train_step); additive.
+                                  cm3_value_particle_packed_bytes / _pack / _rows_f32 and cm3_coma_particle_packed_bytes / _pack /
+                                  _rows_f32 (the IAC / COMA baseline critics V_particle_local, V_particle_global and Q_global over
+                                  transition rows, with the TD targets: the evaluations of alg_baseline.train_step that carry no
+                                  gradient); additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
@@ -605,6 +609,119 @@ int cm3_critic_particle_pack(const cm3_critic_particle_desc *desc, const cm3_cri
  * k_critic_particle_rows<f32,N=..,...,kind=..,form=..>. */
 int cm3_critic_particle_rows_f32(const cm3_critic_particle_desc *desc, const cm3_critic_particle_weights *weights,
                                  const cm3_critic_rows *rows, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The IAC / COMA baseline critics over TRANSITION rows (part of ABI 9, additive; particle env): the value networks
+ * networks.V_particle_local (networks.py:356-374, IAC) and networks.V_particle_global (:377-402), and the COMA critic
+ * networks.Q_global (:84-94) -- the evaluations of alg_baseline.train_step that carry no gradient (V_target / V on the next-step
+ * columns :534, Q_target :576, Q :616).  Float32 weights, row-major [in][out] as the TF variables of the scopes "V_main/...",
+ * "V_target/...", "Q_main/...", "Q_target/..." are shaped.  One form: row r = b N + n, decoded from the base columns; "others" run
+ * over the agents j != n in ascending order.
+ *
+ * Value networks (widths 64 / 128 / 64: the branch-self default, V_n_others, V_n_h2 of config.json):
+ *   w_b1    local: V_particle_branch_self/kernel [6][64], input concat(v_obs[4], goal[2]);  global: V_particle_branch1/kernel [6][64],
+ *           input concat(state_n[4], goal_n[2]);  b_b1 its bias [64]
+ *   w_b1_h2 local: W_branch_self_out [64][64];  global: W_branch1_h2 [64][64]
+ *   w_b2    local: stage-2/V_local_others/kernel [4(N-1)][128], input obs_others;  global: stage-2/V_particle_branch2/kernel
+ *           [6(N-1)][128], input concat(state of the others [4(N-1)], goals of the others [2(N-1)]);  b_b2 its bias [128]
+ *   w_b2_h2 local: stage-2/W_others_out [128][64];  global: stage-2/W_branch2_h2 [128][64]
+ *   w_out   V_particle_out/kernel [64][1]          (h2 and out have no bias)
+ * The three stage-2 tensors are read at stage 2 only; stage 1 with one agent, stage 2 with more.
+ * ---------------------------------------------------------------------------------------- */
+#define CM3_VALUE_LOCAL 0
+#define CM3_VALUE_GLOBAL 1
+typedef struct {
+  int32_t n_agents;              /* 1..CM3_MAX_AGENTS */
+  int32_t stage;                 /* 1 / 2 */
+  int32_t kind;                  /* CM3_VALUE_LOCAL / CM3_VALUE_GLOBAL */
+  int32_t n_h1, n_others, n_h2;  /* 64 / 128 / 64 */
+} cm3_value_particle_desc;
+
+typedef struct {
+  const float *w_b1, *b_b1, *w_b1_h2, *w_b2, *b_b2, *w_b2_h2, *w_out;
+  const void *packed; /* kernel-layout copy written by cm3_value_particle_pack (cm3_value_particle_packed_bytes() bytes, 16-byte
+                         aligned); the rows launch reads ONLY this buffer, re-pack after every weight update */
+} cm3_value_particle_weights;
+
+/* Every output is optional, at least one is required; rows at or past the row count n_steps * N are not written:
+ *   v    float32 [R]     v64  float64 [R], the same value widened
+ *   td   float64 [R] = reward[b][n] + gamma * v * (1 - done[b]), in the order and bits of cm3_td_target_f64 applied to v64 */
+typedef struct {
+  int32_t reward_f64;       /* reward holds float64 (else float32) */
+  int32_t reserved;
+  const float *state;       /* global: v_global [n_steps][N][4]; local: v_obs [n_steps][N][4]; 16-byte aligned */
+  const float *obs_others;  /* local at stage 2: [n_steps][N][4(N-1)], 16-byte aligned */
+  const float *goals;       /* [n_steps][N][2], 8-byte aligned */
+  const void *reward;       /* the LOCAL reward [n_steps][N] (td) */
+  const uint8_t *done;      /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *v;
+  double *v64;
+  double *td;
+  int64_t n_steps;
+} cm3_value_rows;
+
+/* 0 for an agent count outside 1..10 and an unknown kind */
+size_t cm3_value_particle_packed_bytes(int32_t n_agents, int32_t kind);
+/* One small launch per weight update, on persistent tensors (capturable).  CM3_ERR_INVALID: the descriptor checks below, null
+ * weights / packed, a missing tensor. */
+int cm3_value_particle_pack(const cm3_value_particle_desc *desc, const cm3_value_particle_weights *weights, void *packed, void *stream);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device, in this order: null desc, n_agents outside
+ * 1..10, an unknown kind or stage, a stage that does not go with the agent count, other widths than 64/128/64; null weights / rows,
+ * weights->packed NULL; n_steps <= 0 or a row count above 2^31 - 1; a missing input (state, goals; obs_others for a local network at
+ * stage 2); no output requested; td without reward and done; a misaligned input, reward, output, packed.
+ * cm3_last_kernel_variant() names the launch k_value_particle_rows<f32,N=..,...,kind=local|global>. */
+int cm3_value_particle_rows_f32(const cm3_value_particle_desc *desc, const cm3_value_particle_weights *weights,
+                                const cm3_value_rows *rows, void *stream);
+
+/* The COMA critic, fc3 K -> 256 -> 256 -> 5 (ReLU on both hidden layers, biases on all three), N = 2..10:
+ *   input = concat(state of all agents [4N], one-hot actions of the others [5(N-1)], goal_n [2], goals of the others [2(N-1)],
+ *                  one-hot label of n [N], v_obs_n [4]),  K = 12 N - 1
+ *   w_h1 stage-2/Q_goals/h1/kernel [K][256]   b_h1 .../h1/bias [256]      w_h2 .../h2/kernel [256][256]   b_h2 .../h2/bias [256]
+ *   w_out .../out/kernel [256][5]             b_out .../out/bias [5] */
+typedef struct {
+  int32_t n_agents;   /* 2..CM3_MAX_AGENTS */
+  int32_t units;      /* 256 (Q_units) */
+} cm3_coma_particle_desc;
+
+typedef struct {
+  const float *w_h1, *b_h1, *w_h2, *b_h2, *w_out, *b_out;
+  const void *packed; /* written by cm3_coma_particle_pack (cm3_coma_particle_packed_bytes() bytes, 16-byte aligned) */
+} cm3_coma_particle_weights;
+
+/* Every output is optional, at least one is required; rows at or past the row count n_steps * N are not written:
+ *   q          float32 [R][5]
+ *   q_taken    float32 [R] = q[r][own_actions[b][n]] (np.sum(Q * actions_self_1hot, axis=1), alg_baseline.py:577); q_taken64 the same
+ *              value widened; an own action outside 0..4 leaves the row's q_taken, q_taken64 and td unwritten
+ *   td         float64 [R] = reward[b] + gamma * q_taken * (1 - done[b]) with the GLOBAL reward [n_steps] (:581), in the order and
+ *              bits of cm3_td_target_f64 applied to q_taken64 */
+typedef struct {
+  int32_t reward_f64;          /* reward holds float64 (else float32) */
+  int32_t reserved;
+  const float *state;          /* v_global [n_steps][N][4], 16-byte aligned */
+  const float *goals;          /* [n_steps][N][2], 8-byte aligned */
+  const float *v_obs;          /* v_local [n_steps][N][4], 16-byte aligned */
+  const int32_t *actions;      /* [n_steps][N], values 0..4: a row reads those of the OTHER agents */
+  const int32_t *own_actions;  /* optional [n_steps][N], values 0..4: the row's own action (q_taken, q_taken64, td) */
+  const void *reward;          /* the GLOBAL reward [n_steps] (td) */
+  const uint8_t *done;         /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *q;
+  float *q_taken;
+  double *q_taken64;
+  double *td;
+  int64_t n_steps;
+} cm3_coma_rows;
+
+/* 0 for an agent count outside 2..10 */
+size_t cm3_coma_particle_packed_bytes(int32_t n_agents);
+int cm3_coma_particle_pack(const cm3_coma_particle_desc *desc, const cm3_coma_particle_weights *weights, void *packed, void *stream);
+/* CM3_ERR_INVALID before anything touches the device, in this order: null desc, n_agents outside 2..10, another width than 256; null
+ * weights / rows, weights->packed NULL; n_steps <= 0 or a row count above 2^31 - 1; a missing input (state, goals, v_obs; actions);
+ * no output requested; q_taken / q_taken64 / td without own_actions; td without reward and done; a misaligned input, reward,
+ * output, packed.  cm3_last_kernel_variant() names the launch k_coma_particle_rows<f32,N=..,...>. */
+int cm3_coma_particle_rows_f32(const cm3_coma_particle_desc *desc, const cm3_coma_particle_weights *weights, const cm3_coma_rows *rows,
+                               void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * CM3 Checkers critics over TRANSITION rows (part of ABI 9, additive): networks.Q_global_checkers (networks.py:155-183) and
