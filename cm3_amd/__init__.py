@@ -35,7 +35,7 @@ def __getattr__(name):
     if name == "CheckersCritic":
         from .critic import CheckersCritic
         return CheckersCritic
-    if name in ("ParticleValue", "ParticleComaCritic"):
+    if name in ("ParticleValue", "ParticleComaCritic", "CheckersValue", "CheckersComaCritic"):
         from . import baseline
         return getattr(baseline, name)
     if name == "ParticleQmixAgent":

@@ -265,6 +265,39 @@ class ComaRows(ctypes.Structure):
 VALUE_LOCAL, VALUE_GLOBAL = 0, 1
 
 
+class ValueCheckersDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "stage", "kind", "n_h1_1", "n_h1_2", "n_h2")]
+
+
+class ValueCheckersWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("conv_w", "conv_b", "w_b1", "b_b1", "w_b1_h2", "w_b2", "b_b2", "w_b2_h2", "w_out", "b_out",
+                                        "packed")]
+
+
+class ValueCheckersRows(ctypes.Structure):
+    # (cm3_value_checkers_rows: the base columns cm3_value_checkers_rows_f32 decodes its rows from, and its optional outputs)
+    _fields_ = ([(n, c_int32) for n in ("reward_f64", "grid_f64", "windows_f64", "goals_onehot")]
+                + [(n, c_void_p) for n in ("grid", "vec", "goals", "windows", "obs_self_v", "obs_others", "reward", "done")]
+                + [("gamma", c_double), ("v", c_void_p), ("v64", c_void_p), ("td", c_void_p), ("n_steps", c_int64)])
+
+
+class ComaCheckersDesc(ctypes.Structure):
+    _fields_ = [("n_agents", c_int32), ("units", c_int32)]
+
+
+class ComaCheckersWeights(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("conv_s_w", "conv_s_b", "conv_o_w", "conv_o_b", "w_h1", "b_h1", "w_h2", "b_h2", "w_out", "b_out",
+                                        "packed")]
+
+
+class ComaCheckersRows(ctypes.Structure):
+    # (cm3_coma_checkers_rows: the base columns cm3_coma_checkers_rows_f32 decodes its rows from, and its optional outputs)
+    _fields_ = ([(n, c_int32) for n in ("reward_f64", "grid_f64", "windows_f64", "goals_onehot")]
+                + [(n, c_void_p) for n in ("grid", "vec", "goals", "actions", "own_actions", "windows", "obs_self_v", "reward", "done")]
+                + [("gamma", c_double), ("q", c_void_p), ("q_taken", c_void_p), ("q_taken64", c_void_p), ("td", c_void_p),
+                   ("n_steps", c_int64)])
+
+
 class QmixMixerParticleDesc(ctypes.Structure):
     _fields_ = [("n_agents", c_int32), ("embed_dim", c_int32)]
 
@@ -370,6 +403,12 @@ SYMBOLS = {
     "cm3_coma_particle_packed_bytes": (c_size_t, [c_int32]),
     "cm3_coma_particle_pack": (ctypes.c_int, [P(ComaParticleDesc), P(ComaParticleWeights), c_void_p, c_void_p]),
     "cm3_coma_particle_rows_f32": (ctypes.c_int, [P(ComaParticleDesc), P(ComaParticleWeights), P(ComaRows), c_void_p]),
+    "cm3_value_checkers_packed_bytes": (c_size_t, [c_int32, c_int32]),
+    "cm3_value_checkers_pack": (ctypes.c_int, [P(ValueCheckersDesc), P(ValueCheckersWeights), c_void_p, c_void_p]),
+    "cm3_value_checkers_rows_f32": (ctypes.c_int, [P(ValueCheckersDesc), P(ValueCheckersWeights), P(ValueCheckersRows), c_void_p]),
+    "cm3_coma_checkers_packed_bytes": (c_size_t, [c_int32]),
+    "cm3_coma_checkers_pack": (ctypes.c_int, [P(ComaCheckersDesc), P(ComaCheckersWeights), c_void_p, c_void_p]),
+    "cm3_coma_checkers_rows_f32": (ctypes.c_int, [P(ComaCheckersDesc), P(ComaCheckersWeights), P(ComaCheckersRows), c_void_p]),
     "cm3_critic_checkers_packed_bytes": (c_size_t, [c_int32, c_int32]),
     "cm3_critic_checkers_pack": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), c_void_p, c_void_p]),
     "cm3_critic_checkers_rows_f32": (ctypes.c_int, [P(CriticCheckersDesc), P(CriticCheckersWeights), P(CriticCheckersRows), c_void_p]),

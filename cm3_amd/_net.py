@@ -1,5 +1,5 @@
-"""What the ten weight-holding classes share (ParticleActor / CheckersActor, ParticleCritic / CheckersCritic, ParticleQmixAgent /
-CheckersQmixAgent, ParticleQmixMixer / CheckersQmixMixer, ParticleValue / ParticleComaCritic): loading a dict of TF variables into ``self.w`` and the library's packed layout, the soft
+"""What the twelve weight-holding classes share (ParticleActor / CheckersActor, ParticleCritic / CheckersCritic, ParticleQmixAgent /
+CheckersQmixAgent, ParticleQmixMixer / CheckersQmixMixer, ParticleValue / ParticleComaCritic, CheckersValue / CheckersComaCritic): loading a dict of TF variables into ``self.w`` and the library's packed layout, the soft
 update of a target copy, the stream default -- and the staging and output-allocation helpers more than one of them uses.
 
 _DeviceNet defines NO launch hook: cm3_amd.rollout chooses its launch path by which of enqueue / act / enqueue_rollout /

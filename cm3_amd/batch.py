@@ -803,10 +803,11 @@ def train_step_feeds(cols, run, gamma, epsilon, env="particle", use_Q_credit=Tru
     return call.calls
 
 
-# ---- the IAC / COMA baselines (alg_baseline.py:507-655; particle env) ------------------------------------------------------------
+# ---- the IAC / COMA baselines (alg_baseline.py:507-655, particle env; alg_baseline_checkers.py:499-662, Checkers) -----------------
 
-def _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, target_actor, actor):
+def _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, target_actor, actor, checkers=False):
     """The refusals of baseline_train_step_feeds, before any column is read beyond the agent count."""
+    state = "vec" if checkers else "v_global"
     given = lambda *xs: [x is not None for x in xs]                                  # noqa: E731
     if any(given(v_target, v_main)) and not all(given(v_target, v_main)):
         raise ValueError("baseline_train_step_feeds: v_target and v_main come together (the reference fetches V_target and V in one "
@@ -817,33 +818,36 @@ def _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, targ
     nets = (("v_target", v_target), ("v_main", v_main), ("q_target", q_target), ("q_main", q_main))
     if not any(given(v_target, v_main, q_target, q_main, target_actor, actor)):
         return
-    n_batch = cols["v_global"].shape[1]
+    n_batch = cols[state].shape[1]
     if any(c is not None for _, c in nets):
-        from .baseline import ParticleComaCritic, ParticleValue
+        from . import baseline
+        Value = baseline.CheckersValue if checkers else baseline.ParticleValue
+        Coma = baseline.CheckersComaCritic if checkers else baseline.ParticleComaCritic
         kind = "local" if IAC else "global"
         for name, c in nets:
             if c is None:
                 continue
             if name.startswith("v_"):
-                if not isinstance(c, ParticleValue) or c.kind != kind or c.n != n_batch:
-                    raise ValueError("baseline_train_step_feeds: %s takes a ParticleValue of kind %r for %d agents (IAC=%s), got %s"
-                                     % (name, kind, n_batch, bool(IAC), "a %s" % type(c).__name__ if not isinstance(c, ParticleValue)
-                                        else "kind %r for %d agents" % (c.kind, c.n)))
-            elif not isinstance(c, ParticleComaCritic) or c.n != n_batch:
-                raise ValueError("baseline_train_step_feeds: %s takes a ParticleComaCritic for %d agents, got %s"
-                                 % (name, n_batch, "a %s" % type(c).__name__ if not isinstance(c, ParticleComaCritic)
+                if not isinstance(c, Value) or c.kind != kind or c.n != n_batch:
+                    raise ValueError("baseline_train_step_feeds: %s takes a %s of kind %r for %d agents (IAC=%s), got %s"
+                                     % (name, Value.__name__, kind, n_batch, bool(IAC),
+                                        "a %s" % type(c).__name__ if not isinstance(c, Value) else "kind %r for %d agents" % (c.kind, c.n)))
+            elif not isinstance(c, Coma) or c.n != n_batch:
+                raise ValueError("baseline_train_step_feeds: %s takes a %s for %d agents, got %s"
+                                 % (name, Coma.__name__, n_batch, "a %s" % type(c).__name__ if not isinstance(c, Coma)
                                     else "one for %d agents" % c.n))
     if target_actor is not None or actor is not None:
-        from .actor import ParticleActor
+        from . import actor as _actor
+        Actor = _actor.CheckersActor if checkers else _actor.ParticleActor
         for a in (target_actor, actor):
-            if a is not None and not isinstance(a, ParticleActor):
-                raise ValueError("baseline_train_step_feeds: target_actor / actor take ParticleActors, got a %s" % type(a).__name__)
-    if not cols["v_global"].is_cuda:
+            if a is not None and not isinstance(a, Actor):
+                raise ValueError("baseline_train_step_feeds: target_actor / actor take %ss, got a %s" % (Actor.__name__, type(a).__name__))
+    if not cols[state].is_cuda:
         raise ValueError("baseline_train_step_feeds: the device networks evaluate device columns; call without them for host tensors")
 
 
 def baseline_train_step_feeds(cols, run, gamma, epsilon, IAC=False, use_Q=1, use_V=1, l_action=5, target_actor=None, actor=None,
-                              v_target=None, v_main=None, q_target=None, q_main=None, draw=None, keep=None):
+                              v_target=None, v_main=None, q_target=None, q_main=None, draw=None, keep=None, env="particle"):
     """The data movement of alg_baseline.Alg.train_step (alg_baseline.py:507-655; IAC and COMA, particle env), in the reference's
     call order, from the columns of ParticleRollout.as_reference_batch(numpy=False).  ``run(ops, feed)`` and the returned list of
     (ops, feed) mean what they mean in train_step_feeds; IAC / use_Q / use_V are the reference's switches (IAC: IAC=True, use_V=1,
@@ -865,7 +869,24 @@ def baseline_train_step_feeds(cols, run, gamma, epsilon, IAC=False, use_Q=1, use
     CONTRACT, as for q_credit in train_step_feeds: `run` writes the trained variables INTO v_main.w[...] / q_main.w[...] in place;
     v_main.repack() is launched right after call(["V_op", "V"]) and q_main.repack() right after call(["Q_op"]) (the reference reads Q
     after that optimiser step).  The soft updates stay the caller's.  A ParticleValue of the wrong kind for IAC, or a network of the
-    wrong agent count or class, is refused before any column is read.  draw / keep: as in train_step_feeds."""
+    wrong agent count or class, is refused before any column is read.  draw / keep: as in train_step_feeds.
+
+    env="checkers": alg_baseline_checkers.Alg.train_step (alg_baseline_checkers.py:499-662) on the 16 columns of
+    CheckersRollout.as_reference_batch(numpy=False), bit-identical to tests/golden/trainstep_baseline_checkers_*.npz.  The device
+    networks are then cm3_amd.baseline.CheckersValues / CheckersComaCritics and CheckersActors (a network of the other env's class is
+    refused before any column is read), on the base columns:
+      ["V_target", "V"]            v_rows(next_obs_self_t, next_obs_self_v, next_obs_others, goals, local_rewards, done, gamma) with IAC,
+                                   v_rows(next_grid, next_vec, goals, local_rewards, done, gamma) without
+      ["action_samples_target"]    target_actor.sample_rows(next_obs_self_t, next_obs_self_v, next_obs_others, actions, goals, epsilon):
+                                   actions_prev is the action just taken, as :559 feeds it
+      ["Q_target"]                 q_target.q_rows(next_grid, next_vec, goals, a', next_obs_self_t, next_obs_self_v, reward, done, gamma)
+      ["Q", "probs"]               q_main.q_rows(grid, vec, goals, actions, obs_self_t, obs_self_v)["q"] and
+                                   actor.probs_rows(obs_self_t, obs_self_v, obs_others, actions_prev, goals, epsilon)"""
+    if env not in _ENVS:
+        raise ValueError("baseline_train_step_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
+    if env == "checkers":
+        return _baseline_train_step_feeds_checkers(cols, run, gamma, epsilon, IAC, use_Q, use_V, l_action, target_actor, actor, v_target,
+                                                   v_main, q_target, q_main, draw, keep)
     _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, target_actor, actor)
     probs_kw = {} if keep is None else {"keep": keep}
     sample_kw = dict(probs_kw) if draw is None else dict(probs_kw, draw=draw)
@@ -945,6 +966,110 @@ def baseline_train_step_feeds(cols, run, gamma, epsilon, IAC=False, use_Q=1, use
 
     # ---- policy (:618-653) ----
     feed = {"action_taken": a1, "epsilon": epsilon, "obs_others": obs_others, "v_obs": v_local, "v_goal": goals_self}
+    if use_V:
+        feed.update({"V_td_target": v_td_policy, "V_evaluated": v_res})
+    if coma:
+        feed.update({"v_goal_others": goals_others, "v_labels": labels, "Q_evaluated": q_res, "probs_evaluated": probs})
+    call(["policy_op"], feed)
+    call(["list_update_target_ops"], {})
+    return call.calls
+
+
+def _baseline_train_step_feeds_checkers(cols, run, gamma, epsilon, IAC, use_Q, use_V, l_action, target_actor, actor, v_target, v_main,
+                                        q_target, q_main, draw, keep):
+    """baseline_train_step_feeds(env="checkers"): alg_baseline_checkers.Alg.train_step (alg_baseline_checkers.py:499-662)."""
+    _baseline_check_networks(cols, IAC, v_target, v_main, q_target, q_main, target_actor, actor, checkers=True)
+    probs_kw = {} if keep is None else {"keep": keep}
+    sample_kw = dict(probs_kw) if draw is None else dict(probs_kw, draw=draw)
+    call = _Recorder(run)
+    f64 = torch.float64
+    vec, vec_next, goals = cols["vec"], cols["next_vec"], cols["goals"]
+    n_steps, N = vec.shape[0], vec.shape[1]
+    coma = N > 1 and bool(use_Q)
+    if not use_V and not coma:
+        raise ValueError("baseline_train_step_feeds: nothing to train the policy on (use_V = 0 and no COMA critic: use_Q = 0 or one agent)")
+    # process_batch (:377-440): per-agent rows; grid, reward and done repeated N times; both action columns one-hot
+    rows = lambda x: x.reshape(n_steps * N, *x.shape[2:])                           # noqa: E731
+    obs = {nxt: {name: rows(cols[("next_%s" if nxt else "%s") % name]) for name in ("obs_others", "obs_self_t", "obs_self_v")}
+           for nxt in (False, True)}
+    state_env, state_env_next = rep_rows(cols["grid"], N), rep_rows(cols["next_grid"], N)
+    reward_local, reward_rep = cols["local_rewards"].reshape(n_steps * N), rep_rows(cols["reward"], N)
+    a1, ao = process_actions(cols["actions"], l_action)
+    prev1 = torch.nn.functional.one_hot(cols["actions_prev"].long(), l_action).reshape(n_steps * N, l_action)
+    goals_self, goals_others = process_goals(goals)
+    one, others, state = process_global_state(vec)
+    one_next, others_next, state_next = process_global_state(vec_next)
+    labels = torch.eye(N, dtype=f64, device=vec.device).repeat(n_steps, 1)          # np.tile(self.agent_labels, (n_steps, 1)) (:510)
+    not_done = -(rep_rows(cols["done"], N).to(torch.int64) - 1)                     # if true, then 0, else 1 (:531, :576)
+
+    def value_feed(nxt):
+        if IAC:
+            return dict(obs[nxt], v_goal=goals_self)
+        return {"state_env": state_env_next if nxt else state_env, "v_state_one_agent": one_next if nxt else one, "v_goal": goals_self,
+                "v_state_other_agents": others_next if nxt else others}
+
+    def base(nxt, *names):
+        return tuple(cols[("next_%s" if nxt else "%s") % name] for name in names)
+
+    v_res = v_td_policy = None
+    if use_V:                       # ---- local critic (:514-552) ----
+        if v_target is not None:
+            call(["V_target", "V"], value_feed(True), launch=False)
+            args = base(True, "obs_self_t", "obs_self_v", "obs_others") if IAC else base(True, "grid", "vec")
+            v_td = v_target.v_rows(*args, goals, reward_local, cols["done"], gamma, **probs_kw)["td"]
+            v_td_policy = v_main.v_rows(*args, goals, reward_local, cols["done"], gamma, **probs_kw)["td"]      # (on V_next_res, :602)
+        else:
+            v_t, v_next = call(["V_target", "V"], value_feed(True))
+            v_td = td_target(reward_local, v_t, not_done, gamma)
+            v_td_policy = td_target(reward_local, v_next, not_done, gamma)
+        v_res = call(["V_op", "V"], dict(value_feed(False), V_td_target=v_td))[1]
+        if v_main is not None:
+            v_main.repack()         # (the next evaluation reads the V_main weights this step updated)
+        v_res = v_res.reshape(-1)
+
+    if coma:                        # ---- global critic (:556-595) ----
+        # run_actor_target(actions_1hot, obs_others_next, ...): the action just taken is the previous action of the next step (:559)
+        feed = dict(obs[True], v_goal=goals_self, actions_prev=a1, epsilon=epsilon)
+        if target_actor is None:
+            acts = call(["action_samples_target"], feed)[0]
+        else:
+            call(["action_samples_target"], feed, launch=False)
+            acts = target_actor.sample_rows(obs[True]["obs_self_t"], obs[True]["obs_self_v"], obs[True]["obs_others"],
+                                            cols["actions"].reshape(-1), goals_self, epsilon, **sample_kw)["actions"]
+        if acts.is_cuda:
+            a_next, a_others_next, _ = process_actions_device(acts, n_steps, N, l_action, keep=keep)
+        else:
+            a_next, a_others_next = process_actions(acts.reshape(n_steps, N), l_action)
+        feed = {"state_env": state_env_next, "v_state": state_next, "action_others": a_others_next, "v_goal": goals_self,
+                "v_goal_others": goals_others, "v_labels": labels, "obs_self_t": obs[True]["obs_self_t"],
+                "obs_self_v": obs[True]["obs_self_v"]}
+        if q_target is not None:
+            call(["Q_target"], feed, launch=False)
+            q_td = q_target.q_rows(*base(True, "grid", "vec"), goals, acts, *base(True, "obs_self_t", "obs_self_v"), cols["reward"],
+                                   cols["done"], gamma, **probs_kw)["td"]
+        else:
+            q_t = call(["Q_target"], feed)[0]
+            q_taken = (q_t.to(f64) * a_next).sum(dim=1)                             # np.sum(Q_target_res * actions_self_next, axis=1)
+            q_td = td_target(reward_rep, q_taken, not_done, gamma)
+        call(["Q_op"], {"Q_td_target": q_td, "actions_self_1hot": a1, "state_env": state_env, "v_state": state, "action_others": ao,
+                        "v_goal": goals_self, "v_goal_others": goals_others, "v_labels": labels, "obs_self_t": obs[False]["obs_self_t"],
+                        "obs_self_v": obs[False]["obs_self_v"]})
+        if q_main is not None:
+            q_main.repack()         # (Q below reads the Q_main weights this step updated)
+        # ---- Q(s, a, g) and pi(a | o, g) for the policy gradient (:604-617) ----
+        feed = dict(obs[False], state_env=state_env, v_state=state, actions_prev=prev1, action_others=ao, v_goal=goals_self,
+                    v_goal_others=goals_others, v_labels=labels, epsilon=epsilon)
+        if q_main is not None:
+            call(["Q", "probs"], feed, launch=False)
+            q_res = q_main.q_rows(*base(False, "grid", "vec"), goals, cols["actions"], *base(False, "obs_self_t", "obs_self_v"),
+                                  **probs_kw)["q"]
+            probs = actor.probs_rows(obs[False]["obs_self_t"], obs[False]["obs_self_v"], obs[False]["obs_others"],
+                                     cols["actions_prev"].reshape(-1), goals_self, epsilon, **probs_kw)
+        else:
+            q_res, probs = call(["Q", "probs"], feed)
+
+    # ---- policy (:619-660) ----
+    feed = dict(obs[False], action_taken=a1, epsilon=epsilon, actions_prev=prev1, v_goal=goals_self)
     if use_V:
         feed.update({"V_td_target": v_td_policy, "V_evaluated": v_res})
     if coma:

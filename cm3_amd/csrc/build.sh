@@ -49,6 +49,10 @@ done
 "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/baseline.hip" -o "${OBJ}/baseline.o" 2> "${OBJ}/baseline.resource_usage.txt" \
   || { grep -v "remark:" "${OBJ}/baseline.resource_usage.txt" >&2; exit 1; } &
 pids+=($!)
+# ... and their Checkers twins (baseline_checkers.hip), likewise; tests/test_baseline_checkers_abi.py holds the unit to the same rule.
+"${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/baseline_checkers.hip" -o "${OBJ}/baseline_checkers.o" 2> "${OBJ}/baseline_checkers.resource_usage.txt" \
+  || { grep -v "remark:" "${OBJ}/baseline_checkers.resource_usage.txt" >&2; exit 1; } &
+pids+=($!)
 # the one-launch policy episode once more for float64 envs (policy.hip: PolicyReal = double), with the same flags as the float32 build
 "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_PARTICLE_F64 -Rpass-analysis=kernel-resource-usage -c "${HERE}/policy.hip" -o "${OBJ}/policy_f64.o" 2> "${OBJ}/policy_f64.resource_usage.txt" \
   || { grep -v "remark:" "${OBJ}/policy_f64.resource_usage.txt" >&2; exit 1; } &
@@ -60,9 +64,9 @@ pids+=($!)
 pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
 # the matrix units' diagnostics went to their resource-usage files with the remarks: show what is not a remark
-for f in actor critic critic_checkers mixer baseline actor_checkers policy policy_f64 policy_partial policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
+for f in actor critic critic_checkers mixer baseline baseline_checkers actor_checkers policy policy_f64 policy_partial policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
 OBJS=("${OBJ}/particle_f32.o" "${OBJ}/particle_f32_ilp.o" "${OBJ}/particle_f64.o" "${OBJ}/checkers.o" "${OBJ}/util.o" "${OBJ}/advantage.o"
-      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/critic.o" "${OBJ}/critic_checkers.o" "${OBJ}/mixer.o" "${OBJ}/baseline.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_partial.o"
+      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/critic.o" "${OBJ}/critic_checkers.o" "${OBJ}/mixer.o" "${OBJ}/baseline.o" "${OBJ}/baseline_checkers.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_partial.o"
       "${OBJ}/policy_checkers.o")
 if [ "${CM3_SKIP_ISA_LINT:-0}" != 1 ]; then
   python3 "${HERE}/../../tools/isa_lint.py" "${OBJS[@]}"     # (the objects of THIS build, not whatever else sits in ${OBJ})

@@ -76,6 +76,10 @@ extern "C" {
                                   _rows_f32 (the IAC / COMA baseline critics V_particle_local, V_particle_global and Q_global over
                                   transition rows, with the TD targets: the evaluations of alg_baseline.train_step that carry no
                                   gradient); additive.
+                                  cm3_value_checkers_packed_bytes / _pack / _rows_f32 and cm3_coma_checkers_packed_bytes / _pack /
+                                  _rows_f32 (the Checkers IAC / COMA baseline critics V_checkers_local, V_checkers_global and
+                                  Q_coma_checkers over transition rows, with the TD targets: the evaluations of
+                                  alg_baseline_checkers.train_step that carry no gradient); additive.
                                   cm3_actor_particle_rows_f32 (the CM3 particle actor over transition rows: probabilities and sampled
                                   actions, the two actor evaluations of alg_credit.train_step); additive.
                                   cm3_actor_checkers_rows_f32 (the CM3 Checkers actor over transition rows: the two actor evaluations of
@@ -722,6 +726,130 @@ int cm3_coma_particle_pack(const cm3_coma_particle_desc *desc, const cm3_coma_pa
  * output, packed.  cm3_last_kernel_variant() names the launch k_coma_particle_rows<f32,N=..,...>. */
 int cm3_coma_particle_rows_f32(const cm3_coma_particle_desc *desc, const cm3_coma_particle_weights *weights, const cm3_coma_rows *rows,
                                void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The Checkers IAC / COMA baseline critics over TRANSITION rows (part of ABI 9, additive): networks.V_checkers_local
+ * (networks.py:415-435), networks.V_checkers_global (:438-458) and networks.Q_coma_checkers (:293-306) at the widths
+ * alg_baseline_checkers.py:117-138 passes -- the evaluations of alg_baseline_checkers.train_step that carry no gradient (V_target /
+ * V :527, Q_target :572, Q :617).  One form: row r = b N + n, decoded from the base columns of a Checkers batch (dtypes as in
+ * cm3_critic_checkers_rows below: int8 or float64 grids and windows, float64 vectors, uint8 index or int64 one-hot goals; all
+ * rounded to float32 in the kernel); "others" run over the agents j != n in ascending order.  Agent counts 1..8 (COMA: 2..8).
+ * CM3_VALUE_LOCAL / CM3_VALUE_GLOBAL are those of the particle value networks.  Float32 weights as the TF variables of a scope
+ * "V_main/...", "V_target/...", "Q_main/...", "Q_target/..." are shaped:
+ *
+ * Value networks (widths 256 / 32 / 256):
+ *   conv_w   conv/Conv/weights: local [3][3][3][6] over the window [5][5][3] -> 150; global [3][5][2][4] over the grid [3][9][2] ->
+ *            108 (SAME, NHWC flatten);  conv_b conv/Conv/biases [6] / [4]
+ *   w_b1     local: branch_self/kernel [156][256], input concat(conv, obs_self_v[4], goal[2]);  global: V_branch1/kernel [114][256],
+ *            input concat(conv, s_n[4], g_n[2]);  b_b1 its bias [256]
+ *   w_b1_h2  local: W_self_h2 [256][256];  global: W_branch1_h2 [256][256]
+ *   w_b2     local: stage-2/branch_others/kernel [2(N-1)][32], input obs_others;  global: stage-2/V_branch2/kernel [4(N-1)][32],
+ *            input the states of the other agents;  b_b2 its bias [32]
+ *   w_b2_h2  local: stage-2/W_others_h2 [32][256];  global: stage-2/W_branch2_h2 [32][256]
+ *   w_out    local: V_checkers_out/kernel [256][1];  global: V_out/kernel [256][1];  b_out its bias [1]     (h2 has no bias)
+ * The three stage-2 tensors are read at stage 2 only; stage 1 with one agent, stage 2 with more.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_agents;               /* 1..8 */
+  int32_t stage;                  /* 1 / 2 */
+  int32_t kind;                   /* CM3_VALUE_LOCAL / CM3_VALUE_GLOBAL */
+  int32_t n_h1_1, n_h1_2, n_h2;   /* 256 / 32 / 256 */
+} cm3_value_checkers_desc;
+
+typedef struct {
+  const float *conv_w, *conv_b;
+  const float *w_b1, *b_b1, *w_b1_h2, *w_b2, *b_b2, *w_b2_h2, *w_out, *b_out;
+  const void *packed; /* kernel-layout copy written by cm3_value_checkers_pack (cm3_value_checkers_packed_bytes() bytes, 16-byte
+                         aligned); the rows launch reads ONLY this buffer, re-pack after every weight update */
+} cm3_value_checkers_weights;
+
+/* A local network reads windows, obs_self_v, goals (and obs_others at stage 2); a global one grid, vec, goals.  Outputs as in
+ * cm3_value_rows: v float32 [R], v64 the same value widened, td float64 [R] = reward[b][n] + gamma * v * (1 - done[b]) in the bits
+ * of cm3_td_target_f64 applied to v64; at least one is required; rows past the row count are not written. */
+typedef struct {
+  int32_t reward_f64;       /* reward holds float64 (else float32) */
+  int32_t grid_f64;         /* grid holds float64 (else int8) */
+  int32_t windows_f64;      /* windows holds float64 (else int8) */
+  int32_t goals_onehot;     /* goals holds int64 one-hot [n_steps][N][2] (else uint8 indices [n_steps][N]) */
+  const void *grid;         /* global: [n_steps][3][9][2] */
+  const double *vec;        /* global: [n_steps][N][4] agent state */
+  const void *goals;
+  const void *windows;      /* local: [n_steps][N][75] (obs_self_t) */
+  const double *obs_self_v; /* local: [n_steps][N][4] */
+  const double *obs_others; /* local at stage 2: [n_steps][N][2(N-1)] */
+  const void *reward;       /* the LOCAL reward [n_steps][N] (td) */
+  const uint8_t *done;      /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *v;
+  double *v64;
+  double *td;
+  int64_t n_steps;
+} cm3_value_checkers_rows;
+
+/* 0 for an agent count outside 1..8 and an unknown kind */
+size_t cm3_value_checkers_packed_bytes(int32_t n_agents, int32_t kind);
+/* Re-arranges the TensorFlow-shaped weights into the rows kernel's per-lane operand order, the convolution as a Toeplitz matrix: one
+ * launch per weight update, on persistent tensors (capturable). */
+int cm3_value_checkers_pack(const cm3_value_checkers_desc *desc, const cm3_value_checkers_weights *weights, void *packed, void *stream);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device, in this order: null desc, n_agents outside
+ * 1..8, an unknown kind or stage, a stage that does not go with the agent count, other widths than 256/32/256; null weights / rows,
+ * weights->packed NULL; n_steps <= 0 or a row count above 2^31 - 1; a missing input (obs_others for a local network at stage 2
+ * after the others); no output requested; td without reward and done; a misaligned input, reward, output, packed.
+ * cm3_last_kernel_variant() names the launch k_value_checkers_rows<f32,N=..,...,kind=local|global>. */
+int cm3_value_checkers_rows_f32(const cm3_value_checkers_desc *desc, const cm3_value_checkers_weights *weights,
+                                const cm3_value_checkers_rows *rows, void *stream);
+
+/* The Checkers COMA critic, N = 2..8: fc3 K -> 256 -> 256 -> 5 (ReLU on both hidden layers, biases on all three) on
+ *   input = concat(conv_s(grid) [108], states of all agents [4N], one-hot actions of the others [5(N-1)], g_n [2], goals of the
+ *                  others [2(N-1)], one-hot label of n [N], conv_o(window of n) [150], obs_self_v of n [4]),  K = 257 + 12 N
+ *   conv_s_w conv_s/Conv/weights [3][5][2][4]   conv_s_b conv_s/Conv/biases [4]   conv_o_w conv_o/Conv/weights [3][3][3][6]
+ *   conv_o_b conv_o/Conv/biases [6]             w_h1 stage-2/Q_coma_checkers/h1/kernel [K][256]   b_h1 .../h1/bias [256]
+ *   w_h2 .../h2/kernel [256][256]   b_h2 .../h2/bias [256]   w_out .../out/kernel [256][5]   b_out .../out/bias [5] */
+typedef struct {
+  int32_t n_agents;   /* 2..8 */
+  int32_t units;      /* 256 */
+} cm3_coma_checkers_desc;
+
+typedef struct {
+  const float *conv_s_w, *conv_s_b, *conv_o_w, *conv_o_b;
+  const float *w_h1, *b_h1, *w_h2, *b_h2, *w_out, *b_out;
+  const void *packed; /* written by cm3_coma_checkers_pack (cm3_coma_checkers_packed_bytes() bytes, 16-byte aligned) */
+} cm3_coma_checkers_weights;
+
+/* Outputs as in cm3_coma_rows: q float32 [R][5]; q_taken float32 [R] = q[r][own_actions[b][n]], q_taken64 the same value widened (an
+ * own action outside 0..4 leaves the row's q_taken, q_taken64 and td unwritten); td float64 [R] = reward[b] + gamma * q_taken *
+ * (1 - done[b]) with the GLOBAL reward [n_steps], in the bits of cm3_td_target_f64 applied to q_taken64. */
+typedef struct {
+  int32_t reward_f64;          /* reward holds float64 (else float32) */
+  int32_t grid_f64;            /* grid holds float64 (else int8) */
+  int32_t windows_f64;         /* windows holds float64 (else int8) */
+  int32_t goals_onehot;        /* goals holds int64 one-hot [n_steps][N][2] (else uint8 indices [n_steps][N]) */
+  const void *grid;            /* [n_steps][3][9][2] */
+  const double *vec;           /* [n_steps][N][4] agent state */
+  const void *goals;
+  const int32_t *actions;      /* [n_steps][N], values 0..4: a row reads those of the OTHER agents */
+  const int32_t *own_actions;  /* optional [n_steps][N], values 0..4: the row's own action (q_taken, q_taken64, td) */
+  const void *windows;         /* [n_steps][N][75] (obs_self_t) */
+  const double *obs_self_v;    /* [n_steps][N][4] */
+  const void *reward;          /* the GLOBAL reward [n_steps] (td) */
+  const uint8_t *done;         /* [n_steps], 0 / 1 (td) */
+  double gamma;
+  float *q;
+  float *q_taken;
+  double *q_taken64;
+  double *td;
+  int64_t n_steps;
+} cm3_coma_checkers_rows;
+
+/* 0 for an agent count outside 2..8 */
+size_t cm3_coma_checkers_packed_bytes(int32_t n_agents);
+int cm3_coma_checkers_pack(const cm3_coma_checkers_desc *desc, const cm3_coma_checkers_weights *weights, void *packed, void *stream);
+/* CM3_ERR_INVALID before anything touches the device, in this order: null desc, n_agents outside 2..8, another width than 256; null
+ * weights / rows, weights->packed NULL; n_steps <= 0 or a row count above 2^31 - 1; a missing input (grid, vec, goals, windows,
+ * obs_self_v; actions); no output requested; q_taken / q_taken64 / td without own_actions; td without reward and done; a misaligned
+ * input, reward, output, packed.  cm3_last_kernel_variant() names the launch k_coma_checkers_rows<f32,N=..,...>. */
+int cm3_coma_checkers_rows_f32(const cm3_coma_checkers_desc *desc, const cm3_coma_checkers_weights *weights,
+                               const cm3_coma_checkers_rows *rows, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * CM3 Checkers critics over TRANSITION rows (part of ABI 9, additive): networks.Q_global_checkers (networks.py:155-183) and
