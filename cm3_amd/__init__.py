@@ -47,6 +47,9 @@ def __getattr__(name):
     if name == "ParticleQmixMixer":
         from .qmix import ParticleQmixMixer
         return ParticleQmixMixer
+    if name == "ParticleQmixLearner":
+        from .qmix import ParticleQmixLearner
+        return ParticleQmixLearner
     if name == "CheckersQmixMixer":
         from .qmix import CheckersQmixMixer
         return CheckersQmixMixer

@@ -313,6 +313,31 @@ class QmixMixerRows(ctypes.Structure):
                 ("td", c_void_p), ("n_steps", c_int64)]
 
 
+class QmixLearnerParticleDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "n_h", "n_actions", "embed_dim")]
+
+
+class QmixLearnerTensors(ctypes.Structure):
+    # (cm3_qmix_learner_tensors: the eleven weights read, or the eleven gradients written)
+    _fields_ = [(n, c_void_p) for n in ("h_kernel", "h_bias", "h2_kernel", "h2_bias", "out_kernel", "out_bias", "hyper_w_1",
+                                        "hyper_w_final", "hyper_b_1", "hyper_b_final_l1", "hyper_b_final")]
+
+
+class QmixLearnerRows(ctypes.Structure):
+    _fields_ = ([("td_f64", c_int32), ("reserved", c_int32)]
+                + [(n, c_void_p) for n in ("obs_others", "v_obs", "goals", "actions", "state", "td", "loss", "q_tot")]
+                + [("n_steps", c_int64)])
+
+
+class AdamSegment(ctypes.Structure):
+    _fields_ = [("var", c_void_p), ("grad", c_void_p), ("m", c_void_p), ("v", c_void_p), ("count", c_int64)]
+
+
+class AdamDesc(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("epsilon", ctypes.c_float),
+                ("n_segments", c_int32), ("reserved", c_int32), ("total", c_int64)]
+
+
 class QmixMixerCheckersDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("n_agents", "embed_dim", "grid_h", "grid_w", "grid_c", "conv_f", "conv_kh", "conv_kw")]
 
@@ -415,6 +440,10 @@ SYMBOLS = {
     "cm3_qmix_mixer_particle_packed_bytes": (c_size_t, [c_int32]),
     "cm3_qmix_mixer_particle_pack": (ctypes.c_int, [P(QmixMixerParticleDesc), P(QmixMixerParticleWeights), c_void_p, c_void_p]),
     "cm3_qmix_mixer_particle_rows_f32": (ctypes.c_int, [P(QmixMixerParticleDesc), P(QmixMixerParticleWeights), P(QmixMixerRows), c_void_p]),
+    "cm3_qmix_learner_particle_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+    "cm3_qmix_learner_particle_grad_f32": (ctypes.c_int, [P(QmixLearnerParticleDesc), P(QmixLearnerTensors), P(QmixLearnerTensors),
+                                                          P(QmixLearnerRows), c_void_p, c_size_t, c_void_p]),
+    "cm3_adam_step_f32": (ctypes.c_int, [P(AdamDesc), c_void_p, c_void_p, c_void_p]),
     "cm3_qmix_mixer_checkers_packed_bytes": (c_size_t, [c_int32]),
     "cm3_qmix_mixer_checkers_pack": (ctypes.c_int, [P(QmixMixerCheckersDesc), P(QmixMixerCheckersWeights), c_void_p, c_void_p]),
     "cm3_qmix_mixer_checkers_rows_f32": (ctypes.c_int, [P(QmixMixerCheckersDesc), P(QmixMixerCheckersWeights), P(QmixMixerCheckersRows),

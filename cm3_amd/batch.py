@@ -1243,7 +1243,7 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, ke
 
 
 def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="particle", target_mixer=None, keep=None,
-                          mixer_q_agent=None):
+                          mixer_q_agent=None, learner=None):
     """The data side of the QMIX train_step (alg_qmix.py:338-380) from the columns of a sampled particle batch: builds, in the
     reference's order, the feed_dict of its four sess.run calls -- ["argmax_Q_target"], ["mixer_target"], ["mixer_op"],
     ["list_update_target_ops"] -- and returns the list of (ops, feed).  ``run(ops, feed)`` plays sess.run as in train_step_feeds: ops
@@ -1286,8 +1286,18 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     CheckersQmixAgent as mixer_q_agent to evaluate exactly that: one more greedy_rows launch on the main agent, its Q gathered at the
     target's argmax.  A `run` that plays the reference's session computes the same inside sess.run(mixer_target).
 
+    learner (particle only): a cm3_amd.qmix.ParticleQmixLearner on the main agent and mixer.  The ["mixer_op"] entry is still recorded
+    in its place with its keys, but `run` is NOT called for it: ``learner.step(cols, td_target)`` computes loss and gradients and
+    applies Adam to the main networks on the device, so `run` is left with list_update_target_ops alone (the caller's two
+    soft_update_from calls, as above; ParticleQmixLearner.train_step does the whole step with no `run`).  It needs target_agent and
+    target_mixer (the TD target must be on the device) and a learner whose agent count is the batch's; env="checkers" refuses it:
+    the Checkers learner is not built.  Without learner nothing changes.
+
     keep: an optional list that receives the int32 action temporaries the one-hot tiling launch reads -- whoever captures this
     function's launches into a hipGraph holds them for as long as the graph is replayed."""
+    if env == "checkers" and learner is not None:
+        raise ValueError("qmix_train_step_feeds: env='checkers' takes no learner: the Checkers learner is not built; call without "
+                         "learner and `run` answers mixer_op")
     if env == "checkers":
         return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer, mixer_q_agent)
     if env != "particle":
@@ -1295,6 +1305,13 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     if mixer_q_agent is not None:
         raise ValueError("qmix_train_step_feeds: mixer_q_agent belongs to env='checkers'; the particle graph builds mixer_target on the "
                          "target agents' Q values (alg_qmix.py:113), leave it out")
+    if learner is not None:
+        if target_agent is None or target_mixer is None:
+            raise ValueError("qmix_train_step_feeds: learner trains on the device TD target; pass target_agent and target_mixer (the "
+                             "Agent_target / Mixer_target objects) as well")
+        if learner.agent.n != cols["v_global"].shape[1]:
+            raise ValueError("qmix_train_step_feeds: learner is built for %d agents, the batch has %d"
+                             % (learner.agent.n, cols["v_global"].shape[1]))
     if target_mixer is not None:
         from .qmix import ParticleQmixMixer
         n_batch = cols["v_global"].shape[1]
@@ -1343,6 +1360,8 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
         target = qmix_td_target(cols["reward_local"].reshape(B, N), q_tot, cols["done"], gamma)
     # ---- optimiser step of the main mixer, soft update (:371-380) ----
     call(["mixer_op"], {"v_state": state, "v_goal_all": goals_all, "actions_1hot": actions_1hot, "obs_others": obs_others,
-                        "v_obs": v_local, "v_goal": goals_self, "td_target": target})
+                        "v_obs": v_local, "v_goal": goals_self, "td_target": target}, launch=learner is None)
+    if learner is not None:
+        learner.step(cols, target, keep=keep)
     call(["list_update_target_ops"], {})
     return call.calls

@@ -16,9 +16,10 @@ ignored, so ``{v.name: sess.run(v)}`` of either scope loads unchanged.  The netw
 (a float64 env's observation is rounded to float32 as the inputs are staged, as the reference's tf.float32 placeholders do).
 
 Exploration draws come from the build's own Philox stream (csrc/actor.hip, kPurposeExplore): the same law as the reference's
-np.random calls, not the same numbers.  The learner stays on the reference's side; both agents serve a
+np.random calls, not the same numbers.  The Checkers learner stays on the reference's side; both agents serve a
 learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from, and ParticleQmixMixer /
-CheckersQmixMixer (below) evaluate the target mixer -- mixer_target and the TD target -- on the same rows.  soft_update_from and the
+CheckersQmixMixer (below) evaluate the target mixer -- mixer_target and the TD target -- on the same rows; ParticleQmixLearner (at
+the end) is the particle learner itself: loss, gradients and Adam on the device.  soft_update_from and the
 weight loading are cm3_amd._net._DeviceNet's (the agent and mixer halves of list_update_target_ops, alg_qmix.py:135-156,
 alg_qmix_checkers.py:128-130); CheckersQmixAgent shares descriptor and launch bodies with CheckersActor (actor._CheckersPolicyNet).
 """
@@ -340,7 +341,7 @@ class ParticleQmixMixer(_DeviceNet):
           (alg_qmix.py:358-369)                                        (ONE launch of cm3_qmix_mixer_particle_rows_f32)
         the mixer half of list_update_target_ops (:139-156)          mixer.soft_update_from(main_mixer, tau)
 
-    The forward pass only: the main mixer's loss, gradient and optimiser step stay the session's.  Weights stay
+    The forward pass only: the main mixer's loss, gradient and optimiser step are ParticleQmixLearner's (below), or a session's.  Weights stay
     float32 [in][out] as TensorFlow shapes them, in ``self.w`` under the short names of MIXER_NAMES, so a session that trains the
     main mixer can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors, capturable)
     then makes the next launch follow them.  The prefixes "Mixer_main/", "Mixer_target/" and a ":0" suffix of the keys are ignored."""
@@ -528,3 +529,167 @@ class CheckersQmixMixer(_DeviceNet):
         _keep(keep, gr, ve, go, aq, rw, dn, *out.values())
         self.enqueue(B, gr, ve, go, aq, rw, dn, 0.0 if gamma is None else gamma, **out)
         return out
+
+
+# ---- the particle learner -------------------------------------------------------------------------------------------------------------
+_LEARNER_FIELDS = {"h/kernel": "h_kernel", "h/bias": "h_bias", "h2/kernel": "h2_kernel", "h2/bias": "h2_bias", "out/kernel": "out_kernel",
+                   "out/bias": "out_bias", "w1": "hyper_w_1", "w_final": "hyper_w_final", "b1": "hyper_b_1",
+                   "b_final_l1": "hyper_b_final_l1", "b_final": "hyper_b_final"}
+_GUARD = 64          # floats left untouched after every gradient tensor and after the workspace's used part
+
+
+class ParticleQmixLearner(object):
+    """mixer_op of the reference's particle QMIX on the device: loss, gradients and tf.train.AdamOptimizer's step, no session.
+
+        reference                                                    here
+        ---------------------------------------------------------   -----------------------------------------------
+        self.loss_mixer, self.mixer_op = AdamOptimizer(lr)           ParticleQmixLearner(agent, mixer, lr)
+          .minimize(loss) (alg_qmix.py:186-192)                        agent / mixer: the Agent_main / Mixer_main objects
+        sess.run(self.mixer_op, feed) (:371-378)                     learner.step(cols, td_target) -> loss
+        the whole of train_step (:338-380)                           learner.train_step(cols, gamma, target_agent, target_mixer, tau)
+
+    agent is the main ParticleQmixAgent, mixer the main ParticleQmixMixer, for one agent count on one device.  The learner owns the
+    Adam moments ``m`` / ``v`` and the gradient tensors ``grads`` (TF-shaped float32, under the short names of NAMES and MIXER_NAMES),
+    the two power scalars ``powers`` (device memory, advanced by every Adam launch, as TF keeps beta1_power / beta2_power) and a
+    persistent workspace sized for max_batch transitions; a larger batch grows it, outside of a capture only.  step() trains
+    ``agent.w`` / ``mixer.w`` in place and repacks both, so the next launch of either follows the new weights.  Not a _DeviceNet: it
+    holds no weights of its own and none of the launch-hook names cm3_amd.rollout dispatches on."""
+
+    def __init__(self, agent, mixer, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8, max_batch=128):
+        if not isinstance(agent, ParticleQmixAgent) or not isinstance(mixer, ParticleQmixMixer):
+            raise Cm3Error("ParticleQmixLearner takes the main ParticleQmixAgent and the main ParticleQmixMixer, got %s and %s: build "
+                           "them from the Agent_main / Mixer_main variables" % (type(agent).__name__, type(mixer).__name__))
+        if agent.n != mixer.n:
+            raise Cm3Error("ParticleQmixLearner: the agent is built for %d agents, the mixer for %d; build both for one agent count"
+                           % (agent.n, mixer.n))
+        if agent.device != mixer.device:
+            raise Cm3Error("ParticleQmixLearner: the agent is on %s, the mixer on %s; build both on one device" % (agent.device, mixer.device))
+        self.agent, self.mixer = agent, mixer
+        self.n, self.device = agent.n, agent.device
+        self.lr, self.beta1, self.beta2, self.epsilon = float(lr), float(beta1), float(beta2), float(epsilon)
+        self._lib = _lib.lib()
+        self.w = dict(agent.w)
+        self.w.update(mixer.w)
+        # one allocation for the gradients: every tensor 16-byte aligned with _GUARD floats after it
+        offsets, at = {}, 0
+        for name, t in self.w.items():
+            offsets[name] = at
+            at += (t.numel() + 3) // 4 * 4 + _GUARD
+        self._grad_store = torch.zeros(at, dtype=torch.float32, device=self.device)
+        self.grads = {name: self._grad_store[offsets[name]:offsets[name] + t.numel()].view(t.shape) for name, t in self.w.items()}
+        self.m = {name: torch.zeros_like(t) for name, t in self.w.items()}
+        self.v = {name: torch.zeros_like(t) for name, t in self.w.items()}
+        self._state = torch.tensor([self.beta1, self.beta2, 0.0, 0.0], dtype=torch.float32, device=self.device)
+        self.powers = self._state[:2]
+        self._wt, self._gt = _lib.QmixLearnerTensors(), _lib.QmixLearnerTensors()
+        for name, field in _LEARNER_FIELDS.items():
+            setattr(self._wt, field, self.w[name].data_ptr())
+            setattr(self._gt, field, self.grads[name].data_ptr())
+        table = [[self.w[k].data_ptr(), self.grads[k].data_ptr(), self.m[k].data_ptr(), self.v[k].data_ptr(), self.w[k].numel()]
+                 for k in self.w]
+        self._segments = torch.tensor(table, dtype=torch.int64, device=self.device)
+        self._adam = _lib.AdamDesc()
+        self._adam.lr, self._adam.beta1, self._adam.beta2, self._adam.epsilon = self.lr, self.beta1, self.beta2, self.epsilon
+        self._adam.n_segments, self._adam.total = len(table), sum(row[4] for row in table)
+        self.max_batch, self._workspace = 0, None
+        self._reserve(int(max_batch))
+
+    def workspace_floats(self, batch):
+        """Floats of the workspace the gradient launches use for `batch` transitions (cm3_qmix_learner_particle_workspace_bytes)."""
+        nbytes = self._lib.cm3_qmix_learner_particle_workspace_bytes(self.n, int(batch))
+        if nbytes == 0:
+            raise Cm3Error("ParticleQmixLearner: a batch of %d transitions is out of range" % int(batch))
+        return nbytes // 4
+
+    def _reserve(self, batch):
+        if batch <= self.max_batch:
+            return
+        need = self.workspace_floats(batch)
+        if torch.cuda.is_current_stream_capturing():
+            raise Cm3Error("ParticleQmixLearner: a batch of %d transitions needs a larger workspace than max_batch=%d reserved, and a "
+                           "capture cannot allocate; build the learner with max_batch >= %d" % (batch, self.max_batch, batch))
+        self._workspace = torch.zeros(need + _GUARD, dtype=torch.float32, device=self.device)
+        self.max_batch = batch
+
+    def _desc(self):
+        d = _lib.QmixLearnerParticleDesc()
+        d.n_agents, d.n_h, d.n_actions, d.embed_dim = self.n, H, N_ACTIONS, EMBED
+        return d
+
+    def _stage(self, cols, td_target, keep):
+        vg = cols["v_global"]
+        if vg.dim() != 3 or vg.shape[1] != self.n or vg.shape[2] != 4 or vg.shape[0] == 0:
+            raise Cm3Error("ParticleQmixLearner for %d agents takes v_global [B, %d, 4], got %s" % (self.n, self.n, tuple(vg.shape)))
+        B, N, L = int(vg.shape[0]), self.n, self.agent.L
+        f32 = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()      # noqa: E731
+        want = {"obs_others": (B, N, L), "v_local": (B, N, 4), "goals": (B, N, 2), "actions": (B, N)}
+        for name, shape in want.items():
+            if tuple(cols[name].shape) != shape:
+                raise Cm3Error("ParticleQmixLearner takes %s %s, got %s" % (name, list(shape), tuple(cols[name].shape)))
+        if td_target.numel() != B:
+            raise Cm3Error("ParticleQmixLearner takes td_target [B] for %d time steps, got %s" % (B, tuple(td_target.shape)))
+        td = td_target.reshape(-1).to(device=self.device,
+                                      dtype=td_target.dtype if td_target.dtype == torch.float32 else torch.float64).contiguous()
+        staged = (f32(cols["obs_others"]), f32(cols["v_local"]), f32(cols["goals"]),
+                  cols["actions"].to(device=self.device, dtype=torch.int32).contiguous(), f32(vg), td)
+        _keep(keep, *staged)
+        return (B,) + staged
+
+    def enqueue_gradients(self, B, obs_others, v_local, goals, actions, v_global, td, loss, q_tot, stream=None):
+        """Raw launches of cm3_qmix_learner_particle_grad_f32 on contiguous device tensors (float32 columns, int32 actions, float32 or
+        float64 td [B]); loss float32 [1], q_tot float32 [B]."""
+        self._reserve(B)
+        r = _lib.QmixLearnerRows()
+        r.td_f64 = 1 if td.dtype == torch.float64 else 0
+        r.obs_others, r.v_obs, r.goals, r.actions = _lib.ptr(obs_others), _lib.ptr(v_local), _lib.ptr(goals), _lib.ptr(actions)
+        r.state, r.td, r.loss, r.q_tot = _lib.ptr(v_global), _lib.ptr(td), _lib.ptr(loss), _lib.ptr(q_tot)
+        r.n_steps = int(B)
+        d = self._desc()
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_qmix_learner_particle_grad_f32(
+            ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(self._gt), ctypes.byref(r), self._workspace.data_ptr(),
+            (self._workspace.numel() - _GUARD) * 4, s))
+
+    def enqueue_adam(self, stream=None):
+        """Raw launch of cm3_adam_step_f32 over the eleven tensors on whatever ``grads`` holds; advances ``powers``."""
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_adam_step_f32(ctypes.byref(self._adam), self._segments.data_ptr(), self._state.data_ptr(), s))
+
+    def gradients(self, cols, td_target, keep=None):
+        """Loss and gradients of mixer_op's loss on the columns of a sampled batch (sample_batch / as_reference_batch(numpy=False);
+        float64 columns are rounded to float32) and td_target [B] (float64 is rounded as it is read, as the tf.float32 placeholder
+        rounds its feed).  Returns {"loss": float32 [1], "q_tot": float32 [B, 1], "grads": {short name: tensor}}; the gradient tensors
+        are the learner's own and hold the latest call's values.  Changes no weight, moment or power.  keep: an optional list that
+        receives the staged inputs and the outputs, for whoever captures the launches."""
+        B, oo, vl, go, ac, vg, td = self._stage(cols, td_target, keep)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        q_tot = torch.empty(B, 1, dtype=torch.float32, device=self.device)
+        _keep(keep, loss, q_tot)
+        self.enqueue_gradients(B, oo, vl, go, ac, vg, td, loss, q_tot)
+        return {"loss": loss, "q_tot": q_tot, "grads": self.grads}
+
+    def step(self, cols, td_target, keep=None):
+        """sess.run(mixer_op): the launches of gradients(), then ONE Adam launch on agent.w / mixer.w in place, then both repack()s.
+        Returns the loss tensor float32 [1] (of the weights before the step, as the session evaluates it)."""
+        out = self.gradients(cols, td_target, keep)
+        self.enqueue_adam()
+        self.agent.repack()
+        self.mixer.repack()
+        return out["loss"]
+
+    def train_step(self, cols, gamma, target_agent, target_mixer, tau, keep=None):
+        """The whole of alg_qmix.train_step (alg_qmix.py:338-380) with no `run`: the target agents' argmax Q on the next
+        observations (target_agent.greedy_rows), the target mixer's q_tot and the TD target (target_mixer.q_tot), step(), then the
+        soft updates of both target networks (list_update_target_ops).  Returns the loss tensor."""
+        vg = cols["v_global"]
+        B, N = vg.shape[0], vg.shape[1]
+        rows = lambda x: x.reshape(B * N, -1)      # noqa: E731
+        greedy = target_agent.greedy_rows(rows(cols["obs_others_next"]), rows(cols["v_local_next"]), rows(cols["goals"]), onehot=False,
+                                          q_max=True)
+        td = target_mixer.q_tot(cols["v_global_next"], cols["goals"], greedy["q_max"].reshape(B, N), cols["reward_local"].reshape(B, N),
+                                cols["done"], gamma, keep=keep)["td"]
+        _keep(keep, *greedy.values())
+        loss = self.step(cols, td, keep)
+        target_agent.soft_update_from(self.agent, tau)
+        target_mixer.soft_update_from(self.mixer, tau)
+        return loss

@@ -72,6 +72,9 @@ extern "C" {
                                   additive.
                                   cm3_qmix_mixer_checkers_packed_bytes / _pack / _rows_f32 (the Checkers QMIX mixer over transition rows
                                   with the TD target: mixer_target of alg_qmix_checkers.train_step); additive.
+                                  cm3_qmix_learner_particle_workspace_bytes / _grad_f32 (loss and the eleven dense gradients of mixer_op of
+                                  alg_qmix.train_step) and cm3_adam_step_f32 (tf.train.AdamOptimizer's step over a table of tensors, its
+                                  two powers kept on the device): the first train step that needs no session; additive.
                                   cm3_value_particle_packed_bytes / _pack / _rows_f32 and cm3_coma_particle_packed_bytes / _pack /
                                   _rows_f32 (the IAC / COMA baseline critics V_particle_local, V_particle_global and Q_global over
                                   transition rows, with the TD targets: the evaluations of alg_baseline.train_step that carry no
@@ -995,6 +998,92 @@ int cm3_qmix_mixer_particle_pack(const cm3_qmix_mixer_particle_desc *desc, const
  * launch k_qmix_mixer_rows<f32,N=..>. */
 int cm3_qmix_mixer_particle_rows_f32(const cm3_qmix_mixer_particle_desc *desc, const cm3_qmix_mixer_particle_weights *weights,
                                      const cm3_qmix_mixer_rows *rows, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The particle QMIX learner (part of ABI 9, additive): mixer_op of alg_qmix.train_step (alg_qmix.py:186-192, 371-378) -- the loss
+ * mean((float32(td_target) - q_tot)^2) and its dense gradients for the six variables of Agent_main (networks.Qmix_single_particle,
+ * shared by the agents: their gradient sums over the B N agent rows) and the five of Mixer_main (networks.Qmix_mixer), in float32,
+ * with TensorFlow's conventions at the kinks (ReluGrad passes where the input is > 0, d|x|/dx = sign(x) with 0 at 0, EluGrad below
+ * zero is elu + 1).  Five launches on the given stream, every one capturable; no floating-point atomics: every output element is
+ * summed in an order fixed by the row count alone (csrc/learner.hip), so two calls on the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_agents;   /* 1..CM3_MAX_AGENTS */
+  int32_t n_h;        /* 64: both hidden widths of Qmix_single_particle */
+  int32_t n_actions;  /* 5 */
+  int32_t embed_dim;  /* 64 */
+} cm3_qmix_learner_particle_desc;
+
+/* The eleven tensors, float32 row-major as the TF variables are shaped -- the weights read, or the gradients written (dense, every
+ * element).  With L = 4 max(N - 1, 1), K = 6 N: */
+typedef struct {
+  float *h_kernel;          /* Agent_main/h/kernel    [L + 6][64] */
+  float *h_bias;            /* Agent_main/h/bias      [64] */
+  float *h2_kernel;         /* Agent_main/h2/kernel   [64][64] */
+  float *h2_bias;           /* Agent_main/h2/bias     [64] */
+  float *out_kernel;        /* Agent_main/out/kernel  [64][5] */
+  float *out_bias;          /* Agent_main/out/bias    [5] */
+  float *hyper_w_1;         /* Mixer_main/hyper_w_1   [K][64 N] */
+  float *hyper_w_final;     /* Mixer_main/hyper_w_final            [K][64] */
+  float *hyper_b_1;         /* Mixer_main/hyper_b_1                [K][64] */
+  float *hyper_b_final_l1;  /* Mixer_main/hyper_b_final_l1/kernel  [K][64] */
+  float *hyper_b_final;     /* Mixer_main/hyper_b_final/kernel     [64][1] */
+} cm3_qmix_learner_tensors;
+
+/* The columns of a batch of n_steps transitions (B) of N agents, and the two outputs beside the gradients.  The agent rows are the
+ * columns viewed [B N, .]; an action outside 0..4 selects no Q value (q_selected 0, no gradient into that row). */
+typedef struct {
+  int32_t td_f64;           /* td holds float64 (rounded to float32 as it is read: the td_target placeholder is tf.float32), else float32 */
+  int32_t reserved;         /* 0 */
+  const float *obs_others;  /* [B][N][L], 16-byte aligned */
+  const float *v_obs;       /* [B][N][4] v_local, 16-byte aligned */
+  const float *goals;       /* [B][N][2],  8-byte aligned: the agents' goal and the mixer's goals_all */
+  const int32_t *actions;   /* [B][N] the actions taken */
+  const float *state;       /* [B][N][4] v_global, 16-byte aligned */
+  const void *td;           /* [B] the TD target */
+  float *loss;              /* [1] */
+  float *q_tot;             /* [B]: the bits cm3_qmix_mixer_particle_rows_f32 computes from the same weights and Q values */
+  int64_t n_steps;
+} cm3_qmix_learner_rows;
+
+/* Bytes of scratch cm3_qmix_learner_particle_grad_f32 takes for this agent count and batch (csrc/learner.hip: the inputs and
+ * activations of the rows, the deltas, one partial gradient per 256 rows); grows with n_steps.  0 for an agent count outside 1..10
+ * or n_steps outside 1..(2^31 - 1) / 10. */
+size_t cm3_qmix_learner_particle_workspace_bytes(int32_t n_agents, int64_t n_steps);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device, in this order: null desc, n_agents outside
+ * 1..10, other widths than 64 / 5 / 64; null weights / grads / rows, a missing tensor, input, output or workspace, a misaligned
+ * pointer; n_steps <= 0 or above (2^31 - 1) / 10, a workspace smaller than cm3_qmix_learner_particle_workspace_bytes().  Changes
+ * nothing but grads, loss, q_tot and the workspace.  cm3_last_kernel_variant() names the last launch, k_qmix_learner_reduce<f32,N=..,after=fwd+mixer+bwd+xtd>,
+ * and so the four before it. */
+int cm3_qmix_learner_particle_grad_f32(const cm3_qmix_learner_particle_desc *desc, const cm3_qmix_learner_tensors *weights,
+                                       const cm3_qmix_learner_tensors *grads, const cm3_qmix_learner_rows *rows, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+
+/* tf.train.AdamOptimizer's step (TF1: epsilon OUTSIDE the bias correction -- not torch.optim.Adam's formula) in float32 over a table
+ * of tensors, ONE launch:
+ *   lr_t = lr sqrt(1 - beta2_power) / (1 - beta1_power);  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   var = var - lr_t m / (sqrt(v) + epsilon)
+ * state: 16 bytes of device memory, 8-byte aligned, {float beta1_power, float beta2_power, uint32 0, uint32 0}, set up once with the
+ * powers at beta1 and beta2 (as TF initialises beta1_power / beta2_power).  The launch reads the powers and leaves them multiplied by
+ * beta1 / beta2, so a replayed hipGraph takes the next step.  Launches that share a state must be ordered on the device. */
+typedef struct {
+  float *var;         /* updated in place */
+  const float *grad;
+  float *m, *v;       /* the two moments, updated in place (zeros before the first step) */
+  int64_t count;      /* elements */
+} cm3_adam_segment;
+
+typedef struct {
+  float lr, beta1, beta2, epsilon;
+  int32_t n_segments;
+  int32_t reserved;   /* 0 */
+  int64_t total;      /* the sum of the segments' counts: sizes the grid */
+} cm3_adam_desc;
+
+/* segments: a DEVICE array of desc->n_segments cm3_adam_segment, 8-byte aligned.  CM3_ERR_INVALID before anything touches the device,
+ * in this order: null desc, a learning rate that is no number, a beta outside [0, 1), epsilon <= 0, n_segments < 1; null segments /
+ * state, a misaligned pointer; total < 1.  cm3_last_kernel_variant() names the launch k_adam_step<f32,..>. */
+int cm3_adam_step_f32(const cm3_adam_desc *desc, const cm3_adam_segment *segments, void *state, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The Checkers QMIX mixer over TRANSITION rows (part of ABI 9, additive): networks.Qmix_mixer_checkers (networks.py:688-734) at the
