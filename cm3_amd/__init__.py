@@ -53,4 +53,7 @@ def __getattr__(name):
     if name == "CheckersQmixMixer":
         from .qmix import CheckersQmixMixer
         return CheckersQmixMixer
+    if name == "CheckersQmixLearner":
+        from .qmix import CheckersQmixLearner
+        return CheckersQmixLearner
     raise AttributeError(name)

@@ -371,6 +371,18 @@ class ActorCheckersWeights(ctypes.Structure):
                                         "others_w", "others_b", "w_others_h2", "b_h2", "out_w", "out_b", "packed")]
 
 
+class QmixLearnerCheckersDesc(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("n_agents", "conv_f", "n_conv_linear", "n_h1", "n_h2", "n_actions", "embed_dim", "mixer_conv_f")]
+
+
+class QmixLearnerCheckersRows(ctypes.Structure):
+    # (cm3_qmix_learner_checkers_rows: the columns in the forms the Checkers rows kernels read, and loss / q_tot)
+    _fields_ = ([(n, c_int32) for n in ("obs_self_t_f64", "grid_f64", "goals_onehot", "td_f64")]
+                + [(n, c_void_p) for n in ("obs_self_t", "obs_self_v", "obs_others", "actions_prev", "actions", "goals", "grid", "vec",
+                                           "td", "loss", "q_tot")]
+                + [("n_steps", c_int64)])
+
+
 class ActorCheckersBufs(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("obs_self_t", "obs_self_v", "obs_others", "goals", "actions_prev", "steps",
                                         "episode", "actions", "probs", "prev_done", "epsilon_dev")]
@@ -444,6 +456,10 @@ SYMBOLS = {
     "cm3_qmix_learner_particle_grad_f32": (ctypes.c_int, [P(QmixLearnerParticleDesc), P(QmixLearnerTensors), P(QmixLearnerTensors),
                                                           P(QmixLearnerRows), c_void_p, c_size_t, c_void_p]),
     "cm3_adam_step_f32": (ctypes.c_int, [P(AdamDesc), c_void_p, c_void_p, c_void_p]),
+    "cm3_qmix_learner_checkers_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+    "cm3_qmix_learner_checkers_grad_f32": (ctypes.c_int, [P(QmixLearnerCheckersDesc), P(ActorCheckersWeights), P(QmixMixerCheckersWeights),
+                                                          P(ActorCheckersWeights), P(QmixMixerCheckersWeights),
+                                                          P(QmixLearnerCheckersRows), c_void_p, c_size_t, c_void_p]),
     "cm3_qmix_mixer_checkers_packed_bytes": (c_size_t, [c_int32]),
     "cm3_qmix_mixer_checkers_pack": (ctypes.c_int, [P(QmixMixerCheckersDesc), P(QmixMixerCheckersWeights), c_void_p, c_void_p]),
     "cm3_qmix_mixer_checkers_rows_f32": (ctypes.c_int, [P(QmixMixerCheckersDesc), P(QmixMixerCheckersWeights), P(QmixMixerCheckersRows),

@@ -1165,8 +1165,21 @@ def _onehot_rows(columns, l_action, device, keep=None):
     return out
 
 
-def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer=None, mixer_q_agent=None):
+def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer=None, mixer_q_agent=None, learner=None):
     """The Checkers form of qmix_train_step_feeds (alg_qmix_checkers.py:342-393)."""
+    if learner is not None:
+        # (before any column is read: the type; then what the learner needs beside it)
+        from .qmix import CheckersQmixLearner
+        if not isinstance(learner, CheckersQmixLearner):
+            raise ValueError("qmix_train_step_feeds: env='checkers' takes a CheckersQmixLearner as learner, got %s: the Checkers learner is "
+                             "not built from another network's weights; build a CheckersQmixLearner on the main CheckersQmixAgent and "
+                             "CheckersQmixMixer, or call without learner and `run` answers mixer_op" % type(learner).__name__)
+        if target_agent is None or target_mixer is None:
+            raise ValueError("qmix_train_step_feeds: learner trains on the device TD target; pass target_agent and target_mixer (the "
+                             "Agent_target / Mixer_target objects) as well")
+        if learner.agent.n != cols["vec"].shape[1]:
+            raise ValueError("qmix_train_step_feeds: learner is built for %d agents, the batch has %d"
+                             % (learner.agent.n, cols["vec"].shape[1]))
     if target_mixer is not None:
         # (what needs no column comes first: the type, the target agent; then the batch's agent count and where its columns live)
         from .qmix import CheckersQmixMixer
@@ -1237,7 +1250,9 @@ def _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, ke
     # ---- optimiser step of the main mixer, soft update (:381-393) ----
     call(["mixer_op"], {"state_env": cols["grid"], "v_state": state_agents, "v_goal_all": goals_all, "actions_1hot": actions_1hot,
                         "actions_prev": actions_prev_1hot, "obs_others": obs_others, "obs_self_t": obs_self_t,
-                        "obs_self_v": obs_self_v, "v_goal": goals_self, "td_target": target})
+                        "obs_self_v": obs_self_v, "v_goal": goals_self, "td_target": target}, launch=learner is None)
+    if learner is not None:
+        learner.step(cols, target, keep=keep)
     call(["list_update_target_ops"], {})
     return call.calls
 
@@ -1286,20 +1301,18 @@ def qmix_train_step_feeds(cols, run, gamma, target_agent=None, l_action=5, env="
     CheckersQmixAgent as mixer_q_agent to evaluate exactly that: one more greedy_rows launch on the main agent, its Q gathered at the
     target's argmax.  A `run` that plays the reference's session computes the same inside sess.run(mixer_target).
 
-    learner (particle only): a cm3_amd.qmix.ParticleQmixLearner on the main agent and mixer.  The ["mixer_op"] entry is still recorded
+    learner: a cm3_amd.qmix.ParticleQmixLearner (env="checkers": a CheckersQmixLearner) on the main agent and mixer.  The ["mixer_op"] entry is still recorded
     in its place with its keys, but `run` is NOT called for it: ``learner.step(cols, td_target)`` computes loss and gradients and
     applies Adam to the main networks on the device, so `run` is left with list_update_target_ops alone (the caller's two
     soft_update_from calls, as above; ParticleQmixLearner.train_step does the whole step with no `run`).  It needs target_agent and
-    target_mixer (the TD target must be on the device) and a learner whose agent count is the batch's; env="checkers" refuses it:
-    the Checkers learner is not built.  Without learner nothing changes.
+    target_mixer (the TD target must be on the device) and a learner whose agent count is the batch's; env="checkers" refuses
+    anything but a CheckersQmixLearner, before a column is read (the Checkers learner is not built from another network's weights;
+    CheckersQmixLearner.train_step is this function with mixer_q_agent=learner.agent).  Without learner nothing changes.
 
     keep: an optional list that receives the int32 action temporaries the one-hot tiling launch reads -- whoever captures this
     function's launches into a hipGraph holds them for as long as the graph is replayed."""
-    if env == "checkers" and learner is not None:
-        raise ValueError("qmix_train_step_feeds: env='checkers' takes no learner: the Checkers learner is not built; call without "
-                         "learner and `run` answers mixer_op")
     if env == "checkers":
-        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer, mixer_q_agent)
+        return _qmix_train_step_feeds_checkers(cols, run, gamma, target_agent, l_action, keep, target_mixer, mixer_q_agent, learner)
     if env != "particle":
         raise ValueError("qmix_train_step_feeds: env must be 'particle' or 'checkers', got %r" % (env,))
     if mixer_q_agent is not None:

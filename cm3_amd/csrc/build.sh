@@ -58,6 +58,11 @@ pids+=($!)
 "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/learner.hip" -o "${OBJ}/learner.o" 2> "${OBJ}/learner.resource_usage.txt" \
   || { grep -v "remark:" "${OBJ}/learner.resource_usage.txt" >&2; exit 1; } &
 pids+=($!)
+# the Checkers QMIX learner (learner_checkers.hip: the same for the Checkers networks, on the kernels of learner_common.h), likewise;
+# tests/test_qmix_learner_checkers_abi.py holds the unit to the same no-inline-assembly rule.
+"${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_SOURCE_ID="\"${SRC_ID}\"" -Rpass-analysis=kernel-resource-usage -c "${HERE}/learner_checkers.hip" -o "${OBJ}/learner_checkers.o" 2> "${OBJ}/learner_checkers.resource_usage.txt" \
+  || { grep -v "remark:" "${OBJ}/learner_checkers.resource_usage.txt" >&2; exit 1; } &
+pids+=($!)
 # the one-launch policy episode once more for float64 envs (policy.hip: PolicyReal = double), with the same flags as the float32 build
 "${HIPCC}" ${FLAGS} ${PHYS} ${MFMA_FORM} -DCM3_PARTICLE_F64 -Rpass-analysis=kernel-resource-usage -c "${HERE}/policy.hip" -o "${OBJ}/policy_f64.o" 2> "${OBJ}/policy_f64.resource_usage.txt" \
   || { grep -v "remark:" "${OBJ}/policy_f64.resource_usage.txt" >&2; exit 1; } &
@@ -69,9 +74,9 @@ pids+=($!)
 pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
 # the matrix units' diagnostics went to their resource-usage files with the remarks: show what is not a remark
-for f in actor critic critic_checkers mixer baseline baseline_checkers learner actor_checkers policy policy_f64 policy_partial policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
+for f in actor critic critic_checkers mixer baseline baseline_checkers learner learner_checkers actor_checkers policy policy_f64 policy_partial policy_checkers; do grep -v "remark:" "${OBJ}/${f}.resource_usage.txt" | grep -E "warning|error" -A3 >&2 || true; done
 OBJS=("${OBJ}/particle_f32.o" "${OBJ}/particle_f32_ilp.o" "${OBJ}/particle_f64.o" "${OBJ}/checkers.o" "${OBJ}/util.o" "${OBJ}/advantage.o"
-      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/critic.o" "${OBJ}/critic_checkers.o" "${OBJ}/mixer.o" "${OBJ}/baseline.o" "${OBJ}/baseline_checkers.o" "${OBJ}/learner.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_partial.o"
+      "${OBJ}/batch.o" "${OBJ}/episode_route.o" "${OBJ}/actor.o" "${OBJ}/critic.o" "${OBJ}/critic_checkers.o" "${OBJ}/mixer.o" "${OBJ}/baseline.o" "${OBJ}/baseline_checkers.o" "${OBJ}/learner.o" "${OBJ}/learner_checkers.o" "${OBJ}/actor_checkers.o" "${OBJ}/policy.o" "${OBJ}/policy_f64.o" "${OBJ}/policy_partial.o"
       "${OBJ}/policy_checkers.o")
 if [ "${CM3_SKIP_ISA_LINT:-0}" != 1 ]; then
   python3 "${HERE}/../../tools/isa_lint.py" "${OBJS[@]}"     # (the objects of THIS build, not whatever else sits in ${OBJ})

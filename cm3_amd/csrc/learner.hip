@@ -31,14 +31,14 @@
 //      d h2_pre[u] = h2[u] > 0 ? d q_sel out/kernel[u][action] : 0       (one product: exact)
 //      d h1_pre[u] = h1[u] > 0 ? sum_v d h2_pre[v] h2/kernel[u][v] : 0   C[row][u], chain over v = 0 .. 63 from zero
 //    Leaves d Q padded to 16 columns, d h2_pre and d h1_pre.  LDS: [64][66] floats, 16 896 bytes.
-// 4. k_learner_xtd         the weight gradients X^T . Delta with the ROW index as the contraction, four jobs in one launch:
+// 4. k_learner_xtd<4>      (learner_common.h) the weight gradients X^T . Delta with the ROW index as the contraction, four jobs in one launch:
 //      h/kernel, h/bias     X = x,  Delta = d h1_pre        h2/kernel, h2/bias   X = h1, Delta = d h2_pre
 //      out/kernel, out/bias X = h2, Delta = d Q             the mixer's five     X = xm, Delta = the delta rows
 //    One wave per 16 x 16 output tile and per CHUNK of 256 consecutive rows: A[i][k] = X[row k][16 kt + i], B[k][j] =
 //    Delta[row k][16 mt + j], one chain from zero over the chunk's rows in ascending order, four rows per instruction.  A bias gradient
 //    (and hyper_b_final's, the column sums of p_bf) is one more row tile whose A operand is 1 in row 0: the same chain.  The chunk's
 //    tile goes to the workspace.  No LDS.
-// 5. k_learner_reduce      one thread per gradient element: the chunks' partial sums added in ascending chunk order, from the first,
+// 5. k_learner_reduce<4>   (learner_common.h) one thread per gradient element: the chunks' partial sums added in ascending chunk order, from the first,
 //    and stored TF-shaped.  Its last workgroup sums err2: thread t the rows t, t + 256, ... in ascending order from zero, then the 256
 //    partial sums by a halving tree in LDS (t with t + 128, then + 64, ...); loss = sum / B.
 // No floating-point atomics anywhere.  Chunks are cut by the row count alone, so every sum's order depends on the batch and on nothing
@@ -54,13 +54,13 @@
 // agent-scope add, so the store comes after every read).  A replayed graph therefore takes the next step.  Launches that share a state
 // must be ordered on the device.
 #include "actor_common.h"
+#include "learner_common.h"
 
 namespace cm3 {
 namespace learner {
 
 constexpr int kH = 64;          // both hidden widths of Qmix_single_particle
 constexpr int kE = 64;          // embed_dim of Qmix_mixer
-constexpr int kChunk = 256;     // rows per partial sum of a weight gradient
 
 template <int N> struct LL {
   static constexpr int L = 4 * (N > 1 ? N - 1 : 1);
@@ -231,18 +231,6 @@ struct MixParams {
   float *q_tot, *err2, *xm, *dhy, *dqs;         // [B], [B], [B][KMP], [B][MD], [B][N]
 };
 
-// moves inside a 16-lane DPP row: lane ^ 1, lane ^ 2, i <-> 7 - i inside each 8 lanes, i <-> 15 - i (mixer.hip's mix_sum16)
-template <int CTRL> __device__ __forceinline__ float lrn_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float lrn_sum16(float v) {
-  v = v + lrn_dpp<0xB1>(v);
-  v = v + lrn_dpp<0x4E>(v);
-  v = v + lrn_dpp<0x141>(v);
-  v = v + lrn_dpp<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float sign_f32(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
 
 // x . W[:, c0 + e] for this lane's e and four rows: one k-ordered chain from zero over the KMP inputs (zero operands past KM)
 template <int N> __device__ __forceinline__ f32x4 hyper_block(const float *W, int ld, int ce, int hi, const float (&xa)[LL<N>::SM]) {
@@ -440,110 +428,6 @@ __global__ void CM3_MATRIX_KERNEL k_learner_agent_bwd(const AgentBwdParams p) {
     }
 }
 
-// ---- 4. X^T . Delta per chunk of rows ---------------------------------------------------------------------------------------------
-struct XtdJob {
-  const float *X, *D;
-  float *P;                       // [chunks][(KT + 1) 16][16 MT]
-  size_t rows;
-  int ldx, Kx, KT, ldd, MT;
-  unsigned block0, groups;        // the job's first workgroup; workgroups per chunk: ceil((KT + 1) MT / 4)
-};
-struct XtdParams {
-  XtdJob job[4];
-};
-
-__global__ void CM3_MATRIX_KERNEL k_learner_xtd(const XtdParams p) {
-  const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, hi = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int j = 0;
-#pragma unroll
-  for (int i = 1; i < 4; ++i) j = blockIdx.x >= p.job[i].block0 ? i : j;
-  const XtdJob J = j == 0 ? p.job[0] : (j == 1 ? p.job[1] : (j == 2 ? p.job[2] : p.job[3]));
-  const unsigned local = blockIdx.x - J.block0;
-  const unsigned chunk = local / J.groups;
-  const int tiles_k = J.KT + 1, tiles = tiles_k * J.MT;
-  const int tile = (int)(local - chunk * J.groups) * 4 + w;
-  if (tile >= tiles) return;
-  const int kt = tile / J.MT, mt = tile - kt * J.MT;
-  const bool ones = kt == J.KT;
-  const int kx = 16 * kt + col, m = 16 * mt + col;
-  const bool kx_ok = !ones && kx < J.Kx;
-  const size_t r0 = (size_t)chunk * kChunk;
-  const size_t r1 = r0 + kChunk < J.rows ? r0 + kChunk : J.rows;
-  f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  for (size_t r = r0; r < r1; r += 4) {
-    const size_t rr = r + hi;
-    const bool ok = rr < r1;
-    const size_t rc = ok ? rr : r0;
-    float av = kx_ok ? J.X[rc * J.ldx + kx] : ((ones && col == 0) ? 1.0f : 0.0f);
-    float bv = J.D[rc * J.ldd + m];
-    av = ok ? av : 0.0f;
-    bv = ok ? bv : 0.0f;
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-  }
-  float *out = J.P + ((size_t)chunk * tiles_k * 16 + 16 * kt + 4 * hi) * (size_t)(16 * J.MT) + m;
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) out[(size_t)reg * (16 * J.MT)] = acc[reg];
-}
-
-// ---- 5. the chunks' sums, TF-shaped; the loss -------------------------------------------------------------------------------------
-struct RedSeg {
-  int col0, ncols;
-  float *w, *b;                   // [Kx][ncols] (or NULL), [ncols] from the ones row (or NULL)
-};
-struct RedJob {
-  const float *P;
-  size_t chunks;
-  int prow, pcol, Kx, ones_row, nseg;
-  unsigned e0;                    // the job's first element in the launch's flat index
-  RedSeg seg[5];
-};
-struct RedParams {
-  RedJob job[4];
-  unsigned total;
-  uint32_t B;
-  const float *err2;
-  float *loss;
-};
-
-__global__ void __launch_bounds__(256) k_learner_reduce(const RedParams p) {
-  const int tid = threadIdx.x;
-  if (blockIdx.x == gridDim.x - 1) {
-    __shared__ float sh[256];
-    float s = 0.0f;
-    for (uint32_t b = tid; b < p.B; b += 256) s = s + p.err2[b];
-    sh[tid] = s;
-    __syncthreads();
-    for (int stride = 128; stride > 0; stride >>= 1) {
-      if (tid < stride) sh[tid] = sh[tid] + sh[tid + stride];
-      __syncthreads();
-    }
-    if (tid == 0) p.loss[0] = sh[0] / (float)p.B;
-    return;
-  }
-  const unsigned idx = blockIdx.x * 256u + tid;
-  if (idx >= p.total) return;
-  int j = 0;
-#pragma unroll
-  for (int i = 1; i < 4; ++i) j = idx >= p.job[i].e0 ? i : j;
-  const RedJob &J = p.job[j];
-  const unsigned local = idx - J.e0;
-  const int kk = (int)(local / (unsigned)J.pcol), m = (int)(local - (unsigned)kk * J.pcol);
-  const bool is_ones = kk == J.ones_row;
-  if (!(kk < J.Kx || is_ones)) return;
-  float *dst = nullptr;
-  for (int s = 0; s < J.nseg; ++s) {
-    const RedSeg &g = J.seg[s];
-    if (m >= g.col0 && m < g.col0 + g.ncols) dst = is_ones ? (g.b ? g.b + (m - g.col0) : nullptr) : (g.w ? g.w + (size_t)kk * g.ncols + (m - g.col0) : nullptr);
-  }
-  if (!dst) return;
-  const size_t stride = (size_t)J.prow * J.pcol;
-  const float *src = J.P + (size_t)kk * J.pcol + m;
-  float s = src[0];
-  for (size_t c = 1; c < J.chunks; ++c) s = s + src[c * stride];
-  *dst = s;
-}
-
 template <int N> static int grad_launch(const cm3_qmix_learner_tensors *wt, const cm3_qmix_learner_tensors *g, const cm3_qmix_learner_rows *r,
                                         float *ws, hipStream_t s) {
   using T = LL<N>;
@@ -564,20 +448,13 @@ template <int N> static int grad_launch(const cm3_qmix_learner_tensors *wt, cons
     AgentBwdParams p = {R, r->actions, ws + o.dqs, ws + o.h1, ws + o.h2, wt->h2_kernel, wt->out_kernel, ws + o.dq16, ws + o.dh2, ws + o.dh1};
     hipLaunchKernelGGL(k_learner_agent_bwd, dim3(row_blocks), dim3(256), 0, s, p);
   }
-  XtdParams x;
-  RedParams d;
+  XtdParams<4> x;
+  RedParams<4> d;
   memset(&x, 0, sizeof(x));
   memset(&d, 0, sizeof(d));
   unsigned blocks = 0, elems = 0;
   auto job = [&](int i, const float *X, int ldx, int Kx, const float *D, int ldd, size_t rows, size_t chunks, float *P) {
-    XtdJob &J = x.job[i];
-    J.X = X; J.D = D; J.P = P; J.rows = rows; J.ldx = ldx; J.Kx = Kx; J.KT = (Kx + 15) / 16; J.ldd = ldd; J.MT = ldd / 16;
-    J.block0 = blocks;
-    J.groups = (unsigned)(((J.KT + 1) * J.MT + 3) / 4);
-    blocks += (unsigned)chunks * J.groups;
-    RedJob &Q = d.job[i];
-    Q.P = P; Q.chunks = chunks; Q.prow = (J.KT + 1) * 16; Q.pcol = ldd; Q.Kx = Kx; Q.ones_row = J.KT * 16; Q.e0 = elems;
-    elems += (unsigned)(Q.prow * Q.pcol);
+    learner_job(x.job[i], d.job[i], blocks, elems, X, ldx, Kx, D, ldd, rows, chunks, P);
   };
   job(0, ws + o.xa, T::K1P, T::K1, ws + o.dh1, kH, R, o.chunks_a, ws + o.p1);
   job(1, ws + o.h1, kH, kH, ws + o.dh2, kH, R, o.chunks_a, ws + o.p2);
@@ -596,10 +473,10 @@ template <int N> static int grad_launch(const cm3_qmix_learner_tensors *wt, cons
   d.B = (uint32_t)B;
   d.err2 = ws + o.err2;
   d.loss = r->loss;
-  hipLaunchKernelGGL(k_learner_xtd, dim3(blocks), dim3(256), 0, s, x);
+  hipLaunchKernelGGL(k_learner_xtd<4>, dim3(blocks), dim3(256), 0, s, x);
   note_variant("k_qmix_learner_reduce", (int)sizeof(float), N, 4, 0, 0, 0, 0, 0, 0, /* prec=f32 */ 0);
   note_tail(",after=fwd+mixer+bwd+xtd");   // (the four launches before it: k_learner_agent_fwd, _mixer, _agent_bwd, _xtd)
-  hipLaunchKernelGGL(k_learner_reduce, dim3((elems + 255u) / 256u + 1u), dim3(256), 0, s, d);
+  hipLaunchKernelGGL(k_learner_reduce<4>, dim3((elems + 255u) / 256u + 1u), dim3(256), 0, s, d);
   CM3_HIP_CHECK(hipGetLastError());
   return CM3_OK;
 }

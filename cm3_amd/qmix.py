@@ -16,10 +16,10 @@ ignored, so ``{v.name: sess.run(v)}`` of either scope loads unchanged.  The netw
 (a float64 env's observation is rounded to float32 as the inputs are staged, as the reference's tf.float32 placeholders do).
 
 Exploration draws come from the build's own Philox stream (csrc/actor.hip, kPurposeExplore): the same law as the reference's
-np.random calls, not the same numbers.  The Checkers learner stays on the reference's side; both agents serve a
+np.random calls, not the same numbers.  Both agents serve a
 learner's data side with greedy_rows (argmax_Q_target on the rows of a sampled batch) and soft_update_from, and ParticleQmixMixer /
-CheckersQmixMixer (below) evaluate the target mixer -- mixer_target and the TD target -- on the same rows; ParticleQmixLearner (at
-the end) is the particle learner itself: loss, gradients and Adam on the device.  soft_update_from and the
+CheckersQmixMixer (below) evaluate the target mixer -- mixer_target and the TD target -- on the same rows; ParticleQmixLearner and
+CheckersQmixLearner (at the end) are the learners themselves: loss, gradients and Adam on the device.  soft_update_from and the
 weight loading are cm3_amd._net._DeviceNet's (the agent and mixer halves of list_update_target_ops, alg_qmix.py:135-156,
 alg_qmix_checkers.py:128-130); CheckersQmixAgent shares descriptor and launch bodies with CheckersActor (actor._CheckersPolicyNet).
 """
@@ -210,7 +210,8 @@ class CheckersQmixAgent(_CheckersPolicyNet):
     For a learner: greedy_rows evaluates the network on the rows of a sampled batch (argmax_Q_target of the reference's train_step,
     one launch, no draws), soft_update_from moves an Agent_target copy towards the main agent; cm3_amd.batch.qmix_train_step_feeds(
     env="checkers", target_agent=...) builds every feed of train_step around them; with target_mixer= (a CheckersQmixMixer, below) the
-    target mixer's forward pass runs on the device too.  The main mixer's optimiser step stays the caller's.
+    target mixer's forward pass runs on the device too; with learner= (a CheckersQmixLearner, at the end of this module) the optimiser
+    step of mixer_op as well.
     """
     _match = ("n", "precision")
     _refusal = "the main agent must be a CheckersQmixAgent for %(n)d agents at precision %(precision)r"
@@ -442,7 +443,7 @@ class CheckersQmixMixer(_DeviceNet):
           (alg_qmix_checkers.py:364-379)                                   done, gamma)  (ONE launch of cm3_qmix_mixer_checkers_rows_f32)
         the mixer half of list_update_target_ops (:128-130)              mixer.soft_update_from(main_mixer, tau)
 
-    The forward pass only: the main mixer's loss, gradient and optimiser step stay the session's.  Weights stay
+    The forward pass only: the main mixer's loss, gradient and optimiser step are CheckersQmixLearner's (below), or a session's.  Weights stay
     float32 as TensorFlow shapes them, in ``self.w`` under the short names of CK_MIXER_NAMES, so a session that trains the main mixer
     can write updated variables INTO these tensors in place; ``repack()`` (one launch on persistent tensors, capturable) then makes
     the next launch follow them.  The prefixes "Mixer_main/", "Mixer_target/" and a ":0" suffix of the keys are ignored."""
@@ -538,7 +539,109 @@ _LEARNER_FIELDS = {"h/kernel": "h_kernel", "h/bias": "h_bias", "h2/kernel": "h2_
 _GUARD = 64          # floats left untouched after every gradient tensor and after the workspace's used part
 
 
-class ParticleQmixLearner(object):
+class _QmixLearner(object):
+    """What ParticleQmixLearner and CheckersQmixLearner share: the type and count checks of the two main networks, the gradient store
+    (one allocation, every tensor 16-byte aligned with _GUARD floats after it), the Adam moments, powers and segment table
+    (cm3_adam_step_f32), the workspace that grows outside of a capture only, and gradients() / step() around the subclass's
+    _stage / enqueue_gradients.  A subclass names its two network classes, its workspace entry point and, in _tensors(), the flat
+    name -> tensor table of the weights it trains."""
+    _agent_cls = _mixer_cls = None
+    _workspace_bytes = ""
+
+    def __init__(self, agent, mixer, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8, max_batch=128):
+        me, ac, mc = type(self).__name__, self._agent_cls.__name__, self._mixer_cls.__name__
+        if not isinstance(agent, self._agent_cls) or not isinstance(mixer, self._mixer_cls):
+            raise Cm3Error("%s takes the main %s and the main %s, got %s and %s: build "
+                           "them from the Agent_main / Mixer_main variables" % (me, ac, mc, type(agent).__name__, type(mixer).__name__))
+        if agent.n != mixer.n:
+            raise Cm3Error("%s: the agent is built for %d agents, the mixer for %d; build both for one agent count" % (me, agent.n, mixer.n))
+        if agent.device != mixer.device:
+            raise Cm3Error("%s: the agent is on %s, the mixer on %s; build both on one device" % (me, agent.device, mixer.device))
+        self.agent, self.mixer = agent, mixer
+        self.n, self.device = agent.n, agent.device
+        self.lr, self.beta1, self.beta2, self.epsilon = float(lr), float(beta1), float(beta2), float(epsilon)
+        self._lib = _lib.lib()
+        self.w = self._tensors()
+        # one allocation for the gradients: every tensor 16-byte aligned with _GUARD floats after it
+        offsets, at = {}, 0
+        for name, t in self.w.items():
+            offsets[name] = at
+            at += (t.numel() + 3) // 4 * 4 + _GUARD
+        self._grad_store = torch.zeros(at, dtype=torch.float32, device=self.device)
+        self.grads = {name: self._grad_store[offsets[name]:offsets[name] + t.numel()].view(t.shape) for name, t in self.w.items()}
+        self.m = {name: torch.zeros_like(t) for name, t in self.w.items()}
+        self.v = {name: torch.zeros_like(t) for name, t in self.w.items()}
+        self._state = torch.tensor([self.beta1, self.beta2, 0.0, 0.0], dtype=torch.float32, device=self.device)
+        self.powers = self._state[:2]
+        self._bind()
+        table = [[self.w[k].data_ptr(), self.grads[k].data_ptr(), self.m[k].data_ptr(), self.v[k].data_ptr(), self.w[k].numel()]
+                 for k in self.w]
+        self._segments = torch.tensor(table, dtype=torch.int64, device=self.device)
+        self._adam = _lib.AdamDesc()
+        self._adam.lr, self._adam.beta1, self._adam.beta2, self._adam.epsilon = self.lr, self.beta1, self.beta2, self.epsilon
+        self._adam.n_segments, self._adam.total = len(table), sum(row[4] for row in table)
+        self.max_batch, self._workspace = 0, None
+        self._reserve(int(max_batch))
+
+    def workspace_floats(self, batch):
+        """Floats of the workspace the gradient launches use for `batch` transitions (the library's *_workspace_bytes)."""
+        nbytes = getattr(self._lib, self._workspace_bytes)(self.n, int(batch))
+        if nbytes == 0:
+            raise Cm3Error("%s: a batch of %d transitions is out of range" % (type(self).__name__, int(batch)))
+        return nbytes // 4
+
+    def _reserve(self, batch):
+        if batch <= self.max_batch:
+            return
+        need = self.workspace_floats(batch)
+        if torch.cuda.is_current_stream_capturing():
+            raise Cm3Error("%s: a batch of %d transitions needs a larger workspace than max_batch=%d reserved, and a "
+                           "capture cannot allocate; build the learner with max_batch >= %d"
+                           % (type(self).__name__, batch, self.max_batch, batch))
+        self._workspace = torch.zeros(need + _GUARD, dtype=torch.float32, device=self.device)
+        self.max_batch = batch
+
+    def _workspace_args(self):
+        return self._workspace.data_ptr(), (self._workspace.numel() - _GUARD) * 4
+
+    def enqueue_adam(self, stream=None):
+        """Raw launch of cm3_adam_step_f32 over the trained tensors on whatever ``grads`` holds; advances ``powers``."""
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        _lib.check(self._lib.cm3_adam_step_f32(ctypes.byref(self._adam), self._segments.data_ptr(), self._state.data_ptr(), s))
+
+    def gradients(self, cols, td_target, keep=None):
+        """Loss and gradients of mixer_op's loss on the columns of a sampled batch (sample_batch / as_reference_batch(numpy=False);
+        float64 columns are rounded to float32) and td_target [B] (float64 is rounded as it is read, as the tf.float32 placeholder
+        rounds its feed).  Returns {"loss": float32 [1], "q_tot": float32 [B, 1], "grads": {short name: tensor}}; the gradient tensors
+        are the learner's own and hold the latest call's values.  Changes no weight, moment or power.  keep: an optional list that
+        receives the staged inputs and the outputs, for whoever captures the launches."""
+        staged = self._stage(cols, td_target, keep)
+        B = staged[0]
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        q_tot = torch.empty(B, 1, dtype=torch.float32, device=self.device)
+        _keep(keep, loss, q_tot)
+        self.enqueue_gradients(*(staged + (loss, q_tot)))
+        return {"loss": loss, "q_tot": q_tot, "grads": self.grads}
+
+    def step(self, cols, td_target, keep=None):
+        """sess.run(mixer_op): the launches of gradients(), then ONE Adam launch on agent.w / mixer.w in place, then both repack()s.
+        Returns the loss tensor float32 [1] (of the weights before the step, as the session evaluates it)."""
+        out = self.gradients(cols, td_target, keep)
+        self.enqueue_adam()
+        self.agent.repack()
+        self.mixer.repack()
+        return out["loss"]
+
+
+def _stage_td(learner, B, td_target):
+    """td_target [B] contiguous on the learner's device, float32 as it is or float64 (the launch rounds it as it reads)"""
+    if td_target.numel() != B:
+        raise Cm3Error("%s takes td_target [B] for %d time steps, got %s" % (type(learner).__name__, B, tuple(td_target.shape)))
+    return td_target.reshape(-1).to(device=learner.device,
+                                    dtype=td_target.dtype if td_target.dtype == torch.float32 else torch.float64).contiguous()
+
+
+class ParticleQmixLearner(_QmixLearner):
     """mixer_op of the reference's particle QMIX on the device: loss, gradients and tf.train.AdamOptimizer's step, no session.
 
         reference                                                    here
@@ -553,63 +656,21 @@ class ParticleQmixLearner(object):
     the two power scalars ``powers`` (device memory, advanced by every Adam launch, as TF keeps beta1_power / beta2_power) and a
     persistent workspace sized for max_batch transitions; a larger batch grows it, outside of a capture only.  step() trains
     ``agent.w`` / ``mixer.w`` in place and repacks both, so the next launch of either follows the new weights.  Not a _DeviceNet: it
-    holds no weights of its own and none of the launch-hook names cm3_amd.rollout dispatches on."""
+    holds no weights of its own and none of the launch-hook names cm3_amd.rollout dispatches on.  (gradients, step, enqueue_adam,
+    workspace_floats: _QmixLearner, shared with CheckersQmixLearner.)"""
+    _agent_cls, _mixer_cls = ParticleQmixAgent, ParticleQmixMixer
+    _workspace_bytes = "cm3_qmix_learner_particle_workspace_bytes"
 
-    def __init__(self, agent, mixer, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8, max_batch=128):
-        if not isinstance(agent, ParticleQmixAgent) or not isinstance(mixer, ParticleQmixMixer):
-            raise Cm3Error("ParticleQmixLearner takes the main ParticleQmixAgent and the main ParticleQmixMixer, got %s and %s: build "
-                           "them from the Agent_main / Mixer_main variables" % (type(agent).__name__, type(mixer).__name__))
-        if agent.n != mixer.n:
-            raise Cm3Error("ParticleQmixLearner: the agent is built for %d agents, the mixer for %d; build both for one agent count"
-                           % (agent.n, mixer.n))
-        if agent.device != mixer.device:
-            raise Cm3Error("ParticleQmixLearner: the agent is on %s, the mixer on %s; build both on one device" % (agent.device, mixer.device))
-        self.agent, self.mixer = agent, mixer
-        self.n, self.device = agent.n, agent.device
-        self.lr, self.beta1, self.beta2, self.epsilon = float(lr), float(beta1), float(beta2), float(epsilon)
-        self._lib = _lib.lib()
-        self.w = dict(agent.w)
-        self.w.update(mixer.w)
-        # one allocation for the gradients: every tensor 16-byte aligned with _GUARD floats after it
-        offsets, at = {}, 0
-        for name, t in self.w.items():
-            offsets[name] = at
-            at += (t.numel() + 3) // 4 * 4 + _GUARD
-        self._grad_store = torch.zeros(at, dtype=torch.float32, device=self.device)
-        self.grads = {name: self._grad_store[offsets[name]:offsets[name] + t.numel()].view(t.shape) for name, t in self.w.items()}
-        self.m = {name: torch.zeros_like(t) for name, t in self.w.items()}
-        self.v = {name: torch.zeros_like(t) for name, t in self.w.items()}
-        self._state = torch.tensor([self.beta1, self.beta2, 0.0, 0.0], dtype=torch.float32, device=self.device)
-        self.powers = self._state[:2]
+    def _tensors(self):
+        w = dict(self.agent.w)
+        w.update(self.mixer.w)
+        return w
+
+    def _bind(self):
         self._wt, self._gt = _lib.QmixLearnerTensors(), _lib.QmixLearnerTensors()
         for name, field in _LEARNER_FIELDS.items():
             setattr(self._wt, field, self.w[name].data_ptr())
             setattr(self._gt, field, self.grads[name].data_ptr())
-        table = [[self.w[k].data_ptr(), self.grads[k].data_ptr(), self.m[k].data_ptr(), self.v[k].data_ptr(), self.w[k].numel()]
-                 for k in self.w]
-        self._segments = torch.tensor(table, dtype=torch.int64, device=self.device)
-        self._adam = _lib.AdamDesc()
-        self._adam.lr, self._adam.beta1, self._adam.beta2, self._adam.epsilon = self.lr, self.beta1, self.beta2, self.epsilon
-        self._adam.n_segments, self._adam.total = len(table), sum(row[4] for row in table)
-        self.max_batch, self._workspace = 0, None
-        self._reserve(int(max_batch))
-
-    def workspace_floats(self, batch):
-        """Floats of the workspace the gradient launches use for `batch` transitions (cm3_qmix_learner_particle_workspace_bytes)."""
-        nbytes = self._lib.cm3_qmix_learner_particle_workspace_bytes(self.n, int(batch))
-        if nbytes == 0:
-            raise Cm3Error("ParticleQmixLearner: a batch of %d transitions is out of range" % int(batch))
-        return nbytes // 4
-
-    def _reserve(self, batch):
-        if batch <= self.max_batch:
-            return
-        need = self.workspace_floats(batch)
-        if torch.cuda.is_current_stream_capturing():
-            raise Cm3Error("ParticleQmixLearner: a batch of %d transitions needs a larger workspace than max_batch=%d reserved, and a "
-                           "capture cannot allocate; build the learner with max_batch >= %d" % (batch, self.max_batch, batch))
-        self._workspace = torch.zeros(need + _GUARD, dtype=torch.float32, device=self.device)
-        self.max_batch = batch
 
     def _desc(self):
         d = _lib.QmixLearnerParticleDesc()
@@ -626,10 +687,7 @@ class ParticleQmixLearner(object):
         for name, shape in want.items():
             if tuple(cols[name].shape) != shape:
                 raise Cm3Error("ParticleQmixLearner takes %s %s, got %s" % (name, list(shape), tuple(cols[name].shape)))
-        if td_target.numel() != B:
-            raise Cm3Error("ParticleQmixLearner takes td_target [B] for %d time steps, got %s" % (B, tuple(td_target.shape)))
-        td = td_target.reshape(-1).to(device=self.device,
-                                      dtype=td_target.dtype if td_target.dtype == torch.float32 else torch.float64).contiguous()
+        td = _stage_td(self, B, td_target)
         staged = (f32(cols["obs_others"]), f32(cols["v_local"]), f32(cols["goals"]),
                   cols["actions"].to(device=self.device, dtype=torch.int32).contiguous(), f32(vg), td)
         _keep(keep, *staged)
@@ -646,36 +704,9 @@ class ParticleQmixLearner(object):
         r.n_steps = int(B)
         d = self._desc()
         s = _lib.current_stream_handle(self.device) if stream is None else stream
+        ws, ws_bytes = self._workspace_args()
         _lib.check(self._lib.cm3_qmix_learner_particle_grad_f32(
-            ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(self._gt), ctypes.byref(r), self._workspace.data_ptr(),
-            (self._workspace.numel() - _GUARD) * 4, s))
-
-    def enqueue_adam(self, stream=None):
-        """Raw launch of cm3_adam_step_f32 over the eleven tensors on whatever ``grads`` holds; advances ``powers``."""
-        s = _lib.current_stream_handle(self.device) if stream is None else stream
-        _lib.check(self._lib.cm3_adam_step_f32(ctypes.byref(self._adam), self._segments.data_ptr(), self._state.data_ptr(), s))
-
-    def gradients(self, cols, td_target, keep=None):
-        """Loss and gradients of mixer_op's loss on the columns of a sampled batch (sample_batch / as_reference_batch(numpy=False);
-        float64 columns are rounded to float32) and td_target [B] (float64 is rounded as it is read, as the tf.float32 placeholder
-        rounds its feed).  Returns {"loss": float32 [1], "q_tot": float32 [B, 1], "grads": {short name: tensor}}; the gradient tensors
-        are the learner's own and hold the latest call's values.  Changes no weight, moment or power.  keep: an optional list that
-        receives the staged inputs and the outputs, for whoever captures the launches."""
-        B, oo, vl, go, ac, vg, td = self._stage(cols, td_target, keep)
-        loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        q_tot = torch.empty(B, 1, dtype=torch.float32, device=self.device)
-        _keep(keep, loss, q_tot)
-        self.enqueue_gradients(B, oo, vl, go, ac, vg, td, loss, q_tot)
-        return {"loss": loss, "q_tot": q_tot, "grads": self.grads}
-
-    def step(self, cols, td_target, keep=None):
-        """sess.run(mixer_op): the launches of gradients(), then ONE Adam launch on agent.w / mixer.w in place, then both repack()s.
-        Returns the loss tensor float32 [1] (of the weights before the step, as the session evaluates it)."""
-        out = self.gradients(cols, td_target, keep)
-        self.enqueue_adam()
-        self.agent.repack()
-        self.mixer.repack()
-        return out["loss"]
+            ctypes.byref(d), ctypes.byref(self._wt), ctypes.byref(self._gt), ctypes.byref(r), ws, ws_bytes, s))
 
     def train_step(self, cols, gamma, target_agent, target_mixer, tau, keep=None):
         """The whole of alg_qmix.train_step (alg_qmix.py:338-380) with no `run`: the target agents' argmax Q on the next
@@ -689,6 +720,113 @@ class ParticleQmixLearner(object):
         td = target_mixer.q_tot(cols["v_global_next"], cols["goals"], greedy["q_max"].reshape(B, N), cols["reward_local"].reshape(B, N),
                                 cols["done"], gamma, keep=keep)["td"]
         _keep(keep, *greedy.values())
+        loss = self.step(cols, td, keep)
+        target_agent.soft_update_from(self.agent, tau)
+        target_mixer.soft_update_from(self.mixer, tau)
+        return loss
+
+
+# ---- the Checkers learner -------------------------------------------------------------------------------------------------------------
+class CheckersQmixLearner(_QmixLearner):
+    """mixer_op of the reference's Checkers QMIX on the device: loss, gradients and tf.train.AdamOptimizer's step, no session -- the
+    twin of ParticleQmixLearner.
+
+        reference                                                    here
+        ---------------------------------------------------------   -----------------------------------------------
+        self.loss_mixer, self.mixer_op = AdamOptimizer(lr)           CheckersQmixLearner(agent, mixer, lr)
+          .minimize(loss) (alg_qmix_checkers.py:184-190)               agent / mixer: the Agent_main / Mixer_main objects
+        sess.run(self.mixer_op, feed) (:381-391)                     learner.step(cols, td_target) -> loss
+        the whole of train_step (:342-393)                           learner.train_step(cols, gamma, target_agent, target_mixer, tau)
+
+    agent is the main CheckersQmixAgent (either precision), mixer the main CheckersQmixMixer, for one agent count (1..8) on one device.
+    The twenty trained tensors -- ``w``, and with the same keys ``grads``, ``m`` and ``v`` -- are named "agent/<short name of
+    CK_NAMES>" and "mixer/<short name of CK_MIXER_NAMES>" (both networks have a conv_w and a conv_b); ``w`` holds the very tensors of
+    ``agent.w`` / ``mixer.w``.  The learner's forward pass is exact float32 on those tensors whatever the agent's precision (at "f32"
+    its Q values are greedy_rows' bits); step() trains them in place and repacks both networks at their own precision.  cols: the
+    columns of a sampled Checkers batch (either ring's sample_batch, as_reference_batch(numpy=False)), read in the forms the rows
+    kernels read: int8 windows / grids and uint8 index goals as they are, everything else float64 / int64 one-hot."""
+    _agent_cls, _mixer_cls = CheckersQmixAgent, CheckersQmixMixer
+    _workspace_bytes = "cm3_qmix_learner_checkers_workspace_bytes"
+
+    def _tensors(self):
+        w = {"agent/" + k: t for k, t in self.agent.w.items()}
+        w.update({"mixer/" + k: t for k, t in self.mixer.w.items()})
+        return w
+
+    def _bind(self):
+        self._agt, self._mgt = _lib.ActorCheckersWeights(), _lib.QmixMixerCheckersWeights()
+        for k in self.agent.w:
+            setattr(self._agt, k, self.grads["agent/" + k].data_ptr())
+        for k in self.mixer.w:
+            setattr(self._mgt, k, self.grads["mixer/" + k].data_ptr())
+
+    def _desc(self):
+        d = _lib.QmixLearnerCheckersDesc()
+        d.n_agents, d.conv_f, d.n_conv_linear, d.n_h1, d.n_h2, d.n_actions = self.n, 6, 32, 256, 256, N_ACTIONS
+        d.embed_dim, d.mixer_conv_f = CK_EMBED, 4
+        return d
+
+    def _stage(self, cols, td_target, keep):
+        vec = cols["vec"]
+        if vec.dim() != 3 or vec.shape[1] != self.n or vec.shape[2] != 4 or vec.shape[0] == 0:
+            raise Cm3Error("CheckersQmixLearner for %d agents takes vec [B, %d, 4], got %s" % (self.n, self.n, tuple(vec.shape)))
+        B, N = int(vec.shape[0]), self.n
+        if tuple(cols["actions"].shape) != (B, N):
+            raise Cm3Error("CheckersQmixLearner takes actions [%d, %d], got %s" % (B, N, tuple(cols["actions"].shape)))
+        _, ot, ov, oo, ap, vg = stage_checkers_rows("CheckersQmixLearner", self.device, self.agent.Lo, cols["obs_self_t"], cols["obs_self_v"],
+                                                    cols["obs_others"], cols["actions_prev"], cols["goals"])
+        if cols["grid"].numel() != B * 54:
+            raise Cm3Error("CheckersQmixLearner takes grid [B, 3, 9, 2] for %d time steps, got %s" % (B, tuple(cols["grid"].shape)))
+        grid = cols["grid"]
+        grid = grid.to(device=self.device, dtype=torch.int8 if grid.dtype == torch.int8 else torch.float64).contiguous()
+        staged = (ot, ov, oo, ap, cols["actions"].to(device=self.device, dtype=torch.int32).contiguous(), vg, grid,
+                  vec.to(device=self.device, dtype=torch.float64).contiguous(), _stage_td(self, B, td_target))
+        _keep(keep, *staged)
+        return (B,) + staged
+
+    def enqueue_gradients(self, B, obs_self_t, obs_self_v, obs_others, actions_prev, actions, goals, grid, vec, td, loss, q_tot,
+                          stream=None):
+        """Raw launches of cm3_qmix_learner_checkers_grad_f32 on contiguous device tensors: obs_self_t int8 or float64 [B, N, 75],
+        obs_self_v / obs_others / vec float64, actions_prev / actions int32 [B, N], goals uint8 [B, N] or int64 [B, N, 2], grid int8 or
+        float64 [B, 54], td float32 or float64 [B]; loss float32 [1], q_tot float32 [B]."""
+        if (obs_self_t.dtype not in (torch.int8, torch.float64) or grid.dtype not in (torch.int8, torch.float64)
+                or goals.dtype not in (torch.uint8, torch.int64)):
+            raise Cm3Error("enqueue_gradients reads int8 or float64 windows and grids and uint8 index or int64 one-hot goals, not %s / %s "
+                           "/ %s" % (obs_self_t.dtype, grid.dtype, goals.dtype))
+        self._reserve(B)
+        r = _lib.QmixLearnerCheckersRows()
+        r.obs_self_t_f64 = 1 if obs_self_t.dtype == torch.float64 else 0
+        r.grid_f64 = 1 if grid.dtype == torch.float64 else 0
+        r.goals_onehot = 1 if goals.dtype == torch.int64 else 0
+        r.td_f64 = 1 if td.dtype == torch.float64 else 0
+        r.obs_self_t, r.obs_self_v, r.obs_others = _lib.ptr(obs_self_t), _lib.ptr(obs_self_v), _lib.ptr(obs_others)
+        r.actions_prev, r.actions, r.goals, r.grid, r.vec = _lib.ptr(actions_prev), _lib.ptr(actions), _lib.ptr(goals), _lib.ptr(grid), _lib.ptr(vec)
+        r.td, r.loss, r.q_tot = _lib.ptr(td), _lib.ptr(loss), _lib.ptr(q_tot)
+        r.n_steps = int(B)
+        d = self._desc()
+        s = _lib.current_stream_handle(self.device) if stream is None else stream
+        ws, ws_bytes = self._workspace_args()
+        _lib.check(self._lib.cm3_qmix_learner_checkers_grad_f32(
+            ctypes.byref(d), ctypes.byref(self.agent._wt), ctypes.byref(self.mixer._wt), ctypes.byref(self._agt), ctypes.byref(self._mgt),
+            ctypes.byref(r), ws, ws_bytes, s))
+
+    def train_step(self, cols, gamma, target_agent, target_mixer, tau, keep=None):
+        """The whole of alg_qmix_checkers.train_step (alg_qmix_checkers.py:342-393) with no `run`.  The TD target is the reference
+        graph's (:96-106): the target agents' argmax on the next_* columns with the `actions` column fed as actions_prev
+        (target_agent.greedy_rows), agent_qs = the MAIN agent's Q at that argmax, the target mixer's q_tot on it
+        (qmix_train_step_feeds(env="checkers", target_agent=, target_mixer=, mixer_q_agent=learner.agent) forms the same); then
+        step() and the soft updates of both target networks (list_update_target_ops).  Returns the loss tensor."""
+        vec = cols["vec"]
+        B, N = vec.shape[0], vec.shape[1]
+        rows = lambda x: x.reshape(B * N, *x.shape[2:])      # noqa: E731
+        nxt = (rows(cols["next_obs_self_t"]), rows(cols["next_obs_self_v"]), rows(cols["next_obs_others"]), cols["actions"].reshape(B * N),
+               rows(cols["goals"]))
+        greedy = target_agent.greedy_rows(*nxt, onehot=False)
+        q_main = self.agent.greedy_rows(*nxt, q=True, onehot=False)["q"]
+        agent_qs = q_main.gather(1, greedy["argmax"].long().unsqueeze(1))
+        td = target_mixer.q_tot(cols["next_grid"], cols["next_vec"], cols["goals"], agent_qs.reshape(B, N),
+                                cols["local_rewards"].reshape(B, N), cols["done"], gamma, keep=keep)["td"]
+        _keep(keep, q_main, agent_qs, *greedy.values())
         loss = self.step(cols, td, keep)
         target_agent.soft_update_from(self.agent, tau)
         target_mixer.soft_update_from(self.mixer, tau)

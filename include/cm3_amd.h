@@ -75,6 +75,8 @@ extern "C" {
                                   cm3_qmix_learner_particle_workspace_bytes / _grad_f32 (loss and the eleven dense gradients of mixer_op of
                                   alg_qmix.train_step) and cm3_adam_step_f32 (tf.train.AdamOptimizer's step over a table of tensors, its
                                   two powers kept on the device): the first train step that needs no session; additive.
+                                  cm3_qmix_learner_checkers_workspace_bytes / _grad_f32 (loss and the twenty dense gradients of mixer_op
+                                  of alg_qmix_checkers.train_step, applied by cm3_adam_step_f32): additive.
                                   cm3_value_particle_packed_bytes / _pack / _rows_f32 and cm3_coma_particle_packed_bytes / _pack /
                                   _rows_f32 (the IAC / COMA baseline critics V_particle_local, V_particle_global and Q_global over
                                   transition rows, with the TD targets: the evaluations of alg_baseline.train_step that carry no
@@ -1254,6 +1256,63 @@ int cm3_actor_checkers_pack(const cm3_actor_checkers_desc *desc, const cm3_actor
                             void *stream);
 int cm3_actor_checkers_f32(const cm3_actor_checkers_desc *desc, const cm3_actor_checkers_weights *weights,
                            const cm3_actor_checkers_bufs *bufs, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The Checkers QMIX learner (part of ABI 9, additive): mixer_op of alg_qmix_checkers.train_step (alg_qmix_checkers.py:184-190,
+ * 381-391) -- the loss mean((float32(td_target) - q_tot)^2) and its dense float32 gradients for the thirteen variables of Agent_main
+ * (networks.Qmix_single_checkers, shared by the agents: their gradient sums over the B N agent rows) and the seven of Mixer_main
+ * (networks.Qmix_mixer_checkers), with TensorFlow's conventions at the kinks (ReluGrad passes where the input is > 0, d|x|/dx =
+ * sign(x) with 0 at 0, EluGrad below zero is elu + 1).  Fourteen launches on the given stream (csrc/learner_checkers.hip), every one
+ * capturable; no floating-point atomics: every sum's order is fixed by the row count alone, so two calls on the same inputs give the
+ * same bits.  Weights and gradients go in as cm3_actor_checkers_weights / cm3_qmix_mixer_checkers_weights (TF-shaped tensors; `packed`
+ * is not read: the launches follow the tensors as they are); the gradient structs name the tensors WRITTEN, dense, every element.
+ * cm3_adam_step_f32 over a table of the twenty tensors applies them.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_agents;                               /* 1..8 */
+  int32_t conv_f, n_conv_linear, n_h1, n_h2;      /* 6, 32, 256, 256 */
+  int32_t n_actions;                              /* 5 */
+  int32_t embed_dim;                              /* 128 */
+  int32_t mixer_conv_f;                           /* 4 */
+} cm3_qmix_learner_checkers_desc;
+
+/* The columns of a batch of n_steps transitions (B) of N agents in the forms the rows kernels read (cm3_qmix_checkers_rows,
+ * cm3_qmix_mixer_checkers_rows), each value rounded to float32 as it is read, and the two outputs beside the gradients.  The agent
+ * rows are the columns viewed [B N, .]; Lo = 2 max(N - 1, 1).  An action outside 0..4 selects no Q value (q_selected 0, no gradient
+ * into that row). */
+typedef struct {
+  int32_t obs_self_t_f64;     /* obs_self_t holds float64 (else int8) */
+  int32_t grid_f64;           /* grid holds float64 (else int8) */
+  int32_t goals_onehot;       /* goals holds int64 one-hot [B][N][2] (else the uint8 index [B][N]) */
+  int32_t td_f64;             /* td holds float64 (the td_target placeholder is tf.float32), else float32 */
+  const void *obs_self_t;     /* [B][N][75]; float64: 8-byte aligned */
+  const double *obs_self_v;   /* [B][N][4] */
+  const double *obs_others;   /* [B][N][Lo] */
+  const int32_t *actions_prev;/* [B][N], 0..4 */
+  const int32_t *actions;     /* [B][N] the actions taken */
+  const void *goals;          /* the agents' goal and the mixer's goals_all; one-hot: 8-byte aligned */
+  const void *grid;           /* [B][3][9][2]; float64: 8-byte aligned */
+  const double *vec;          /* [B][N][4] the agents' states */
+  const void *td;             /* [B] the TD target */
+  float *loss;                /* [1] */
+  float *q_tot;               /* [B]: the bits cm3_qmix_mixer_checkers_rows_f32 computes from the same weights and Q values */
+  int64_t n_steps;
+} cm3_qmix_learner_checkers_rows;
+
+/* Bytes of scratch cm3_qmix_learner_checkers_grad_f32 takes for this agent count and batch; grows with n_steps.  0 for an agent
+ * count outside 1..8 or n_steps outside 1..(2^31 - 1) / 216 (every row index of the launches -- 27 grid positions per transition, 25
+ * window positions per agent row -- stays in int32). */
+size_t cm3_qmix_learner_checkers_workspace_bytes(int32_t n_agents, int64_t n_steps);
+/* CM3_ERR_INVALID with a readable cm3_last_error() before anything touches the device, in this order: null desc, n_agents outside
+ * 1..8, other widths than 6 / 32 / 256 / 256 / 5 and 128 / 4; null weights / grads / rows, a missing tensor, input, output or
+ * workspace, a misaligned pointer; n_steps <= 0 or above (2^31 - 1) / 216, a workspace smaller than
+ * cm3_qmix_learner_checkers_workspace_bytes().  Changes nothing but the gradients, loss, q_tot and the workspace.
+ * cm3_last_kernel_variant() names the last launch, k_qmix_learner_checkers_reduce<f32,N=..,after=stage+6gemm+mixer+4gemm+xtd>, and so the
+ * thirteen before it. */
+int cm3_qmix_learner_checkers_grad_f32(const cm3_qmix_learner_checkers_desc *desc, const cm3_actor_checkers_weights *agent_weights,
+                                       const cm3_qmix_mixer_checkers_weights *mixer_weights,
+                                       const cm3_actor_checkers_weights *agent_grads, const cm3_qmix_mixer_checkers_weights *mixer_grads,
+                                       const cm3_qmix_learner_checkers_rows *rows, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * On-device Checkers QMIX agent (part of ABI 9, additive): networks.Qmix_single_checkers (networks.py:617-637) + the
